@@ -14,10 +14,15 @@ case118v2 (118 buses / 186 branches, synthetic topology per SURVEY.md 8d), batch
     python bench.py --mode infer --batch 1  (per-sample latency: the one timing the reference itself takes,
                                              perfomance_evaluator.py:61-74)
 
-Rank 0 prints ONE JSON line.  Besides the contract's keys it carries
+Rank 0 prints ONE JSON line.  A plain run measures only the headline: set-up, warm-up, the K timed steps, the line.  The timed
+region starts from the training state the three eager warm-up steps left (restored after the clock ramp and the W warm-up
+steps), so the same arguments give the same last step on every run and every build: `--dump-outputs DIR` writes what that
+step computed (DIR/<name>.npy, float32).  `--full` adds everything else the line can carry:
   roofline     : dominant kernel class, algorithmic bytes|flops per launch / HIP-event launch duration
   cpu_baseline : the CPU oracle (oracle/ref_cpu.py, kind "port") timed on this box's host cores, bounded sample
   kernels      : per-kernel-class table behind `roofline` (count per step, avg us, achieved, fraction of peak)
+  median / min step time, eager / new-topology / reference-loop / world-1-RCCL step times, the isolated scatter-add, and
+  short runs of BASELINE.json's other single-GPU configurations (`other_configs`)
 """
 from __future__ import annotations
 
@@ -68,7 +73,31 @@ def parse():
                     help="skip the short runs of BASELINE.json's other single-GPU configurations (reported under `other_configs`)")
     ap.add_argument("--loss", default="mse", choices=["mse", "masked_l2"],
                     help="mse = BASELINE.json's metric (train.py:103); masked_l2 = the reference's default --train_loss_fn")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: median / min step time, the per-kernel pass (--profile-steps) and roofline, live "
+                         "traffic, the eager and reference-loop step times, the isolated scatter-add, the CPU baseline and the "
+                         "other configurations (the --no-* switches above thin this set out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): `output` (the "
+                         "model's prediction), and in training `loss` and `params` (the flat parameter buffer after AdamW)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20      # bytes, all arrays of --dump-outputs together
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: device tensor} as outdir/<name>.npy in float32.  Arrays that together exceed DUMP_BUDGET are replaced by a
+    fixed sample of their flattened entries (numpy default_rng(0), indices sorted) of each array's share of the budget."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    share = DUMP_BUDGET // (4 * max(len(host), 1))
+    for name, a in host.items():
+        if total > DUMP_BUDGET and a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def alg_bytes(n, e, h, fe, K=3, train=True):
@@ -175,7 +204,7 @@ def live_traffic(args, klass):
     pat = KERNEL_OF_CLASS.get(klass)
     if pat is None:
         return None, f"no kernel-name pattern for class {klass}"
-    child = [sys.executable, os.path.abspath(__file__), "--child", "--no-graph", "--steps", "2", "--warmup", "1", "--profile-steps", "0",
+    child = [sys.executable, os.path.abspath(__file__), "--child", "--full", "--no-graph", "--steps", "2", "--warmup", "1", "--profile-steps", "0",
              "--clock-ramp-ms", "0",
              "--no-cpu-baseline", "--no-live-traffic", "--no-dp-overhead", "--case", str(args.case), "--batch", str(args.batch),
              "--config", args.config, "--mode", args.mode, "--hub-frac", str(args.hub_frac), "--loss", args.loss]
@@ -295,13 +324,13 @@ OTHER_CONFIGS = {   # BASELINE.json configs[2] and configs[3] (configs[1] is the
 
 
 def other_configs():
-    """The default invocation also times BASELINE.json's other single-GPU configurations, briefly (a child process each: its own
+    """The default invocation with --full also times BASELINE.json's other single-GPU configurations, briefly (a child process each: its own
     workspace, a few replayed steps, the per-kernel pass for the dominant kernel's roofline fraction; no CPU baseline, no counter
     passes), so that the record a driver keeps of `python bench.py` holds a number for every configuration -- not a headline."""
     import subprocess
     out = {}
     for name, extra in OTHER_CONFIGS.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--no-cpu-baseline", "--no-live-traffic", "--no-dp-overhead",
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--full", "--no-cpu-baseline", "--no-live-traffic", "--no-dp-overhead",
                "--no-other-configs", "--profile-steps", "2"] + extra
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -375,6 +404,7 @@ def main():
     masked = args.loss == "masked_l2"
     loss_fn = Masked_L2_loss() if masked else MSELoss()   # MSELoss: torch.nn.MSELoss semantics (train.py:103), fwd+bwd in one pass
     loss_box = [None]
+    out_box = [None]         # the model's prediction of the last step (--dump-outputs); in training, written by the backward pass
 
     if train:
         model.train()
@@ -388,9 +418,11 @@ def main():
                 loss_fn.attach(model, data.y, data.pred_mask)
             else:
                 loss_fn.attach(model, data.y)
-            loss = loss_fn(model(data), data.y, data.pred_mask) if masked else loss_fn(model(data), data.y)
+            out = model(data)
+            loss = loss_fn(out, data.y, data.pred_mask) if masked else loss_fn(out, data.y)
             loss.backward(loss_fn.unit_grad(loss))     # == loss.backward(), minus autograd's ones_like + mul kernels
             loss_box[0] = loss
+            out_box[0] = out.detach()
 
         def step_eager():
             fwd_bwd()
@@ -401,7 +433,7 @@ def main():
 
         def step_eager():
             with torch.no_grad():
-                loss_box[0] = model(data)
+                loss_box[0] = out_box[0] = model(data)
 
     # ---- warm-up on a side stream (builds the topology cache, autotunes nothing, primes the allocator)
     side = torch.cuda.Stream()
@@ -412,6 +444,11 @@ def main():
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     directed, e_eff = model._graphs._graph.info()
+    # what a step changes (parameters, AdamW moments and step count, the dropout stream's offset): kept as the warm-up left it,
+    # and put back in place right before the timed steps, which therefore compute the same values however many ramp steps ran
+    state = [t for t in (opt.flat_param, opt.exp_avg, opt.exp_avg_sq, opt.step_count, model._rng_state) if t is not None] \
+        if train else []
+    saved = [t.clone() for t in state]
 
     use_graph = not args.no_graph
     launch_mode = "eager"
@@ -466,6 +503,8 @@ def main():
         ramp_steps = 8 + more
     for _ in range(args.warmup):
         step()
+    for t, t0 in zip(state, saved):
+        t.copy_(t0)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
@@ -484,23 +523,30 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = args.batch * world * args.steps / elapsed
     ranks_info = rank_roster(dev, local_rank, 1e3 * own_elapsed / args.steps, world, dist_on)
-    # the same K steps once more with one event per step boundary: median / min step time (SURVEY 8d asks for the median; the
-    # contract's timed region above stays free of event records, each of which costs a few microseconds on the stream)
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record()
-    for i in range(args.steps):
-        step()
-        evs[i + 1].record()
-    torch.cuda.synchronize()
-    barrier()
-    per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
-    median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": out_box[0], "loss": loss_box[0], "params": opt.flat_param} if train
+                     else {"output": out_box[0]})
+    median_ms = min_ms = None
+    if args.full:
+        # the same K steps once more with one event per step boundary: median / min step time (SURVEY 8d asks for the median;
+        # the contract's timed region above stays free of event records, each of which costs a few microseconds on the stream)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record()
+        for i in range(args.steps):
+            step()
+            evs[i + 1].record()
+        torch.cuda.synchronize()
+        barrier()
+        per_step = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
+        median_ms = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+        min_ms = per_step[0]
     final = loss_box[0]
     final_loss = float(final.float().mean().item()) if final is not None else None
 
     # ---- per-kernel timing pass (eager, HIP events on the launch stream) -> roofline of the dominant kernel
     roofline, kernels, step_flops = None, {}, None
-    if args.profile_steps > 0:
+    profile_steps = args.profile_steps if args.full else 0
+    if profile_steps > 0:
         # every rank runs the eager steps (they contain the gradient all-reduce: a rank that skipped them would leave the
         # others waiting in the collective); only rank 0 records and reports
         # one untimed eager step first: the eager pass allocates its own workspaces (the replayed step's live in the graph's
@@ -511,11 +557,11 @@ def main():
         if rank == 0:
             L.profile_report(reset=True)
             L.profile_enable(True)
-        for _ in range(args.profile_steps):
+        for _ in range(profile_steps):
             step_eager()
         torch.cuda.synchronize()
         barrier()
-    if rank == 0 and args.profile_steps > 0:
+    if rank == 0 and profile_steps > 0:
         L.profile_enable(False)
         rep = L.profile_report(reset=True)
         ab = alg_bytes(n_nodes, e_eff, h, 2, K, train)
@@ -593,7 +639,7 @@ def main():
     # ---- SURVEY 8(d) extras (single GPU, training): the optimiser-free step, and a step with a COLD topology cache (a new
     # edge_index tensor: adjacency rebuilt on device, one host sync for the id-range check), both eager-launched
     extras = {}
-    if rank == 0 and world == 1 and not train and not args.child:
+    if rank == 0 and world == 1 and not train and not args.child and args.full:
         def timed_inf(fn, reps):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -605,7 +651,7 @@ def main():
         if args.batch == 1:
             # the reference's own latency loop (perfomance_evaluator.py:61-74): model(sample) per sample, batch of one
             extras["latency_us_per_sample"] = {"hipGraph_replay": round(1e3 * median_ms, 2), "eager_launches": round(1e3 * extras["eager_ms_per_step"], 2)}
-    if rank == 0 and world == 1 and train and not args.child:
+    if rank == 0 and world == 1 and train and not args.child and args.full:
         def timed(fn, reps):
             """ms per call: the best of three loops of `reps` pipelined calls (one untimed call first: first-use allocations of
             this stream's memory pool; best-of-three: a one-off allocator or driver hiccup of ~0.3 s inside a 10-call loop was
@@ -720,7 +766,7 @@ def main():
     # ---- the scatter-add in isolation (north_star's 40 % figure): pfn_scatter_add over this batch's adjacency, F = hidden_dim,
     # against B_sa(F) = 4 [E F + E + N F + (N+1)]; HIP events on the launch stream around 20 back-to-back launches
     scatter = None
-    if rank == 0 and not args.child:
+    if rank == 0 and not args.child and args.full:
         gws = model._graphs._graph
         xs = torch.randn(n_nodes, (h + 3) // 4 * 4, device=dev)
         xs[:, h:] = 0
@@ -753,11 +799,11 @@ def main():
 
     bytes_step = b_fwd(n_nodes, e_eff, h, Lg, K) * (3.0 if train else 1.0)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.full:
         cpu = cpu_baseline(args, (h, Lg, K), data_cpu, args.cpu_seconds)
 
     others = None
-    if rank == 0 and world == 1 and not args.child and not args.no_other_configs and train and str(args.case) == "118v2" \
+    if rank == 0 and world == 1 and not args.child and args.full and not args.no_other_configs and train and str(args.case) == "118v2" \
             and args.batch == 128 and args.config == "standard" and not under_profiler():
         del data, model                                # (the children need the memory more than this process does from here on)
         torch.cuda.empty_cache()
@@ -784,8 +830,8 @@ def main():
                       f"case{args.case} batch={args.batch}",
             "value": round(value, 1), "unit": "graphs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "clock_ramp_steps": ramp_steps,
-            "ms_per_step": round(ms_per_step, 4), "median_ms_per_step": round(median_ms, 4),
-            "min_ms_per_step": round(per_step[0], 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "ms_per_step": round(ms_per_step, 4), "median_ms_per_step": None if median_ms is None else round(median_ms, 4),
+            "min_ms_per_step": None if min_ms is None else round(min_ms, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": f"case{args.case} ({n_case} buses, {e_case} branches, synthetic topology) "
                                    f"MaskEmbdMultiMPN {args.config}.json (H{h} L{Lg} K{K} dropout 0.2) "

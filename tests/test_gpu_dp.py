@@ -93,7 +93,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     """bench.py's multi-process path as the driver launches it for N > 1 (torchrun).  Under gloo (the collective goes through
     the host and cannot be captured) the step is hipGraph(fwd+bwd) -> eager all-reduce -> hipGraph(AdamW); every rank enters
     every collective including the ones inside rank 0's profiling pass."""
-    cmd, env = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    cmd, env = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
                              "--profile-steps", "2", "--no-cpu-baseline", "--case", "14", "--batch", "8"],
                          {"PFN_SINGLE_DEVICE": "1", "PFN_DIST_BACKEND": "gloo"})
     out, _ = _run(cmd, env, 420)
@@ -194,7 +194,7 @@ def test_bench_rccl_collective_path_world1():
     RCCL on the compute stream, graph replay -- next to a live process group and its watchdog."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PFN_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), PFN_HANG_DUMP="150")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--profile-steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--profile-steps", "2",
            "--no-cpu-baseline", "--case", "14", "--batch", "16"]
     out, err = _run(cmd, env, 420)
     lines = [l for l in out.splitlines() if l.startswith("{")]
@@ -213,7 +213,7 @@ def test_bench_under_torchrun_world1_with_rccl_overhead_probe():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PFN_FORCE_DIST"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full",
            "--profile-steps", "2", "--no-cpu-baseline", "--no-live-traffic", "--case", "14", "--batch", "16"]
     out, err = _run(cmd, env, 300)
     lines = [l for l in out.splitlines() if l.startswith("{")]

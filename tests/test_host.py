@@ -66,8 +66,9 @@ def test_train_and_eval_epoch_semantics_on_oracle_model():
 
 
 def _dp_worker(rank, world, port, ret):
+    # a host-only rank (gloo, CPU tensors): on a box with fewer GPUs than ranks, init_from_env must not select device `rank`
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port))
+                      MASTER_PORT=str(port), PFN_SINGLE_DEVICE="1")
     torch.set_num_threads(1)
     r, _, w = dp.init_from_env(backend="gloo")
     ds = make_dataset("14", 8)

@@ -8,7 +8,7 @@ d=/tmp/ab_b; rm -rf $d; mkdir -p $d; cp -r $R/poweflownet_amd $R/include $R/benc
 for rep in $(seq $REPS); do for side in A B; do
   if [ $side = A ]; then cd $R; tag="tree"; else cd $d; tag="$FLAGS"; fi
   for cfgargs in "--case 118v2 --batch 128 --mode train --steps 200 --warmup 20" "--case 118v2 --batch 2048 --mode infer --steps 40 --warmup 5" "--case 6470rte --batch 64 --mode train --steps 12 --warmup 3"; do
-    python bench.py $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 3 2>/dev/null | KCLASS=$KCLASS python -c "
+    python bench.py --full $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 3 2>/dev/null | KCLASS=$KCLASS python -c "
 import sys, json, os
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,7 @@ cp $R/ab_ref/poweflownet_amd/csrc/*.hip $R/ab_ref/poweflownet_amd/csrc/*.hpp $d/
 for rep in $(seq $REPS); do for side in A B; do
   if [ $side = A ]; then cd $R; tag="tree"; else cd $d; tag="ref "; fi
   for cfgargs in "--case 118v2 --batch 128 --mode train --steps 200 --warmup 20" "--case 118v2 --batch 2048 --mode infer --steps 40 --warmup 5" "--case 6470rte --batch 64 --mode train --steps 12 --warmup 3" $EXTRA_CFG; do
-    python bench.py $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 0 2>/dev/null | python -c "
+    python bench.py --full $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

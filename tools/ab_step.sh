@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; cd $R
 VAR=$1; VALS=$2; REPS=${3:-2}
 for rep in $(seq $REPS); do for v in $VALS; do
   for cfgargs in "--case 118v2 --batch 2048 --mode infer --steps 40 --warmup 5" "--case 6470rte --batch 64 --mode train --steps 12 --warmup 3"; do
-    env $VAR=$v python bench.py $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 0 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full $cfgargs --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead --profile-steps 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

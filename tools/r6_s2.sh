@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/s2; mkdir -p $O
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 600 python -m pytest tests/test_torch_ops.py tests/test_gpu_parity.py -m gpu -q -x -k "bad_graph or rebuilt_on_the_device or mse_tail_ops or wide_json_on_case6470 or graphed_train_step or dynamic_topology or guarded" > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log
-python bench.py --no-cpu-baseline --no-live-traffic > $O/b2.json 2> $O/b2.err
+python bench.py --full --no-cpu-baseline --no-live-traffic > $O/b2.json 2> $O/b2.err
 bash tools/ubench/run_gemm_nt_small.sh > $O/nt_small.txt 2>&1
 bash tools/ubench/run_gemm_nt_ts.sh > $O/nt_ts.txt 2>&1
 bash tools/ubench/run_gemm_nt_ts2_small.sh > $O/nt_ts2_small.txt 2>&1

@@ -12,6 +12,6 @@ for cfg in "15104 129 129 4 1" "15104 129 129 2 1" "7552 129 129 4 1" "15104 129
 done; done > $O/harness.txt 2>&1
 timeout 900 python -m pytest tests/test_gpu_mse_tail.py tests/test_gpu_parity.py -m gpu -q -x > $O/pytest.log 2>&1; echo "pytest exit $?" >> $O/pytest.log
 for rep in 1 2; do
-python bench.py --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_pub_$rep.json 2> $O/b2_pub_$rep.err
-PFN_NO_NT_PUB=1 python bench.py --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_nopub_$rep.json 2> $O/b2_nopub_$rep.err
+python bench.py --full --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_pub_$rep.json 2> $O/b2_pub_$rep.err
+PFN_NO_NT_PUB=1 python bench.py --full --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_nopub_$rep.json 2> $O/b2_nopub_$rep.err
 done

@@ -8,6 +8,6 @@ cp gpurun_out/parity_report.json $O/parity_report_pair.json
 PFN_NO_NT_PAIR=1 timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "config2 or config3_size or hidden512 or wide" > $O/pytest_nopair.log 2>&1; echo "pytest exit $?" >> $O/pytest_nopair.log
 cp gpurun_out/parity_report.json $O/parity_report_nopair.json
 for rep in 1 2; do
-python bench.py --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_pair_$rep.json 2> $O/b2_pair_$rep.err
-PFN_NO_NT_PAIR=1 python bench.py --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_nopair_$rep.json 2> $O/b2_nopair_$rep.err
+python bench.py --full --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_pair_$rep.json 2> $O/b2_pair_$rep.err
+PFN_NO_NT_PAIR=1 python bench.py --full --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b2_nopair_$rep.json 2> $O/b2_nopair_$rep.err
 done

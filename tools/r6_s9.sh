@@ -12,9 +12,9 @@ for rep in 1 2; do for cfg in "241664 129 129 1 1" "241664 129 129 2 2" "414080 
   echo "== $cfg plain"; PFN_NO_NT_ILF=1 /tmp/gemm_nt_bench $cfg 30 | grep -v "bad element"
 done; done > $O/harness.txt 2>&1
 for rep in 1 2; do
-python bench.py --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_ilf4_$rep.json 2> $O/b3_ilf4_$rep.err
-PFN_NO_NT_ILF4=1 python bench.py --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_ilf2_$rep.json 2> $O/b3_ilf2_$rep.err
-PFN_NO_NT_ILF=1 python bench.py --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_plain_$rep.json 2> $O/b3_plain_$rep.err
+python bench.py --full --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_ilf4_$rep.json 2> $O/b3_ilf4_$rep.err
+PFN_NO_NT_ILF4=1 python bench.py --full --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_ilf2_$rep.json 2> $O/b3_ilf2_$rep.err
+PFN_NO_NT_ILF=1 python bench.py --full --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs > $O/b3_plain_$rep.json 2> $O/b3_plain_$rep.err
 done
-python bench.py --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b4_ilf4.json 2> $O/b4_ilf4.err
-PFN_NO_NT_ILF=1 python bench.py --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b4_plain.json 2> $O/b4_plain.err
+python bench.py --full --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b4_ilf4.json 2> $O/b4_ilf4.err
+PFN_NO_NT_ILF=1 python bench.py --full --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead > $O/b4_plain.json 2> $O/b4_plain.err

@@ -10,7 +10,7 @@ for v in BASE NOGATHER NOSTORE NOLOADX NOCSR "NOGATHER -DBH_EXP_NOSTORE -DBH_EXP
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $d/*.o -o $d/libpfn_hip.so
   cp $C/libpfn_hip.so /tmp/libpfn_keep.so; cp $d/libpfn_hip.so $C/libpfn_hip.so
   echo "== $v"
-  (cd $S && python bench.py --case 6470rte --batch 64 --steps 3 --warmup 1 --profile-steps 3 --no-cpu-baseline --no-live-traffic --no-dp-overhead 2>/dev/null) | python -c "
+  (cd $S && python bench.py --full --case 6470rte --batch 64 --steps 3 --warmup 1 --profile-steps 3 --no-cpu-baseline --no-live-traffic --no-dp-overhead 2>/dev/null) | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -12,7 +12,7 @@ for v in BASE NOFLUSH; do
   echo "== $v harness"
   for cfg in "241664 129 129 1 1" "241664 129 129 2 2" "241664 129 129 4 1"; do PFN_NT_TINY_MAX_TILES=0 $d/bench $cfg 20 | grep -v "bad element\|waves:"; done
   echo "== $v config-3 step"
-  ( cd $d && python bench.py --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs 2>/dev/null | python -c "
+  ( cd $d && python bench.py --full --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ms_per_step', d['ms_per_step'], 'gemm_nt', d['kernels'].get('gemm_nt'))" )
 done

@@ -12,11 +12,11 @@ for v in plain nt "sc0 sc1" ; do
   ( cd $d/poweflownet_amd/csrc && rm -f gemm_nt.o libpfn_hip.so && make -j16 libpfn_hip.so > /tmp/sh_make.log 2>&1 ) || tail -5 /tmp/sh_make.log
   test -f $d/poweflownet_amd/csrc/libpfn_hip.so || exit 1
   for rep in 1 2; do
-  ( cd $d && python bench.py --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs 2>/dev/null | python -c "
+  ( cd $d && python bench.py --full --mode infer --batch 2048 --no-cpu-baseline --no-live-traffic --no-other-configs 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('[$v] config 3 ms_per_step', d['ms_per_step'], 'gemm_nt', d['kernels']['gemm_nt']['avg_us'])" )
   done
-  ( cd $d && python bench.py --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead 2>/dev/null | python -c "
+  ( cd $d && python bench.py --full --case 6470rte --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('[$v] config 4 ms_per_step', d['ms_per_step'], 'gemm_nt', d['kernels']['gemm_nt']['avg_us'])" )
 done

@@ -10,7 +10,7 @@ grep -c "blockIdx.x + 1" $d/poweflownet_amd/csrc/seg_lin_hops.hip
 ( cd $d/poweflownet_amd/csrc && rm -f seg_lin_hops.o libpfn_hip.so && make -j16 libpfn_hip.so > /tmp/mis_make.log 2>&1 ) || tail -5 /tmp/mis_make.log
 for rep in 1 2 3; do for side in tree shifted; do
   if [ $side = tree ]; then cd $R; else cd $d; fi
-  python bench.py --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-live-traffic --no-other-configs --no-dp-overhead 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']; print('[$side]', d['ms_per_step'], d['median_ms_per_step'], {n:k[n]['avg_us'] for n in ('seg_lin_hops_fwd','seg_lin_hops_bwd','gemm_nt','ea_seg_fwd','ea_seg_bwd') if n in k})"
 done; done
