@@ -260,6 +260,38 @@ int pfn_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* e
 int pfn_adamw_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t count,
                            const float* hyper, int64_t* step, const float* guard, void* stream);
 
+/* ------------------------------------------------------------------------------- k-hop locality analysis
+ * The device side of utils/explanation.py (counterpart of the reference's explain_epoch, utils/explanation.py:34-114, which
+ * reruns the model on the edge list cut down to the m-hop ball around a center bus, PyG k_hop_subgraph(directed=False) over
+ * _make_bidirectional(edge_index)).  Additive within ABI 8.  `graph_ws` is an adjacency pfn_graph_build made in mode 1 (always
+ * undirect) from ONE graph's stored edge list (n_nodes, e_stored): no entry point assumes that list to be symmetric.
+ *
+ * Hop distances from each of `n_centers` centers (node ids in [0, n_nodes)): dist[c][v] (uint16, [n_centers][n_nodes], row-major)
+ * = BFS hop count, 0xFFFF for a node that is unreachable or farther than `max_hops` (<= 65534); ecc[c] = the largest finite
+ * distance, or -1 when some node was not reached.  dist may be NULL (eccentricities only: the all-pairs diameter without an n x n
+ * table) while a distance row fits in LDS (n_nodes <= 76800); larger graphs need the buffer.                                   */
+int pfn_khop_distances(const void* graph_ws, int64_t n_nodes, int64_t e_stored, const int32_t* centers, int64_t n_centers,
+                       int32_t max_hops, uint16_t* dist, int32_t* ecc, void* stream);
+/* Ball sizes of every (center, radius r = 0..max_radius) at once, cumulative over r ([n_centers][max_radius + 1] int32):
+ * node_count = |{v : dist <= r}|, edge_count = |{edges (u, v) of the bidirectional list : max(dist u, dist v) <= r}|.          */
+int pfn_khop_histograms(const void* graph_ws, int64_t n_nodes, int64_t e_stored, const uint16_t* dist, int64_t n_centers,
+                        int32_t max_radius, int32_t* node_count, int32_t* edge_count, void* stream);
+/* Packs `n_inst` balls as one batch of small graphs.  Instance i = (distance row inst_row[i] of `dist`, whose center is
+ * centers[inst_row[i]]; radius inst_radius[i] >= 0; batch position inst_sample[i]); node_off / edge_off [n_inst + 1] are the
+ * exclusive offsets of the instances' sizes (node_count / edge_count above), edge_off[n_inst] = total_edges.  Per instance:
+ *   node_ids[node_off[i] ...]     the ball's nodes in ascending id order, as batch ids inst_sample * n_nodes + v;
+ *   edge_index_out [2][total_edges] the induced edges in the order of the bidirectional list (stored edges in stored order, then
+ *                                 their reverses), relabelled to packed rows node_off[i] + local id;
+ *   edge_ids                      each edge's id in that list (< e_stored: stored edge k, >= e_stored: reverse of k - e_stored);
+ *   center_pos[i]                 the packed row of the center.
+ * `edge_index` is the stored list graph_ws was built from.  *err (device int, cleared by the caller) is set when an instance's
+ * size disagrees with its offsets (nothing is written past them) or the build recorded an id out of range.  n_nodes <= 38400
+ * (the old -> new id map lives in LDS).                                                                                     */
+int pfn_khop_pack(const void* graph_ws, int64_t n_nodes, int64_t e_stored, const int64_t* edge_index, const int32_t* centers,
+                  const uint16_t* dist, const int32_t* inst_row, const int32_t* inst_radius, const int32_t* inst_sample,
+                  const int64_t* node_off, const int64_t* edge_off, int64_t n_inst, int64_t total_edges, int64_t* node_ids,
+                  int64_t* edge_index_out, int64_t* edge_ids, int64_t* center_pos, int32_t* err, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

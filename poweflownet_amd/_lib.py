@@ -23,6 +23,7 @@ SYMBOLS = (
     "pfn_tag_conv_workspace_bytes", "pfn_tag_conv_forward", "pfn_tag_conv_backward",
     "pfn_scatter_add", "pfn_pad_rows", "pfn_mse_loss", "pfn_masked_l2_loss", "pfn_power_imbalance", "pfn_dropout_mask", "pfn_adamw_step", "pfn_adamw_step_dev", "pfn_adamw_step_guarded",
     "pfn_profile_enable", "pfn_profile_report",
+    "pfn_khop_distances", "pfn_khop_histograms", "pfn_khop_pack",
 )
 
 
@@ -86,6 +87,9 @@ def load() -> C.CDLL:
         "pfn_adamw_step_guarded": (C.c_int, [p, p, p, p, i64, p, p, p, p]),
         "pfn_profile_enable": (C.c_int, [i32]),
         "pfn_profile_report": (C.c_int, [C.c_char_p, sz, i32]),
+        "pfn_khop_distances": (C.c_int, [p, i64, i64, p, i64, i32, p, p, p]),
+        "pfn_khop_histograms": (C.c_int, [p, i64, i64, p, i64, i32, p, p, p]),
+        "pfn_khop_pack": (C.c_int, [p, i64, i64, p, p, p, p, p, p, p, p, i64, i64, p, p, p, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
