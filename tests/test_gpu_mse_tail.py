@@ -6,7 +6,7 @@ gradient bit for bit, the loss to the rounding of another summation order; and a
 import pytest
 import torch
 
-from tests.util import assert_close
+from tests.util import _run, _run_masked, assert_close
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -17,27 +17,6 @@ def _models(p=0.2, seed=6):
     torch.manual_seed(seed)
     m = MaskEmbdMultiMPN(4, 2, 4, 129, 4, 3, p).to(DEV)
     return m
-
-
-def _run(m, d, loss_fn, attach, x_grad=False):
-    from poweflownet_amd import _lib as L
-    m.seed_dropout(78)
-    m.zero_grad(set_to_none=True)
-    d.x.grad = None
-    d.x.requires_grad_(x_grad)
-    L.profile_report(reset=True)
-    L.profile_enable(True)
-    if attach:
-        loss_fn.attach(m, d.y)
-    out = m(d)
-    loss = loss_fn(out, d.y)
-    loss.backward(loss_fn.unit_grad(loss))
-    torch.cuda.synchronize()
-    L.profile_enable(False)
-    rep = L.profile_report(reset=True)
-    launches = {k: v["count"] for k, v in rep.items() if not k.startswith("__")}
-    return {"out": out.detach().clone(), "loss": loss.detach().clone(), "g": m.flat_grad().clone(),
-            "gx": d.x.grad.clone() if x_grad else None, "launches": launches}
 
 
 @pytest.mark.parametrize("case,B,train", [("118v2", 128, True), ("118v2", 16, False), ("14", 37, True), ("14", 300, True)])
@@ -179,24 +158,6 @@ def test_attached_pair_leaves_no_reference_cycle():
 
 
 # ------------------------------------------------------------------------------------------------ Masked_L2_loss
-def _run_masked(m, d, loss_fn, attach):
-    from poweflownet_amd import _lib as L
-    m.seed_dropout(78)
-    m.zero_grad(set_to_none=True)
-    L.profile_report(reset=True)
-    L.profile_enable(True)
-    if attach:
-        loss_fn.attach(m, d.y, d.pred_mask)
-    out = m(d)
-    loss = loss_fn(out, d.y, d.pred_mask)
-    loss.backward(loss_fn.unit_grad(loss))
-    torch.cuda.synchronize()
-    L.profile_enable(False)
-    rep = L.profile_report(reset=True)
-    return {"out": out.detach().clone(), "loss": loss.detach().clone(), "g": m.flat_grad().clone(),
-            "launches": {k: v["count"] for k, v in rep.items() if not k.startswith("__")}}
-
-
 @pytest.mark.parametrize("case,B,train,float_mask,reg,coeff", [("118v2", 128, True, False, True, 1), ("118v2", 16, False, True, True, 0.5),
                                                                 ("14", 37, True, False, False, 1), ("14", 300, True, True, True, 2.0)])
 def test_attached_masked_l2_is_bit_identical_to_the_plain_path(case, B, train, float_mask, reg, coeff):

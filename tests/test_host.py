@@ -204,3 +204,164 @@ def test_gemm_nt_block_order_covers_every_row_group_and_slice_once():
             if ns > 1:
                 for b in range(gx & ~7):
                     assert len({seen[(b, s)][0] % 8 for s in range(ns)}) == 1, (gx, ns, b)
+
+
+# ------------------------------------------------------------------------------------------ tests/regimes.py, pinned to csrc/
+REGIME_PINS = {
+    # the graph-resident EdgeAggregation / seg_lin_hops / front_seg kernels
+    "seg_tile.hpp": ("constexpr int SG_MAX_ROWS = 128;", "constexpr int SG_LDS_BYTES = 78 * 1024;", "constexpr int SG_NCH = 17;",
+                     "constexpr int SG_TW = 36;"),
+    "ea_seg.hip": ("constexpr int SG_W2A_CH = 34;",
+                   "if (seg <= 0 || seg > SG_MAX_ROWS || n <= 0 || n % seg != 0) return false;",
+                   "const int gpb = std::max(1, SG_MAX_ROWS / seg);", "p.trows = (p.rows_pb + 31) / 32 * 32;", "p.cap = p.rows_pb * 4;",
+                   "return p.ny >= 1 && ld <= 8 * SG_NCH &&", "(!bwd_limits || p.nblocks <= 1024) &&",
+                   "size_t f = (size_t)(bwd ? 3 : 2) * trows * SG_TW + (bwd ? 0 : 2 * SG_NCH * 256) + 2 * SG_TW + (bwd ? 4 * SG_TW + 4 * "
+                   "SG_W2A_CH * 4 + 8 * 16 * 2 * 4 : 0) + (size_t)(bwd ? 2 : 1) * 2 * cap;",
+                   "size_t i = (size_t)(bwd ? 2 : 1) * (rows_pb + 1 + cap);", "return (f + i) * 4 + 16;",
+                   "const long per_cu = 4L;",
+                   "return !off && fe == 2 && seg_plan(seg, n, ld, p, bwd) && (long)p.nblocks * p.ny <= per_cu * device_cus();",
+                   "return !off && ld / 4 <= 64 && front_latency_regime(h, n) && ea_seg_fit(seg, n, fe, ld, false);"),
+    "seg_lin_hops.hip": ("const long per_cu = 4L;   // (ea_seg_fit's bound)", "fused_hops_fit(seg, ld, n) &&",
+                         "slh_plan(seg, n, ld, nterm, p) && (long)p.nblocks * p.ny <= per_cu * device_cus();"),
+    "model.hip": ("const bool generic_fwd = !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) || (fused_front && i == 0);",
+                  "return c.need_backward != 0 && lo.fe == 2 && generic_fwd && !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true);",
+                  "return !off && fused_front && lo.nlayers > 1 && lo.fe == 2 && lo.f0 == 4 && !front_latency_regime(lo.h, lo.n) &&",
+                  "(c.need_backward == 0 || ea_saves_mask(c, lo, seg, fused_front, 0));",
+                  "return fused_front && ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) && !first_layer_fly(c, lo, seg, fused_front) && lo.nlayers > 1 &&",
+                  "front_seg_fit(seg, lo.n, lo.h, lo.fe) && !(c.need_backward && lo.fe == 2 && !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true));",
+                  "lin_out4_ok(lo.h, lo.fo, lo.ldo, lo.n) && back_fused_ok() && ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) &&",
+                  "ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true) && lo.ld / 4 <= 34;",
+                  "return (mse_tail_ok(*c, lo, (int)seg_nodes) && uses_seg_front(*c, lo, (int)seg_nodes)) ? 1 : 0;",
+                  "} else if (K > 0 && fused_hops_fit(seg, ldx, g.n)) {", "} else if (K > 0 && big_hops_fit(seg, g.n, g.e_stored)) {"),
+    # the row-per-wave front and the last layer
+    "front.hip": ("static int wave_max_rows() { return 32768; }",
+                  "return !off && fo >= 1 && fo <= 4 && ldo == 4 && ld_of(h) / 4 <= 64 && n <= wave_max_rows();",
+                  "return !off && f0 == 4 && ld_of(h) / 4 <= 256;", "return !off && nchunk <= 64 && n <= wave_max_rows();",
+                  "bool front_latency_regime(int h, int n) { return front_row_per_wave(ld_of(h) / 4, n); }"),
+    # TAGConv hops, edge rows
+    "edge.hip": ("constexpr int FH_LDS_BYTES = 156 * 1024;",
+                 "if (seg <= 0 || (size_t)2 * seg * 4 * sizeof(float) + (size_t)(2 * seg + 1) * sizeof(int) > (size_t)FH_LDS_BYTES / 2) return false;",
+                 "constexpr int BH_THREADS = 1024;", "constexpr int BH_RPT = 8;", "constexpr int BH_HUB_DEG = 32;", "constexpr int BH_HUB_CAP = 128;",
+                 "return (size_t)BH_HUB_CAP * 16 + (size_t)BH_HUB_CAP * 2 + 16;",
+                 "if (off || seg <= 0 || n <= 0 || n % seg != 0 || seg > BH_RPT * BH_THREADS || seg >= 65536) return false;",
+                 "return (size_t)(seg + 1) * 16 + bh_hub_bytes() + (size_t)((seg + 2 + 7) & ~7) * 2 + 1024 <= (size_t)160 * 1024;",
+                 "if (!(ne + 4 <= nb_cap && ne < 65536)) {",
+                 "const size_t fixed = (size_t)(a.seg + 1) * 16 + bh_hub_bytes() + (size_t)((a.seg + 2 + 7) & ~7) * 2;",
+                 "const size_t want_nb = (size_t)(2 * (int64_t)g.e_stored / std::max(1, ngraphs) + 64) * 2;",
+                 "const size_t lds_total = std::min((size_t)160 * 1024, fixed + want_nb);",
+                 "const int nb_cap = (int)((lds_total - fixed) / 2);",
+                 "if (cnt > BH_HUB_DEG && rowu < seg) {", "if (sl < BH_HUB_CAP) {", "((uint32_t)min(cnt, 255) << 16)",
+                 "constexpr int RH_THREADS = 512;", "constexpr int RH_IPT = 8;", "constexpr int ER_THREADS = 512;", "constexpr int ER_IPT = 8;",
+                 "if (seg <= 0 || seg > 1023 || (long)seg * nchunk > (long)RH_IPT * RH_THREADS) return 0;",
+                 "int gpb = std::min((RH_IPT * RH_THREADS) / (seg * nchunk), 1023 / seg);",
+                 "while (gpb > 0 && (size_t)gpb * seg * nchunk * 16 + (size_t)((gpb * seg + 2 + 7) & ~7) * 2 + 4096 > (size_t)78 * 1024) --gpb;",
+                 "if (!off && !a.transpose && gpb > 0 && (long)(ngraphs + gpb - 1) / gpb >= 4L * device_cus()) {",
+                 "if (seg <= 0 || seg > 1023 || (long)seg * nchunk > (long)ER_IPT * ER_THREADS || 8 * nchunk > ER_THREADS) return 0;",
+                 "int gpb = std::min((ER_IPT * ER_THREADS) / (seg * nchunk), 1023 / seg);",
+                 "while (gpb > 0 && (size_t)gpb * seg * nchunk * 16 + 4096 > (size_t)66 * 1024) --gpb;",
+                 "if (!off && gpb > 0 && (long)(ngraphs + gpb - 1) / gpb >= 4L * device_cus()) {"),
+    # the TAGConv products
+    "gemm_nt.hip": ("constexpr int NT_THREADS = 512;", "constexpr int NCH = 17;", "constexpr int KP = 8 * NCH;", "constexpr int NT_MAX_PIECES = 16;",
+                    "constexpr int NT_LDS_BYTES = 160 * 1024;", "constexpr int TINY_MAX_PIECES = 8;",
+                    'atoi(diag_env("PFN_NT_TINY_MAX_TILES")) : 256;', 'atoi(diag_env("PFN_NT_WS_MIN_TILES")) : 2;',
+                    "bool tiny_ok = tiny_max > 0 && nrt <= tiny_max && nq == 4 && remv == 4 && nrem == 1 &&",
+                    "pieces.size() <= (size_t)TINY_MAX_PIECES",
+                    "const long per_round = (long)ncu * NT_WAVES;",
+                    "bool ws_ok = ws_min > 0 && nq == 4 && remv == 4 && nrem == 1 && nslices > 2 && pieces.size() <= (size_t)NT_MAX_PIECES &&",
+                    "(long)nrt >= (long)ws_min * per_round;", "const long nround = nrt / per_round;",
+                    "const long rows_ws = std::min<long>(a.M, nround * per_round * 32);",
+                    "bool wide_ok = remv == 0 && nq >= 8 && nq % 4 == 0 && pieces.size() <= (size_t)NT_MAX_PIECES && a.ldc == 32 * nq;",
+                    "if (fast && tps >= 2 && (long)nrt * nslices * (tps / 2) >= 2L * ncu * NT_WAVES) CT = 2;",
+                    "if (tot <= lds_budget && pieces.size() <= (size_t)NT_MAX_PIECES) break;"),
+    "pfn_internal.hpp": ("remv = (m != 0 && m <= 4) ? m : 0;", "nq = (ld - remv + 31) / 32;", "static inline int ld_of(int f) { return (int)round_up(f, 4); }"),
+}
+
+
+def regime_pin_failures(csrc):
+    """(file, line) of every pinned line that is no longer in `csrc` (whitespace runs compared as one blank)."""
+    import re
+    missing = []
+    for name, lines in REGIME_PINS.items():
+        src = re.sub(r"\s+", " ", open(os.path.join(csrc, name)).read())
+        missing += [(name, ln) for ln in lines if re.sub(r"\s+", " ", ln) not in src]
+    return missing
+
+
+def test_regime_constants_are_still_in_the_source():
+    """tests/regimes.py restates the dispatch predicates of the forward and backward passes (tests/test_gpu_boundaries.py picks
+    the shapes on both sides of every edge from it).  Every constant and formula it restates must still be written in csrc/,
+    literally: a threshold that moves fails here, on the CPU, before the GPU tests straddle the wrong place."""
+    from tests import regimes as R
+    assert regime_pin_failures(os.path.join(ROOT, "poweflownet_amd", "csrc")) == []
+    # the restatement's own constants are the pinned ones
+    assert (R.SG_MAX_ROWS, R.SG_LDS_BYTES, R.SG_NCH, R.SG_TW, R.SG_W2A_CH, R.SG_BWD_MAX_BLOCKS, R.PER_CU) == (128, 78 * 1024, 17, 36, 34, 1024, 4)
+    assert (R.WAVE_MAX_ROWS, R.FH_LDS_BYTES, R.BH_RPT, R.BH_THREADS, R.BH_HUB_DEG, R.BH_HUB_CAP) == (32768, 156 * 1024, 8, 1024, 32, 128)
+    assert (R.RH_THREADS, R.RH_IPT, R.ER_THREADS, R.ER_IPT) == (512, 8, 512, 8)
+    assert (R.NT_THREADS, R.NCH, R.KP, R.NT_MAX_PIECES, R.NT_LDS_BYTES, R.TINY_MAX_PIECES, R.TINY_MAX_TILES, R.WS_MIN_ROUNDS) == \
+        (512, 17, 136, 16, 160 * 1024, 8, 256, 2)
+
+
+def test_regime_pins_fail_on_a_moved_threshold(tmp_path):
+    """The pin check itself: a copy of csrc/ with one threshold moved (SG_MAX_ROWS, per_cu, wave_max_rows, FH_LDS_BYTES, BH_RPT,
+    BH_HUB_CAP, the tiny / streaming defaults, NT_MAX_PIECES, TINY_MAX_PIECES) must fail it."""
+    import shutil
+    csrc = os.path.join(ROOT, "poweflownet_amd", "csrc")
+    moves = [("seg_tile.hpp", "SG_MAX_ROWS = 128", "SG_MAX_ROWS = 129"), ("ea_seg.hip", "per_cu = 4L", "per_cu = 8L"),
+             ("seg_lin_hops.hip", "per_cu = 4L", "per_cu = 2L"), ("front.hip", "return 32768;", "return 32767;"),
+             ("edge.hip", "FH_LDS_BYTES = 156 * 1024", "FH_LDS_BYTES = 160 * 1024"), ("edge.hip", "BH_RPT = 8;", "BH_RPT = 9;"),
+             ("edge.hip", "BH_HUB_CAP = 128;", "BH_HUB_CAP = 64;"), ("gemm_nt.hip", "TINY_MAX_TILES\")) : 256;", "TINY_MAX_TILES\")) : 255;"),
+             ("gemm_nt.hip", "WS_MIN_TILES\")) : 2;", "WS_MIN_TILES\")) : 3;"), ("gemm_nt.hip", "NT_MAX_PIECES = 16;", "NT_MAX_PIECES = 12;"),
+             ("gemm_nt.hip", "TINY_MAX_PIECES = 8;", "TINY_MAX_PIECES = 7;"), ("seg_tile.hpp", "SG_LDS_BYTES = 78 * 1024", "SG_LDS_BYTES = 80 * 1024")]
+    for name, old, new in moves:
+        work = tmp_path / "csrc"
+        if work.exists():
+            shutil.rmtree(work)
+        work.mkdir()
+        for f in REGIME_PINS:
+            shutil.copy(os.path.join(csrc, f), work / f)
+        text = (work / name).read_text()
+        assert text.count(old) >= 1, (name, old)
+        (work / name).write_text(text.replace(old, new))
+        assert regime_pin_failures(str(work)) != [], (name, old, new)
+
+
+def test_regime_restatement_agrees_with_what_the_gpu_tests_assert():
+    """The restated predicates (256 CUs, the MI355X the existing GPU tests were written against) give the regimes those tests
+    assert from the profile classes or the segment check."""
+    from tests import regimes as R
+    cus = 256
+    # tests/test_gpu_mse_tail.py: the attached tail at 118v2 x 128, 118v2 x 16, 14 x 37, 14 x 300 (H 129, L 4); not at 118v2 x 2048
+    for seg, B in ((118, 128), (118, 16), (14, 37), (14, 300), (118, 32), (118, 8)):
+        assert R.mse_tail_available(True, seg * B, 129, 4, 2, seg, cus), (seg, B)
+        r = R.model_regime(seg * B, seg, 129, 4, 3, 2, True, cus)
+        assert r["seg_front"] and r["ea_seg_bwd"] and r["slh"] and "front_seg_fwd+pack" in r["must"], (seg, B)
+    assert not R.mse_tail_available(True, 118 * 2048, 129, 4, 2, 118, cus)
+    r = R.model_regime(118 * 2048, 118, 129, 4, 3, 2, True, cus)
+    assert not r["ea_seg_fwd"] and not r["seg_front"] and "edge_bwd" in r["must"] and "ea_seg_bwd+out+mse" in r["must_not"]
+    # test_fused_lds_hops_match_generic_path: 118 x 6 and 14 x 37 take the graph-resident kernels and the fused LDS hops
+    for seg, B in ((118, 6), (14, 37)):
+        assert R.ea_seg_fit(seg, seg * B, 2, 132, False, cus) and R.hop_kernel(seg, seg * B, 3) == "fused"
+    # the big-graph tests: 2,500- and 6,470-node grids take big_graph_hops_kernel, never the two-tile one
+    for seg in (2500, 6470):
+        assert R.hop_kernel(seg, seg * 4, 6) == "big" and not R.fused_hops_fit(seg)
+    # test_train_mode_matches_oracle_fed_the_exported_masks / test_wide_k6_large_batch_streaming_gemm_vs_oracle: K = 6 at 1,152
+    # 118-bus graphs = 135,936 rows: the 7-term TAGConv products stream over whole rounds, the stationary kernel takes the tail
+    plan = R.gemm_nt_plan(118 * 1152, 129, 129, 7, cus)
+    assert plan["kind"] == "ws+stationary" and plan["rows_ws"] == 2 * cus * 8 * 32, plan
+    # the thresholds of the issue's table at 256 CUs
+    first_out = {(seg, H): R.first_graph_count(lambda b: not R.ea_seg_fit(seg, seg * b, 2, R.ld_of(H), False, cus))
+                 for seg, H in ((118, 129), (14, 129), (118, 32))}
+    assert first_out == {(118, 129): 257, (14, 129): 2305, (118, 32): 1025}
+    assert max(s for s in range(1, 5000) if R.fused_hops_fit(s)) == 1996
+    assert max(s for s in range(1, 20000) if R.big_hops_fit(s, s)) == 8192
+    # big_graph_hops_kernel's staging: nb_cap is what decides; its `ne < 65536` clause cannot (nb_cap <= 62,776 for seg >= 1,997)
+    assert max(R.big_hops_nb_cap(s, s, 1 << 40) for s in range(1997, 8193)) == 62776
+    assert R.big_hops_nb_cap(2000, 4000, 1 << 40) == 62744 and R.big_hops_nb_cap(8000, 16000, 54000) == 8744
+    assert R.big_hops_staged(2000, 4000, 2 * 62740, 62740) and not R.big_hops_staged(2000, 4000, 2 * 62741, 62741)
+    assert R.big_hops_staged(8192, 16384, 14000, 7000) and not R.big_hops_staged(8192, 16384, 2 * 24576, 24576)
+    assert [R.gemm_nt_plan(M, 129, 129, 4, cus)["kind"] for M in (8192, 8193, 8224)] == ["tiny", "stationary", "stationary"]
+    assert [R.gemm_nt_plan(M, 129, 129, 5, cus)["kind"] for M in (131040, 131041, 131072, 131073, 196641)] == \
+        ["stationary", "ws", "ws", "ws+stationary", "ws+stationary"]
+    assert [R.gemm_nt_plan(1000, ci, co, K + 1, cus)["kind"] for ci, co, K in ((512, 512, 3), (512, 512, 7), (300, 129, 7))] == \
+        ["wide", "multi", "multi"]
+    assert [R.gemm_nt_plan(M, 129, 129, 2, cus)["CT"] for M in (65504, 65505)] == [1, 2]
