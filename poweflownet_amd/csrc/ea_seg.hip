@@ -925,7 +925,7 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                 float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
                 float q1 = 0.f, q0 = 0.f;
                 if (a.mse.maskf) {
-                    // Masked_L2_loss: masked_l2_grad_kernel's expressions (model.hip) on the batch-wide counts
+                    // Masked_L2_loss: masked_l2_grad_kernel's expressions (util_kernels.hip) on the batch-wide counts
                     const int* cw = reinterpret_cast<const int*>(l.part) + 768;
                     int c1 = 0, c0 = 0;
 #pragma unroll
@@ -1081,7 +1081,7 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
     }
     if (LOSS && wave == 0 && sc.q == max(0, sc.nq - 2)) {
         // the loss: the last of the partial-owning blocks to get here sums the partials in BLOCK order (deterministic).  Same
-        // hand-off as mse_kernel (model.hip): write-through partial, drained, then the ticket; agent-scope loads on the consumer
+        // hand-off as mse_kernel (util_kernels.hip): write-through partial, drained, then the ticket; agent-scope loads on the consumer
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "the loss hand-off relies on gfx950 semantics (sc1 write-through stores drained by s_waitcnt vmcnt(0))"
 #endif

@@ -644,7 +644,7 @@ int launch_front_pq(int n, int h, int ldw1, const float* x0, const float* w1, co
 }
 
 // ---- the backward front beyond the latency regime when mask_embd's hidden layer was NOT stored (FrontFwdArgs::me_h null in a
-// training forward: model.hip front_recomputes_meh).  me_h is four fmas per element away from the 16-byte mask row, and dh, which
+// training forward: model.hip Route::meh_recompute).  me_h is four fmas per element away from the 16-byte mask row, and dh, which
 // the block kernel above writes, has ONE reader: the weight-gradient pair (dh, maskf).  So this kernel recomputes me_h (the
 // forward's chain: the same gate bits), forms g0 and dh as above, and accumulates mask_embd's four weight gradients itself
 //     dWb[f][u] += g0[row][f] me_h[row][u]   dbb[f] += g0[row][f]   dWa[u][f] += dh[row][u] mask[row][f]   dba[u] += dh[row][u]

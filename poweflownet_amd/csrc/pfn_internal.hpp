@@ -578,6 +578,11 @@ int launch_front_pq(int n, int h, int ldw1, const float* x0, const float* w1, co
 // ------------------------------------------------------------------------------------ small kernels
 int launch_pad_rows(const float* src, int64_t ld_src, float* dst, int64_t ld_dst, int64_t rows, int64_t f,
                     hipStream_t s);
+// the ReLU gate export of pfn_mpn_export_gates (util_kernels.hip): the edge stage of one EdgeAggregation layer from its saved
+// P | Q, and the rows of a layer output (cm: chunk-major, Act::out_cm) or of mask_embd's hidden layer
+int launch_export_edge_gates(const GraphView& g, const float* P, const float* Q, const float* ea, const float* w1, int ld, int h, int fi,
+                             int fe, uint8_t* out, hipStream_t s);
+int launch_export_row_gates(int64_t n, int h, int ld, const float* y, int cm, uint8_t* out, hipStream_t s);
 
 // 16-byte WRITE-THROUGH store of a kernel OUTPUT (global memory only; sc1).  A chain kernel's plain stores leave its output dirty
 // in the XCD's L2, and the kernel boundary then waits for the write-back (MI355X_MICROARCH.md "boundary"); written through, the

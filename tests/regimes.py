@@ -1,4 +1,5 @@
-"""The dispatch predicates of the forward and backward passes, restated in Python (a plain helper module for the tests).
+"""The dispatch predicates of the forward and backward passes, restated in Python (a plain helper module for the tests).  The
+whole-model ones are the lines of csrc/model.hip make_route (one Route per entry point), the rest live next to their kernels.
 
 Every constant and formula here is a copy of one in csrc/; tests/test_host.py::test_regime_constants_are_still_in_the_source checks
 that each of them is still written there, literally, so a threshold that moves fails on the CPU first.  The GPU tests
@@ -181,7 +182,7 @@ def big_hops_staged(seg, n, e_stored, ne):
 
 
 def hop_kernel(seg, n, K):
-    """Which hop kernel a TAGConv over a graph with segment hint `seg` takes (model.hip tag_forward): 'fused' (two-tile / row
+    """Which hop kernel a TAGConv over a graph with segment hint `seg` takes (model.hip hop_kind): 'fused' (two-tile / row
     kernels, profile class fused_hops_*), 'big' (big_graph_hops_kernel, ALSO profiled as fused_hops_*), 'generic' (K hop_norm)."""
     if K == 0:
         return None
@@ -289,6 +290,38 @@ def gemm_nt_plan(M, cin, cout, nterm, cus):
 
 
 # ------------------------------------------------------------------------------------------ a whole MaskEmbdMultiMPN step
+def route(n, seg, H, L, K, fe, train, cus):
+    """model.hip make_route for MaskEmbdMultiMPN(4, fe, 4, H, L, K) without the diagnostic switches: the Route's fields by name."""
+    ld = ld_of(H)
+    fused_front = front_fused_ok(4, H)
+    r = dict(fused_front=fused_front, ea_seg_fwd=ea_seg_fit(seg, n, fe, ld, False, cus), ea_seg_bwd=ea_seg_fit(seg, n, fe, ld, True, cus),
+             mask0=ea_saves_mask(train, n, fe, ld, seg, fused_front, 0, cus), mask1=ea_saves_mask(train, n, fe, ld, seg, fused_front, 1, cus),
+             l0_fly=first_layer_fly(train, n, H, L, fe, seg, cus), seg_front=uses_seg_front(train, n, H, L, fe, seg, cus),
+             lin_out4=lin_out4_ok(H, 4, 4, n), mse_tail=mse_tail_ok(train, n, H, L, fe, seg, cus), hops=hop_kernel(seg, n, K))
+    # (front_recomputes_meh: me_h holds front_bwd_wg_kernel's partial sums -- a bound on the batch that is not restated; the check
+    #  only needs that it is never set without l0_fly)
+    r["meh_recompute"] = train and r["l0_fly"]
+    r["masked_tail"] = r["mse_tail"] and r["seg_front"]
+    r["big_cm"] = n if (K > 0 and not fused_hops_fit(seg) and big_hops_fit(seg, n)) else 0
+    r["slh_fwd"] = r["slh_bwd"] = not r["big_cm"] and seg_lin_hops_fit(seg, n, ld, H, K, cus)
+    return r
+
+
+def route_contradictions(r):
+    """The check make_route ends with: what forward, backward, the loss tails and the gate export take for granted of each other.
+    Returns the names of the violated implications (empty: sound)."""
+    checks = {
+        "ea_seg_bwd -> ea_seg_fwd": not r["ea_seg_bwd"] or r["ea_seg_fwd"],
+        "seg_front -> layer 0 saves no masks": not r["seg_front"] or not r["mask0"],
+        "l0_fly -> fused_front and not seg_front": not r["l0_fly"] or (r["fused_front"] and not r["seg_front"]),
+        "meh_recompute -> l0_fly": not r["meh_recompute"] or r["l0_fly"],
+        "mse_tail -> ea_seg_fwd, ea_seg_bwd, lin_out4": not r["mse_tail"] or (r["ea_seg_fwd"] and r["ea_seg_bwd"] and r["lin_out4"]),
+        "slh -> fused hops, row-major": not (r["slh_fwd"] or r["slh_bwd"]) or (r["hops"] == "fused" and not r["big_cm"]),
+        "big_cm -> big hops": not r["big_cm"] or r["hops"] == "big",
+    }
+    return [name for name, ok in checks.items() if not ok]
+
+
 def model_regime(n, seg, H, L, K, fe, train, cus):
     """The regime of every stage of MaskEmbdMultiMPN(4, fe, 4, H, L, K) on n rows of graphs of `seg` nodes, and the profile classes
     that must and must not appear in its forward (+ backward, when `train`).  `train` is the model's need_backward: a forward under

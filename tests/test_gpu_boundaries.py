@@ -144,11 +144,11 @@ def test_graph_resident_kernels_at_every_graph_size_edge(seg, p):
 # ------------------------------------------------------------------------------------------ batch count at the latency-regime bound
 @pytest.mark.parametrize("seg,H,partial", [(118, 129, False), (14, 129, True), (118, 32, False)])
 def test_latency_regime_batch_bound_with_attached_losses(seg, H, partial):
-    """ea_seg_fit / seg_lin_hops_fit / front_seg_fit / mse_tail_ok: ceil(n / rows_pb) * ny <= 4 * CUs (and <= 1024 row blocks in
+    """ea_seg_fit / seg_lin_hops_fit / front_seg_fit / Route::mse_tail: ceil(n / rows_pb) * ny <= 4 * CUs (and <= 1024 row blocks in
     backward).  The largest graph count inside the bound and the first one past it (and, for 14-bus grids, one graph fewer, whose
     last workgroup is partial) -- 118-bus and 14-bus at H = 129 (ny = 4, the seg_lin_hops layers), 118-bus at H = 32 (ny = 1: the
     forward bound and the backward's 1,024 blocks coincide).  The H = 129 pairs stay within 32,768 rows, so front_seg_fwd and the
-    graph-resident backward switch off together there: model.hip:590's invariant (front_seg_fwd never runs where layer 0's backward
+    graph-resident backward switch off together there: the check that ends model.hip make_route (front_seg_fwd never runs where layer 0's backward
     would read ReLU masks).  The H = 32 pair is above 32,768 rows: no front_seg_fwd and no loss tail on either side.  Training
     with dropout 0.2 against the oracle fed the exported masks; the attached MSELoss and Masked_L2_loss tails bit for bit equal to
     the three-call path inside, cleanly absent outside."""
@@ -187,7 +187,7 @@ def test_latency_regime_batch_bound_with_attached_losses(seg, H, partial):
 # ------------------------------------------------------------------------------------------ row-per-wave front / lin_out4
 @pytest.mark.parametrize("train", [True, False])
 def test_row_per_wave_front_at_its_row_bound(train):
-    """front_row_per_wave / front_latency_regime / lin_out4_ok / first_layer_fly (front.hip, model.hip): n <= wave_max_rows() =
+    """front_row_per_wave / front_latency_regime / lin_out4_ok / Route::l0_fly (front.hip, model.hip make_route): n <= wave_max_rows() =
     32,768 rows.  16-node grids: 32,768 rows exactly (front_seg_fwd, the fused front + first edge stage) and one graph more
     (the block front; in inference layer 0's P | Q formed on the fly in the edge walk), in training and in inference."""
     seg = 16

@@ -1006,7 +1006,7 @@ torch.save(res, sys.argv[1])
 def test_first_layer_pq_from_x0_is_bit_identical_to_stored_pq(tmp_path):
     """Beyond the latency regime (> 32,768 rows) the first EdgeAggregation layer's P | Q rows are not written when nothing reads
     them from memory (inference; training whose backward walks read saved ReLU masks): the edge walk forms them from the 16-byte
-    x0 rows with the front's own fma chains (edge.hip FLY, model.hip first_layer_fly), and the inference front, left with 32
+    x0 rows with the front's own fma chains (edge.hip FLY, model.hip Route::l0_fly), and the inference front, left with 32
     bytes of output per row, runs one row per thread with the block kernel's summation order (front.hip).  Same operands in the
     same order -> the SAME BITS as the path that stores and gathers the rows (PFN_NO_L0_FLY=1) and as the block front
     (PFN_FRONT_NO_THREAD_ROWS=1; switches are read once per process -> child processes): outputs, every gradient, and the
@@ -1425,7 +1425,7 @@ def test_wide_json_on_case6470rte_vs_oracle():
 
 
 def test_mse_loss_handoff_stress():
-    """pfn_mse_loss's last-arriver hand-off (write-through partial, drained, relaxed ticket; csrc/model.hip mse_kernel) under
+    """pfn_mse_loss's last-arriver hand-off (write-through partial, drained, relaxed ticket; csrc/util_kernels.hip mse_kernel) under
     load: grids from 1 to 256 blocks, back to back with other work in flight on a second stream, 300 launches each -- every
     launch must return bit for bit the value of the first (a stale partial would change the sum) and the float64 mean to 1e-6."""
     from poweflownet_amd import _lib as L

@@ -223,16 +223,23 @@ REGIME_PINS = {
                    "return !off && ld / 4 <= 64 && front_latency_regime(h, n) && ea_seg_fit(seg, n, fe, ld, false);"),
     "seg_lin_hops.hip": ("const long per_cu = 4L;   // (ea_seg_fit's bound)", "fused_hops_fit(seg, ld, n) &&",
                          "slh_plan(seg, n, ld, nterm, p) && (long)p.nblocks * p.ny <= per_cu * device_cus();"),
-    "model.hip": ("const bool generic_fwd = !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) || (fused_front && i == 0);",
-                  "return c.need_backward != 0 && lo.fe == 2 && generic_fwd && !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true);",
-                  "return !off && fused_front && lo.nlayers > 1 && lo.fe == 2 && lo.f0 == 4 && !front_latency_regime(lo.h, lo.n) &&",
-                  "(c.need_backward == 0 || ea_saves_mask(c, lo, seg, fused_front, 0));",
-                  "return fused_front && ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) && !first_layer_fly(c, lo, seg, fused_front) && lo.nlayers > 1 &&",
-                  "front_seg_fit(seg, lo.n, lo.h, lo.fe) && !(c.need_backward && lo.fe == 2 && !ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true));",
-                  "lin_out4_ok(lo.h, lo.fo, lo.ldo, lo.n) && back_fused_ok() && ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false) &&",
-                  "ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true) && lo.ld / 4 <= 34;",
-                  "return (mse_tail_ok(*c, lo, (int)seg_nodes) && uses_seg_front(*c, lo, (int)seg_nodes)) ? 1 : 0;",
-                  "} else if (K > 0 && fused_hops_fit(seg, ldx, g.n)) {", "} else if (K > 0 && big_hops_fit(seg, g.n, g.e_stored)) {"),
+    # (make_route: every whole-model decision, once per entry point; hop_kind: the TAGConv hop kernel)
+    "model.hip": ("r.ea_seg_fwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false);", "r.ea_seg_bwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true);",
+                  "r.fused_front = front_fused_ok(lo.f0, lo.h);",
+                  "const bool generic_fwd = !r.ea_seg_fwd || (r.fused_front && i == 0);",
+                  "r.mask[i] = train && lo.fe == 2 && generic_fwd && !r.ea_seg_bwd;",
+                  "r.l0_fly = !no_fly && r.fused_front && lo.nlayers > 1 && lo.fe == 2 && lo.f0 == 4 && !front_latency_regime(lo.h, lo.n) &&",
+                  "(!train || r.mask[0]);",
+                  "r.seg_front = r.fused_front && r.ea_seg_fwd && !r.l0_fly && lo.nlayers > 1 &&",
+                  "front_seg_fit(seg, lo.n, lo.h, lo.fe) && !(train && lo.fe == 2 && !r.ea_seg_bwd);",
+                  "const bool train = c.need_backward != 0, out4 = lin_out4_ok(lo.h, lo.fo, lo.ldo, lo.n);",
+                  "r.mse_tail = !no_tail && train && lo.n > 0 && lo.nlayers > 1 && lo.fe == 2 && lo.fo == 4 && lo.ldo == 4 &&",
+                  "out4 && r.back_fused && r.ea_seg_fwd && r.ea_seg_bwd && lo.ld / 4 <= 34;",
+                  "r.masked_tail = r.mse_tail && r.seg_front;", "return r.masked_tail ? 1 : 0;",
+                  "if (K > 0 && fused_hops_fit(seg, ld, n)) return HOPS_FUSED;", "if (K > 0 && big_hops_fit(seg, n, e_stored)) return HOPS_BIG;",
+                  "r.hops = hop_kind(seg, lo.ld, lo.n, e_stored, lo.K);",
+                  "r.slh_fwd = !r.big_cm && seg_lin_hops_fit(seg, lo.n, lo.ld, lo.h, lo.h, lo.K, 1);",
+                  "r.slh_bwd = !r.big_cm && seg_lin_hops_fit(seg, lo.n, lo.ld, lo.h, lo.h, lo.K, 2);"),
     # the row-per-wave front and the last layer
     "front.hip": ("static int wave_max_rows() { return 32768; }",
                   "return !off && fo >= 1 && fo <= 4 && ldo == 4 && ld_of(h) / 4 <= 64 && n <= wave_max_rows();",
@@ -299,6 +306,37 @@ def test_regime_constants_are_still_in_the_source():
     assert (R.RH_THREADS, R.RH_IPT, R.ER_THREADS, R.ER_IPT) == (512, 8, 512, 8)
     assert (R.NT_THREADS, R.NCH, R.KP, R.NT_MAX_PIECES, R.NT_LDS_BYTES, R.TINY_MAX_PIECES, R.TINY_MAX_TILES, R.WS_MIN_ROUNDS) == \
         (512, 17, 136, 16, 160 * 1024, 8, 256, 2)
+
+
+def test_route_invariants_hold_over_a_sweep_of_models_and_batches():
+    """csrc/model.hip make_route ends with a check of what the passes take for granted of each other (the graph-resident backward
+    reads what the graph-resident forward filled, front_seg_fwd_kernel never runs where layer 0's backward reads ReLU masks, ...) and
+    refuses the call if it fails.  Each implication follows from the predicates: swept here over their restatement -- CU counts,
+    hidden widths, graph sizes and graph counts on both sides of every threshold, training and inference -- so the check can never
+    refuse a valid call, and a predicate edited into contradiction with another fails on the CPU."""
+    import re
+    from tests import regimes as R
+    src = re.sub(r"\s+", " ", open(os.path.join(ROOT, "poweflownet_amd", "csrc", "model.hip")).read())
+    for clause in ("(!r.ea_seg_bwd || r.ea_seg_fwd)", "(!r.seg_front || !r.mask[0])", "(!r.l0_fly || (r.fused_front && !r.seg_front))",
+                   "(!r.meh_recompute || r.l0_fly)", "(!r.mse_tail || (r.ea_seg_fwd && r.ea_seg_bwd && out4))",
+                   "(!(r.slh_fwd || r.slh_bwd) || (r.hops == HOPS_FUSED && !r.big_cm))", "(!r.big_cm || r.hops == HOPS_BIG)"):
+        assert clause in src, clause
+    count = 0
+    for cus in (32, 64, 256, 304):
+        for H in (8, 16, 64, 128, 129, 136, 256, 257, 512):
+            for seg in (1, 2, 14, 30, 118, 127, 128, 129, 300, 1023, 1024, 1996, 1997, 2500, 6470, 8192, 8193):
+                for B in (1, 2, 8, 9, 37, 128, 277, 278, 1024, 2048, 2171, 33000):
+                    for train in (False, True):
+                        for L, K in ((2, 1), (4, 3), (4, 6), (2, 6)):
+                            r = R.route(seg * B, seg, H, L, K, 2, train, cus)
+                            assert R.route_contradictions(r) == [], (cus, H, seg, B, train, L, K, r)
+                            count += 1
+    assert count == 4 * 9 * 17 * 12 * 2 * 4
+    # the check itself: a route with one decision flipped is refused
+    r = R.route(118 * 128, 118, 129, 4, 3, 2, True, 256)
+    assert r["mse_tail"] and r["seg_front"] and r["slh_fwd"] and R.route_contradictions(r) == []
+    for key, value in (("ea_seg_fwd", False), ("mask0", True), ("l0_fly", True), ("hops", "generic"), ("big_cm", 118 * 128)):
+        assert R.route_contradictions(dict(r, **{key: value})) != [], key
 
 
 def test_regime_pins_fail_on_a_moved_threshold(tmp_path):

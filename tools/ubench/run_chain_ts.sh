@@ -4,7 +4,7 @@ export ASYNC_CHECK=${GRAFT_REPO_ROOT:-/root/repo}/tools/check_async_fragments.py
 R=$GRAFT_REPO_ROOT
 export PFN_SEG_CHAIN=1
 d=/tmp/exp_chain_ts; rm -rf $d; mkdir -p $d; cp -r $R/poweflownet_amd $R/bench.py $R/oracle $R/include $R/BASELINE.json $d/; bash $R/tools/ubench/apply_experiments.sh $d/poweflownet_amd/csrc
-( cd $d/poweflownet_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -DCH_EXP_TS $CH_DEFS -c seg_chain.hip -o seg_chain.o && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC graph.o edge.o gemm.o gemm_nt.o front.o ea_seg.o seg_lin_hops.o seg_chain.o model.o physics.o prof.o -o libpfn_hip.so ) || exit 1
+( cd $d/poweflownet_amd/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -w -DCH_EXP_TS $CH_DEFS -c seg_chain.hip -o seg_chain.o && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC graph.o edge.o gemm.o gemm_nt.o front.o ea_seg.o seg_lin_hops.o seg_chain.o model.o util_kernels.o physics.o prof.o -o libpfn_hip.so ) || exit 1
 cd $d && python - <<'PY'
 import ctypes as C, torch, numpy as np, sys
 sys.path.insert(0, ".")
