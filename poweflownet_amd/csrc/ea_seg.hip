@@ -97,10 +97,10 @@ __device__ __forceinline__ void seg_rem_dots(int t, const float* __restrict__ A,
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int g = min(g0 + PARTS * j, G - 1);
-                const float4 v = sg_ld4(arow + 4 * min(g, gmax));
+                const float4 v = ld4(arow + 4 * min(g, gmax));
                 xa[j] = g0 + PARTS * j < G ? v : make_float4(0.f, 0.f, 0.f, 0.f);   // (past G: zeroed by a select, no divergent branch)
-                w1[j] = sg_ld4(Bp1 + roff + (size_t)g * 16);
-                if (TWO) w2[j] = sg_ld4(Bp2 + roff + (size_t)g * 16);
+                w1[j] = ld4(Bp1 + roff + (size_t)g * 16);
+                if (TWO) w2[j] = ld4(Bp2 + roff + (size_t)g * 16);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
@@ -110,14 +110,14 @@ __device__ __forceinline__ void seg_rem_dots(int t, const float* __restrict__ A,
         }
     } else {
         for (int g = part; g < G; g += PARTS) {
-            const float4 xa = sg_ld4(arow + 4 * min(g, gmax));
+            const float4 xa = ld4(arow + 4 * min(g, gmax));
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 if (c < nreal) {
-                    const float4 w = sg_ld4(Bp1 + roff + (size_t)g * 16 + c * 4);
+                    const float4 w = ld4(Bp1 + roff + (size_t)g * 16 + c * 4);
                     v1[c] = fmaf(xa.w, w.w, fmaf(xa.z, w.z, fmaf(xa.y, w.y, fmaf(xa.x, w.x, v1[c]))));
                     if (TWO) {
-                        const float4 w2 = sg_ld4(Bp2 + roff + (size_t)g * 16 + c * 4);
+                        const float4 w2 = ld4(Bp2 + roff + (size_t)g * 16 + c * 4);
                         v2[c] = fmaf(xa.w, w2.w, fmaf(xa.z, w2.z, fmaf(xa.y, w2.y, fmaf(xa.x, w2.x, v2[c]))));
                     }
                 }
@@ -236,7 +236,7 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
     if (async_a) {
         seg_drain_visible();
         if (mfma_on) seg_load_a_async(ta, a.x, a.ldx, r0 + 32 * wave, r0 + rows - 1, lane);
-        seg_lds_barrier();
+        lds_barrier();
         if (mfma_on) {
             const f32x16 accp = seg_mma_async(ta, l.B0, lane);
             seg_store_tile(accp, sc.q, a.b1, a.h, l.P, 32 * wave, lane);
@@ -244,7 +244,7 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
             seg_store_tile(accq, sc.q, nullptr, a.h, l.Q, 32 * wave, lane);
         }
     } else {
-        seg_dma_wait();
+        vmem_drain();
         __syncthreads();
         if (mfma_on) {
             const f32x16 accp = seg_mma(ta, l.B0, K8, lane);
@@ -258,11 +258,11 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
     for (int it = threadIdx.x; it < rows * sc.cw; it += SG_THREADS) {
         const int lr = it / sc.cw, lc = it - lr * sc.cw;
         const int tc = seg_tcol(sc, lc), gc = seg_gcol(sc, lc);
-        const float4 p4 = sg_ld4(l.P + (size_t)lr * SG_TW + tc);
+        const float4 p4 = ld4(l.P + (size_t)lr * SG_TW + tc);
         const size_t o = (size_t)(r0 + lr) * a.ld + gc;
-        sg_st4_wt(a.P + o, p4);
-        sg_st4_wt(a.Q + o, sg_ld4(l.Q + (size_t)lr * SG_TW + tc));
-        const float4 w0 = sg_ld4(l.we + tc), w1 = sg_ld4(l.we + SG_TW + tc);
+        st4_wt(a.P + o, p4);
+        st4_wt(a.Q + o, ld4(l.Q + (size_t)lr * SG_TW + tc));
+        const float4 w0 = ld4(l.we + tc), w1 = ld4(l.we + SG_TW + tc);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         const int beg = cin.rp[lr], end = cin.rp[lr + 1];
         if (cin.in_lds) {   // four slots per trip (slots past the row's end re-read its last edge and are not added): the walk is a
@@ -278,13 +278,13 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                 }
                 float4 q_[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) q_[u] = sg_ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
+                for (int u = 0; u < 4; ++u) q_[u] = ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    float4 v = sg_add4(p4, q_[u]);
-                    v = sg_fma4(a_[u].x, w0, v);
-                    v = sg_fma4(a_[u].y, w1, v);
-                    const float4 r = sg_add4(acc, sg_relu4(v));
+                    float4 v = add4(p4, q_[u]);
+                    v = fma4(a_[u].x, w0, v);
+                    v = fma4(a_[u].y, w1, v);
+                    const float4 r = add4(acc, relu4(v));
                     const bool k = p + u < end;
                     acc.x = k ? r.x : acc.x;
                     acc.y = k ? r.y : acc.y;
@@ -297,13 +297,13 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                 int ls;
                 float2 a2;
                 csr_slot(cin, p, r0, nbr, a.ea_in, ls, a2);
-                float4 v = sg_add4(p4, sg_ld4(l.Q + (size_t)ls * SG_TW + tc));
-                v = sg_fma4(a2.x, w0, v);
-                v = sg_fma4(a2.y, w1, v);
-                acc = sg_add4(acc, sg_relu4(v));
+                float4 v = add4(p4, ld4(l.Q + (size_t)ls * SG_TW + tc));
+                v = fma4(a2.x, w0, v);
+                v = fma4(a2.y, w1, v);
+                acc = add4(acc, relu4(v));
             }
         }
-        sg_st4_wt(a.S + o, acc);
+        st4_wt(a.S + o, acc);
     }
 }
 
@@ -321,16 +321,6 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
 //   * the walk over the incoming edges runs on the tiles exactly as in ea_seg_fwd_kernel (edge attributes through the edge ids:
 //     the slot-ordered copy is written by the pack blocks of this very launch).
 // The weight re-layout ("pack") blocks of the forward pass ride behind the graph blocks, as they did behind the front's.
-__device__ __forceinline__ float4 sg_wave_sum4(float4 v) {   // (front.hip wave_sum4: fixed butterfly, every lane ends with the same sum)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.x += __shfl_xor(v.x, off);
-        v.y += __shfl_xor(v.y, off);
-        v.z += __shfl_xor(v.z, off);
-        v.w += __shfl_xor(v.w, off);
-    }
-    return v;
-}
 __global__ __launch_bounds__(SG_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, int nseg_y, int pack_bx, int rows_pb, int trows, int cap,
                           int e_stored, const int* __restrict__ rowptr, const int* __restrict__ nbr, const int* __restrict__ eid,
@@ -401,15 +391,15 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
     float4* s_tab = s_me + 3 * h + 1;                            // [16]: the residual term of the 16 binary mask patterns
     if (tid < 2) s_cnt[tid] = 0;
     if (tid < h) {
-        const float4 a4 = sg_ld4(f.wa + (size_t)tid * 4);
+        const float4 a4 = ld4(f.wa + (size_t)tid * 4);
         const float b0 = f.ba[tid], w0_ = f.wb[tid], w1_ = f.wb[h + tid], w2_ = f.wb[2 * h + tid], w3_ = f.wb[3 * h + tid];
         s_me[3 * tid] = a4;
         s_me[3 * tid + 1] = make_float4(b0, w0_, w1_, w2_);
         s_me[3 * tid + 2] = make_float4(w3_, 0.f, 0.f, 0.f);
     }
-    seg_lds_barrier();
+    lds_barrier();
     // ---- x0 = x + bb + Wb relu(Wa mask + ba): FOUR THREADS PER ROW.  The chunk sums a[c] (four hidden units each, an fma chain
-    // from zero) are added in the order of the row-per-wave kernel's xor butterfly (front.hip wave_sum4, lane 0's tree:
+    // from zero) are added in the order of the row-per-wave kernel's xor butterfly (wave_sum4, lane 0's tree:
     // s[c] = a[c] + a[c + 32]; t = s[c] + s[c + 16]; u = t[c] + t[c + 8]; v = u[c] + u[c + 4]; w = v[c] + v[c + 2]; w[0] + w[1]), so
     // x0 carries the bits that kernel stores: thread p of a row forms v[p], two quad shuffles finish the tree.  (As a butterfly
     // per row in every one of a graph's four blocks the LDS crossbar was the whole kernel: 24 ds_bpermute per row.)
@@ -447,19 +437,19 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
 #pragma unroll
                 for (int c3 = 0; c3 < 2; ++c3) {
                     const int c = pq + 4 * c2 + 8 * c3;
-                    const float4 sa = sg_add4(chunk_sum(c), chunk_sum(c + 32)), sb = sg_add4(chunk_sum(c + 16), chunk_sum(c + 48));
-                    const float4 t = sg_add4(sa, sb);
-                    if (c3 == 0) t0 = t; else tt = sg_add4(t0, t);
+                    const float4 sa = add4(chunk_sum(c), chunk_sum(c + 32)), sb = add4(chunk_sum(c + 16), chunk_sum(c + 48));
+                    const float4 t = add4(sa, sb);
+                    if (c3 == 0) t0 = t; else tt = add4(t0, t);
                 }
-                if (c2 == 0) u0 = tt; else vp = sg_add4(u0, tt);
+                if (c2 == 0) u0 = tt; else vp = add4(u0, tt);
             }
             // w[p & 1] = v[p & 1] + v[(p & 1) + 2] (partner: lane ^ 2), then w[0] + w[1] (partner: lane ^ 1): lower index first
             float4 vo;
             vo.x = __shfl_xor(vp.x, 2); vo.y = __shfl_xor(vp.y, 2); vo.z = __shfl_xor(vp.z, 2); vo.w = __shfl_xor(vp.w, 2);
-            const float4 wp = (pq & 2) ? sg_add4(vo, vp) : sg_add4(vp, vo);
+            const float4 wp = (pq & 2) ? add4(vo, vp) : add4(vp, vo);
             float4 wo;
             wo.x = __shfl_xor(wp.x, 1); wo.y = __shfl_xor(wp.y, 1); wo.z = __shfl_xor(wp.z, 1); wo.w = __shfl_xor(wp.w, 1);
-            return (pq & 1) ? sg_add4(wo, wp) : sg_add4(wp, wo);
+            return (pq & 1) ? add4(wo, wp) : add4(wp, wo);
         };
         // the row's inputs are requested before the table is built
         const int lr = tid >> 2;
@@ -470,16 +460,16 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
             const int64_t* mp = static_cast<const int64_t*>(f.mask) + (size_t)row * 4;
             m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
         } else {
-            m = sg_ld4(static_cast<const float*>(f.mask) + (size_t)row * 4);
+            m = ld4(static_cast<const float*>(f.mask) + (size_t)row * 4);
         }
-        const float4 xi = sg_ld4(f.x + (size_t)row * 4);
+        const float4 xi = ld4(f.x + (size_t)row * 4);
         if (tid < 64) {   // pattern k = tid >> 2: bit j set = mask entry j is 1
             const int k = tid >> 2;
             const float4 mk = make_float4((k & 1) ? 1.f : 0.f, (k & 2) ? 1.f : 0.f, (k & 4) ? 1.f : 0.f, (k & 8) ? 1.f : 0.f);
             const float4 sk = x0_tree(mk);
             if (pq == 0) s_tab[k] = sk;
         }
-        seg_lds_barrier();
+        lds_barrier();
         const bool b0 = m.x == 0.f || m.x == 1.f, b1 = m.y == 0.f || m.y == 1.f, b2 = m.z == 0.f || m.z == 1.f, b3 = m.w == 0.f || m.w == 1.f;
         float4 s4;
         if (b0 && b1 && b2 && b3) s4 = s_tab[(m.x != 0.f ? 1 : 0) | (m.y != 0.f ? 2 : 0) | (m.z != 0.f ? 4 : 0) | (m.w != 0.f ? 8 : 0)];
@@ -490,8 +480,8 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
             s_x0[lr] = o;
             s_m[lr] = m;
             if (by == 0) {   // (one of the graph's blocks stores the 4-wide tensors)
-                sg_st4_wt(f.maskf + (size_t)row * 4, m);
-                sg_st4_wt(f.x0 + (size_t)row * 4, o);
+                st4_wt(f.maskf + (size_t)row * 4, m);
+                st4_wt(f.x0 + (size_t)row * 4, o);
             }
             // the block's mask census for a Masked_L2_loss riding in the backward pass (MseTail::counts): integer sums, any order
             c1 = (m.x != 0.f) + (m.y != 0.f) + (m.z != 0.f) + (m.w != 0.f);
@@ -508,7 +498,7 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
             }
         }
     }
-    seg_lds_barrier();
+    lds_barrier();
     if (f.mask_counts && by == 0 && tid < 2) f.mask_counts[2 * bx + tid] = s_cnt[tid];
     // ---- me_h, P | Q of the block's chunks: item = (row, chunk), the row-per-wave kernel's fma chains
     for (int it = tid; it < rows * sc.cw; it += SG_THREADS) {
@@ -530,20 +520,20 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
             pv[i] = pa_;
             qv[i] = qb;
         }
-        if (f.me_h) sg_st4_wt(f.me_h + (size_t)row * ld + gc, make_float4(hv[0], hv[1], hv[2], hv[3]));
+        if (f.me_h) st4_wt(f.me_h + (size_t)row * ld + gc, make_float4(hv[0], hv[1], hv[2], hv[3]));
         const float4 p4 = make_float4(pv[0], pv[1], pv[2], pv[3]), q4 = make_float4(qv[0], qv[1], qv[2], qv[3]);
-        sg_st4(l.P + (size_t)lr * SG_TW + tcw, p4);
-        sg_st4(l.Q + (size_t)lr * SG_TW + tcw, q4);
-        sg_st4_wt(f.P + (size_t)row * ld + gc, p4);
-        sg_st4_wt(f.Q + (size_t)row * ld + gc, q4);
+        st4(l.P + (size_t)lr * SG_TW + tcw, p4);
+        st4(l.Q + (size_t)lr * SG_TW + tcw, q4);
+        st4_wt(f.P + (size_t)row * ld + gc, p4);
+        st4_wt(f.Q + (size_t)row * ld + gc, q4);
     }
-    seg_lds_barrier();
+    lds_barrier();
     // ---- the walk (ea_seg_fwd_kernel's: four slots per trip, edge-id order)
     for (int it = tid; it < rows * sc.cw; it += SG_THREADS) {
         const int lr = it / sc.cw, lc = it - lr * sc.cw;
         const int tcw = seg_tcol(sc, lc), gc = seg_gcol(sc, lc);
-        const float4 p4 = sg_ld4(l.P + (size_t)lr * SG_TW + tcw);
-        const float4 w0 = sg_ld4(l.we + tcw), w1 = sg_ld4(l.we + SG_TW + tcw);
+        const float4 p4 = ld4(l.P + (size_t)lr * SG_TW + tcw);
+        const float4 w0 = ld4(l.we + tcw), w1 = ld4(l.we + SG_TW + tcw);
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         const int beg = cin.rp[lr], end = cin.rp[lr + 1];
         if (cin.in_lds) {
@@ -559,13 +549,13 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
                 }
                 float4 q_[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) q_[u] = sg_ld4(l.Q + (size_t)s_[u] * SG_TW + tcw);
+                for (int u = 0; u < 4; ++u) q_[u] = ld4(l.Q + (size_t)s_[u] * SG_TW + tcw);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    float4 v = sg_add4(p4, q_[u]);
-                    v = sg_fma4(a_[u].x, w0, v);
-                    v = sg_fma4(a_[u].y, w1, v);
-                    const float4 r = sg_add4(acc, sg_relu4(v));
+                    float4 v = add4(p4, q_[u]);
+                    v = fma4(a_[u].x, w0, v);
+                    v = fma4(a_[u].y, w1, v);
+                    const float4 r = add4(acc, relu4(v));
                     const bool k = p + u < end;
                     acc.x = k ? r.x : acc.x;
                     acc.y = k ? r.y : acc.y;
@@ -579,13 +569,13 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
                 int id = eid[cin.e0 + p];
                 id = id >= e_stored ? id - e_stored : id;
                 const float2 a2 = *reinterpret_cast<const float2*>(ea + (size_t)id * 2);
-                float4 v = sg_add4(p4, sg_ld4(l.Q + (size_t)ls * SG_TW + tcw));
-                v = sg_fma4(a2.x, w0, v);
-                v = sg_fma4(a2.y, w1, v);
-                acc = sg_add4(acc, sg_relu4(v));
+                float4 v = add4(p4, ld4(l.Q + (size_t)ls * SG_TW + tcw));
+                v = fma4(a2.x, w0, v);
+                v = fma4(a2.y, w1, v);
+                acc = add4(acc, relu4(v));
             }
         }
-        sg_st4_wt(S + (size_t)(r0 + lr) * ld + gc, acc);
+        st4_wt(S + (size_t)(r0 + lr) * ld + gc, acc);
     }
     if (pack_bx < 0) {
         const int per = -pack_bx, job = sb / per;
@@ -602,8 +592,8 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
 // cut it from 9.2 to ~4 us per launch.  Sums stay in slot (= edge id) order.
 __device__ __forceinline__ void seg_bwd_row(const SegLds& l, const SegCsr& cin, const SegCsr& cout, int lr, int tc, float4 w0,
                                             float4 w1, float4& accP, float4& accQ, float4& dwe0, float4& dwe1) {
-    const float4 p4 = sg_ld4(l.P + (size_t)lr * SG_TW + tc), q4 = sg_ld4(l.Q + (size_t)lr * SG_TW + tc);
-    const float4 g4 = sg_ld4(l.D + (size_t)lr * SG_TW + tc);
+    const float4 p4 = ld4(l.P + (size_t)lr * SG_TW + tc), q4 = ld4(l.Q + (size_t)lr * SG_TW + tc);
+    const float4 g4 = ld4(l.D + (size_t)lr * SG_TW + tc);
     accP = make_float4(0.f, 0.f, 0.f, 0.f);
     accQ = accP;
     const int b1 = cin.rp[lr], e1 = cin.rp[lr + 1], b2 = cout.rp[lr], e2 = cout.rp[lr + 1];
@@ -626,26 +616,26 @@ __device__ __forceinline__ void seg_bwd_row(const SegLds& l, const SegCsr& cin, 
         float4 qs[2], pd[2], gd[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            qs[u] = sg_ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
-            pd[u] = sg_ld4(l.P + (size_t)d_[u] * SG_TW + tc);
-            gd[u] = sg_ld4(l.D + (size_t)d_[u] * SG_TW + tc);
+            qs[u] = ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
+            pd[u] = ld4(l.P + (size_t)d_[u] * SG_TW + tc);
+            gd[u] = ld4(l.D + (size_t)d_[u] * SG_TW + tc);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            float4 v = sg_add4(p4, qs[u]);
-            v = sg_fma4(ai[u].x, w0, v);
-            v = sg_fma4(ai[u].y, w1, v);
+            float4 v = add4(p4, qs[u]);
+            v = fma4(ai[u].x, w0, v);
+            v = fma4(ai[u].y, w1, v);
             float4 dh;
             dh.x = (ki[u] && v.x > 0.f) ? g4.x : 0.f;
             dh.y = (ki[u] && v.y > 0.f) ? g4.y : 0.f;
             dh.z = (ki[u] && v.z > 0.f) ? g4.z : 0.f;
             dh.w = (ki[u] && v.w > 0.f) ? g4.w : 0.f;
-            accP = sg_add4(accP, dh);
-            dwe0 = sg_fma4(ai[u].x, dh, dwe0);
-            dwe1 = sg_fma4(ai[u].y, dh, dwe1);
-            float4 z = sg_add4(pd[u], q4);
-            z = sg_fma4(ao[u].x, w0, z);
-            z = sg_fma4(ao[u].y, w1, z);
+            accP = add4(accP, dh);
+            dwe0 = fma4(ai[u].x, dh, dwe0);
+            dwe1 = fma4(ai[u].y, dh, dwe1);
+            float4 z = add4(pd[u], q4);
+            z = fma4(ao[u].x, w0, z);
+            z = fma4(ao[u].y, w1, z);
             accQ.x += (ko[u] && z.x > 0.f) ? gd[u].x : 0.f;
             accQ.y += (ko[u] && z.y > 0.f) ? gd[u].y : 0.f;
             accQ.z += (ko[u] && z.z > 0.f) ? gd[u].z : 0.f;
@@ -656,7 +646,7 @@ __device__ __forceinline__ void seg_bwd_row(const SegLds& l, const SegCsr& cin, 
 // One direction only (the trailing chunk's second pass gives a row's two walks to two threads), four slots per trip
 __device__ __forceinline__ void seg_bwd_row_dst(const SegLds& l, const SegCsr& cin, int lr, int tc, float4 w0, float4 w1,
                                                 float4& accP, float4& dwe0, float4& dwe1) {
-    const float4 p4 = sg_ld4(l.P + (size_t)lr * SG_TW + tc), g4 = sg_ld4(l.D + (size_t)lr * SG_TW + tc);
+    const float4 p4 = ld4(l.P + (size_t)lr * SG_TW + tc), g4 = ld4(l.D + (size_t)lr * SG_TW + tc);
     accP = make_float4(0.f, 0.f, 0.f, 0.f);
     const int beg = cin.rp[lr], end = cin.rp[lr + 1], last = end - 1;
     for (int p = beg; p < end; p += 4) {
@@ -670,27 +660,27 @@ __device__ __forceinline__ void seg_bwd_row_dst(const SegLds& l, const SegCsr& c
         }
         float4 qs[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) qs[u] = sg_ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
+        for (int u = 0; u < 4; ++u) qs[u] = ld4(l.Q + (size_t)s_[u] * SG_TW + tc);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            float4 v = sg_add4(p4, qs[u]);
-            v = sg_fma4(ai[u].x, w0, v);
-            v = sg_fma4(ai[u].y, w1, v);
+            float4 v = add4(p4, qs[u]);
+            v = fma4(ai[u].x, w0, v);
+            v = fma4(ai[u].y, w1, v);
             const bool k = p + u < end;
             float4 dh;
             dh.x = (k && v.x > 0.f) ? g4.x : 0.f;
             dh.y = (k && v.y > 0.f) ? g4.y : 0.f;
             dh.z = (k && v.z > 0.f) ? g4.z : 0.f;
             dh.w = (k && v.w > 0.f) ? g4.w : 0.f;
-            accP = sg_add4(accP, dh);
-            dwe0 = sg_fma4(ai[u].x, dh, dwe0);
-            dwe1 = sg_fma4(ai[u].y, dh, dwe1);
+            accP = add4(accP, dh);
+            dwe0 = fma4(ai[u].x, dh, dwe0);
+            dwe1 = fma4(ai[u].y, dh, dwe1);
         }
     }
 }
 __device__ __forceinline__ void seg_bwd_row_src(const SegLds& l, const SegCsr& cout, int lr, int tc, float4 w0, float4 w1,
                                                 float4& accQ) {
-    const float4 q4 = sg_ld4(l.Q + (size_t)lr * SG_TW + tc);
+    const float4 q4 = ld4(l.Q + (size_t)lr * SG_TW + tc);
     accQ = make_float4(0.f, 0.f, 0.f, 0.f);
     const int beg = cout.rp[lr], end = cout.rp[lr + 1], last = end - 1;
     for (int p = beg; p < end; p += 4) {
@@ -705,14 +695,14 @@ __device__ __forceinline__ void seg_bwd_row_src(const SegLds& l, const SegCsr& c
         float4 pd[4], gd[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            pd[u] = sg_ld4(l.P + (size_t)d_[u] * SG_TW + tc);
-            gd[u] = sg_ld4(l.D + (size_t)d_[u] * SG_TW + tc);
+            pd[u] = ld4(l.P + (size_t)d_[u] * SG_TW + tc);
+            gd[u] = ld4(l.D + (size_t)d_[u] * SG_TW + tc);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            float4 z = sg_add4(pd[u], q4);
-            z = sg_fma4(ao[u].x, w0, z);
-            z = sg_fma4(ao[u].y, w1, z);
+            float4 z = add4(pd[u], q4);
+            z = fma4(ao[u].x, w0, z);
+            z = fma4(ao[u].y, w1, z);
             const bool k = p + u < end;
             accQ.x += (k && z.x > 0.f) ? gd[u].x : 0.f;
             accQ.y += (k && z.y > 0.f) ? gd[u].y : 0.f;
@@ -726,34 +716,34 @@ __device__ __forceinline__ void seg_bwd_row_slow(const SegLds& l, const SegCsr& 
                                                  const int* __restrict__ in_src, const int* __restrict__ out_dst,
                                                  const float* __restrict__ ea_in, const float* __restrict__ ea_out, float4 w0,
                                                  float4 w1, float4& accP, float4& accQ, float4& dwe0, float4& dwe1) {
-    const float4 p4 = sg_ld4(l.P + (size_t)lr * SG_TW + tc), q4 = sg_ld4(l.Q + (size_t)lr * SG_TW + tc);
-    const float4 g4 = sg_ld4(l.D + (size_t)lr * SG_TW + tc);
+    const float4 p4 = ld4(l.P + (size_t)lr * SG_TW + tc), q4 = ld4(l.Q + (size_t)lr * SG_TW + tc);
+    const float4 g4 = ld4(l.D + (size_t)lr * SG_TW + tc);
     accP = make_float4(0.f, 0.f, 0.f, 0.f);
     accQ = accP;
     for (int p = cin.rp[lr]; p < cin.rp[lr + 1]; ++p) {
         int ls;
         float2 a2;
         csr_slot(cin, p, r0, in_src, ea_in, ls, a2);
-        float4 v = sg_add4(p4, sg_ld4(l.Q + (size_t)ls * SG_TW + tc));
-        v = sg_fma4(a2.x, w0, v);
-        v = sg_fma4(a2.y, w1, v);
+        float4 v = add4(p4, ld4(l.Q + (size_t)ls * SG_TW + tc));
+        v = fma4(a2.x, w0, v);
+        v = fma4(a2.y, w1, v);
         float4 dh;
         dh.x = v.x > 0.f ? g4.x : 0.f;
         dh.y = v.y > 0.f ? g4.y : 0.f;
         dh.z = v.z > 0.f ? g4.z : 0.f;
         dh.w = v.w > 0.f ? g4.w : 0.f;
-        accP = sg_add4(accP, dh);
-        dwe0 = sg_fma4(a2.x, dh, dwe0);
-        dwe1 = sg_fma4(a2.y, dh, dwe1);
+        accP = add4(accP, dh);
+        dwe0 = fma4(a2.x, dh, dwe0);
+        dwe1 = fma4(a2.y, dh, dwe1);
     }
     for (int p = cout.rp[lr]; p < cout.rp[lr + 1]; ++p) {
         int ld_;
         float2 a2;
         csr_slot(cout, p, r0, out_dst, ea_out, ld_, a2);
-        float4 v = sg_add4(sg_ld4(l.P + (size_t)ld_ * SG_TW + tc), q4);
-        v = sg_fma4(a2.x, w0, v);
-        v = sg_fma4(a2.y, w1, v);
-        const float4 gd = sg_ld4(l.D + (size_t)ld_ * SG_TW + tc);
+        float4 v = add4(ld4(l.P + (size_t)ld_ * SG_TW + tc), q4);
+        v = fma4(a2.x, w0, v);
+        v = fma4(a2.y, w1, v);
+        const float4 gd = ld4(l.D + (size_t)ld_ * SG_TW + tc);
         accQ.x += v.x > 0.f ? gd.x : 0.f;
         accQ.y += v.y > 0.f ? gd.y : 0.f;
         accQ.z += v.z > 0.f ? gd.z : 0.f;
@@ -792,8 +782,8 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         if (it < rows * sc.cw) {
             const int lr = it / sc.cw, lc = it - lr * sc.cw;
             const size_t o = (size_t)(r0 + lr) * a.ld + seg_gcol(sc, lc);
-            pv[j] = sg_ld4(a.P + o);
-            qv[j] = sg_ld4(a.Q + o);
+            pv[j] = ld4(a.P + o);
+            qv[j] = ld4(a.Q + o);
         }
     }
     csr_issue2(cin, cri, cap, in_src, a.ea_in);
@@ -806,11 +796,11 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
     float dgv = 0.f;
     if (LOSS) {   // (requested with the rest of the prologue: behind its commits they were one more exposed round trip)
 #pragma unroll
-        for (int k = 0; k < 9; ++k) sv[k] = sg_ld4(a.mse.S + (size_t)mrow * a.ld + 4 * min(mpq + 4 * k, nch - 1));
+        for (int k = 0; k < 9; ++k) sv[k] = ld4(a.mse.S + (size_t)mrow * a.ld + 4 * min(mpq + 4 * k, nch - 1));
         if (mpq == 0) {
-            yv = sg_ld4(a.mse.y + (size_t)mrow * 4);
+            yv = ld4(a.mse.y + (size_t)mrow * 4);
             dgv = a.mse.deg[mrow];
-            if (a.mse.maskf) mkv = sg_ld4(a.mse.maskf + (size_t)mrow * 4);
+            if (a.mse.maskf) mkv = ld4(a.mse.maskf + (size_t)mrow * 4);
         }
     }
     csr_commit(cin, cri, r0, rows);
@@ -822,8 +812,8 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         if (it < rows * sc.cw) {
             const int lr = it / sc.cw, lc = it - lr * sc.cw;
             const int tc = seg_tcol(sc, lc);
-            sg_st4(l.P + (size_t)lr * SG_TW + tc, pv[j]);
-            sg_st4(l.Q + (size_t)lr * SG_TW + tc, qv[j]);
+            st4(l.P + (size_t)lr * SG_TW + tc, pv[j]);
+            st4(l.Q + (size_t)lr * SG_TW + tc, qv[j]);
         }
     }
     // the trailing columns of dS: VALU dot products on the four waves that carry no tile (rows <= 128), in the shadow of the
@@ -870,7 +860,7 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
             for (int j = 0; j < 3; ++j) {
                 const int it = threadIdx.x + j * SG_THREADS;
                 gv[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (it < rows * sc.cw) gv[j] = sg_ld4(a.gout + (size_t)(r0 + it / sc.cw) * 4);
+                if (it < rows * sc.cw) gv[j] = ld4(a.gout + (size_t)(r0 + it / sc.cw) * 4);
             }
         }
         for (int i = threadIdx.x; i < 4 * SG_TW; i += SG_THREADS) {
@@ -904,18 +894,18 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
 #pragma unroll
                 for (int k2 = 0; k2 < 2; ++k2) {
                     const int k = k1 + 2 * k2;
-                    const float4 sa = sg_add4(slot(k), slot(k + 8)), sb = sg_add4(slot(k + 4), slot(k + 12));
-                    const float4 t = sg_add4(sa, sb);
-                    if (k2 == 0) t0 = t; else tt = sg_add4(t0, t);
+                    const float4 sa = add4(slot(k), slot(k + 8)), sb = add4(slot(k + 4), slot(k + 12));
+                    const float4 t = add4(sa, sb);
+                    if (k2 == 0) t0 = t; else tt = add4(t0, t);
                 }
-                if (k1 == 0) u0 = tt; else vp = sg_add4(u0, tt);
+                if (k1 == 0) u0 = tt; else vp = add4(u0, tt);
             }
             float4 vo;
             vo.x = __shfl_xor(vp.x, 2); vo.y = __shfl_xor(vp.y, 2); vo.z = __shfl_xor(vp.z, 2); vo.w = __shfl_xor(vp.w, 2);
-            const float4 wp = (mpq & 2) ? sg_add4(vo, vp) : sg_add4(vp, vo);
+            const float4 wp = (mpq & 2) ? add4(vo, vp) : add4(vp, vo);
             float4 wo;
             wo.x = __shfl_xor(wp.x, 1); wo.y = __shfl_xor(wp.y, 1); wo.z = __shfl_xor(wp.z, 1); wo.w = __shfl_xor(wp.w, 1);
-            const float4 t4 = (mpq & 1) ? sg_add4(wo, wp) : sg_add4(wp, wo);
+            const float4 t4 = (mpq & 1) ? add4(wo, wp) : add4(wp, wo);
             if (mpq == 0) {
                 const float b0 = a.mse.b2[0], b1_ = a.fo > 1 ? a.mse.b2[1] : 0.f, b2_ = a.fo > 2 ? a.mse.b2[2] : 0.f, b3_ = a.fo > 3 ? a.mse.b2[3] : 0.f;
                 const float4 o4 = make_float4(fmaf(dgv, b0, t4.x), a.fo > 1 ? fmaf(dgv, b1_, t4.y) : 0.f,
@@ -955,11 +945,11 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                     sq[SG_MAX_ROWS + mlr] = on ? q0 : 0.f;
                 }
                 if (on && sc.q == max(0, sc.nq - 2)) {   // ONE quarter per graph stores the 4-wide tensors (an early, light one)
-                    sg_st4_wt(a.mse.out + (size_t)mrow * 4, o4);
-                    sg_st4_wt(a.mse.gout + (size_t)mrow * 4, g4);
+                    st4_wt(a.mse.out + (size_t)mrow * 4, o4);
+                    st4_wt(a.mse.gout + (size_t)mrow * 4, g4);
                 }
             }
-            seg_lds_barrier();
+            lds_barrier();
             // the block's loss partial: rows l and l + 64, then a fixed xor tree (wave 0; once per block)
             if (wave == 0 && sc.q == max(0, sc.nq - 2)) {
                 float v = sq[lane] + sq[lane + 64], v0 = sq[SG_MAX_ROWS + lane] + sq[SG_MAX_ROWS + lane + 64];
@@ -967,7 +957,7 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                     v += __shfl_xor(v, off);
                     v0 += __shfl_xor(v0, off);
                 }
-                if (lane == 0) {   // sc1: write-through
+                if (lane == 0) {   // (agent-scope atomic stores: write-through)
                     if (a.mse.maskf) {
                         __hip_atomic_store(a.mse.partial + 2 * blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(a.mse.partial + 2 * blockIdx.x + 1, v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -990,12 +980,12 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
                 const int lr = it / sc.cw, lc = it - lr * sc.cw;
                 const int tc = seg_tcol(sc, lc);
                 const float4 g = gv[j];
-                const float4 x0 = sg_ld4(l.w2s + tc);
+                const float4 x0 = ld4(l.w2s + tc);
                 float4 r = make_float4(g.x * x0.x, g.x * x0.y, g.x * x0.z, g.x * x0.w);
-                r = sg_fma4(g.y, sg_ld4(l.w2s + SG_TW + tc), r);
-                r = sg_fma4(g.z, sg_ld4(l.w2s + 2 * SG_TW + tc), r);
-                r = sg_fma4(g.w, sg_ld4(l.w2s + 3 * SG_TW + tc), r);
-                sg_st4(l.D + (size_t)lr * SG_TW + tc, r);
+                r = fma4(g.y, ld4(l.w2s + SG_TW + tc), r);
+                r = fma4(g.z, ld4(l.w2s + 2 * SG_TW + tc), r);
+                r = fma4(g.w, ld4(l.w2s + 3 * SG_TW + tc), r);
+                st4(l.D + (size_t)lr * SG_TW + tc, r);
             }
         }
     } else {
@@ -1004,11 +994,11 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         if (async_a) {
             seg_drain_visible();
             if (mfma_on) seg_load_a_async(ta, a.gout, a.ldgo, r0 + 32 * wave, r0 + rows - 1, lane);
-            seg_lds_barrier();
+            lds_barrier();
             if (mfma_on) acc = seg_mma_async(ta, l.B0, lane);
             else if (rem_helper) seg_rem_dots<false, 1, 5>(threadIdx.x - 256, a.gout, a.ldgo, a.fo, r0, rows, a.Bd, nullptr, sc.nq, nreal, v1, v2);
         } else {
-            seg_dma_wait();
+            vmem_drain();
             __syncthreads();
             if (mfma_on) acc = seg_mma(ta, l.B0, K8, lane);
         }
@@ -1022,15 +1012,15 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
     // trailing columns walks that ninth chunk in a second, short pass (two threads per row, one per direction): as a ninth lane it halved the row lanes and
     // made those blocks -- the launch's critical path -- twice as long.
     auto walk_rows = [&](int lr0, int lr_step, int tc, int gc, float4& dwe0, float4& dwe1) {
-        const float4 w0 = sg_ld4(l.we + tc), w1 = sg_ld4(l.we + SG_TW + tc);
+        const float4 w0 = ld4(l.we + tc), w1 = ld4(l.we + SG_TW + tc);
         for (int lr = lr0; lr < rows; lr += lr_step) {
             float4 accP, accQ;
             if (cin.in_lds && cout.in_lds)
                 seg_bwd_row(l, cin, cout, lr, tc, w0, w1, accP, accQ, dwe0, dwe1);
             else
                 seg_bwd_row_slow(l, cin, cout, lr, tc, r0, in_src, out_dst, a.ea_in, a.ea_out, w0, w1, accP, accQ, dwe0, dwe1);
-            sg_st4_wt(a.dP + (size_t)(r0 + lr) * a.ld + gc, accP);
-            sg_st4_wt(a.dQ + (size_t)(r0 + lr) * a.ld + gc, accQ);
+            st4_wt(a.dP + (size_t)(r0 + lr) * a.ld + gc, accP);
+            st4_wt(a.dQ + (size_t)(r0 + lr) * a.ld + gc, accQ);
         }
     };
     const int cwm = sc.cw - (sc.rem ? 1 : 0);             // chunks of the 32-column quarter itself (<= 8)
@@ -1041,14 +1031,14 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         const int lr = threadIdx.x >> 1, gc = 32 * sc.nq;
         if (lr < rows) {
             if (cin.in_lds && cout.in_lds) {
-                const float4 w0 = sg_ld4(l.we + 32), w1 = sg_ld4(l.we + SG_TW + 32);
+                const float4 w0 = ld4(l.we + 32), w1 = ld4(l.we + SG_TW + 32);
                 float4 acc;
                 if (threadIdx.x & 1) {
                     seg_bwd_row_src(l, cout, lr, 32, w0, w1, acc);
-                    sg_st4_wt(a.dQ + (size_t)(r0 + lr) * a.ld + gc, acc);
+                    st4_wt(a.dQ + (size_t)(r0 + lr) * a.ld + gc, acc);
                 } else {
                     seg_bwd_row_dst(l, cin, lr, 32, w0, w1, acc, rwe0, rwe1);
-                    sg_st4_wt(a.dP + (size_t)(r0 + lr) * a.ld + gc, acc);
+                    st4_wt(a.dP + (size_t)(r0 + lr) * a.ld + gc, acc);
                 }
             } else if (!(threadIdx.x & 1)) {
                 walk_rows(lr, SG_THREADS, 32, gc, rwe0, rwe1);
@@ -1070,24 +1060,24 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         l.part[(wave * 16 + 8) * 2] = rwe0;
         l.part[(wave * 16 + 8) * 2 + 1] = rwe1;
     }
-    seg_lds_barrier();   // (not __syncthreads(): the dP / dQ stores of the walks drain meanwhile)
+    lds_barrier();   // (not __syncthreads(): the dP / dQ stores of the walks drain meanwhile)
     if (threadIdx.x < 32) {
         const int f = threadIdx.x >> 4, c2 = threadIdx.x & 15;
         if (c2 < sc.cw) {
             float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int w = 0; w < SG_WAVES; ++w) s = sg_add4(s, l.part[(w * 16 + c2) * 2 + f]);
-            sg_st4_wt(a.dWe_partial + ((size_t)blockIdx.x * 2 + f) * a.ld + seg_gcol(sc, c2), s);
+            for (int w = 0; w < SG_WAVES; ++w) s = add4(s, l.part[(w * 16 + c2) * 2 + f]);
+            st4_wt(a.dWe_partial + ((size_t)blockIdx.x * 2 + f) * a.ld + seg_gcol(sc, c2), s);
         }
     }
     if (LOSS && wave == 0 && sc.q == max(0, sc.nq - 2)) {
         // the loss: the last of the partial-owning blocks to get here sums the partials in BLOCK order (deterministic).  Same
         // hand-off as mse_kernel (util_kernels.hip): write-through partial, drained, then the ticket; agent-scope loads on the consumer
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "the loss hand-off relies on gfx950 semantics (sc1 write-through stores drained by s_waitcnt vmcnt(0))"
+#error "the loss hand-off relies on gfx950 semantics (write-through stores drained by s_waitcnt vmcnt(0))"
 #endif
         int last = 0;
         if (lane == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            vmem_drain();
             last = __hip_atomic_fetch_add(a.mse.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
         }
         last = __shfl(last, 0);

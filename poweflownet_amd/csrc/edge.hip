@@ -16,29 +16,12 @@
 
 namespace pfn {
 
-// Barrier that publishes LDS traffic only: __syncthreads() also waits (vmcnt(0)) until every global STORE of the wave is
-// acknowledged -- a round trip of 1-2 us under load at every barrier that follows output stores (seg_tile.hpp seg_lds_barrier).
-// Only where no thread reads another thread's GLOBAL writes behind the barrier: the hop kernels' tiles live in LDS.
-__device__ __forceinline__ void bh_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float4 fma4(float a, float4 x, float4 acc) {
-    acc.x = fmaf(a, x.x, acc.x);
-    acc.y = fmaf(a, x.y, acc.y);
-    acc.z = fmaf(a, x.z, acc.z);
-    acc.w = fmaf(a, x.w, acc.w);
-    return acc;
-}
-__device__ __forceinline__ float4 mul4(float a, float4 x) { return make_float4(a * x.x, a * x.y, a * x.z, a * x.w); }
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ unsigned char relu_bits(float4 v) {   // bit i = component i > 0 (the edge stage's ReLU mask)
     return (unsigned char)((v.x > 0.f ? 1 : 0) | (v.y > 0.f ? 2 : 0) | (v.z > 0.f ? 4 : 0) | (v.w > 0.f ? 8 : 0));
 }
 __device__ __forceinline__ float4 mask4(unsigned m, float4 g) {   // g where the mask bit is set, else 0
     return make_float4((m & 1) ? g.x : 0.f, (m & 2) ? g.y : 0.f, (m & 4) ? g.z : 0.f, (m & 8) ? g.w : 0.f);
 }
-__device__ __forceinline__ float4 sel4(bool k, float4 a, float4 b) { return make_float4(k ? a.x : b.x, k ? a.y : b.y, k ? a.z : b.z, k ? a.w : b.w); }
-__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
 
 __device__ __forceinline__ int exp_block(int b, int) { return b; }
 // ------------------------------------------------------------------------------------------- hop
@@ -326,11 +309,11 @@ __global__ __launch_bounds__(RH_THREADS, 4) void row_hops_kernel(int n, int rows
             __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler interleaves all eight items' gathers and spills)
         }
         if (k == K) break;
-        bh_lds_barrier();          // (not __syncthreads(): the hop's output stores drain under the next hop)
+        lds_barrier();   // (not __syncthreads(): the hop's output stores drain under the next hop)
 #pragma unroll
         for (int r = 0; r < RH_IPT; ++r)
             if (t + r * RH_THREADS < items) rh_tile[t + r * RH_THREADS] = z[r];
-        bh_lds_barrier();
+        lds_barrier();
     }
 }
 // whole graphs per block: rows x chunks <= 4,096 items, rows <= 1,024, tile + offsets in HALF of the LDS (two blocks per CU)
@@ -549,9 +532,9 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
         // opaque per hop: what is derived from them -- the rows' global offsets (64-bit), their lane masks (degree > 0..4, hub,
         // row < seg: SGPR pairs) and the unpacked plan fields -- is loop-invariant, gets hoisted out of both loops and spilled
         int to = t;
-        asm volatile("" : "+v"(to));
+        PFN_OPAQUE(to);
 #pragma unroll
-        for (int r = 0; r < BH_RPT; ++r) asm volatile("" : "+v"(plan[r]), "+v"(id01[r]), "+v"(id23[r]));
+        for (int r = 0; r < BH_RPT; ++r) asm volatile("" : "+v"(plan[r]), "+v"(id01[r]), "+v"(id23[r]));   // (PFN_OPAQUE, three registers in one)
         // ---- hub rows first: one wave per row, lanes stride over its edges, fixed xor tree
         for (int hs = wave_; hs < nhub; hs += BH_THREADS / 64) {
             const int row = s_hub_row[hs];
@@ -567,7 +550,7 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
             }
             if (lane_ == 0) s_hub_y[hs] = part;
         }
-        if (nhub > 0) bh_lds_barrier();
+        if (nhub > 0) lds_barrier();
 #pragma unroll
         for (int r = 0; r < BH_RPT; ++r) {
             const int row = to + r * BH_THREADS;
@@ -604,7 +587,7 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
             if (row < seg) st4(outc + (size_t)row * 4, y);
             if (KEEP) z[r] = mul4(di[r], y);
         }
-        bh_lds_barrier();                       // every read of the tile is done
+        lds_barrier();   // every read of the tile is done
     };
     for (int c = w; c < nchunk; c += wpg) {
         // ---- the tile of chunk c: z = D^-1/2 x  (every read of the previous chunk's tile is behind the barrier of its last hop)
@@ -613,7 +596,7 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
             const int row = t + r * BH_THREADS;
             if (row < seg) bh_tile[row] = mul4(di[r], z[r]);
         }
-        bh_lds_barrier();
+        lds_barrier();
         float* outc = xk + ((size_t)c * n_total + r0) * 4;
         for (int k = 1; k < K; ++k) {
             hop(std::true_type{}, outc);
@@ -622,7 +605,7 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
                 const int row = t + r * BH_THREADS;
                 if (row < seg) bh_tile[row] = z[r];
             }
-            bh_lds_barrier();
+            lds_barrier();
             outc += stride;
         }
         // the next chunk's rows are requested now (z is dead until that chunk's tile write) and arrive under the last hop; after
@@ -630,7 +613,7 @@ __global__ __launch_bounds__(BH_THREADS) void big_graph_hops_kernel(int seg, int
         {
             const int cn = c + wpg < nchunk ? c + wpg : c;
             int to = t;
-            asm volatile("" : "+v"(to));
+            PFN_OPAQUE(to);
 #pragma unroll
             for (int r = 0; r < BH_RPT; ++r) z[r] = ld4(xb + (size_t)cn * xchunk + (size_t)min(to + r * BH_THREADS, seg - 1) * xrow);
         }
@@ -1165,7 +1148,7 @@ __device__ __forceinline__ float4 ds_row(const float* __restrict__ dS, int row, 
     if (!DSG) return ld4(dS + (size_t)row * ld + col);
     const float4 g = ld4(dS + (size_t)row * 4);          // gout row, ld 4 (columns >= Fo are zero-weighted)
     int co = col;
-    asm volatile("" : "+v"(co));                         // re-read the chunk here: hoisted out of the walk it is 16 live VGPRs
+    PFN_OPAQUE(co);   // re-read the chunk here: hoisted out of the walk it is 16 live VGPRs
     float4 r = mul4(g.x, ld4(w2s + co));
     r = fma4(g.y, ld4(w2s + ld + co), r);
     r = fma4(g.z, ld4(w2s + 2 * ld + co), r);

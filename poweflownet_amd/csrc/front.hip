@@ -32,9 +32,7 @@ static int wave_blocks_per_cu(int which) {
     return 3;
 }
 
-__device__ __forceinline__ float4 ld4f(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void st4f(float* p, float4 v) { st4_wt(p, v); }   // (every store of this file is a kernel output)
-
+// (every 16-byte store of this file is a kernel output: st4_wt, the write-through store)
 // block = rows_pb rows x nchunk chunk-lanes (nchunk = ld / 4), PERSISTENT over row groups: a thread keeps ONE chunk of four
 // hidden units for every row it visits, so its slices of all five weights live in registers for the whole kernel (as
 // per-element global loads they made the kernel 3x slower than its memory traffic).  LDS: part[rows_pb][nchunk] | vec[rows_pb].
@@ -78,9 +76,9 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
                 const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
                 m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
             } else {
-                m = ld4f(static_cast<const float*>(a.mask) + (size_t)row * 4);
+                m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
             }
-            if (c == 0) st4f(a.maskf + (size_t)row * 4, m);
+            if (c == 0) st4_wt(a.maskf + (size_t)row * 4, m);
             float hv[4];
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // this chunk's share of me_h Wb^T
 #pragma unroll
@@ -92,17 +90,17 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
                 acc.x = fmaf(rwb[i][0], v, acc.x); acc.y = fmaf(rwb[i][1], v, acc.y);
                 acc.z = fmaf(rwb[i][2], v, acc.z); acc.w = fmaf(rwb[i][3], v, acc.w);
             }
-            if (a.me_h) st4f(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));   // (null: no backward follows)
+            if (a.me_h) st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));   // (null: no backward follows)
             part[r * nchunk + c] = acc;
         }
         __syncthreads();
         row_sum(part, r, c, nchunk, on);   // fixed-order sum over the row's chunks, left in part[r * nchunk]
         if (on && c == 0) {
             const float4 s = part[r * nchunk];
-            const float4 xi = ld4f(a.x + (size_t)row * 4);   // (requested at the top of the trip instead: no gain at 128 graphs, 4-8 % slower at 2048)
+            const float4 xi = ld4(a.x + (size_t)row * 4);   // (requested at the top of the trip instead: no gain at 128 graphs, 4-8 % slower at 2048)
             const float4 o = make_float4(xi.x + (s.x + bb4.x), xi.y + (s.y + bb4.y), xi.z + (s.z + bb4.z), xi.w + (s.w + bb4.w));
             vec[r] = o;
-            st4f(a.x0 + (size_t)row * 4, o);
+            st4_wt(a.x0 + (size_t)row * 4, o);
         }
         __syncthreads();
         if (on && a.P) {                            // (P null: the first edge stage forms P | Q rows from x0 itself, edge.hip FLY)
@@ -117,8 +115,8 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
                 p[i] = pa;
                 q[i] = qb;
             }
-            st4f(a.P + (size_t)row * ld + 4 * c, make_float4(p[0], p[1], p[2], p[3]));
-            st4f(a.Q + (size_t)row * ld + 4 * c, make_float4(q[0], q[1], q[2], q[3]));
+            st4_wt(a.P + (size_t)row * ld + 4 * c, make_float4(p[0], p[1], p[2], p[3]));
+            st4_wt(a.Q + (size_t)row * ld + 4 * c, make_float4(q[0], q[1], q[2], q[3]));
         }
         // (the next trip writes part[] only after every reader of this trip has passed the barriers above)
     }
@@ -128,16 +126,6 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
 // of DPP / permute shuffles: no LDS, no barrier, so every wave runs its own chain of loads and 32 of them per CU hide each
 // other's latency.  Used for small batches (front_row_per_wave); the block-per-row-group body above remains for wider models
 // and large batches.
-__device__ __forceinline__ float4 wave_sum4(float4 v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v.x += __shfl_xor(v.x, off);
-        v.y += __shfl_xor(v.y, off);
-        v.z += __shfl_xor(v.z, off);
-        v.w += __shfl_xor(v.w, off);
-    }
-    return v;
-}
 __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int bid, int nblk, int ld, int nchunk) {
     const int n = a.n, h = a.h, ldw1 = a.ldw1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane;
@@ -169,9 +157,9 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
             const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
             m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
         } else {
-            m = ld4f(static_cast<const float*>(a.mask) + (size_t)row * 4);
+            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
         }
-        xi = ld4f(a.x + (size_t)row * 4);
+        xi = ld4(a.x + (size_t)row * 4);
     };
     float4 m_n = make_float4(0.f, 0.f, 0.f, 0.f), xi_n = m_n;
     const int row_first = bid * wpb + wave;
@@ -190,12 +178,12 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
             acc.x = fmaf(rwb[i][0], v, acc.x); acc.y = fmaf(rwb[i][1], v, acc.y);
             acc.z = fmaf(rwb[i][2], v, acc.z); acc.w = fmaf(rwb[i][3], v, acc.w);
         }
-        if (lane_on && a.me_h) st4f(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
+        if (lane_on && a.me_h) st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
         const float4 s4 = wave_sum4(acc);            // fixed butterfly: every lane ends with the same, deterministic sum
         const float4 o = make_float4(xi.x + (s4.x + bb4.x), xi.y + (s4.y + bb4.y), xi.z + (s4.z + bb4.z), xi.w + (s4.w + bb4.w));
         if (lane == 0) {
-            st4f(a.maskf + (size_t)row * 4, m);
-            st4f(a.x0 + (size_t)row * 4, o);
+            st4_wt(a.maskf + (size_t)row * 4, m);
+            st4_wt(a.x0 + (size_t)row * 4, o);
         }
         if (lane_on && a.P) {
             float pv[4], qv[4];
@@ -208,8 +196,8 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
                 pv[i] = pa;
                 qv[i] = qb;
             }
-            st4f(a.P + (size_t)row * ld + 4 * c, make_float4(pv[0], pv[1], pv[2], pv[3]));
-            st4f(a.Q + (size_t)row * ld + 4 * c, make_float4(qv[0], qv[1], qv[2], qv[3]));
+            st4_wt(a.P + (size_t)row * ld + 4 * c, make_float4(pv[0], pv[1], pv[2], pv[3]));
+            st4_wt(a.Q + (size_t)row * ld + 4 * c, make_float4(qv[0], qv[1], qv[2], qv[3]));
         }
     }
 }
@@ -234,9 +222,9 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
             const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
             m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
         } else {
-            m = ld4f(static_cast<const float*>(a.mask) + (size_t)row * 4);
+            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
         }
-        const float4 xi = ld4f(a.x + (size_t)row * 4);
+        const float4 xi = ld4(a.x + (size_t)row * 4);
         float4 sub[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) sub[j] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -281,8 +269,8 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
             if (j >= nchunk) break;
             t.x += sub[j].x; t.y += sub[j].y; t.z += sub[j].z; t.w += sub[j].w;
         }
-        st4f(a.maskf + (size_t)row * 4, m);
-        st4f(a.x0 + (size_t)row * 4, make_float4(xi.x + (t.x + bb4.x), xi.y + (t.y + bb4.y), xi.z + (t.z + bb4.z), xi.w + (t.w + bb4.w)));
+        st4_wt(a.maskf + (size_t)row * 4, m);
+        st4_wt(a.x0 + (size_t)row * 4, make_float4(xi.x + (t.x + bb4.x), xi.y + (t.y + bb4.y), xi.z + (t.z + bb4.z), xi.w + (t.w + bb4.w)));
     }
 }
 
@@ -317,7 +305,7 @@ __device__ __forceinline__ void front_meh_body(const FrontFwdArgs& a, int bid, i
             const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
             m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
         } else {
-            m = ld4f(static_cast<const float*>(a.mask) + (size_t)row * 4);
+            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
         }
         float hv[4];
 #pragma unroll
@@ -326,7 +314,7 @@ __device__ __forceinline__ void front_meh_body(const FrontFwdArgs& a, int bid, i
             v = fmaf(rwa[i][0], m.x, v); v = fmaf(rwa[i][1], m.y, v); v = fmaf(rwa[i][2], m.z, v); v = fmaf(rwa[i][3], m.w, v);
             hv[i] = fmaxf(v, 0.f);
         }
-        st4f(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
+        st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
     }
 }
 
@@ -384,9 +372,9 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
         const int row = row0 + r;
         const bool on = lane_on && row < n;
         float4 y = make_float4(0.f, 0.f, 0.f, 0.f);   // (requested with dP / dQ, used after the row sum's barriers)
-        if (on) y = ld4f(me_h + (size_t)row * ld + 4 * c);
+        if (on) y = ld4(me_h + (size_t)row * ld + 4 * c);
         if (on) {
-            const float4 p4 = ld4f(dP + (size_t)row * ld + 4 * c), q4 = ld4f(dQ + (size_t)row * ld + 4 * c);
+            const float4 p4 = ld4(dP + (size_t)row * ld + 4 * c), q4 = ld4(dQ + (size_t)row * ld + 4 * c);
             const float pv[4] = {p4.x, p4.y, p4.z, p4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -403,7 +391,7 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
         if (on && c == 0) {
             const float4 s = part[r * nchunk];
             vec[r] = s;
-            st4f(g0 + (size_t)row * 4, s);
+            st4_wt(g0 + (size_t)row * 4, s);
         }
         __syncthreads();
         if (on) {
@@ -416,7 +404,7 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
                 v = fmaf(g.x, rwb[i][0], v); v = fmaf(g.y, rwb[i][1], v); v = fmaf(g.z, rwb[i][2], v); v = fmaf(g.w, rwb[i][3], v);
                 o[i] = yv[i] > 0.f ? v : 0.f;
             }
-            st4f(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
+            st4_wt(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
 }
@@ -449,16 +437,16 @@ __global__ __launch_bounds__(256) void front_bwd_wave_kernel(int n, int h, int l
     const int step = gridDim.x * wpb, row_first = blockIdx.x * wpb + wave;
     float4 p_n = make_float4(0.f, 0.f, 0.f, 0.f), q_n = p_n, y_n = p_n;
     if (row_first < n) {
-        p_n = ld4f(dP + (size_t)row_first * ld + 4 * cc);
-        q_n = ld4f(dQ + (size_t)row_first * ld + 4 * cc);
-        y_n = ld4f(me_h + (size_t)row_first * ld + 4 * cc);
+        p_n = ld4(dP + (size_t)row_first * ld + 4 * cc);
+        q_n = ld4(dQ + (size_t)row_first * ld + 4 * cc);
+        y_n = ld4(me_h + (size_t)row_first * ld + 4 * cc);
     }
     for (int row = row_first; row < n; row += step) {
         const float4 p4 = p_n, q4 = q_n, y = y_n;
         if (row + step < n) {   // the next row's inputs, in flight during this row
-            p_n = ld4f(dP + (size_t)(row + step) * ld + 4 * cc);
-            q_n = ld4f(dQ + (size_t)(row + step) * ld + 4 * cc);
-            y_n = ld4f(me_h + (size_t)(row + step) * ld + 4 * cc);
+            p_n = ld4(dP + (size_t)(row + step) * ld + 4 * cc);
+            q_n = ld4(dQ + (size_t)(row + step) * ld + 4 * cc);
+            y_n = ld4(me_h + (size_t)(row + step) * ld + 4 * cc);
         }
         const float pv[4] = {p4.x, p4.y, p4.z, p4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -470,7 +458,7 @@ __global__ __launch_bounds__(256) void front_bwd_wave_kernel(int n, int h, int l
             acc.z = fmaf(qv[i], rw1[i][6], acc.z); acc.w = fmaf(qv[i], rw1[i][7], acc.w);
         }
         const float4 g = wave_sum4(acc);
-        if (lane == 0) st4f(g0 + (size_t)row * 4, g);
+        if (lane == 0) st4_wt(g0 + (size_t)row * 4, g);
         if (lane_on) {
             const float yv[4] = {y.x, y.y, y.z, y.w};
             float o[4];
@@ -480,7 +468,7 @@ __global__ __launch_bounds__(256) void front_bwd_wave_kernel(int n, int h, int l
                 v = fmaf(g.x, rwb[i][0], v); v = fmaf(g.y, rwb[i][1], v); v = fmaf(g.z, rwb[i][2], v); v = fmaf(g.w, rwb[i][3], v);
                 o[i] = yv[i] > 0.f ? v : 0.f;
             }
-            st4f(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
+            st4_wt(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
 }
@@ -506,7 +494,7 @@ __global__ __launch_bounds__(256) void lin_out4_wave_kernel(int n, int h, int ld
     const float4 bv = make_float4(b2[0], fo > 1 ? b2[1] : 0.f, fo > 2 ? b2[2] : 0.f, fo > 3 ? b2[3] : 0.f);
     const int wpb = blockDim.x >> 6, cc = lane_on ? c : 0;
     for (int row = blockIdx.x * wpb + wave; row < n; row += gridDim.x * wpb) {
-        const float4 s4 = ld4f(S + (size_t)row * ld + 4 * cc);
+        const float4 s4 = ld4(S + (size_t)row * ld + 4 * cc);
         const float d = deg[row];
         float4 acc;
         acc.x = fmaf(s4.w, rw[0][3], fmaf(s4.z, rw[0][2], fmaf(s4.y, rw[0][1], s4.x * rw[0][0])));
@@ -515,7 +503,7 @@ __global__ __launch_bounds__(256) void lin_out4_wave_kernel(int n, int h, int ld
         acc.w = fmaf(s4.w, rw[3][3], fmaf(s4.z, rw[3][2], fmaf(s4.y, rw[3][1], s4.x * rw[3][0])));
         const float4 t = wave_sum4(acc);
         if (lane == 0)
-            st4f(out + (size_t)row * 4, make_float4(fmaf(d, bv.x, t.x), fo > 1 ? fmaf(d, bv.y, t.y) : 0.f,
+            st4_wt(out + (size_t)row * 4, make_float4(fmaf(d, bv.x, t.x), fo > 1 ? fmaf(d, bv.y, t.y) : 0.f,
                                                     fo > 2 ? fmaf(d, bv.z, t.z) : 0.f, fo > 3 ? fmaf(d, bv.w, t.w) : 0.f));
     }
 }
@@ -618,7 +606,7 @@ __global__ __launch_bounds__(256) void front_pq_kernel(int n, int h, int ld, int
     const long item = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int row = (int)(item / nchunk), c = (int)(item - (long)row * nchunk);
     if (row >= n) return;
-    const float4 v = ld4f(x0 + (size_t)row * 4);
+    const float4 v = ld4(x0 + (size_t)row * 4);
     float p[4], q[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -631,8 +619,8 @@ __global__ __launch_bounds__(256) void front_pq_kernel(int n, int h, int ld, int
         p[i] = u < h ? pa : 0.f;
         q[i] = u < h ? qb : 0.f;
     }
-    st4f(P + (size_t)row * ld + 4 * c, make_float4(p[0], p[1], p[2], p[3]));
-    st4f(Q + (size_t)row * ld + 4 * c, make_float4(q[0], q[1], q[2], q[3]));
+    st4_wt(P + (size_t)row * ld + 4 * c, make_float4(p[0], p[1], p[2], p[3]));
+    st4_wt(Q + (size_t)row * ld + 4 * c, make_float4(q[0], q[1], q[2], q[3]));
 }
 int launch_front_pq(int n, int h, int ldw1, const float* x0, const float* w1, const float* b1, float* P, float* Q, hipStream_t s) {
     if (n == 0) return PFN_OK;
@@ -652,9 +640,6 @@ int launch_front_pq(int n, int h, int ldw1, const float* x0, const float* w1, co
 // second kernel in workgroup order (fixed order throughout: deterministic).  Neither me_h nor dh touches memory: the forward front
 // writes 32 bytes per row, this kernel reads dP and dQ and writes 16 bytes per row, and two N x H pairs leave the weight-gradient
 // launch.  Partial sums per workgroup: [9][ld] floats (dWb f = 0..3, dWa f = 0..3, dba) + dbb[4].
-// a workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding GLOBAL access (vmcnt(0)),
-// which would pull the prefetched next row group in front of each of the four barriers of a trip
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // row_sum (pfn_internal.hpp) on that barrier: same two-level order, same result
 __device__ __forceinline__ void row_sum_lb(float4* part, int r, int c, int nchunk, bool on) {
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -723,9 +708,9 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
     {
         const int row = blockIdx.x * rows_pb + r;
         if (lane_on && row < n) {
-            m_n = ld4f(maskf + (size_t)row * 4);
-            p_n = ld4f(dP + (size_t)row * ld + 4 * c);
-            q_n = ld4f(dQ + (size_t)row * ld + 4 * c);
+            m_n = ld4(maskf + (size_t)row * 4);
+            p_n = ld4(dP + (size_t)row * ld + 4 * c);
+            q_n = ld4(dQ + (size_t)row * ld + 4 * c);
         }
     }
     for (int row0 = blockIdx.x * rows_pb; row0 < n; row0 += gridDim.x * rows_pb) {
@@ -735,9 +720,9 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
         {
             const int rown = row + gridDim.x * rows_pb;
             if (lane_on && rown < n) {
-                m_n = ld4f(maskf + (size_t)rown * 4);
-                p_n = ld4f(dP + (size_t)rown * ld + 4 * c);
-                q_n = ld4f(dQ + (size_t)rown * ld + 4 * c);
+                m_n = ld4(maskf + (size_t)rown * 4);
+                p_n = ld4(dP + (size_t)rown * ld + 4 * c);
+                q_n = ld4(dQ + (size_t)rown * ld + 4 * c);
             }
         }
         if (on) {
@@ -758,7 +743,7 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
         if (on && c == 0) {
             const float4 s = part[r * nchunk];
             vec[r] = s;
-            st4f(g0 + (size_t)row * 4, s);
+            st4_wt(g0 + (size_t)row * 4, s);
         }
         lds_barrier();
         if (on) {
@@ -811,7 +796,7 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
                 const float4 p = part[k * nchunk + c];
                 t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
             }
-            st4f(slot < FWG_SLOTS ? mine + slot * ld + 4 * c : mine + FWG_SLOTS * ld, t);
+            st4_wt(slot < FWG_SLOTS ? mine + slot * ld + 4 * c : mine + FWG_SLOTS * ld, t);
         }
     }
 }

@@ -38,9 +38,6 @@
 
 namespace pfn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int T3_THREADS = 512;            // 8 waves = two per SIMD
 constexpr int T3_WAVES = 8;
 constexpr int T3_R = 8;                    // ring depth: steps (row pairs) in flight per wave
@@ -72,7 +69,6 @@ struct T3Args {
 };
 __device__ __forceinline__ bool t3_bad(const T3Args& a) { return a.stamp != nullptr && *a.stamp != a.stamp_want; }
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int W>
 struct T3Frag {   // one operand of one MFMA step: 4 (A) / 2 (B) adjacent columns of a wide operand, 1 column of a narrow one
     typedef typename std::conditional<W == 4, f32x4, typename std::conditional<W == 2, f32x2, float>::type>::type type;
@@ -268,13 +264,13 @@ __device__ __forceinline__ void t3_body(const T3Args& a, const T3Task& tk, int b
             const char* pa = baseA + row * rowA * 4;
             const char* pb = baseB + row * rowB * 4;
             const char* prs = baseR + row * rs_stride * 4;
-            if (TA == 4) asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(t.a) : "v"(voA), "s"(pa) : "memory");
-            else asm volatile("global_load_dword %0, %1, %2" : "+v"(t.a) : "v"(voA), "s"(pa) : "memory");
-            if (TB == 2) asm volatile("global_load_dwordx2 %0, %1, %2" : "+v"(t.b) : "v"(voB), "s"(pb) : "memory");
-            else asm volatile("global_load_dword %0, %1, %2" : "+v"(t.b) : "v"(voB), "s"(pb) : "memory");
-            asm volatile("global_load_dword %0, %1, %2" : "+v"(t.xv) : "v"(voX), "s"(pb) : "memory");
-            asm volatile("global_load_dword %0, %1, %2" : "+v"(t.yv) : "v"(voY), "s"(pa) : "memory");
-            asm volatile("global_load_dword %0, %1, %2" : "+v"(t.rs) : "v"(voR), "s"(prs) : "memory");
+            if (TA == 4) PFN_VLOAD_INTO("global_load_dwordx4", t.a, pa, voA);
+            else PFN_VLOAD_INTO("global_load_dword", t.a, pa, voA);
+            if (TB == 2) PFN_VLOAD_INTO("global_load_dwordx2", t.b, pb, voB);
+            else PFN_VLOAD_INTO("global_load_dword", t.b, pb, voB);
+            PFN_VLOAD_INTO("global_load_dword", t.xv, pb, voX);
+            PFN_VLOAD_INTO("global_load_dword", t.yv, pa, voY);
+            PFN_VLOAD_INTO("global_load_dword", t.rs, prs, voR);
         };
         Slot ring[T3_R];
 #pragma unroll
@@ -304,7 +300,7 @@ __device__ __forceinline__ void t3_body(const T3Args& a, const T3Task& tk, int b
             }
             if (TWO_LEVEL && ((t0 / T3_R) & (T3_FLUSH - 1)) == T3_FLUSH - 1) flush();
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the over-fetched slots: nothing of the ring is in flight past here
+        vmem_drain();   // the over-fetched slots: nothing of the ring is in flight past here
     }
     // ragged tail: an odd row count leaves ONE row (kh = 0 only) for the row group whose turn it is -- compiler-visible
     // loads, the upper lane half contributes zeros

@@ -9,7 +9,7 @@
 //         per 32-column quarter q, per group g of four k's, 32 columns x 4 k's  ->  image[q][g][col][k & 3]; then the
 //         up to 4 trailing columns (H = 129 = 4*32 + 1) as rem[g][col][k & 3].  K is padded to a multiple of 8 with
 //         zeros.  A lane's B operands for four consecutive MFMA steps are one aligned 16-byte LDS read, and a quarter's
-//         k range is one contiguous run of whole KiBs -> copied to LDS by global_load_lds, no VGPR round trip.
+//         k range is one contiguous run of whole KiBs -> copied to LDS by LDS-DMA (device_prims.hpp dma_1k), no VGPR round trip.
 //  gemm : WEIGHT-STATIONARY.  The weights of ALL terms of a launch (<= 4 x 129 x 129 floats, for a slice of 128 / 64 /
 //         32 output columns) are loaded into LDS ONCE per block (<= 160 KiB), then the block's 8 waves run free:
 //         NO barrier and no LDS traffic other than B reads in the steady state.  Every wave owns 32-row tiles of A
@@ -35,9 +35,6 @@
 #include "pfn_internal.hpp"
 
 namespace pfn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NT_THREADS = 512;                 // (the streaming kernel's DMA deal assumes 8 waves)
 constexpr int NT_WAVES = NT_THREADS / 64;
@@ -97,25 +94,6 @@ int launch_pack(const PackJob* jobs, int njobs, uint64_t* rng_advance, hipStream
 }
 
 // ------------------------------------------------------------------------------------------------- NT
-// One 1 KiB LDS-DMA (64 lanes x 16 bytes; LDS destination = wave-uniform base + lane * 16).
-// Inline asm on purpose: while hipcc can see an LDS-DMA in flight it waits vmcnt(0) -- not a counted vmcnt -- for every
-// ordinary load it later needs.  Hidden from the compiler, the DMA is waited for by hand (dma_wait) before the barrier
-// that publishes the weights; the compiler's own counted waits stay correct because VMEM returns in issue order.
-__device__ __forceinline__ void dma_1k(const char* g, float* lds_dst) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((__attribute__((address_space(3))) float*)lds_dst));
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(g), "s"(m0v)
-        : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 // 4 x 4 transpose across the four lanes of a quad (DPP quad_perm, no LDS): on entry lane j of the quad holds v[i] =
 // M[i][j], on exit v[i] = M[j][i].  Turns the 32x32 accumulator layout (one column per lane) into four consecutive
 // columns of ONE row per lane, so the epilogue stores 16 bytes per lane (whole 128-byte lines per 8 lanes) instead of
@@ -191,68 +169,12 @@ struct NtArgs {
     float p_drop, gate_scale;
 };
 
-// ---- hand-managed VMEM.  In the steady state EVERY vector-memory instruction of a wave is inline asm, invisible to
-// hipcc's waitcnt insertion, and every wait is a hand-counted `s_waitcnt vmcnt(N)` tied to the registers it protects:
-//   * the A refill writes IN PLACE ("+v"): one 68-register fragment instead of the two sets the register allocator
-//     keeps for a visible load (a spill anywhere in the flush costs a vmcnt(0) drain per reload -- measured 18 us/flush);
-//   * a compiler-inserted wait would be vmcnt(0) (it cannot see the 17 younger prefetch loads) and drain the prefetch.
-// VMEM returns in issue order and vmcnt counts loads and stores alike, so "wait until at most N younger ops are
-// outstanding" is exact when N counts the ops issued after the one needed, and merely early when N is smaller.
-__device__ __forceinline__ void vload_x4(f32x4& dst, const char* sbase, uint32_t voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst) : "v"(voff), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ f32x4 vload_x4_addr(const float* p) {
-    f32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ float vload_x1_addr(const float* p) {
-    float r;
-    asm volatile("global_load_dword %0, %1, off" : "=v"(r) : "v"(p) : "memory");
-    return r;
-}
-__device__ __forceinline__ float vload_x1_sv(const char* sbase, uint32_t voff) {
-    float r;
-    asm volatile("global_load_dword %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");
-    return r;
-}
-// wave-uniform 64-bit base (SGPRs) + 32-bit per-lane byte offset: the address costs the VECTOR unit nothing (see vstore_x4 for WT and the s_nop)
-template <bool WT = false>
-__device__ __forceinline__ void vstore_x4_sv(const char* sbase, uint32_t voff, f32x4 v) {
-    if (WT) asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
-    else asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(sbase) : "memory");
-}
-// the same store under a lane mask held in SGPRs -- exec narrowed and restored INSIDE the asm block: no branch, so the store stays
-// in the basic block of the MFMAs it is interleaved with (gemm_nt_kernel's ILF); a lane whose mask bit is clear stores nothing
-__device__ __forceinline__ void vstore_x4_sv_masked(const char* sbase, uint32_t voff, f32x4 v, uint64_t mask) {
-    uint64_t keep;
-    asm volatile("s_mov_b64 %0, exec\n\ts_and_b64 exec, exec, %4\n\tglobal_store_dwordx4 %1, %2, %3\n\ts_mov_b64 exec, %0\n\ts_nop 1"
-                 : "=&s"(keep)
-                 : "v"(voff), "v"(v), "s"(sbase), "s"(mask)
-                 : "memory");
-}
-template <bool WT = false>
-__device__ __forceinline__ void vstore_x4(float* p, f32x4 v) {
-    // the s_nop is the ISA's "VMEM store wider than 64 bits -> VALU overwrites its data registers" hazard (2 wait states),
-    // which hipcc fills in for its own stores but cannot see inside inline asm (without it: intermittently wrong elements).
-    // WT = WRITE-THROUGH (sc1), the small-M kernels (CT < 2: one row tile per wave, the latency regime): a kernel's plain stores
-    // leave its output dirty in the XCD's L2 and the kernel boundary then waits for the write-back (MI355X_MICROARCH.md
-    // "boundary": + B / 6 TB/s behind B dirty bytes) -- ~1 us per launch of a chain whose every link is 10-30 us long; written
-    // through, the lines drain while the waves still multiply (back to back at 15,104 rows: 12.7 -> 11.9 / 18.9 -> 17.9 /
-    // 29.5 -> 28.7 us for 1 / 2 / 4 terms; `nt`: no change).  At large M it buys nothing and costs a few per cent: plain.
-    if (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-    else asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-}
+// (hand-managed VMEM -- vload_x4, vstore_x4*, wait_a and their wait-count rules: device_prims.hpp)
 // float offset of element (row, col) of an activation tensor: row-major [rows][ld] -- or chunk-major [ld / 4 planes][cm_rows][float4]
 // when cm_rows > 0 (col a multiple of 4 here: the kernels move float4s)
 __device__ __forceinline__ size_t act_off(int row, int col, int ld, int cm_rows) {
     return cm_rows > 0 ? ((size_t)(col >> 2) * cm_rows + row) * 4 : (size_t)row * ld + col;
 }
-template <int N>
-__device__ __forceinline__ void wait_a(f32x4& v) {   // the fragment chunk about to be consumed has landed
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
 // Multiply one LDS-resident piece into the accumulators and refill the A fragment for the next piece.
 //   NFAST: 17 / 16 = the piece has exactly that many chunks -> straight-line code; 0 = generic (per-chunk guard).
 //   LS   : MFMA steps of the LAST chunk that carry real k's (H = 129: k = 128 alone -> 1 step instead of 4; the other
@@ -332,7 +254,7 @@ __device__ __forceinline__ void nt_multiply(f32x16 (&acc)[CT > 0 ? CT : 1], floa
             // in-flight fragment registers.  Naming the sum here pins every chunk's fmas to their chunk.
             if (SLICED) {
 #pragma unroll
-                for (int c = 0; c < NR; ++c) asm volatile("" : "+v"(racc[c]));
+                for (int c = 0; c < NR; ++c) PFN_OPAQUE(racc[c]);
             }
         }
         // chunks consumed: refill them IN PLACE for the next piece -- four at a time.  A 128-byte line of a row holds four
@@ -482,7 +404,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
         const float* bsrc = a.rowscale ? a.rowbias : a.bias;
         for (int i = tid; i < a.ldc; i += NT_THREADS) lds[a.bias_lds_off + i] = (bsrc && i < a.ncols) ? bsrc[i] : 0.f;
     }
-    dma_wait();
+    vmem_drain();
     __syncthreads();   // the only barrier: from here on the waves run free
     if (rt >= nrt || !(mfma_on || rem_on)) return;
 
@@ -554,7 +476,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
     const NtPieceK pk = (NtPieceK)((const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(NtArgs, piece));
     int cur_gl = pk[0].gl, cur_lds = pk[0].lds_off, cur_klen = pk[0].klen;
     while (true) {
-        asm volatile("" : "+v"(kh4));   // opaque per round: keeps the 17 refill offsets from being hoisted into 17 VGPRs
+        PFN_OPAQUE(kh4);   // opaque per round: keeps the 17 refill offsets from being hoisted into 17 VGPRs
         // ---- the piece after this one: same row tile, next piece -- or the wave's next row tile, first piece
         int np = p + 1, nrt_ = rt;
         if (np == a.npiece) {
@@ -603,8 +525,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
         if constexpr (ILF) {
             if (a.rowscale)   // (clamped rows; loaded IN PLACE: a fresh output register would be merged into il_rs by a copy that runs
                               //  before the hidden load has landed)
-                asm volatile("global_load_dword %0, %1, %2" : "+v"(il_rs)
-                             : "v"((uint32_t)min(r32, a.M - 1 - rbase) * 4u), "s"(reinterpret_cast<const char*>(a.rowscale + rbase)) : "memory");
+                PFN_VLOAD_INTO("global_load_dword", il_rs, reinterpret_cast<const char*>(a.rowscale + rbase), (uint32_t)min(r32, a.M - 1 - rbase) * 4u);
         }
 #pragma unroll
         for (int ct = 0; ct < CTE; ++ct)
@@ -670,7 +591,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                 nt_multiply<CT, NR, NFAST, LS, 0, true>(acc, racc, a_cur, S, klen, a.tps, tsel, kh4, r32, nbase, nvoff, nkmax,
                                                         (uint32_t)nx_kscale, slice);
                 // ---- the tile just multiplied is parked (every piece of an ILF launch ends one); the next multiply flushes it
-                asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[CTE - 1]));   // (XDL write -> VALU read, see the flush)
+                PFN_XDL_SETTLE("+v"(acc[0]), "+v"(acc[CTE - 1]));   // (XDL write -> VALU read)
                 const bool use_bias = a.bias && (a.bias_group < 0 || a.bias_group == group);
                 if (a.rowscale) {   // the row scales requested before the multiply: the 17 refills (and the slices' stores) are younger
                     asm volatile("s_waitcnt vmcnt(17)" : "+v"(il_rs));
@@ -715,12 +636,10 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
             // ---- flush straight from registers: acc[q] of lane (r32, kh) is D[row (q&3) + 8 (q>>2) + 4 kh][col r32];
             // after the quad transpose lane (u = r32 >> 2, j = r32 & 3) holds, for register group g, row
             // rbase + j + 8 g + 4 kh and the four columns col0 .. col0 + 3
-            // The last MFMA was issued a few instructions ago and its 16 passes are still writing the accumulators; hipcc's
-            // hazard recognizer does not look past the inline asm that closes the multiply, so the >= 18 wait states an
-            // XDL write needs before a VALU read are spent by hand (without them: intermittently stale accumulator rows).
+            // (first the XDL write -> VALU read settle: device_prims.hpp PFN_XDL_SETTLE)
             if (CT > 0) {
-                if (CT == 2) asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[CTE - 1]));
-                else asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]));
+                if (CT == 2) PFN_XDL_SETTLE("+v"(acc[0]), "+v"(acc[CTE - 1]));
+                else PFN_XDL_SETTLE("+v"(acc[0]));
             }
             if constexpr (PAIR) {   // (earlier pieces) + this one: the pieces in piece order
 #pragma unroll
@@ -819,7 +738,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                             //  rounds' invariant parts out of the tile loop -- per-lane values alive through the whole
                             //  kernel, i.e. spills)
                             uint32_t cgv = (uint32_t)(col0 >> 2);
-                            asm volatile("" : "+v"(cgv));
+                            PFN_OPAQUE(cgv);
 #pragma unroll
                             for (int g = 0; g < 4; ++g) {
                                 float u[4];
@@ -863,7 +782,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                         float ud[4] = {1.f, 1.f, 1.f, 1.f};
                         if (ep.act == ACT_DROPOUT_RELU) {
                             uint32_t cgv = (uint32_t)(rem_col >> 2);
-                            asm volatile("" : "+v"(cgv));
+                            PFN_OPAQUE(cgv);
                             dropout_uniform4(ep.dk, (uint32_t)(row + a.row0), cgv, ud);
                         }
 #pragma unroll
@@ -891,7 +810,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
         }
         if constexpr (PAIR) {
             if (!flush_after) {   // a piece of the tile is done, more follow: its sum joins the finished ones, the chain starts anew
-                if (CT > 0) asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]));   // (XDL write -> VALU read, see the flush)
+                if (CT > 0) PFN_XDL_SETTLE("+v"(acc[0]));   // (XDL write -> VALU read)
 #pragma unroll
                 for (int ct = 0; ct < CTE; ++ct)
 #pragma unroll
@@ -1051,7 +970,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
 
     int p = 0;
     for (int s = 0; s < total; ++s) {
-        asm volatile("" : "+v"(kh4));   // opaque per round: keeps the 17 refill offsets from being hoisted into 17 VGPRs
+        PFN_OPAQUE(kh4);   // opaque per round: keeps the 17 refill offsets from being hoisted into 17 VGPRs
         int np = p + 1, nrt_ = rt;
         if (np == a.npiece) {
             np = 0;
@@ -1062,7 +981,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
         const bool flush_after = last || np == 0 || a.piece[np].group != group;
         // ---- piece s has landed in buffer s & 1 (this wave's share: the first piece is the youngest thing in flight; later the
         // 17 refills of the previous multiply are younger), every wave is done reading the other buffer: one barrier says both
-        if (s == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (s == 0) vmem_drain();
         else asm volatile("s_waitcnt vmcnt(17)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");
         issue_dma(last ? p : np, (s + 1) & 1);              // (nothing follows the last piece: a harmless copy keeps the counts)
@@ -1073,8 +992,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
                                                            a_voff(rti, pi), a.piece[pi].kmax, (uint32_t)a.piece[pi].kscale);
         }
         if (flush_after) {
-            // the accumulators are still being written by the last MFMAs (see the stationary kernel's flush)
-            asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
+            PFN_XDL_SETTLE("+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
             const int rbase = prt(rt < nrt ? rt : nrt - 1) * 32;
             const bool live = rt < nrt;
             float* C = a.C[group];
@@ -1166,7 +1084,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
                         for (int e = 0; e < 4; ++e) v[g][e] = fmaxf(v[g][e], 0.f);
                 } else if (ep.act == ACT_DROPOUT_RELU) {
                     uint32_t cgv = (uint32_t)(col0 >> 2);
-                    asm volatile("" : "+v"(cgv));
+                    PFN_OPAQUE(cgv);
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         float u[4];
@@ -1198,7 +1116,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
                     } else if (ep.act == ACT_DROPOUT_RELU) {
                         float ud[4];
                         uint32_t cgv = (uint32_t)(rem_col >> 2);
-                        asm volatile("" : "+v"(cgv));
+                        PFN_OPAQUE(cgv);
                         dropout_uniform4(ep.dk, (uint32_t)(row + a.row0), cgv, ud);
                         x = (ud[0] >= ep.p_drop && x > 0.f) ? x * ep.keep_scale : 0.f;
                     }
@@ -1215,7 +1133,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
         p = np;
         rt = nrt_;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last DMA / refills: nothing of this block is in flight past here
+    vmem_drain();   // the last DMA / refills: nothing of this block is in flight past here
 }
 
 

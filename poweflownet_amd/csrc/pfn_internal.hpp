@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "../../include/pfn_hip.h"
+#include "device_prims.hpp"
 
 namespace pfn {
 
@@ -158,20 +159,18 @@ size_t packed_floats(int K, int ld_out);
 // 544): every piece of a wide product is then the straight-line 17-chunk kind (the zero rows multiply clamped A reads), which is
 // what lets the weight-streaming kernel take it
 __host__ __device__ inline int k8_of(int K) { return K <= 136 ? ((K + 7) & ~7) : (K + 135) / 136 * 136; }
-__host__ __device__ inline size_t packed_fp32_floats(int K, int ld_out) {
-    int remv, nq;
-    const int m = ld_out & 31;
-    remv = (m != 0 && m <= 4) ? m : 0;
-    nq = (ld_out - remv + 31) / 32;
-    const int G = k8_of(K) >> 2;
-    return (size_t)(((int64_t)nq * G * 128 + (int64_t)G * 16 + 255) / 256 * 256);
-}
 // column plan of an output of `ld` (padded) columns: `remv` trailing columns (0 or 4) go to the VALU path when that
 // saves a whole MFMA quarter; `nq` 32-column MFMA quarters.
 __host__ __device__ inline void col_plan(int ld, int& remv, int& nq) {
     const int m = ld & 31;
     remv = (m != 0 && m <= 4) ? m : 0;
     nq = (ld - remv + 31) / 32;
+}
+__host__ __device__ inline size_t packed_fp32_floats(int K, int ld_out) {
+    int remv, nq;
+    col_plan(ld_out, remv, nq);
+    const int G = k8_of(K) >> 2;
+    return (size_t)(((int64_t)nq * G * 128 + (int64_t)G * 16 + 255) / 256 * 256);
 }
 // one block's share (block bx of nbx) of one weight re-layout job
 __device__ inline void pack_job_body(const PackJob& jb, int bx, int nbx) {
@@ -583,16 +582,6 @@ int launch_pad_rows(const float* src, int64_t ld_src, float* dst, int64_t ld_dst
 int launch_export_edge_gates(const GraphView& g, const float* P, const float* Q, const float* ea, const float* w1, int ld, int h, int fi,
                              int fe, uint8_t* out, hipStream_t s);
 int launch_export_row_gates(int64_t n, int h, int ld, const float* y, int cm, uint8_t* out, hipStream_t s);
-
-// 16-byte WRITE-THROUGH store of a kernel OUTPUT (global memory only; sc1).  A chain kernel's plain stores leave its output dirty
-// in the XCD's L2, and the kernel boundary then waits for the write-back (MI355X_MICROARCH.md "boundary"); written through, the
-// lines drain while the kernel still runs.  Inline asm (hipcc has no 128-bit scoped store); the s_nop is the ISA's "VMEM store
-// wider than 64 bits -> VALU overwrites its data registers" hazard, invisible to hipcc inside the asm.
-__device__ __forceinline__ void st4_wt(float* p, float4 v) {
-    typedef float f4wt_ __attribute__((ext_vector_type(4)));
-    const f4wt_ d = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
-}
 
 // ---------------------------------------------------------------------------------------- dropout RNG
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter-based, so the mask of a

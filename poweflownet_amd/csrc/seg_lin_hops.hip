@@ -23,10 +23,6 @@
 
 namespace pfn {
 
-__device__ __forceinline__ float4 slh_sel4(bool k, float4 a, float4 b) {   // (element-wise: a ?: on the struct goes through scratch)
-    return make_float4(k ? a.x : b.x, k ? a.y : b.y, k ? a.z : b.z, k ? a.w : b.w);
-}
-
 constexpr int SLH_REM_FLOATS = SG_NCH * 32;   // trailing-column image of one term: 34 k groups x [4 columns][4 k's]
 
 struct SlhLds {
@@ -140,8 +136,8 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
     float4 rem0 = make_float4(0.f, 0.f, 0.f, 0.f), rem1 = rem0;
     if (sc.rem && tid < SLH_REM_FLOATS / 4) {       // trailing-column images: behind the nq quarters of the packed image
         const size_t roff = (size_t)sc.nq * (K8 >> 2) * 128;
-        rem0 = sg_ld4(a.B0 + roff + tid * 4);
-        if (NTERM > 1) rem1 = sg_ld4(a.B1 + roff + tid * 4);
+        rem0 = ld4(a.B0 + roff + tid * 4);
+        if (NTERM > 1) rem1 = ld4(a.B1 + roff + tid * 4);
     }
     float bv = 0.f;
     if (tid < SG_TW) {
@@ -156,7 +152,7 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
         gv[j] = make_float4(1.f, 1.f, 1.f, 1.f);
         if (a.gate && it < nitems) {
             const int lr = it / sc.cw, lc = it - lr * sc.cw;
-            gv[j] = sg_ld4(a.gate + (size_t)(r0 + lr) * a.ldg + seg_gcol(sc, lc));
+            gv[j] = ld4(a.gate + (size_t)(r0 + lr) * a.ldg + seg_gcol(sc, lc));
         }
     }
     const int nbv = (nb_in_lds && tid < ne) ? nbr[e0 + tid] : 0;   // (second level: needs e0)
@@ -168,8 +164,8 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
     if (nb_in_lds && tid < ne) l.nb[tid] = nbv - r0;
     if (tid < SG_TW) l.bias[tid] = bv;
     if (sc.rem && tid < SLH_REM_FLOATS / 4) {
-        sg_st4(l.R[0] + tid * 4, rem0);
-        if (NTERM > 1) sg_st4(l.R[1] + tid * 4, rem1);
+        st4(l.R[0] + tid * 4, rem0);
+        if (NTERM > 1) st4(l.R[1] + tid * 4, rem1);
     }
     // the gate is only ever asked `> 0`: four bits per item instead of four registers through the multiply phase
     unsigned gbits = 0u;
@@ -180,7 +176,7 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
     // multiply runs while it arrives (protocol: seg_tile.hpp seg_load_a_async)
     seg_drain_visible();
     if (mfma_on) seg_load_a_async(ta, (NTERM > 1 && mterm) ? a.A1 : a.A0, a.lda, r0 + 32 * mtile, r0 + rows - 1, lane);
-    seg_lds_barrier();
+    lds_barrier();
     // ---- the Linear's tiles.  The terms of a tile go into ONE accumulator chain in term order (gemm_nt's order: bit-identical
     // sums): the wave that owns (tile, term 1) takes over the accumulators -- and the trailing column's two half-chains -- that
     // the wave of (tile, term 0) leaves in LDS.  (One wave running both terms needs the second fragment refilled in place under
@@ -204,7 +200,7 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
                     l.rq[mtile * 64 + lane] = racc;
                 } else {
                     const float tot = racc + __shfl_xor(racc, 32);           // the two k halves
-                    if (lane < 32) sg_st4(l.t0 + (size_t)(32 * mtile + lane) * SG_TW + 32, make_float4(tot, 0.f, 0.f, 0.f));
+                    if (lane < 32) st4(l.t0 + (size_t)(32 * mtile + lane) * SG_TW + 32, make_float4(tot, 0.f, 0.f, 0.f));
                 }
             }
         }
@@ -223,11 +219,11 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
         if (it < nitems) {
             const int lr = it / sc.cw, lc = it - lr * sc.cw;
             const int tc = seg_tcol(sc, lc), gc = seg_gcol(sc, lc);
-            const float4 v4 = sg_ld4(l.t0 + (size_t)lr * SG_TW + tc);
+            const float4 v4 = ld4(l.t0 + (size_t)lr * SG_TW + tc);
             float v[4] = {v4.x, v4.y, v4.z, v4.w};
             if (a.rowscale) {
                 const float rs = l.rsc[lr];
-                const float4 cb = sg_ld4(l.bias + tc);
+                const float4 cb = ld4(l.bias + tc);
                 v[0] = fmaf(rs, cb.x, v[0]); v[1] = fmaf(rs, cb.y, v[1]); v[2] = fmaf(rs, cb.z, v[2]); v[3] = fmaf(rs, cb.w, v[3]);
             }
             if (a.act == ACT_RELU) {
@@ -246,11 +242,11 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = gc + e < a.ncols ? v[e] : 0.f;   // (pad columns stay zero: the layout invariant)
             const float4 o4 = make_float4(v[0], v[1], v[2], v[3]);
-            sg_st4(l.t0 + (size_t)lr * SG_TW + tc, o4);
-            sg_st4_wt(a.y + (size_t)(r0 + lr) * a.ld + gc, o4);
+            st4(l.t0 + (size_t)lr * SG_TW + tc, o4);
+            st4_wt(a.y + (size_t)(r0 + lr) * a.ld + gc, o4);
         }
     }
-    seg_lds_barrier();   // (not __syncthreads(): the y stores drain while the hops run)
+    lds_barrier();   // (not __syncthreads(): the y stores drain while the hops run)
     // ---- K hops, ping-pong between the two tiles (fused_hops_kernel's walk: four slots per trip, edge-id order).  A row's first
     // four slots -- all of most rows of a power grid -- are planned ONCE for the K hops: tile offsets of the neighbour rows and the
     // edge weights dinv[src] * dinv[dst] in registers, so a hop is four independent tile reads and four fmas per item instead of
@@ -274,15 +270,15 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 w_[u] = l.dinv[s_[u]] * di;
-                x_[u] = sg_ld4(slh_smem + cur + (uint32_t)(s_[u] * SG_TW + tc));
+                x_[u] = ld4(slh_smem + cur + (uint32_t)(s_[u] * SG_TW + tc));
             }
-            h = sg_fma4(w_[0], x_[0], h);
-            h = slh_sel4(p + 1 < end, sg_fma4(w_[1], x_[1], h), h);
-            h = slh_sel4(p + 2 < end, sg_fma4(w_[2], x_[2], h), h);
-            h = slh_sel4(p + 3 < end, sg_fma4(w_[3], x_[3], h), h);
+            h = fma4(w_[0], x_[0], h);
+            h = sel4(p + 1 < end, fma4(w_[1], x_[1], h), h);
+            h = sel4(p + 2 < end, fma4(w_[2], x_[2], h), h);
+            h = sel4(p + 3 < end, fma4(w_[3], x_[3], h), h);
         }
-        if (!last) sg_st4(slh_smem + nxt + (uint32_t)(lr * SG_TW + tc), h);
-        sg_st4_wt(gout + (size_t)(r0 + lr) * a.ld + gc, h);
+        if (!last) st4(slh_smem + nxt + (uint32_t)(lr * SG_TW + tc), h);
+        st4_wt(gout + (size_t)(r0 + lr) * a.ld + gc, h);
     };
     if (nb_in_lds) {
         uint32_t h_to[2], h_go[2], h_so[2][4];
@@ -312,14 +308,14 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v_[j][u] = sg_ld4(slh_smem + cur + h_so[j][u]);
+                for (int u = 0; u < 4; ++u) v_[j][u] = ld4(slh_smem + cur + h_so[j][u]);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-                float4 h = slh_sel4(h_cnt[j] > 0, sg_fma4(h_w[j][0], v_[j][0], z), z);
-                h = slh_sel4(h_cnt[j] > 1, sg_fma4(h_w[j][1], v_[j][1], h), h);
-                h = slh_sel4(h_cnt[j] > 2, sg_fma4(h_w[j][2], v_[j][2], h), h);
-                h = slh_sel4(h_cnt[j] > 3, sg_fma4(h_w[j][3], v_[j][3], h), h);
+                float4 h = sel4(h_cnt[j] > 0, fma4(h_w[j][0], v_[j][0], z), z);
+                h = sel4(h_cnt[j] > 1, fma4(h_w[j][1], v_[j][1], h), h);
+                h = sel4(h_cnt[j] > 2, fma4(h_w[j][2], v_[j][2], h), h);
+                h = sel4(h_cnt[j] > 3, fma4(h_w[j][3], v_[j][3], h), h);
                 if (h_cnt[j] > 4) {   // the rest of a longer row: the generic walk
                     const int end = h_beg[j] + h_cnt[j], lastp = end - 1;
                     for (int p = h_beg[j] + 4; p < end; p += 4) {
@@ -331,21 +327,21 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
 #pragma unroll
                         for (int u = 0; u < 4; ++u) {
                             w_[u] = l.dinv[s_[u]] * h_di[j];
-                            x_[u] = sg_ld4(slh_smem + cur + (uint32_t)(s_[u] * SG_TW + h_tc[j]));
+                            x_[u] = ld4(slh_smem + cur + (uint32_t)(s_[u] * SG_TW + h_tc[j]));
                         }
-                        h = sg_fma4(w_[0], x_[0], h);
-                        h = slh_sel4(p + 1 < end, sg_fma4(w_[1], x_[1], h), h);
-                        h = slh_sel4(p + 2 < end, sg_fma4(w_[2], x_[2], h), h);
-                        h = slh_sel4(p + 3 < end, sg_fma4(w_[3], x_[3], h), h);
+                        h = fma4(w_[0], x_[0], h);
+                        h = sel4(p + 1 < end, fma4(w_[1], x_[1], h), h);
+                        h = sel4(p + 2 < end, fma4(w_[2], x_[2], h), h);
+                        h = sel4(p + 3 < end, fma4(w_[3], x_[3], h), h);
                     }
                 }
                 if (tid + j * SG_THREADS < nitems) {
-                    if (!last) sg_st4(slh_smem + nxt + h_to[j], h);
-                    sg_st4_wt(gout + h_go[j], h);
+                    if (!last) st4(slh_smem + nxt + h_to[j], h);
+                    st4_wt(gout + h_go[j], h);
                 }
             }
             for (int it = tid + 2 * SG_THREADS; it < nitems; it += SG_THREADS) walk_item(it, gout, last);
-            seg_lds_barrier();
+            lds_barrier();
             const uint32_t t = cur;
             cur = nxt;
             nxt = t;
@@ -354,7 +350,7 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
         for (int k = 1; k <= a.nhops; ++k) {
             float* gout = a.xk + (size_t)(k - 1) * a.stride;
             for (int it = tid; it < nitems; it += SG_THREADS) walk_item(it, gout, k == a.nhops);
-            seg_lds_barrier();
+            lds_barrier();
             const uint32_t t = cur;
             cur = nxt;
             nxt = t;

@@ -5,9 +5,6 @@
 
 namespace pfn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SG_WAVES = 8;          // waves that share one seg_copy_b (ea_seg.hip: 512-thread blocks)
 
 // One 32 x 32 MFMA tile of  A[rows r_first..][0..K) * image quarter q  (K <= 136: one piece), written to an LDS tile.
@@ -36,7 +33,7 @@ __device__ __forceinline__ void seg_load_a(SegA& t, const float* __restrict__ A,
 //   1. every OTHER load of the prologue is consumed and a compiler-VISIBLE `s_waitcnt vmcnt(0)` (seg_drain_visible) has run before
 //      these loads go out: hipcc then knows of nothing pending and places no wait of its own behind them (with visible loads it
 //      cannot prove finished across the kernels' branches it puts a vmcnt(0) -- a full drain -- in front of the first MFMA);
-//   2. the barrier that follows waits for LDS only (seg_lds_barrier);
+//   2. the barrier that follows waits for LDS only (lds_barrier);
 //   3. nothing reads, copies or spills t.av[] before its chunk's wait (no "+v" ties: those made hipcc copy a fragment register
 //      BEFORE the wait); the waits are pinned between sched_barriers so no MFMA moves above its wait.
 // Why: the fragment -- 16 bytes per lane out of 32 different rows per instruction -- is the slowest thing a graph-resident
@@ -65,33 +62,12 @@ __device__ __forceinline__ void seg_wait_chunk(const SegA& t) {
     asm volatile("" ::"v"(t.av[M]));
     __builtin_amdgcn_sched_barrier(0);
 }
-// One 1 KiB LDS-DMA (64 lanes x 16 bytes; LDS destination = wave-uniform base + lane * 16); inline asm as in gemm_nt.hip: hidden
-// from the compiler, waited for by hand (seg_dma_wait) before the barrier that publishes the copy
-__device__ __forceinline__ void seg_dma_1k(const char* g, float* lds_dst) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((__attribute__((address_space(3))) float*)lds_dst));
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(g), "s"(m0v)
-        : "memory");
-}
-// Barrier that publishes LDS writes only: __syncthreads() also waits (vmcnt(0)) until every global STORE of the wave is acknowledged --
-// a round trip of 1-2 us under load that a kernel pays at every barrier that follows its output stores (phase timestamps: 1.5 us
-// per hop of seg_lin_hops_kernel).  Use only where no thread reads another thread's GLOBAL writes after the barrier.
-__device__ __forceinline__ void seg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ void sg_st4_wt(float* p, float4 v) { st4_wt(p, v); }   // (pfn_internal.hpp: write-through output store)
-__device__ __forceinline__ void seg_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // quarter q of a packed image (G * 128 floats, whole KiBs) -> LDS, the 1 KiB pieces dealt round-robin to the block's waves
 __device__ __forceinline__ void seg_copy_b(float* dst, const float* __restrict__ Bp, int q, int K8, int wave, int lane,
                                            int nwaves = SG_WAVES) {
     const int nfl = (K8 >> 2) * 128;
     const char* src = reinterpret_cast<const char*>(Bp + (size_t)q * nfl) + lane * 16;
-    for (int off = wave * 256; off < nfl; off += nwaves * 256) seg_dma_1k(src + (size_t)off * 4, dst + off);
+    for (int off = wave * 256; off < nfl; off += nwaves * 256) dma_1k(src + (size_t)off * 4, dst + off);
 }
 // (one accumulator chain: a second, independent one changed nothing -- the MFMA pipe is shared by 2-4 waves per SIMD here, and
 //  tools/ubench/mfma_peak.hip reaches 147 TF with a single dependent chain per wave)
@@ -149,9 +125,6 @@ constexpr int SG_TW = 36;            // LDS tile row stride (floats): 32 quarter
 constexpr int SG_MAX_ROWS = 128;     // rows of whole graphs per workgroup (4 row tiles: one MFMA task per wave at most)
 constexpr int SG_LDS_BYTES = 78 * 1024;   // two workgroups per CU
 
-__device__ __forceinline__ float4 sg_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void sg_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-
 // accumulator register 4g + e of lane (r32, kh) = row 8g + 4kh + e, column r32
 __device__ __forceinline__ void seg_store_tile(const f32x16& acc, int q, const float* __restrict__ bias, int ncols, float* tile,
                                                int trow0, int lane) {
@@ -185,12 +158,6 @@ __device__ __forceinline__ int seg_tcol(const SegCols& c, int lc) { return (c.re
 __device__ __forceinline__ int seg_gcol(const SegCols& c, int lc) { return (c.rem && lc == c.cw - 1) ? 32 * c.nq : c.col0 + 4 * lc; }
 // global column of LDS tile column t (0..31: the quarter; 32..35: the trailing columns), -1: not in this block
 __device__ __forceinline__ int seg_col_of_tile(const SegCols& c, int t) { return t < 32 ? c.col0 + t : (c.rem && t - 32 < c.remv ? 32 * c.nq + t - 32 : -1); }
-
-__device__ __forceinline__ float4 sg_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 sg_fma4(float a, float4 x, float4 acc) {
-    return make_float4(fmaf(a, x.x, acc.x), fmaf(a, x.y, acc.y), fmaf(a, x.z, acc.z), fmaf(a, x.w, acc.w));
-}
-__device__ __forceinline__ float4 sg_relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
 
 
 }  // namespace pfn

@@ -103,16 +103,16 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ o, c
     }
     if (threadIdx.x == 0) {
         // hand-off to the last arriver without __threadfence() (an L2 write-back + L1 invalidate, ~3.5 us each on this
-        // multi-XCD part, and the kernel had two): the partial is stored WRITE-THROUGH (agent-scope atomic store = sc1), the
-        // store is drained, then the ticket is taken; the last arriver reads the partials with agent-scope atomic loads (sc1:
-        // served by L2 / memory, never by its L1).  This is the "sc1 payload -> asm vmcnt(0) -> flag, sc1 loads on the consumer"
-        // form MI355X_MICROARCH.md lists as valid ON gfx950 (vmcnt covers stores there; the language memory model does not
+        // multi-XCD part, and the kernel had two): the partial is stored WRITE-THROUGH (agent-scope atomic store), the
+        // store is drained (vmem_drain), then the ticket is taken; the last arriver reads the partials with agent-scope atomic loads
+        // (served by L2 / memory, never by its L1).  This is the "write-through payload -> asm vmcnt(0) -> flag, agent-scope loads on
+        // the consumer" form MI355X_MICROARCH.md lists as valid ON gfx950 (vmcnt covers stores there; the language memory model does not
         // promise it) -- hence the target guard below, and tests/test_gpu_parity.py::test_mse_loss_handoff_stress.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "mse_kernel's last-arriver hand-off relies on gfx950 semantics (sc1 write-through stores drained by s_waitcnt vmcnt(0))"
+#error "mse_kernel's last-arriver hand-off relies on gfx950 semantics (write-through stores drained by s_waitcnt vmcnt(0))"
 #endif
         __hip_atomic_store(partial + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vmem_drain();
         const int t = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_last = t == (int)gridDim.x - 1;
     }

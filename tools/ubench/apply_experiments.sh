@@ -5,6 +5,6 @@
 set -e
 here=$(cd "$(dirname "$0")" && pwd)
 cd "$1"
-for f in ea_seg.hip edge.hip gemm.hip gemm_nt.hip seg_lin_hops.hip pfn_internal.hpp seg_tile.hpp; do
+for f in ea_seg.hip edge.hip gemm.hip gemm_nt.hip seg_lin_hops.hip pfn_internal.hpp device_prims.hpp seg_tile.hpp; do
     patch -s -p0 "$f" < "$here/experiments_${f%.*}.patch.txt"
 done

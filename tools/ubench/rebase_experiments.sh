@@ -11,7 +11,7 @@ mkdir "$tmp/csrc"
 cp "$root"/poweflownet_amd/csrc/*.hip "$root"/poweflownet_amd/csrc/*.hpp "$tmp/csrc/"
 bash "$here/apply_experiments.sh" "$tmp/csrc"
 if ls "$tmp"/csrc/*.rej >/dev/null 2>&1; then echo "rejected hunks:"; ls "$tmp"/csrc/*.rej; exit 1; fi
-for f in ea_seg.hip edge.hip gemm.hip gemm_nt.hip seg_lin_hops.hip pfn_internal.hpp seg_tile.hpp; do
+for f in ea_seg.hip edge.hip gemm.hip gemm_nt.hip seg_lin_hops.hip pfn_internal.hpp device_prims.hpp seg_tile.hpp; do
     out="$here/experiments_${f%.*}.patch.txt"
     (cd "$root" && diff -u --label "poweflownet_amd/csrc/$f" --label "$f (with the experiment switches)" "poweflownet_amd/csrc/$f" "$tmp/csrc/$f" > "$out") || true
 done
