@@ -292,6 +292,34 @@ int pfn_khop_pack(const void* graph_ws, int64_t n_nodes, int64_t e_stored, const
                   const int64_t* node_off, const int64_t* edge_off, int64_t n_inst, int64_t total_edges, int64_t* node_ids,
                   int64_t* edge_index_out, int64_t* edge_ids, int64_t* center_pos, int32_t* err, void* stream);
 
+/* ------------------------------------------------------------------------- mixed-size batches in equal segments
+ * A batch whose graphs differ in size, re-laid on the device into n_pad / seg_nodes segments of seg_nodes rows (the plan comes from
+ * the host: poweflownet_amd/segpack.py, first-fit-decreasing into bins of max(size) rows): graph g -- the caller's rows
+ * ptr[g] .. ptr[g + 1] -- starts at padded row start[g]; the graphs of a segment are contiguous; the last seg_nodes - fill[seg] rows
+ * of a segment are padding.  No edge then crosses a multiple of seg_nodes, which is all pfn_graph_segments asks, so the model entry
+ * points run on the padded tensors with that seg_nodes; an isolated padding row receives and sends no message and adds exact
+ * zeros to every weight gradient.  Per-batch host -> device traffic is ptr, start and fill: O(graphs), not O(nodes).
+ *
+ * pfn_segpack_pack (two launches, nothing waits across workgroups): ptr [n_graphs + 1], start [n_graphs], fill [n_pad / seg_nodes]
+ * int32; x [N, 4] f32; pred_mask [N, 4] (mask_dtype 0: int64, 1: float32); edge_index [2, e_stored] int64 ->
+ *   x_pad, mask_pad [n_pad, 4] f32     the rows moved, mask as float, padding rows all zero
+ *   edge_index_pad [2, e_stored]       the same edges in the same order, endpoints relabelled (edge_attr and the edge ids stay what
+ *                                      they were); an id outside [0, N) becomes -1, which pfn_graph_build then reports
+ *   row_of [N], src_of [n_pad] int32   the padded row of every real row, and the real row of every padded row (-1: padding)
+ * x, pred_mask, edge_index and their padded copies must be 16-byte aligned.                                                     */
+int pfn_segpack_pack(const int32_t* ptr, const int32_t* start, const int32_t* fill, int64_t n_graphs, int64_t n_nodes,
+                     int64_t seg_nodes, int64_t n_pad, const float* x, const void* pred_mask, int mask_dtype, const int64_t* edge_index,
+                     int64_t e_stored, float* x_pad, float* mask_pad, int64_t* edge_index_pad, int32_t* row_of, int32_t* src_of,
+                     void* stream);
+/* dst[i, :f] = src_pad[row_of[i], :f] for the n_nodes real rows (separate leading dimensions): un-pads outputs, input gradients
+ * and exported gates.                                                                                                           */
+int pfn_segpack_gather_rows(const float* src_pad, int64_t ld_src, int64_t n_pad, const int32_t* row_of, float* dst, int64_t ld_dst,
+                            int64_t n_nodes, int64_t f, void* stream);
+/* Its adjoint, dst_pad[row_of[i], :f] = src[i, :f], evaluated as a gather through src_of: ONE launch writes every row of dst_pad,
+ * the padding rows as zeros (no memset beside it).                                                                              */
+int pfn_segpack_scatter_rows(const float* src, int64_t ld_src, int64_t n_nodes, const int32_t* src_of, float* dst_pad, int64_t ld_dst,
+                             int64_t n_pad, int64_t seg_nodes, int64_t f, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

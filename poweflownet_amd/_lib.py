@@ -24,6 +24,7 @@ SYMBOLS = (
     "pfn_scatter_add", "pfn_pad_rows", "pfn_mse_loss", "pfn_masked_l2_loss", "pfn_power_imbalance", "pfn_dropout_mask", "pfn_adamw_step", "pfn_adamw_step_dev", "pfn_adamw_step_guarded",
     "pfn_profile_enable", "pfn_profile_report",
     "pfn_khop_distances", "pfn_khop_histograms", "pfn_khop_pack",
+    "pfn_segpack_pack", "pfn_segpack_gather_rows", "pfn_segpack_scatter_rows",
 )
 
 
@@ -90,6 +91,9 @@ def load() -> C.CDLL:
         "pfn_khop_distances": (C.c_int, [p, i64, i64, p, i64, i32, p, p, p]),
         "pfn_khop_histograms": (C.c_int, [p, i64, i64, p, i64, i32, p, p, p]),
         "pfn_khop_pack": (C.c_int, [p, i64, i64, p, p, p, p, p, p, p, p, i64, i64, p, p, p, p, p, p]),
+        "pfn_segpack_pack": (C.c_int, [p, p, p, i64, i64, i64, i64, p, p, i32, p, i64, p, p, p, p, p, p]),
+        "pfn_segpack_gather_rows": (C.c_int, [p, i64, i64, p, p, i64, i64, i64, p]),
+        "pfn_segpack_scatter_rows": (C.c_int, [p, i64, i64, p, p, i64, i64, i64, i64, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -50,6 +50,7 @@ class Data:
         for k in self._keys:
             v = getattr(self, k)
             setattr(out, k, v.to(device, non_blocking=non_blocking) if torch.is_tensor(v) else v)
+        self._carry_sizes(out)
         return out
 
     def clone(self):
@@ -58,7 +59,15 @@ class Data:
         for k in self._keys:
             v = getattr(self, k)
             setattr(out, k, v.clone() if torch.is_tensor(v) else v)
+        self._carry_sizes(out)
         return out
+
+    def _carry_sizes(self, out):
+        # `_graph_sizes` (Batch): host-side node counts of the collated graphs.  An underscore attribute -- not a key, so
+        # `keys()` and `len()` are what they are without it -- hence carried by hand
+        sizes = self.__dict__.get("_graph_sizes")
+        if sizes is not None:
+            out._graph_sizes = sizes
 
     def __repr__(self):
         parts = [f"{k}={list(getattr(self, k).shape)}" if torch.is_tensor(getattr(self, k)) else f"{k}={getattr(self, k)!r}"
@@ -67,7 +76,10 @@ class Data:
 
 
 class Batch(Data):
-    """Block-diagonal concatenation of `Data` objects (PyG `Batch.from_data_list` rule)."""
+    """Block-diagonal concatenation of `Data` objects (PyG `Batch.from_data_list` rule).
+
+    `_graph_sizes`: the node count of every collated graph as a tuple of ints ON THE HOST (what `ptr` holds on the device): lets
+    the model see that a batch is ragged, and plan its segment layout, without a device read-back (`segpack.plan`)."""
 
     @classmethod
     def from_data_list(cls, data_list: Sequence[Data]) -> "Batch":
@@ -91,6 +103,7 @@ class Batch(Data):
         out.batch = torch.repeat_interleave(torch.arange(len(data_list), device=dev),
                                             torch.tensor(counts, device=dev))
         out.ptr = torch.tensor(offsets, dtype=torch.long, device=dev)
+        out._graph_sizes = tuple(counts)
         return out
 
     @property

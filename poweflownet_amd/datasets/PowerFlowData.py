@@ -208,8 +208,9 @@ class PowerFlowData:
 
     def collate_indices(self, indices: Sequence[int]) -> Batch:
         """The batch PyG's collate would build from samples `indices` (cat along dim 0, edge_index offset by the cumulative
-        node count, `batch`, `ptr`) -- assembled on the dataset's device with one gather per field.  Falls back to the
-        per-sample rule for list-backed datasets, mixed grid cases in one batch, and sample-dependent topologies."""
+        node count, `batch`, `ptr`) -- assembled on the dataset's device with one gather per field; with several grid cases in one
+        split (`case='mixed'`) with one gather and one indexed write per case and field (`_collate_blocks`).  Falls back to the
+        per-sample rule for list-backed datasets and datasets with a transform."""
         if self._list is None and len(self._blocks) == 1 and self.transform is None:
             b = self._blocks[0]
             dev = b.x.device
@@ -234,4 +235,58 @@ class PowerFlowData:
             out.batch = torch.arange(B, device=dev).repeat_interleave(n)
             out.ptr = torch.arange(B + 1, device=dev) * n
             return out
+        if self._list is None and self.transform is None and len(self._blocks) > 1:
+            return self._collate_blocks(indices)
         return Batch.from_data_list([self[i] for i in indices])
+
+    def _collate_blocks(self, indices: Sequence[int]) -> Batch:
+        """`Batch.from_data_list([self[i] for i in indices])`, field by field and bit for bit, for a split of several grid cases:
+        the indices are grouped by case on the host; per case and field ONE index_select takes the samples and ONE indexed write
+        puts them at the rows (edges) `ptr` assigns to their batch positions -- the number of torch calls follows the number of
+        cases, not of samples.  The batch carries its size list (`Batch._graph_sizes`)."""
+        idx = np.asarray(list(indices), dtype=np.int64)
+        if idx.size == 0:
+            raise ValueError("empty data list")
+        total = self._dense_len()
+        idx = np.where(idx < 0, idx + total, idx)
+        if idx.min() < 0 or idx.max() >= total:
+            raise IndexError("sample index out of range")
+        bounds = np.cumsum([0] + [len(b) for b in self._blocks])
+        which = np.searchsorted(bounds, idx, side="right") - 1            # the case every batch position draws from
+        n_of = np.asarray([b.x.shape[1] for b in self._blocks], dtype=np.int64)
+        e_of = np.asarray([b.edge_index.shape[2] for b in self._blocks], dtype=np.int64)
+        sizes, esizes = n_of[which], e_of[which]
+        ptr = np.concatenate([[0], np.cumsum(sizes)])
+        eptr = np.concatenate([[0], np.cumsum(esizes)])
+        N, E, B = int(ptr[-1]), int(eptr[-1]), int(idx.size)
+        b0 = self._blocks[0]
+        dev = b0.x.device
+        out = Batch()
+        out.x = torch.empty(N, b0.x.shape[2], dtype=b0.x.dtype, device=dev)
+        out.y = torch.empty(N, b0.y.shape[2], dtype=b0.y.dtype, device=dev)
+        out.bus_type = torch.empty(N, dtype=b0.bus_type.dtype, device=dev)
+        out.pred_mask = torch.empty(N, b0.pred_mask.shape[2], dtype=b0.pred_mask.dtype, device=dev)
+        out.edge_index = torch.empty(2, E, dtype=torch.long, device=dev)
+        out.edge_attr = torch.empty(E, b0.edge_attr.shape[2], dtype=b0.edge_attr.dtype, device=dev)
+        for k, b in enumerate(self._blocks):
+            pos = np.flatnonzero(which == k)                               # batch positions of this case, ascending
+            if pos.size == 0:
+                continue
+            n, e = int(n_of[k]), int(e_of[k])
+            # one host -> device copy per case: sample indices | first row | first edge of every position
+            host = torch.from_numpy(np.stack([idx[pos] - bounds[k], ptr[pos], eptr[pos]]))
+            sel, row0, edge0 = host.to(dev)
+            rows = (row0.view(-1, 1) + torch.arange(n, device=dev)).reshape(-1)
+            edges = (edge0.view(-1, 1) + torch.arange(e, device=dev)).reshape(-1)
+            out.x[rows] = b.x.index_select(0, sel).reshape(-1, b.x.shape[2])
+            out.y[rows] = b.y.index_select(0, sel).reshape(-1, b.y.shape[2])
+            out.bus_type[rows] = b.bus_type.index_select(0, sel).reshape(-1)
+            out.pred_mask[rows] = b.pred_mask.index_select(0, sel).reshape(-1, b.pred_mask.shape[2])
+            out.edge_attr[edges] = b.edge_attr.index_select(0, sel).reshape(-1, b.edge_attr.shape[2])
+            ei = b.edge_index.index_select(0, sel) + row0.view(-1, 1, 1)   # (P, 2, e), offset by the position's first row
+            out.edge_index[:, edges] = ei.permute(1, 0, 2).reshape(2, -1)
+        sizes_t = torch.from_numpy(np.stack([sizes, ptr[1:]])).to(dev)
+        out.batch = torch.repeat_interleave(torch.arange(B, device=dev), sizes_t[0], output_size=N)
+        out.ptr = torch.cat([sizes_t.new_zeros(1), sizes_t[1]])
+        out._graph_sizes = tuple(int(v) for v in sizes)
+        return out

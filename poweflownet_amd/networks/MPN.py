@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import segpack
 
 
 def _padded(f: int) -> int:
@@ -293,6 +294,76 @@ def _hip_linear(graph: GraphCSR, x, lin: nn.Linear):
     return _TagConvFn.apply(graph, (lin.in_features, lin.out_features, 0), L.f32c(x, "x"), lin.bias, lin.weight)
 
 
+# ================================================================================= mixed-size batches
+class PackedSegments:
+    """One ragged batch laid out in equal segments on the device (`segpack.plan` + pfn_segpack_pack): what
+    `MaskEmbdMultiMPN.last_segment_plan` holds after a packed forward.  `row_of` (N,) int32 = the padded row of every row of the
+    caller's batch, `src_of` (n_pad,) int32 = its inverse, -1 on padding rows."""
+
+    def __init__(self, plan: "segpack.SegPlan", device):
+        self.plan, self.S, self.n, self.n_pad, self.n_seg = plan, plan.S, plan.n, plan.n_pad, plan.n_seg
+        self.meta = torch.from_numpy(plan.meta()).to(device)      # ptr | start | fill: the one host -> device copy of a pack, O(graphs)
+        self.row_of = torch.empty(self.n, dtype=torch.int32, device=device)
+        self.src_of = torch.empty(self.n_pad, dtype=torch.int32, device=device)
+
+    def gather(self, src_pad: torch.Tensor) -> torch.Tensor:
+        """(n_pad, f) float32 -> (N, f) in the caller's row order."""
+        f = src_pad.shape[1]
+        dst = torch.empty(self.n, f, dtype=torch.float32, device=src_pad.device)
+        L.check(L.load().pfn_segpack_gather_rows(src_pad.data_ptr(), f, self.n_pad, self.row_of.data_ptr(), dst.data_ptr(), f,
+                                                 self.n, f, L.stream_ptr()), "pfn_segpack_gather_rows")
+        return dst
+
+    def scatter(self, src: torch.Tensor) -> torch.Tensor:
+        """(N, f) float32 -> (n_pad, f), padding rows zero."""
+        f = src.shape[1]
+        dst = torch.empty(self.n_pad, f, dtype=torch.float32, device=src.device)
+        L.check(L.load().pfn_segpack_scatter_rows(src.data_ptr(), f, self.n, self.src_of.data_ptr(), dst.data_ptr(), f,
+                                                  self.n_pad, self.S, f, L.stream_ptr()), "pfn_segpack_scatter_rows")
+        return dst
+
+
+class _SegPackFn(torch.autograd.Function):
+    """(x, pred_mask, edge_index) of a ragged batch -> (x_pad, mask_pad as float32, edge_index_pad); the gradient of x_pad
+    comes back through `row_of`."""
+
+    @staticmethod
+    def forward(ctx, pk: PackedSegments, x, mask, edge_index):
+        dev, e = x.device, int(edge_index.shape[1])
+        x_pad = torch.empty(pk.n_pad, 4, dtype=torch.float32, device=dev)
+        mask_pad = torch.empty(pk.n_pad, 4, dtype=torch.float32, device=dev)
+        ei_pad = torch.empty(2, e, dtype=torch.int64, device=dev)
+        g, m = pk.plan.n_graphs, pk.meta
+        L.check(L.load().pfn_segpack_pack(m.data_ptr(), m.data_ptr() + 4 * (g + 1), m.data_ptr() + 4 * (2 * g + 1), g, pk.n, pk.S,
+                                          pk.n_pad, x.data_ptr(), mask.data_ptr(), 0 if mask.dtype == torch.int64 else 1,
+                                          edge_index.data_ptr(), e, x_pad.data_ptr(), mask_pad.data_ptr(), ei_pad.data_ptr(),
+                                          pk.row_of.data_ptr(), pk.src_of.data_ptr(), L.stream_ptr()), "pfn_segpack_pack")
+        ctx.pk = pk
+        ctx.mark_non_differentiable(mask_pad, ei_pad)
+        return x_pad, mask_pad, ei_pad
+
+    @staticmethod
+    def backward(ctx, gx_pad, _gm, _ge):
+        return None, ctx.pk.gather(L.f32c(gx_pad, "grad_x")), None, None
+
+
+class _SegUnpadFn(torch.autograd.Function):
+    """Rows of the padded output back in the caller's order; backward = the adjoint, padding rows zero."""
+
+    @staticmethod
+    def forward(ctx, pk: PackedSegments, out_pad):
+        ctx.pk = pk
+        return pk.gather(out_pad)
+
+    @staticmethod
+    def backward(ctx, gout):
+        return None, ctx.pk.scatter(L.f32c(gout, "grad_out"))
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 # ============================================================================================ whole model
 class _MpnFn(torch.autograd.Function):
     """One autograd node for the whole network: forward = pfn_mpn_forward, backward = pfn_mpn_backward writing
@@ -339,7 +410,8 @@ class _MpnFn(torch.autograd.Function):
         ctx.model, ctx.graph, ctx.cfg, ctx.ws, ctx.mask_dtype = model, graph, cfg, ws, mask_dtype
         ctx.save_for_backward(x, pred_mask, edge_attr, *params)
         # (verification aid, `export_gates`: what the last recorded forward left behind -- weak, nothing is kept alive)
-        model._last_forward = (weakref.ref(ws), weakref.ref(graph), cfg, weakref.ref(edge_attr)) if cfg.need_backward else None
+        model._last_forward = ((weakref.ref(ws), weakref.ref(graph), cfg, weakref.ref(edge_attr), model._packing_now)
+                               if cfg.need_backward else None)
         return _unpad_rows(out, fo)
 
     @staticmethod
@@ -415,6 +487,7 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
     _mse_attach = None   # (target, workspace) announced by loss.MSELoss.attach for the NEXT forward, consumed by it (one-shot)
     _mse_tail = None
     _mask_seen = None
+    _packing_now = None  # the PackedSegments of the forward in flight (read by _MpnFn.forward for `export_gates`)
 
     def __init__(self, nfeature_dim, efeature_dim, output_dim, hidden_dim, n_gnn_layers, K, dropout_rate):
         super().__init__()
@@ -449,6 +522,14 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
         # whose topology differs per sample: the reference's `perturbed` sets, dataset_generator.py:250-253) -- hipGraph-
         # capturable; the id-range / segment checks then surface as a NaN output (GraphCSR.unverified)
         self.dynamic_topology = False
+        # True: a batch whose graphs differ in size and that carries its size list (`data.Batch._graph_sizes`) is re-laid on the
+        # device into equal segments of max(size) rows (segpack.plan: first-fit-decreasing, padding capped at `segment_max_padding`)
+        # and runs the segment kernels on that layout; the caller sees ragged tensors only.  Off by default: measured, big
+        # inference batches gain 9 %, the host-bound eager training step gains nothing and batches of many distinct sizes lose to
+        # the planning time.  Uniform batches, batches without a size list and batches the cap rejects are untouched by either value.
+        self.segment_packing = False
+        self.segment_max_padding = 0.25
+        self.last_segment_plan: Optional[PackedSegments] = None    # of the last forward; None: that forward was not packed
 
     # ------------------------------------------------------------------------------------- plumbing
     def _config(self) -> L.MpnConfig:
@@ -507,7 +588,8 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
         """Verification aid (`pfn_mpn_export_gates`): the ReLU decisions of the last forward pass that autograd recorded, while
         its workspace is still alive (i.e. before the output / loss tensor is dropped): {"edge": {layer index: bool (E_eff, H)},
         "out": {layer index: bool (N, H)}, "mask_embd": bool (N, H)}, edges in the order `undirect_graph` produces.  Tests feed
-        them to a float64 run of the CPU oracle so that gradients are compared on the SAME piecewise-linear branch."""
+        them to a float64 run of the CPU oracle so that gradients are compared on the SAME piecewise-linear branch.  After a
+        segment-packed forward the node gates come back in the caller's row order (through `row_of`); edge ids never moved."""
         lf = getattr(self, "_last_forward", None)
         ws, graph, edge_attr = (lf[0](), lf[1](), lf[3]()) if lf is not None else (None, None, None)
         if ws is None or graph is None or edge_attr is None:
@@ -532,6 +614,11 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
             if i + 1 < nlayers:
                 gates["out"][i] = run(1, i, n).bool()
         gates["mask_embd"] = run(2, 0, n).bool()
+        pk = lf[4]
+        if pk is not None:
+            rows = pk.row_of.long()
+            gates["out"] = {i: g[rows] for i, g in gates["out"].items()}
+            gates["mask_embd"] = gates["mask_embd"][rows]
         return gates
 
     # -------------------------------------------------------------------------------------- forward
@@ -573,6 +660,17 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
             ptr = getattr(data, "ptr", None)
             nseg = int(ptr.numel()) - 1 if torch.is_tensor(ptr) else 0
             seg_hint = x.shape[0] // nseg if nseg > 0 and x.shape[0] % nseg == 0 else 0
+            if self.last_segment_plan is not None:
+                self.last_segment_plan = None
+            # the host-side size list a collated batch carries (data.Batch): known AND non-uniform = a ragged batch
+            sizes = getattr(data, "_graph_sizes", None)
+            if sizes is not None and len(sizes) > 1 and min(sizes) != max(sizes):
+                # (never the N // n_graphs hint: as many 14- as 118-bus graphs divide evenly into "66-node graphs", which the first
+                #  validated build rejects and every later build of that shape would take on trust -- and poison the output)
+                seg_hint = 0
+                plan = segpack.plan(sizes, self.segment_max_padding) if self.segment_packing and not _capturing() else None
+                if plan is not None:
+                    return self._forward_packed(plan, x, mask, edge_index, edge_features, params)
             graph = self._graphs.get(edge_index, x.shape[0], -1, seg_hint, rebuild=self.dynamic_topology)   # is_directed + undirect_graph (:539)
             self._grad_mode_at_apply = torch.is_grad_enabled()
             self._mse_tail = None
@@ -580,6 +678,32 @@ class MaskEmbdMultiMPN(_UndirectHelpers, nn.Module):
             if self._mse_tail is not None:     # loss.MSELoss.forward finds the arrangement on the tensor it is handed
                 out._pfn_mse_tail, self._mse_tail = self._mse_tail, None
             return out
+
+
+    def _forward_packed(self, plan, x, mask, edge_index, edge_features, params):
+        """The forward pass of a ragged batch on its segment layout: pack -> the unchanged model kernels with seg_nodes = S ->
+        rows back in the caller's order.  The adjacency of the relabelled edge list goes through the same cache and the same rules
+        as any other (first build of a shape validated with a read-back, later ones checked on the device and poisoned)."""
+        if plan.n != x.shape[0]:
+            raise RuntimeError(f"the batch's size list adds up to {plan.n} nodes, x has {x.shape[0]} rows")
+        pk = PackedSegments(plan, x.device)
+        edge_index = edge_index if edge_index.is_contiguous() else edge_index.contiguous()
+        x_pad, mask_pad, ei_pad = _SegPackFn.apply(pk, _aligned16(x), _aligned16(mask), _aligned16(edge_index))
+        graph = self._graphs.get(ei_pad, pk.n_pad, -1, pk.S, rebuild=self.dynamic_topology)
+        if not graph.unverified and graph.seg_nodes != pk.S:
+            raise RuntimeError(f"the batch's size list does not describe its edge_index: an edge joins two graphs that the list "
+                               f"keeps apart (segments of {pk.S} rows)")
+        # the loss tails need `out` unwritten, which cannot be un-padded: an attached loss is consumed here, the plain path runs
+        self._mse_attach = None
+        self._grad_mode_at_apply = torch.is_grad_enabled()
+        self._mse_tail = None
+        self._packing_now = pk
+        try:
+            out_pad = _MpnFn.apply(self, graph, x_pad, mask_pad, edge_features, *params)
+        finally:
+            self._packing_now = None
+        self.last_segment_plan = pk
+        return _SegUnpadFn.apply(pk, out_pad)
 
 
 # ============================================================================================ MPN_simplenet
