@@ -244,3 +244,19 @@ def train_step(model, data, optimizer, loss_fn=None):
     loss.backward()
     optimizer.step()
     return loss.detach()
+
+
+def adamw_step(p, g, m, v, t, lr, b1, b2, eps, wd):
+    """One decoupled-weight-decay AdamW update (torch.optim.AdamW, amsgrad off; train.py:123 of the reference) in float64, the
+    yardstick of `adamw_kernel`.  `t` is the number of THIS update (1 for the first one).  Inputs of any float dtype are widened,
+    nothing is modified; returns the new (p, m, v):
+        p <- p (1 - lr wd);  m <- b1 m + (1 - b1) g;  v <- b2 v + (1 - b2) g^2
+        p <- p - lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)"""
+    p, g, m, v = (a.detach().double() for a in (p, g, m, v))
+    lr, b1, b2, eps, wd = float(lr), float(b1), float(b2), float(eps), float(wd)
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    bc1, bc2 = 1.0 - b1 ** int(t), 1.0 - b2 ** int(t)
+    denom = v.sqrt() / bc2 ** 0.5 + eps
+    p = p * (1.0 - lr * wd) - (lr / bc1) * (m / denom)
+    return p, m, v
