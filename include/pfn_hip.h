@@ -384,6 +384,52 @@ int pfn_mse_loss_rows(const float* out, const float* y, const int32_t* valid, in
 int pfn_masked_l2_loss_rows(const float* out, const float* y, const void* mask, int mask_dtype, const int32_t* valid, int64_t n_rows,
                             int regularize, float regcoeff, float* loss, float* grad, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------- evaluation metrics
+ * Every metric test.py reports (reference test.py:113-130; utils/custom_loss_functions.py:10-97), from one pass over a batch's
+ * output rows, with the epoch's running sums kept on the device.  Additive within ABI 8.  New layer: the reference runs the
+ * model once per metric and syncs the host on every term of every batch (utils/evaluation.py:106-165).
+ *
+ * The batch terms, one fp32 each, in this order.  With m = mask as float, d = out - y, cnt[f] = sum_rows m[:, f]:
+ *   CNT_*            cnt[f]
+ *   L2_* / L1_*      MaskedL2V2 / MaskedL1 on the rows as given: column means pf[f] = sum m * err / max(cnt[f], 1e-6) with err = d^2
+ *                    or |d| (the four named features), TOTAL = sum_f pf[f] * max(cnt[f], 1e-6) / max(sum_f cnt[f], 1e-6),
+ *                    BALANCED = mean_f pf[f]
+ *   L2D_* / L1D_*    the same on de-normalised rows: err from d * std[f] -- the mean cancels, and forming out * std + mean and
+ *                    y * std + mean first loses up to 7.6e-5 relative in fp32 where (out - y) * std stays within 3.3e-7
+ *   ML2_SELECTED     Masked_L2_loss's mean of d^2 over mask != 0;  ML2_REGULARIZER  its mean over 1 - mask != 0
+ *                    (an empty selection: 0/0 = NaN, as pfn_masked_l2_loss)
+ *   MSE              mean of d^2 over all 4 n entries (an empty batch: NaN)
+ * The mask MULTIPLIES (error * mask.float()): a NaN under a zero mask entry poisons its column, as in the reference.        */
+enum pfn_eval_term {
+    PFN_EVAL_CNT_VM = 0, PFN_EVAL_CNT_VA, PFN_EVAL_CNT_P, PFN_EVAL_CNT_Q,
+    PFN_EVAL_L2_TOTAL, PFN_EVAL_L2_BALANCED, PFN_EVAL_L2_VM, PFN_EVAL_L2_VA, PFN_EVAL_L2_P, PFN_EVAL_L2_Q,
+    PFN_EVAL_L2D_TOTAL, PFN_EVAL_L2D_BALANCED, PFN_EVAL_L2D_VM, PFN_EVAL_L2D_VA, PFN_EVAL_L2D_P, PFN_EVAL_L2D_Q,
+    PFN_EVAL_L1_TOTAL, PFN_EVAL_L1_BALANCED, PFN_EVAL_L1_VM, PFN_EVAL_L1_VA, PFN_EVAL_L1_P, PFN_EVAL_L1_Q,
+    PFN_EVAL_L1D_TOTAL, PFN_EVAL_L1D_BALANCED, PFN_EVAL_L1D_VM, PFN_EVAL_L1D_VA, PFN_EVAL_L1D_P, PFN_EVAL_L1D_Q,
+    PFN_EVAL_ML2_SELECTED, PFN_EVAL_ML2_REGULARIZER, PFN_EVAL_MSE,
+    PFN_EVAL_N_TERMS
+};
+/* index of the int64 batch counter behind the PFN_EVAL_N_TERMS doubles of an epoch accumulator (32 x 8 bytes in all) */
+#define PFN_EVAL_ACC_BATCHES PFN_EVAL_N_TERMS
+/* One launch per batch, no host sync, capturable.  out, y [n_rows, 4] f32; x [n_rows, 4] f32 or NULL; mask [n_rows, 4]
+ * (mask_dtype 0: int64, 1: float32) -- all 16-byte aligned.  std4: four HOST floats baked into the launch (NULL: 1).
+ *   terms [PFN_EVAL_N_TERMS] f32    the batch terms
+ *   epoch_acc (optional)            double[PFN_EVAL_N_TERMS] + the int64 batch counter: acc[k] += w * (double)terms[k], product
+ *                                   and sum rounded separately; w = 1 on the FIRST batch (counter 0) when first_unweighted is
+ *                                   set (the quirk of evaluate_epoch_v2, reference :158-163), else `weight`; counter += 1.
+ *                                   Cleared by the caller between epochs, outside a captured graph.
+ *   mixed_out (optional, needs x)   [n_rows, 4] f32 = out * mask + x * (1 - mask), bit for bit the torch expression
+ * Block partials are combined by the last arriver in an order fixed by the grid: a launch is a pure function of its inputs.
+ * n_rows == 0 writes the terms of an empty batch (0 for the clamped means, NaN for the selected means and the MSE).
+ * `ws`: >= 26640 bytes; its int32 at byte 26624 is an arrival counter, zero before the first call and after every call.    */
+int pfn_eval_metrics(const float* out, const float* y, const float* x, const void* mask, int mask_dtype, int64_t n_rows,
+                     const float* std4, double weight, int first_unweighted, float* terms, double* epoch_acc, float* mixed_out,
+                     void* ws, size_t ws_bytes, void* stream);
+/* acc[0] += (double)loss[0] * w (w as above, from the int64 batch counter acc[1]); acc[1] += 1.  One thread: lets the per-batch
+ * body of an evaluation loop with ANY loss be captured with its running sum on the device; the double is exactly what the host
+ * loop's `loss.item() * len(data)` adds.                                                                                   */
+int pfn_eval_accumulate(const float* loss, double weight, int first_unweighted, double* acc, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

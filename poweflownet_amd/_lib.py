@@ -27,7 +27,20 @@ SYMBOLS = (
     "pfn_khop_distances", "pfn_khop_histograms", "pfn_khop_pack",
     "pfn_segpack_pack", "pfn_segpack_gather_rows", "pfn_segpack_scatter_rows",
     "pfn_segpack_gather_slots", "pfn_mse_loss_rows", "pfn_masked_l2_loss_rows",
+    "pfn_eval_metrics", "pfn_eval_accumulate",
 )
+
+# enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
+EVAL_TERMS = (
+    "cnt_vm", "cnt_va", "cnt_p", "cnt_q",
+    "l2_total", "l2_balanced", "l2_vm", "l2_va", "l2_p", "l2_q",
+    "l2d_total", "l2d_balanced", "l2d_vm", "l2d_va", "l2d_p", "l2d_q",
+    "l1_total", "l1_balanced", "l1_vm", "l1_va", "l1_p", "l1_q",
+    "l1d_total", "l1d_balanced", "l1d_vm", "l1d_va", "l1d_p", "l1d_q",
+    "ml2_selected", "ml2_regularizer", "mse",
+)
+EVAL_ACC_DOUBLES = len(EVAL_TERMS) + 1      # an epoch accumulator: one double per term + the int64 batch counter
+EVAL_WS_FLOATS = 6660                       # struct EvalWs (csrc/eval.hip): 26640 bytes
 
 
 class MpnConfig(C.Structure):
@@ -116,6 +129,8 @@ def load() -> C.CDLL:
         "pfn_segpack_gather_slots": (C.c_int, [C.POINTER(SlotCase), i32, i32, p, p, p, p, p, p, i64, i64, i64, p, p, p, p, p, p, p]),
         "pfn_mse_loss_rows": (C.c_int, [p, p, p, i64, p, p, p, sz, p]),
         "pfn_masked_l2_loss_rows": (C.c_int, [p, p, p, C.c_int, p, i64, C.c_int, C.c_float, p, p, p, sz, p]),
+        "pfn_eval_metrics": (C.c_int, [p, p, p, p, C.c_int, i64, C.POINTER(C.c_float), C.c_double, C.c_int, p, p, p, p, sz, p]),
+        "pfn_eval_accumulate": (C.c_int, [p, C.c_double, C.c_int, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -289,3 +289,68 @@ def power_imbalance(x, graph, edge_attr, stats, workspace=None):
     """PowerImbalance.forward on HIP tensors; `graph` = the GraphCSR of the stored-once edge_index (mode -1), `stats` = 12
     floats {xymean[4], xystd[4], edgemean[2], edgestd[2]}; `workspace` as in masked_l2_loss."""
     return _PowerImbalanceFn.apply(x, graph, edge_attr, stats, workspace or _Workspace(POWER_IMBALANCE_WS_FLOATS))
+
+
+# ------------------------------------------------------------------------------------------ evaluation metrics
+def eval_accumulator(device, rows: int = 1, width: int = 2) -> torch.Tensor:
+    """`rows` epoch accumulators of `width` 8-byte slots, zeroed: doubles followed by ONE int64 batch counter (its bits).
+    width 2 = what `eval_accumulate` updates ({sum, batches}); `L.EVAL_ACC_DOUBLES` = what `eval_metrics` updates.  Clear it
+    between epochs with `zero_()` -- outside a captured graph."""
+    return torch.zeros(rows, width, dtype=torch.float64, device=device)
+
+
+def eval_metrics(out, y, mask, x=None, std=None, weight=1.0, first_unweighted=False, acc=None, mixed_out=None, terms=None,
+                 workspace=None):
+    """Every evaluation term of one batch in ONE launch (`pfn_eval_metrics`): returns the fp32 tensor of `L.EVAL_TERMS`.
+    `std`: four host floats (the de-normalised families use `(out - y) * std`; None = 1).  `acc` (float64, `L.EVAL_ACC_DOUBLES`
+    slots): acc[k] += w * terms[k] on the device, w = 1 on the first batch when `first_unweighted`.  `mixed_out` (needs `x`):
+    receives out * mask + x * (1 - mask).  `workspace`: a `_Workspace(L.EVAL_WS_FLOATS)` of the caller (a throw-away one
+    otherwise).  No host sync; capturable."""
+    import ctypes as C
+    L.require_device(out, y, mask, x, acc, mixed_out, terms, what="eval_metrics input")
+    out, y = L.f32c(out, "out"), L.f32c(y, "y")
+    n = out.shape[0]
+    if out.dim() != 2 or out.shape[1] != 4 or y.shape != out.shape or mask.shape != out.shape:
+        raise RuntimeError(f"eval_metrics: out, y and mask must be (N, 4); got {tuple(out.shape)} / {tuple(y.shape)} / {tuple(mask.shape)}")
+    if mask.dtype == torch.int64:
+        code = 0
+    else:
+        mask, code = mask.to(torch.float32), 1
+    mask = mask.contiguous()
+    if x is not None:
+        x = L.f32c(x, "x")
+        if x.shape != out.shape:
+            raise RuntimeError(f"eval_metrics: x must be {tuple(out.shape)}, got {tuple(x.shape)}")
+    if mixed_out is not None and (x is None or mixed_out.dtype != torch.float32 or mixed_out.shape != out.shape
+                                  or not mixed_out.is_contiguous()):
+        raise RuntimeError("eval_metrics: mixed_out needs x and must be a contiguous float32 tensor of out's shape")
+    if acc is not None and (acc.dtype != torch.float64 or acc.numel() != L.EVAL_ACC_DOUBLES or not acc.is_contiguous()):
+        raise RuntimeError(f"eval_metrics: acc must be a contiguous float64 tensor of {L.EVAL_ACC_DOUBLES} elements")
+    if terms is None:
+        terms = torch.empty(len(L.EVAL_TERMS), dtype=torch.float32, device=out.device)
+    elif terms.dtype != torch.float32 or terms.numel() != len(L.EVAL_TERMS) or not terms.is_contiguous():
+        raise RuntimeError(f"eval_metrics: terms must be a contiguous float32 tensor of {len(L.EVAL_TERMS)} elements")
+    if std is not None:
+        std = [float(v) for v in std]
+        if len(std) != 4:
+            raise RuntimeError("eval_metrics: std must hold four values")
+        std = (C.c_float * 4)(*std)
+    ws = (workspace or _Workspace(L.EVAL_WS_FLOATS)).on(out.device)
+    with torch.cuda.device(out.device):
+        L.check(L.load().pfn_eval_metrics(out.data_ptr(), y.data_ptr(), L.ptr(x), mask.data_ptr(), code, n, std, float(weight),
+                                          int(bool(first_unweighted)), terms.data_ptr(), L.ptr(acc), L.ptr(mixed_out),
+                                          ws.data_ptr(), ws.numel() * 4, L.stream_ptr()), "pfn_eval_metrics")
+    return terms
+
+
+def eval_accumulate(loss, acc, weight=1.0, first_unweighted=False):
+    """acc[0] += double(loss) * w on the device (`pfn_eval_accumulate`; acc: float64 {sum, batch counter}, w = 1 on the first
+    batch when `first_unweighted`): the running sum of an evaluation loop without its per-batch `loss.item()`."""
+    L.require_device(loss, acc, what="eval_accumulate input")
+    if loss.dtype != torch.float32 or loss.numel() != 1:
+        raise RuntimeError(f"eval_accumulate: loss must be one float32 value (got {loss.dtype} {tuple(loss.shape)})")
+    if acc.dtype != torch.float64 or acc.numel() != 2 or not acc.is_contiguous():
+        raise RuntimeError("eval_accumulate: acc must be a contiguous float64 tensor of 2 elements {sum, batch counter}")
+    with torch.cuda.device(loss.device):
+        L.check(L.load().pfn_eval_accumulate(loss.data_ptr(), float(weight), int(bool(first_unweighted)), acc.data_ptr(),
+                                             L.stream_ptr()), "pfn_eval_accumulate")

@@ -49,6 +49,14 @@ def argument_parser(argv=None):
     # per_sample_topology).  On by default -- measured; it only ever applies to such a split (single GPU, MSELoss or
     # Masked_L2_loss), every other run is untouched.  --no-per-sample-topology: the dynamic path (generic build inside the graph).
     p.add_argument("--per-sample-topology", action=argparse.BooleanOptionalAction, default=True)
+    # evaluation epochs (train.py's validation, test.py's report) replayed from one hipGraph per batch size, their running sums on
+    # the device (utils.evaluation.GraphedEvalStep).  Unset, each script follows the measurement of DESIGN 7e: train.py replays
+    # its validation (one step kept across epochs: --no-graphed-eval for the eager loop); test.py, whose single pass has no
+    # later epoch to repay the captures, does not (--graphed-eval turns it on).
+    p.add_argument("--graphed-eval", action=argparse.BooleanOptionalAction, default=None)
+    # test.py: the reference's six passes over the test split (one evaluate_epoch_v2 per line group) instead of ONE
+    # evaluate_report pass that computes every line
+    p.add_argument("--per-metric-passes", action="store_true", default=False)
     args, left = cfg.parse_known_args(argv)
     if args.cfg_json is not None:
         path = args.cfg_json

@@ -23,7 +23,7 @@ from poweflownet_amd.optim import FlatAdamW
 from poweflownet_amd.synth import make_dataset
 from poweflownet_amd.utils.argument_parser import argument_parser
 from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss, MixedMSEPoweImbalance, PowerImbalance
-from poweflownet_amd.utils.evaluation import evaluate_epoch
+from poweflownet_amd.utils.evaluation import GraphedEvalStep, evaluate_epoch
 from poweflownet_amd.utils.training import GraphedTrainStep, append_to_json, train_epoch
 
 
@@ -91,15 +91,18 @@ def main():
     best_val = float("inf")
     graphed = GraphedTrainStep(model, loss_fn, optimizer, dp_mode=getattr(args, "dp_mode", None),   # one hipGraph launch per batch; under DP it contains the all-reduce
                                per_sample_topology=bool(getattr(args, "per_sample_topology", True)))
+    # validation replays from one hipGraph per batch size, kept across epochs (--no-graphed-eval: the eager loop)
+    graphed_eval = GraphedEvalStep(model, eval_loss_fn) if getattr(args, "graphed_eval", None) is not False else None
     for epoch in range(args.num_epochs):
         t0 = time.time()
         train_loss = train_epoch(model, train_loader, loss_fn, optimizer, device, graph=graphed)
-        t_train = time.time() - t0
-        val_loss = evaluate_epoch(model, val_loader, eval_loss_fn, device)
+        t_train = time.time() - t0                                # (train_epoch ends with its one read-back: the device is idle)
+        val_loss = evaluate_epoch(model, val_loader, eval_loss_fn, device, graph=graphed_eval)
+        t_val = time.time() - t0 - t_train                        # (... and so does evaluate_epoch)
         scheduler.step()                                          # once per epoch, like train.py:145
         if rank == 0:
             print(f"Epoch {epoch + 1} / {args.num_epochs}, train={train_loss:.4f}, val={val_loss:.4f}, "
-                  f"{len(trainset) / max(t_train, 1e-9):.0f} train graphs/s")
+                  f"{len(trainset) / max(t_train, 1e-9):.0f} train graphs/s, {len(valset) / max(t_val, 1e-9):.0f} val graphs/s")
             if args.save and val_loss < best_val:
                 best_val = val_loss
                 os.makedirs("models", exist_ok=True)
