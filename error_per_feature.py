@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Per-bus error analysis entry, the counterpart of the reference's error_per_feature.py: the de-normalised error of every bus of
+every test sample, its per-feature report (overall, load buses, generator buses) and a 300-bin error histogram per (bus, feature),
+from ONE device pass over the test split (poweflownet_amd/utils/error_analysis.py).
+
+    python error_per_feature.py --cfg_json configs/standard.json --case 118v2 --data-dir DATA --run-id <id> [--save-predictions]
+
+`--run-id`, `--case`, `--data-dir` and `--cfg_json` replace what the reference hard-codes (error_per_feature.py:38-53, :80).  The
+checkpoint is models/model_<run-id>.pt; without one the model keeps its random initialisation.  Data: the test split of
+`<data-dir>/raw/case<case>_*.npy` when present (normalised with the run's saved parameters if
+`<data-dir>/params/data_params_<run-id>.pt` exists), else `--synthetic-samples` synthetic grids of the case, of which the last 30 %
+are the test split (their values are already normalised: errors are then in normalised units).  Writes
+results/<case>_{errors,masks,types}.npy -- the three files the reference writes, [S, n, 4] / [S, n, 4] / [S, n] -- and
+results/<case>_error_hist.npy [n, 4, nbins] with results/<case>_error_hist_edges.npy [4, nbins + 1]; `--save-predictions` adds
+results/<case>_predictions.npy.  `--graphed-eval` replays the per-batch body from a hipGraph.  No plots: the .npy files are what
+the reference's plotting half reads."""
+import os
+import sys
+
+import numpy as np
+import torch
+
+from poweflownet_amd.data import DataLoader
+from poweflownet_amd.datasets import PowerFlowData
+from poweflownet_amd.networks.MPN import MaskEmbdMultiMPN, MPN_simplenet
+from poweflownet_amd.synth import make_dataset
+from poweflownet_amd.utils.argument_parser import argument_parser
+from poweflownet_amd.utils.error_analysis import bus_error_epoch, bus_error_histograms, histogram_edges, mask_scale, report_lines
+from poweflownet_amd.utils.evaluation import GraphedEvalStep, load_model
+
+
+def _take(argv, flag, has_value=True, default=None):
+    if flag not in argv:
+        return default
+    i = argv.index(flag)
+    value = argv[i + 1] if has_value else True
+    del argv[i:i + (2 if has_value else 1)]
+    return value
+
+
+@torch.no_grad()
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    run_id = _take(argv, "--run-id", default="synthetic")
+    save_predictions = _take(argv, "--save-predictions", has_value=False, default=False)
+    nbins = int(_take(argv, "--nbins", default=300))
+    out_dir = _take(argv, "--results-dir", default="results")
+    args = argument_parser(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("error_per_feature.py needs a HIP device: poweflownet_amd has no CPU fallback")
+    device = torch.device("cuda")
+    xymean = xystd = None
+    raw = os.path.join(args.data_dir, "raw", f"case{args.case}_node_features.npy")
+    if os.path.exists(raw):
+        params, kw = os.path.join(args.data_dir, "params", f"data_params_{run_id}.pt"), {}
+        if os.path.exists(params):
+            p = torch.load(params, map_location="cpu")
+            kw = {k: p[k] for k in ("xymean", "xystd", "edgemean", "edgestd")}
+        testset = PowerFlowData(root=args.data_dir, case=args.case, split=[.5, .2, .3], task="test", device=device, **kw)
+        xymean, xystd = testset.xymean, testset.xystd
+        nin, nout, ne = testset.get_data_dimensions()
+    else:
+        n = args.synthetic_samples
+        testset = make_dataset(args.case, n, seed=0)[int(0.5 * n) + int(0.2 * n):]      # split [.5, .2, .3], as train.py
+        nin, nout, ne = 4, 4, 2
+    loader = DataLoader(testset, batch_size=args.batch_size, shuffle=False)
+    models = {"MaskEmbdMultiMPN": MaskEmbdMultiMPN, "MPN_simplenet": MPN_simplenet}
+    model = models[args.model](nfeature_dim=nin, efeature_dim=ne, output_dim=nout, hidden_dim=args.hidden_dim,
+                               n_gnn_layers=args.n_gnn_layers, K=args.K, dropout_rate=args.dropout_rate).to(device)
+    model.eval()
+    if os.path.exists(os.path.join("models", f"model_{run_id}.pt")):
+        model, _ = load_model(model, run_id, device)
+    else:
+        print(f"no checkpoint models/model_{run_id}.pt: the model keeps its random initialisation")
+    print(f"Model: {args.model}\nCase: {args.case}\nNumber of samples: {len(testset)}")
+    graphed = getattr(args, "graphed_eval", None) is True           # (off unless asked for: one pass cannot repay the captures)
+    res = bus_error_epoch(model, loader, device, xymean=xymean, xystd=xystd, graph=GraphedEvalStep(model) if graphed else None,
+                          keep_errors=True, keep_predictions=bool(save_predictions))
+    if res.flags & 1:
+        raise SystemExit("error_per_feature.py: a batch named a sample outside the table")
+    for key, value in report_lines(res.moments, res.mask0, res.types0).items():
+        print(f"{key}: {value}")
+    scale = mask_scale(res.mask0)
+    edges = histogram_edges(res.moments, scale, nbins=nbins)
+    hist, outside = bus_error_histograms(res.errors, edges, scale)
+    S = res.num_samples
+    os.makedirs(out_dir, exist_ok=True)
+    path = lambda name: os.path.join(out_dir, f"{args.case}_{name}.npy")      # noqa: E731
+    np.save(path("errors"), res.errors.cpu().numpy())
+    np.save(path("masks"), np.broadcast_to(res.mask0.to(torch.float32).numpy(), (S,) + tuple(res.mask0.shape)).copy())
+    np.save(path("types"), np.broadcast_to(res.types0.numpy(), (S,) + tuple(res.types0.shape)).copy())
+    np.save(path("error_hist"), hist.cpu().numpy())
+    np.save(path("error_hist_edges"), edges)
+    if save_predictions:
+        np.save(path("predictions"), res.predictions.cpu().numpy())
+    inside = int(hist.sum())
+    print(f"histograms: {nbins} bins per (bus, feature); {inside} of {S * hist.shape[0] * 4} scaled errors inside the range, "
+          f"{int(outside[..., 0].sum())} below, {int(outside[..., 1].sum())} above, {int(outside[..., 2].sum())} NaN")
+    print(f"wrote {out_dir}/{args.case}_{{errors,masks,types,error_hist,error_hist_edges{',predictions' if save_predictions else ''}}}.npy")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -430,6 +430,41 @@ int pfn_eval_metrics(const float* out, const float* y, const float* x, const voi
  * loop's `loss.item() * len(data)` adds.                                                                                   */
 int pfn_eval_accumulate(const float* loss, double weight, int first_unweighted, double* acc, void* stream);
 
+/* ------------------------------------------------------------------------------- per-bus error analysis
+ * WHERE the error of an evaluation split is (reference error_per_feature.py:120-172, :247-324, :362-405): the de-normalised error
+ * and prediction of every bus of every sample, running moments per (bus, feature, mask group), and a histogram per (bus, feature).
+ * Additive within ABI 8.  New layer: the reference runs one forward and one `.cpu()` per sample and n x 4 np.histogram calls.
+ *
+ * pfn_bus_errors_accumulate: one launch per batch, no host sync, capturable.  out, y, mask [n_graphs * n_bus, 4] are a uniform
+ * batch of ONE case, graph g owning rows [g n_bus, (g + 1) n_bus); mask_dtype 0: int64, 1: float32; all 16-byte aligned.
+ * std4 / mean4: four HOST floats each, baked into the launch (NULL: 1 / 0).
+ *   error        e = (out - y) * std[f] in fp32, difference and product rounded separately (the expression of pfn_eval_metrics'
+ *                de-normalised terms)
+ *   prediction   out * std[f] + mean[f], product and sum rounded separately: torch's `denormalize`, bit for bit
+ *   err_table, pred_table (each optional; [table_rows, n_bus, 4] f32): graph g writes its n_bus rows to row sample_idx[g]
+ *                (device int64 [n_graphs]; may be NULL when both tables are).  A sample_idx[g] outside [0, table_rows) sets bit 0
+ *                of flags[0] (a plain vector store) and the graph is skipped entirely, tables and moments: nothing is ever
+ *                written outside a table.
+ *   moments      double[n_bus][4][2][6], accumulated INTO (cleared by the caller between epochs, outside a captured graph, with
+ *                min = +inf and max = -inf): group 0 = entries with mask != 0 (predicted), group 1 = mask == 0 (given); the
+ *                six values are {count, sum e, sum |e|, sum e^2, min e, max e}, every e widened to double first.  min / max
+ *                ignore NaN (fmin / fmax); the sums propagate it.
+ * One owner per (bus, feature), a fixed work split and combine order, no float atomics: a launch is a pure function of its
+ * inputs and of the moments it found.
+ *
+ * pfn_bus_errors_histogram: one launch over a finished table [n_samples, n_bus, 4] f32.  hist [n_bus, 4, nbins] and outside
+ * [n_bus, 4, 3] (below the first edge, above the last, NaN) are OVERWRITTEN.  The binned value is v = table[s, b, f] * scale[b, f]
+ * (one fp32 product; scale [n_bus, 4] f32 or NULL: v = table); the rule is np.histogram(v, bins=edges[f]) with an explicit edge
+ * array (edges: DEVICE double [4, nbins + 1], increasing), compared in float64: bin i holds edges[i] <= v < edges[i + 1], the last
+ * bin also v == edges[nbins]; nothing counted in `outside` enters a bin.  A workgroup owns a tile of consecutive buses with its
+ * counters and the edges in LDS (integer LDS atomics, no global atomics).  nbins in 1..2048, n_samples < 2^31 (uint32 counts):
+ * anything else is PFN_EINVAL.                                                                                              */
+int pfn_bus_errors_accumulate(const float* out, const float* y, const void* mask, int mask_dtype, int64_t n_graphs, int64_t n_bus,
+                              const float* std4, const float* mean4, const int64_t* sample_idx, int64_t table_rows, float* err_table,
+                              float* pred_table, double* moments, int32_t* flags, void* stream);
+int pfn_bus_errors_histogram(const float* table, int64_t n_samples, int64_t n_bus, const float* scale, const double* edges, int nbins,
+                             uint32_t* hist, uint32_t* outside, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

@@ -28,6 +28,7 @@ SYMBOLS = (
     "pfn_segpack_pack", "pfn_segpack_gather_rows", "pfn_segpack_scatter_rows",
     "pfn_segpack_gather_slots", "pfn_mse_loss_rows", "pfn_masked_l2_loss_rows",
     "pfn_eval_metrics", "pfn_eval_accumulate",
+    "pfn_bus_errors_accumulate", "pfn_bus_errors_histogram",
 )
 
 # enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
@@ -131,6 +132,9 @@ def load() -> C.CDLL:
         "pfn_masked_l2_loss_rows": (C.c_int, [p, p, p, C.c_int, p, i64, C.c_int, C.c_float, p, p, p, sz, p]),
         "pfn_eval_metrics": (C.c_int, [p, p, p, p, C.c_int, i64, C.POINTER(C.c_float), C.c_double, C.c_int, p, p, p, p, sz, p]),
         "pfn_eval_accumulate": (C.c_int, [p, C.c_double, C.c_int, p, p]),
+        "pfn_bus_errors_accumulate": (C.c_int, [p, p, p, C.c_int, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), p, i64, p, p,
+                                                p, p, p]),
+        "pfn_bus_errors_histogram": (C.c_int, [p, i64, i64, p, p, C.c_int, p, p, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

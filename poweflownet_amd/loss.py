@@ -354,3 +354,104 @@ def eval_accumulate(loss, acc, weight=1.0, first_unweighted=False):
     with torch.cuda.device(loss.device):
         L.check(L.load().pfn_eval_accumulate(loss.data_ptr(), float(weight), int(bool(first_unweighted)), acc.data_ptr(),
                                              L.stream_ptr()), "pfn_eval_accumulate")
+
+
+# ------------------------------------------------------------------------------------------ per-bus error analysis
+BUS_MOMENTS = ("count", "sum", "sum_abs", "sum_sq", "min", "max")      # the six values per (bus, feature, mask group)
+
+
+def bus_error_moments(device, n_bus: int) -> torch.Tensor:
+    """The running moments of `bus_errors_accumulate`, cleared: float64 [n_bus, 4, 2, 6] (group 0: mask != 0, group 1: mask == 0;
+    `BUS_MOMENTS`), min = +inf and max = -inf.  Clear it between epochs with `reset_bus_error_moments` -- outside a captured graph."""
+    return reset_bus_error_moments(torch.empty(int(n_bus), 4, 2, 6, dtype=torch.float64, device=device))
+
+
+def reset_bus_error_moments(moments: torch.Tensor) -> torch.Tensor:
+    moments[..., :4] = 0.0
+    moments[..., 4] = float("inf")
+    moments[..., 5] = float("-inf")
+    return moments
+
+
+def _host4(v, what):
+    import ctypes as C
+    if v is None:
+        return None
+    v = [float(a) for a in v]
+    if len(v) != 4:
+        raise RuntimeError(f"bus_errors_accumulate: {what} must hold four values")
+    return (C.c_float * 4)(*v)
+
+
+def bus_errors_accumulate(out, y, mask, n_bus, sample_idx, moments, flags, std=None, mean=None, err_table=None, pred_table=None,
+                          table_rows=None):
+    """One uniform batch of ONE case (graph g = rows [g n_bus, (g + 1) n_bus) of out / y / mask) in ONE launch
+    (`pfn_bus_errors_accumulate`): the de-normalised errors (out - y) * std go to row sample_idx[g] of `err_table`, the predictions
+    out * std + mean to that row of `pred_table` (each [rows, n_bus, 4] float32 or None) and into `moments` (`bus_error_moments`).
+    `std` / `mean`: four host floats each (None: 1 / 0).  `sample_idx`: device int64 [n_graphs]; an index outside the table sets bit
+    0 of `flags` (device int32) and its graph is left out.  `table_rows`: the bound of the indices when no table is given (with a
+    table: its rows; neither: the indices are not read and every graph counts).  No host sync; capturable."""
+    L.require_device(out, y, mask, sample_idx, moments, flags, err_table, pred_table, what="bus_errors_accumulate input")
+    out, y = L.f32c(out, "out"), L.f32c(y, "y")
+    n_bus = int(n_bus)
+    if out.dim() != 2 or out.shape[1] != 4 or y.shape != out.shape or mask.shape != out.shape:
+        raise RuntimeError(f"bus_errors_accumulate: out, y and mask must be (N, 4); got {tuple(out.shape)} / {tuple(y.shape)} / {tuple(mask.shape)}")
+    if n_bus <= 0 or out.shape[0] % n_bus != 0:
+        raise RuntimeError(f"bus_errors_accumulate: {out.shape[0]} rows are not whole graphs of {n_bus} buses")
+    n_graphs = out.shape[0] // n_bus
+    if mask.dtype == torch.int64:
+        code = 0
+    else:
+        mask, code = mask.to(torch.float32), 1
+    mask = mask.contiguous()
+    if sample_idx.dtype != torch.int64 or sample_idx.numel() != n_graphs or not sample_idx.is_contiguous():
+        raise RuntimeError(f"bus_errors_accumulate: sample_idx must be a contiguous int64 tensor of {n_graphs} elements")
+    rows = None
+    for name, tab in (("err_table", err_table), ("pred_table", pred_table)):
+        if tab is None:
+            continue
+        if tab.dtype != torch.float32 or tab.dim() != 3 or tuple(tab.shape[1:]) != (n_bus, 4) or not tab.is_contiguous():
+            raise RuntimeError(f"bus_errors_accumulate: {name} must be a contiguous float32 tensor of shape (rows, {n_bus}, 4)")
+        if rows is not None and tab.shape[0] != rows:
+            raise RuntimeError("bus_errors_accumulate: the two tables must have the same number of rows")
+        rows = int(tab.shape[0])
+    if rows is None:
+        rows = None if table_rows is None else int(table_rows)
+    elif table_rows is not None and int(table_rows) != rows:
+        raise RuntimeError(f"bus_errors_accumulate: table_rows {int(table_rows)} against tables of {rows} rows")
+    if moments.dtype != torch.float64 or moments.numel() != n_bus * 48 or not moments.is_contiguous():
+        raise RuntimeError(f"bus_errors_accumulate: moments must be a contiguous float64 tensor of {n_bus} x 4 x 2 x 6 elements")
+    if flags.dtype != torch.int32 or flags.numel() < 1:
+        raise RuntimeError("bus_errors_accumulate: flags must be an int32 tensor")
+    with torch.cuda.device(out.device):
+        L.check(L.load().pfn_bus_errors_accumulate(out.data_ptr(), y.data_ptr(), mask.data_ptr(), code, n_graphs, n_bus,
+                                                   _host4(std, "std"), _host4(mean, "mean"),
+                                                   sample_idx.data_ptr() if rows is not None else None, rows if rows is not None else 0, L.ptr(err_table), L.ptr(pred_table),
+                                                   moments.data_ptr(), flags.data_ptr(), L.stream_ptr()), "pfn_bus_errors_accumulate")
+
+
+def bus_errors_histogram(table, edges, scale=None):
+    """np.histogram(table[:, b, f] * scale[b, f], bins=edges[f]) for every (bus, feature) of a finished [S, n_bus, 4] float32 table
+    in ONE launch (`pfn_bus_errors_histogram`).  `edges`: float64 [4, nbins + 1], increasing (moved to the device); `scale`: float32
+    [n_bus, 4] or None.  Returns (hist int32 [n_bus, 4, nbins], outside int32 [n_bus, 4, 3] = below / above / NaN) on the device."""
+    L.require_device(table, scale, what="bus_errors_histogram input")
+    table = L.f32c(table, "table")
+    if table.dim() != 3 or table.shape[2] != 4:
+        raise RuntimeError(f"bus_errors_histogram: the table must be (S, n_bus, 4); got {tuple(table.shape)}")
+    S, n_bus = int(table.shape[0]), int(table.shape[1])
+    if S >= 2 ** 31:
+        raise RuntimeError("bus_errors_histogram: counts are 32-bit, the table must hold fewer than 2^31 samples")
+    edges = torch.as_tensor(edges, dtype=torch.float64).to(table.device).contiguous()
+    if edges.dim() != 2 or edges.shape[0] != 4:
+        raise RuntimeError(f"bus_errors_histogram: edges must be (4, nbins + 1); got {tuple(edges.shape)}")
+    nbins = int(edges.shape[1]) - 1
+    if scale is not None:
+        scale = L.f32c(scale, "scale")
+        if tuple(scale.shape) != (n_bus, 4):
+            raise RuntimeError(f"bus_errors_histogram: scale must be ({n_bus}, 4); got {tuple(scale.shape)}")
+    hist = torch.empty(n_bus, 4, max(nbins, 0), dtype=torch.int32, device=table.device)
+    outside = torch.empty(n_bus, 4, 3, dtype=torch.int32, device=table.device)
+    with torch.cuda.device(table.device):
+        L.check(L.load().pfn_bus_errors_histogram(table.data_ptr(), S, n_bus, L.ptr(scale), edges.data_ptr(), nbins, hist.data_ptr(),
+                                                  outside.data_ptr(), L.stream_ptr()), "pfn_bus_errors_histogram")
+    return hist, outside

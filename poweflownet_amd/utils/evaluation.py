@@ -134,11 +134,17 @@ def _std4(xystd):
 # ------------------------------------------------------------------------------------------------ the step
 class _Child:
     """One captured per-batch body: its input tensors, (indexed modes) its index buffer, the graph and the adjacencies it reads."""
-    __slots__ = ("static", "idx", "topo_graph", "dynamic", "graph", "held", "n_keys")
+    __slots__ = ("static", "idx", "topo_graph", "dynamic", "graph", "held", "n_keys", "pos")
 
     def __init__(self, static, idx=None, topo_graph=None, dynamic=False):
         self.static, self.idx, self.topo_graph, self.dynamic = static, idx, topo_graph, bool(dynamic)
         self.graph, self.held, self.n_keys = None, [], len(static)
+        self.pos = None                # errors, copied batches: the table rows of the batch (device int64, filled per batch)
+
+
+def _num_graphs(data) -> int:
+    ptr = getattr(data, "ptr", None)
+    return 1 if ptr is None else int(ptr.numel()) - 1
 
 
 def _same_device(a, b) -> bool:
@@ -180,8 +186,8 @@ class GraphedEvalStep:
 
     def __init__(self, model, loss_fn=None, pre_loss_fn: Optional[Callable] = None):
         self.model, self.loss_fn, self.pre_loss_fn = model, loss_fn, pre_loss_fn
-        self.kind = "epoch"            # epoch | v2 | report
-        self._extras = None            # report: (std4, PowerImbalance or None)
+        self.kind = "epoch"            # epoch | v2 | report | errors
+        self._extras = None            # report: (std4, PowerImbalance or None); errors: utils/error_analysis.py bus_error_epoch
         self.captures = 0
         self.eager_batches = 0         # batches of the last epoch that ran the eager body
         self.disabled = False
@@ -193,6 +199,9 @@ class GraphedEvalStep:
         self._racc = None              # report: the accumulator of pfn_eval_metrics
         self._keys = None              # v2: the term names, in the loss's dict order
         self._metrics_ws = None
+        # errors (utils/error_analysis.py): the tables the captured launches write, the moments + flags word, the running position
+        self._etab = self._ptab = self._mom = None
+        self._pos, self._eager_idx, self.rows_by_index = 0, None, False
 
     # ------------------------------------------------------------------------------------------ plumbing
     def _topology_owners(self):
@@ -228,6 +237,38 @@ class GraphedEvalStep:
             self._drop_all()
         self._acc.zero_()                             # between epochs, OUTSIDE the graph (no memset nodes in a capture)
         self._racc.zero_()
+        if self.kind == "errors":
+            self._error_buffers(device)
+
+    def _error_buffers(self, device):
+        """The tables ([rows, n_bus, 4], NaN where no sample was written) and the moments of an `errors` epoch, owned by the step
+        because the captured launches hold their addresses; the flags word is the int32 behind the moments (one read-back)."""
+        from ..loss import reset_bus_error_moments
+        _, _, keep_e, keep_p, rows, n_bus = self._extras
+        shape = (rows, n_bus, 4)
+        if self._mom is None or self._mom.device != device or self._mom.numel() != n_bus * 48 + 1:
+            self._mom = torch.empty(n_bus * 48 + 1, dtype=torch.float64, device=device)
+            self._etab = self._ptab = None
+            self._drop_all()
+        for name, keep in (("_etab", keep_e), ("_ptab", keep_p)):
+            tab = getattr(self, name)
+            if (tab is not None) != keep or (keep and (tuple(tab.shape) != shape or tab.device != device)):
+                setattr(self, name, torch.empty(shape, dtype=torch.float32, device=device) if keep else None)
+                self._drop_all()
+            if keep:
+                getattr(self, name).fill_(float("nan"))
+        reset_bus_error_moments(self._mom[:-1].view(n_bus, 4, 2, 6))
+        self._mom[-1:].zero_()
+        self._pos, self._eager_idx = 0, None
+
+    def _error_batch(self, data) -> int:
+        """The number of graphs of an `errors` batch; ValueError unless it is a uniform batch of the epoch's case."""
+        n_bus = self._extras[5]
+        sizes, B = getattr(data, "_graph_sizes", None), _num_graphs(data)
+        if (sizes is not None and any(int(v) != n_bus for v in sizes)) or int(data.x.shape[0]) != B * n_bus:
+            raise ValueError(f"bus_error_epoch: a batch of {B} graphs with {int(data.x.shape[0])} rows is not a uniform batch of "
+                             f"{n_bus}-bus grids (mixed splits are not covered: the tables are [samples, buses, 4])")
+        return B
 
     # -------------------------------------------------------------------------------------- the body
     def _body(self, ch, data):
@@ -257,6 +298,12 @@ class GraphedEvalStep:
                 raise RuntimeError(f"GraphedEvalStep: the loss returned the terms {keys}, earlier batches {self._keys}")
             for i, k in enumerate(keys):
                 eval_accumulate(terms[k], self._acc[i], w, first_unweighted=True)
+        elif self.kind == "errors":
+            from ..loss import bus_errors_accumulate
+            std4, mean4, _, _, table_rows, n_bus = self._extras
+            rows = self._eager_idx if ch is None else (ch.idx[1] if ch.idx is not None else ch.pos)
+            bus_errors_accumulate(out, data.y, data.pred_mask, n_bus, rows, self._mom[:-1], self._mom[-1:].view(torch.int32),
+                                  std=std4, mean=mean4, err_table=self._etab, pred_table=self._ptab, table_rows=table_rows)
         else:
             std4, pi = self._extras
             mixed = torch.empty_like(out) if pi is not None else None
@@ -268,6 +315,13 @@ class GraphedEvalStep:
 
     def _eager(self, data):
         self.eager_batches += 1
+        if self.kind == "errors":
+            B = self._error_batch(data)
+            if self._eager_idx is None:                            # the running position: one index copy per batch
+                self._eager_idx = torch.arange(self._pos, self._pos + B).to(data.x.device)
+            self._body(None, data)
+            self._pos, self._eager_idx = self._pos + B, None
+            return len(data)
         self._body(None, data)
         return len(data)
 
@@ -285,6 +339,8 @@ class GraphedEvalStep:
         if ch.topo_graph is not None:
             model.segment_build = True
         snap = (self._acc.clone(), self._racc.clone())            # the warm-up passes leave no trace in the running sums
+        if self.kind == "errors":
+            snap += (self._mom.clone(),)
         gc_was_on = gc.isenabled()
         try:
             side.wait_stream(torch.cuda.current_stream())
@@ -294,6 +350,8 @@ class GraphedEvalStep:
             torch.cuda.current_stream().wait_stream(side)
             self._acc.copy_(snap[0])
             self._racc.copy_(snap[1])
+            if len(snap) > 2:
+                self._mom.copy_(snap[2])
             g = torch.cuda.CUDAGraph()
             gc.disable()                                           # (no cyclic collection inside a capture window: dp.GraphedStep._try)
             with torch.cuda.graph(g):
@@ -329,6 +387,8 @@ class GraphedEvalStep:
             self._drop_all()
             self._acc.zero_()
             self._racc.zero_()
+            if self.kind == "errors":
+                self._error_buffers(self._mom.device)
             raise _CaptureFailed() from exc
         self._children[key] = ch
         return ch
@@ -347,15 +407,19 @@ class GraphedEvalStep:
             return _Child(static, idx=(ds, idx.clone()), topo_graph=tg, dynamic=topo)
         ch = self._ready(("topo" if topo else "indexed", id(ds), B), make)
         if ch is None:
+            self._eager_idx = idx if self.kind == "errors" else None
             return self._eager(ds.collate_indices(idx.tolist()))
         ch.idx[1].copy_(idx)
         ch.graph.replay()
+        self._pos += B
         return ch.n_keys
 
     def _step_data(self, data):
         sizes = getattr(data, "_graph_sizes", None)
         if not data.x.is_cuda or (sizes is not None and len(sizes) > 1 and min(sizes) != max(sizes)):
             return self._eager(data)
+        errors = self.kind == "errors"
+        B = self._error_batch(data) if errors else 0
         ptr = getattr(data, "ptr", None)
         sig = (tuple(data.x.shape), tuple(data.edge_index.shape), tuple(data.edge_attr.shape), data.pred_mask.dtype,
                None if ptr is None else tuple(ptr.shape), len(data), str(data.x.device))
@@ -372,26 +436,48 @@ class GraphedEvalStep:
             static = data.clone()
             if not self._copy_dynamic:
                 static.edge_index = data.edge_index                # identity matters: the adjacency caches key on it
-            return _Child(static, dynamic=self._copy_dynamic)
+            ch = _Child(static, dynamic=self._copy_dynamic)
+            if errors:
+                ch.pos = torch.arange(self._pos, self._pos + B).to(data.x.device)
+            return ch
         ch = self._ready(("copy", sig), make)
         if ch is None:
             return self._eager(data)
+        if errors:                                                 # the running position: one index copy per batch
+            ch.pos.copy_(torch.arange(self._pos, self._pos + B))
+            self._pos += B
         for k in ("x", "y", "pred_mask", "edge_attr") + (("edge_index",) if ch.dynamic else ()):
             getattr(ch.static, k).copy_(getattr(data, k))
         ch.graph.replay()
         return ch.n_keys
 
-    def _loop(self, loader, device):
-        ds = getattr(loader, "dataset", None)
-        if self.disabled:                                          # the plain loop: collate, forward, losses, device sums
-            return sum(self._eager(data.to(device)) for data in loader)
+    def _index_mode(self, loader, ds, device):
+        """"indexed" / "topo": the batches are gathered inside the graph from the loader's device index batches; None: collated."""
         indexed = hasattr(loader, "index_batches") and ds is not None and getattr(ds, "transform", None) is None
         on_dev = indexed and hasattr(ds, "device") and _same_device(ds.device, device)
         if on_dev and hasattr(ds, "can_gather") and ds.can_gather():
-            return sum(self._step_indexed(ds, idx, False) for idx in loader.index_batches(device))
+            return "indexed"
         if (on_dev and hasattr(ds, "can_gather_topologies") and ds.can_gather_topologies() and hasattr(self.model, "segment_build")
                 and hasattr(getattr(self.model, "_graphs", None), "adopt") and self._topology_owners() == [self.model]):
-            return sum(self._step_indexed(ds, idx, True) for idx in loader.index_batches(device))
+            return "topo"
+        return None
+
+    def _loop(self, loader, device):
+        ds = getattr(loader, "dataset", None)
+        if self.disabled:                                          # the plain loop: collate, forward, losses, device sums
+            if self.kind == "errors" and self._index_mode(loader, ds, device) is not None:
+                # the table row is the SAMPLE index wherever the graphed pass would hold it on the device: the eager pass
+                # fills the same rows (one index copy per batch, no read-back)
+                self.rows_by_index, n = True, 0
+                for rows in loader._index_lists():
+                    self._eager_idx = torch.tensor(rows, dtype=torch.long).to(device)
+                    n += self._eager(ds.collate_indices(rows))
+                return n
+            return sum(self._eager(data.to(device)) for data in loader)
+        mode = self._index_mode(loader, ds, device)
+        if mode is not None:
+            self.rows_by_index = True
+            return sum(self._step_indexed(ds, idx, mode == "topo") for idx in loader.index_batches(device))
         n = 0
         transform = getattr(ds, "transform", None) is not None
         for data in loader:
@@ -410,7 +496,7 @@ class GraphedEvalStep:
         was_training = model.training
         attach = model.__dict__.get("_mse_attach")
         model.eval()
-        self.eager_batches = 0
+        self.eager_batches, self.rows_by_index = 0, False
         try:
             with torch.no_grad(), torch.cuda.device(device):
                 self._check_params()
@@ -419,6 +505,8 @@ class GraphedEvalStep:
                     n = self._loop(loader, device)
                 except _CaptureFailed:
                     n = self._loop(loader, device)                 # (disabled now: every batch runs the eager body)
+                if self.kind == "errors":                          # moments + flags word: ONE read-back
+                    return self._mom.cpu(), None, n
                 return self._acc.cpu(), self._racc.cpu(), n
         finally:
             model.train(was_training)
