@@ -11,13 +11,14 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import gc
 import os
 import sys
 from typing import Iterable, Optional
 
 import torch
 import torch.distributed as dist
+
+from .utils.captured import no_gc
 
 
 def init_from_env(backend: Optional[str] = None):
@@ -219,23 +220,13 @@ class GraphedStep:
     def _try(self, build) -> bool:
         """Run one capture attempt; True iff it succeeded on EVERY rank."""
         err = None
-        # No cyclic collection inside a capture window.  The backward pass of the captured step runs on autograd's thread and allocates
-        # Python objects there, so an automatic collection can begin in the middle of the capture, on a thread that is not the
-        # capturing one; what its finalizers do (freeing device tensors, destroying events or graphs) are runtime calls a capture in
-        # progress does not permit, and an error raised inside a destructor ends the process (seen once: an abort from a collection
-        # that had started at the first allocation of MaskEmbdMultiMPN's captured backward).  The collector is held back until the
-        # attempt is over; nothing is lost, the next pass collects the same objects.
-        gc_was_on = gc.isenabled()
-        gc.disable()
         try:
-            build()
+            with no_gc():                          # (for the whole attempt: the backward pass allocates on autograd's thread)
+                build()
         except Exception as exc:                   # noqa: BLE001
             err = exc
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
-        finally:
-            if gc_was_on:
-                gc.enable()
         if not self.allreduce:
             if err is not None:
                 raise err

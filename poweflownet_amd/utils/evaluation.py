@@ -1,7 +1,6 @@
 """`evaluate_epoch` / `load_model` / `num_params` counterparts of the reference's utils/evaluation.py:20-104, plus what the
 reference does not have: `GraphedEvalStep` (an evaluation epoch replayed from one hipGraph per batch size, its running sums kept
 on the device) and `evaluate_report` (every line test.py prints from ONE pass over the split, `pfn_eval_metrics`)."""
-import gc
 import warnings
 from typing import Callable, Optional
 
@@ -9,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .captured import BatchSource, capture_state, copy_batch, held_adjacencies, no_gc, topologies_gatherable, topology_owners, warm_up
 from .custom_loss_functions import Masked_L2_loss, MaskedL1, MaskedL2V2, MixedMSEPoweImbalance, PowerImbalance
 
 
@@ -133,11 +133,12 @@ def _std4(xystd):
 
 # ------------------------------------------------------------------------------------------------ the step
 class _Child:
-    """One captured per-batch body: its input tensors, (indexed modes) its index buffer, the graph and the adjacencies it reads."""
-    __slots__ = ("static", "idx", "topo_graph", "dynamic", "graph", "held", "n_keys", "pos")
+    """One captured per-batch body: its input tensors, (indexed modes) their BatchSource, the graph and the adjacencies it reads."""
+    __slots__ = ("static", "source", "topo_graph", "dynamic", "graph", "held", "n_keys", "pos")
 
-    def __init__(self, static, idx=None, topo_graph=None, dynamic=False):
-        self.static, self.idx, self.topo_graph, self.dynamic = static, idx, topo_graph, bool(dynamic)
+    def __init__(self, static, source=None, dynamic=False):
+        self.static, self.source, self.dynamic = static, source, bool(dynamic)
+        self.topo_graph = None if source is None else source.topo_graph     # (the adjacency a `topo` source builds into)
         self.graph, self.held, self.n_keys = None, [], len(static)
         self.pos = None                # errors, copied batches: the table rows of the batch (device int64, filled per batch)
 
@@ -164,12 +165,10 @@ class GraphedEvalStep:
     `evaluate_epoch_v2` or `evaluate_report` as `graph=`; it serves ONE of them with ONE loss at a time (another loss, another
     `pre_loss_fn` or another kind of epoch drops the captured graphs and captures again).
 
-    How a batch gets into the captured inputs:
-      * a `can_gather()` dataset on the model's device is gathered INSIDE the graph from a device index buffer: per batch one index
-        copy and one graph launch, no collate (as `GraphedTrainStep.step_indexed`);
-      * a `can_gather_topologies()` dataset (one line set per sample) goes through `gather_topologies_into` + `_GraphCache.adopt`
-        with the adjacency build inside the graph; `model.segment_build` is raised for the warm-up and the capture only.  The
-        checks of such a build stay on the device: a bad batch gives a NaN loss instead of an exception;
+    How a batch gets into the captured inputs (the capture rules are those of utils/captured.py):
+      * a `can_gather()` dataset on the model's device is pulled INSIDE the graph (`BatchSource.indexed`, as
+        `GraphedTrainStep.step_indexed`), a `can_gather_topologies()` one (one line set per sample) with its adjacency
+        (`BatchSource.topo`).  The checks of such a build stay on the device: a bad batch gives a NaN loss instead of an exception;
       * any other loader whose batch has the captured shapes is copied into the captured inputs -- with the captured `edge_index`
         tensor itself the adjacency is the cached one; a loader that hands out a NEW `edge_index` per batch (a list-backed one)
         switches to the dynamic form, where the list is copied too and the adjacency is rebuilt inside the graph (again: a bad
@@ -177,8 +176,7 @@ class GraphedEvalStep:
       * everything else runs the eager body on the same device accumulators: ragged batches (a mixed split), a dataset with a
         per-sample transform, more shapes than `max_children`, a failed capture (with a warning).
 
-    The step holds the `GraphCSR`s its launches read (training and evaluation take turns in the model's one-entry adjacency
-    cache), leaves the model as it found it (mode, dropout RNG state, gradients, `dynamic_topology`, `segment_build`, an attached
+    The step leaves the model as it found it (mode, dropout RNG state, gradients, `dynamic_topology`, `segment_build`, an attached
     loss) and captures again when a parameter's storage moved (`FlatAdamW` re-flattens them) -- not when values changed in place.
     `captures` counts the captures."""
 
@@ -204,13 +202,9 @@ class GraphedEvalStep:
         self._pos, self._eager_idx, self.rows_by_index = 0, None, False
 
     # ------------------------------------------------------------------------------------------ plumbing
-    def _topology_owners(self):
-        owners = [self.model] if hasattr(self.model, "dynamic_topology") else []
-        mods = [self.loss_fn] + ([self._extras[1]] if self._extras else [])
-        for m in mods:
-            if isinstance(m, nn.Module):
-                owners += [o for o in m.modules() if hasattr(o, "dynamic_topology") and o not in owners]
-        return owners
+    def _owners(self):
+        """captured.topology_owners of the model, the loss and (report) the PowerImbalance behind `_extras`."""
+        return topology_owners(self.model, self.loss_fn, *(self._extras[1:2] if self._extras else ()))
 
     def _drop_all(self):
         self._children = {}
@@ -275,13 +269,8 @@ class GraphedEvalStep:
         """One batch: (indexed modes) pull it, forward, losses, running sums.  Runs under no_grad with the model in eval mode;
         captured as it stands."""
         from ..loss import eval_accumulate, eval_metrics
-        if ch is not None and ch.idx is not None:
-            ds = ch.idx[0]
-            if ch.topo_graph is not None:
-                ds.gather_topologies_into(data, ch.idx[1], ch.topo_graph)
-                self.model._graphs.adopt(data.edge_index, ch.topo_graph)
-            else:
-                ds.gather_into(data, ch.idx[1])
+        if ch is not None and ch.source is not None:
+            ch.source.pull(data, self.model)
         out = self.model(data)
         w = float(len(data))
         pre = self.pre_loss_fn or _identity
@@ -301,7 +290,7 @@ class GraphedEvalStep:
         elif self.kind == "errors":
             from ..loss import bus_errors_accumulate
             std4, mean4, _, _, table_rows, n_bus = self._extras
-            rows = self._eager_idx if ch is None else (ch.idx[1] if ch.idx is not None else ch.pos)
+            rows = self._eager_idx if ch is None else (ch.source.buffer if ch.source is not None else ch.pos)
             bus_errors_accumulate(out, data.y, data.pred_mask, n_bus, rows, self._mom[:-1], self._mom[-1:].view(torch.int32),
                                   std=std4, mean=mean4, err_table=self._etab, pred_table=self._ptab, table_rows=table_rows)
         else:
@@ -327,47 +316,23 @@ class GraphedEvalStep:
 
     # ------------------------------------------------------------------------------------ capture
     def _capture(self, ch):
-        model = self.model
         if self.side is None:
             self.side = torch.cuda.Stream()
-        side, owners = self.side, self._topology_owners()
-        prev = [(o, o.dynamic_topology) for o in owners]
-        prev_seg = getattr(model, "segment_build", False)
-        if ch.dynamic:
-            for o in owners:
-                o.dynamic_topology = True
-        if ch.topo_graph is not None:
-            model.segment_build = True
+        owners = self._owners()
         snap = (self._acc.clone(), self._racc.clone())            # the warm-up passes leave no trace in the running sums
         if self.kind == "errors":
             snap += (self._mom.clone(),)
-        gc_was_on = gc.isenabled()
-        try:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                          # warm-up off the capture stream (allocator, adjacency cache)
-                for _ in range(2):
-                    self._body(ch, ch.static)
-            torch.cuda.current_stream().wait_stream(side)
+        with capture_state(owners, self.model, ch.dynamic, ch.topo_graph is not None):
+            warm_up(self.side, lambda: self._body(ch, ch.static))
             self._acc.copy_(snap[0])
             self._racc.copy_(snap[1])
             if len(snap) > 2:
                 self._mom.copy_(snap[2])
             g = torch.cuda.CUDAGraph()
-            gc.disable()                                           # (no cyclic collection inside a capture window: dp.GraphedStep._try)
-            with torch.cuda.graph(g):
+            with no_gc(), torch.cuda.graph(g):
                 self._body(ch, ch.static)
-        finally:
-            if gc_was_on:
-                gc.enable()
-            for o, was in prev:
-                o.dynamic_topology = was
-            if ch.topo_graph is not None:
-                model.segment_build = prev_seg
         ch.graph = g
-        # the captured launches read the workspaces of these adjacencies, whose only other owner is a one-entry cache
-        ch.held = [o._graphs._graph for o in owners if getattr(o, "_graphs", None) is not None]
-        if ch.topo_graph is not None:
-            ch.held.append(ch.topo_graph)
+        ch.held = held_adjacencies(owners, ch.topo_graph)
         self.captures += 1
 
     def _ready(self, key, make):
@@ -399,17 +364,13 @@ class GraphedEvalStep:
 
         def make():
             static = ds.collate_indices(idx.tolist())
-            tg = None
-            if topo:
-                from ..networks.MPN import GraphCSR
-                n_of, e_of, _ = ds.case_sizes()
-                tg = GraphCSR.for_block(B * n_of[0], B * e_of[0], n_of[0], e_of[0], static.x.device)
-            return _Child(static, idx=(ds, idx.clone()), topo_graph=tg, dynamic=topo)
+            source = BatchSource.topo(ds, idx, static.x.device) if topo else BatchSource.indexed(ds, idx)
+            return _Child(static, source, dynamic=topo)
         ch = self._ready(("topo" if topo else "indexed", id(ds), B), make)
         if ch is None:
             self._eager_idx = idx if self.kind == "errors" else None
             return self._eager(ds.collate_indices(idx.tolist()))
-        ch.idx[1].copy_(idx)
+        ch.source.buffer.copy_(idx)
         ch.graph.replay()
         self._pos += B
         return ch.n_keys
@@ -446,8 +407,7 @@ class GraphedEvalStep:
         if errors:                                                 # the running position: one index copy per batch
             ch.pos.copy_(torch.arange(self._pos, self._pos + B))
             self._pos += B
-        for k in ("x", "y", "pred_mask", "edge_attr") + (("edge_index",) if ch.dynamic else ()):
-            getattr(ch.static, k).copy_(getattr(data, k))
+        copy_batch(ch.static, data, ch.dynamic)
         ch.graph.replay()
         return ch.n_keys
 
@@ -457,8 +417,7 @@ class GraphedEvalStep:
         on_dev = indexed and hasattr(ds, "device") and _same_device(ds.device, device)
         if on_dev and hasattr(ds, "can_gather") and ds.can_gather():
             return "indexed"
-        if (on_dev and hasattr(ds, "can_gather_topologies") and ds.can_gather_topologies() and hasattr(self.model, "segment_build")
-                and hasattr(getattr(self.model, "_graphs", None), "adopt") and self._topology_owners() == [self.model]):
+        if on_dev and topologies_gatherable(self.model, self._owners(), ds):
             return "topo"
         return None
 

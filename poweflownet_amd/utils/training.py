@@ -11,6 +11,8 @@ import torch.nn as nn
 
 from .. import dp
 from ..loss import MSELoss, slot_validity
+from .captured import (BatchSource, capture_state, copy_batch, held_adjacencies, run_on, topologies_gatherable, topology_owners,
+                       warm_up)
 from .custom_loss_functions import Masked_L2_loss, MixedMSEPoweImbalance, PowerImbalance
 
 
@@ -93,6 +95,25 @@ def _guarded_opt_step(optimizer, model, loss, allreduce: bool):
         optimizer.guard = None
 
 
+def _fwd_bwd(model, loss_fn, optimizer, data, source=None):
+    """The loop body of utils/training.py:55-74 up to the optimizer; a child of a GraphedTrainStep pulls its batch first."""
+    if source is not None:
+        source.pull(data, model)
+    optimizer.zero_grad()
+    _announce_loss(loss_fn, model, data)
+    loss = _dispatch_loss(loss_fn, model(data), data)
+    _backward(loss_fn, loss)
+    return loss.detach()
+
+
+def _eager_step(model, loss_fn, optimizer, data, allreduce: bool, source=None):
+    loss = _fwd_bwd(model, loss_fn, optimizer, data, source)
+    if allreduce:
+        dp.allreduce_gradients(model)
+    _guarded_opt_step(optimizer, model, loss, allreduce)
+    return loss
+
+
 class GraphedTrainStep:
     """The per-batch body of `train_epoch` (zero_grad -> forward -> loss -> backward -> step) captured ONCE into a hipGraph
     and replayed for every following batch of the same shape and topology: the ~34 kernel launches of a step cost one
@@ -111,25 +132,20 @@ class GraphedTrainStep:
     def __init__(self, model, loss_fn, optimizer, allreduce: Optional[bool] = None, dp_mode: Optional[str] = None,
                  mixed_slots: bool = False, slot_granule: int = 8, per_sample_topology: bool = False):
         self.model, self.loss_fn, self.opt = model, loss_fn, optimizer
-        # per_sample_topology: a device-resident split whose samples each have their own line set (`dataset.
-        # can_gather_topologies()`) is driven through `step_topologies` -- the captured step pulls its samples AND builds their
-        # adjacency from the dataset's dense edge block, one workgroup per graph (pfn_graph_build_segments); per batch one index
-        # copy and one graph launch, no host-side collate.  Off by default
+        # A device-resident dataset is driven through child steps whose captured body pulls its own batch (captured.BatchSource):
+        # step_indexed, one child per batch SIZE (the epoch's short last batch gets a graph of its own);
+        self._children = {}
+        # per_sample_topology: step_topologies for a split whose samples each have their own line set -- the pull builds their
+        # adjacency too, one workgroup per graph (pfn_graph_build_segments).  Off by default;
         self.per_sample_topology = bool(per_sample_topology)
         self._topo_children = {}   # batch size -> child
-        self._topo_graph = None    # a child of step_topologies: the GraphCSR its captured gather builds into
-        # mixed_slots: a split of several grid cases (`dataset.can_gather_slots()`) is driven through `step_slots` -- every batch's
-        # per-case counts rounded up to `slot_granule` name a bucket with a static shape, topology and segment layout, spare slots
-        # filled with graphs of loss weight 0; one captured child per bucket, per batch one slot-table copy and one graph launch
+        # mixed_slots: step_slots for a split of several grid cases -- a batch's per-case counts rounded up to `slot_granule` name a
+        # bucket with a static shape, topology and segment layout, spare slots filled with graphs of loss weight 0
         self.mixed_slots, self.slot_granule = bool(mixed_slots), int(slot_granule)
         self._slot_children = {}   # bucket -> child
-        self._slots = False        # a child of step_slots: _source = (dataset, captured slot table)
         self.slot_fallbacks = 0    # batches of a mixed_slots epoch that ran the eager path (bucket cap reached)
+        self.source = None         # a child: where its captured body pulls the batch from; `_template` is what it pulls it into
         self.dp_mode = dp_mode     # graph | split | eager (dp.GraphedStep; None: PFN_DP_MODE or "graph")
-        # indexed mode (step_indexed): one child step per batch SIZE (the epoch's short last batch gets a graph of its own), each
-        # gathering its samples from the device-resident dataset INSIDE its captured graph
-        self._children = {}
-        self._source = None        # (dataset, captured index buffer) of a child
         self._guard_buf = None     # data parallel + guarded update: the loss, SUM-all-reduced, so that every rank skips together
         # data parallel (dp.py): the gradient all-reduce is part of the replayed step -- ONE hipGraph with the RCCL collective
         # captured between backward and optimizer, or graph / eager all-reduce / graph for a backend that cannot be captured
@@ -145,17 +161,12 @@ class GraphedTrainStep:
         self.dynamic = False
         self._held = []            # GraphCSRs whose workspaces the captured launches read (kept alive as long as the graph is)
 
-    def _topology_owners(self):
-        """Everything that keeps an adjacency per `edge_index`: the model and the loss modules that walk the grid themselves
-        (PowerImbalance, also inside MixedMSEPoweImbalance)."""
-        owners = [self.model] if hasattr(self.model, "dynamic_topology") else []
-        if isinstance(self.loss_fn, nn.Module):
-            owners += [m for m in self.loss_fn.modules() if hasattr(m, "dynamic_topology")]
-        return owners
+    def _owners(self):
+        return topology_owners(self.model, self.loss_fn)
 
-    def _set_dynamic_topology(self, on: bool):
-        for o in self._topology_owners():
-            o.dynamic_topology = bool(on)
+    def _capture_state(self):
+        """dynamic_topology when `dynamic`, segment_build for a child of step_topologies."""
+        return capture_state(self._owners(), self.model, self.dynamic, self.source is not None and self.source.kind == "topo")
 
     def _drop_graph(self):
         self.graph = self.static = None
@@ -171,48 +182,19 @@ class GraphedTrainStep:
         betas = tuple(float(b) for b in g.get("betas", ()))
         return (float(g["lr"]), betas, float(g.get("eps", 0.0)), float(g.get("weight_decay", 0.0)))
 
-    def _fwd_bwd(self, data):
-        if self._source is not None:                               # indexed mode: pull the batch named by the index buffer
-            if self._slots:
-                self._source[0].gather_slots_into(data, self._source[1])
-            elif self._topo_graph is not None:
-                # the gather wrote data.edge_index AND its adjacency in one call: the model's next cache lookup takes it as built
-                self._source[0].gather_topologies_into(data, self._source[1], self._topo_graph)
-                self.model._graphs.adopt(data.edge_index, self._topo_graph)
-            else:
-                self._source[0].gather_into(data, self._source[1])
-        self.opt.zero_grad()
-        _announce_loss(self.loss_fn, self.model, data)
-        loss = _dispatch_loss(self.loss_fn, self.model(data), data)
-        _backward(self.loss_fn, loss)
-        return loss.detach()
-
     def _eager_body(self, data):
-        loss = self._fwd_bwd(data)
-        if self.allreduce:
-            dp.allreduce_gradients(self.model)
-        _guarded_opt_step(self.opt, self.model, loss, self.allreduce)
-        return loss
+        return _eager_step(self.model, self.loss_fn, self.opt, data, self.allreduce, self.source)
 
     def _replay_eager_form(self):
         """dp.GraphedStep demoted to (or asked for) its "eager" form calls the captured closure on every step: it needs the
         state `_capture` raised around the capture -- per-batch topologies rebuilt on the device instead of the cached,
         host-synchronising build -- and must not leave the optimizer's guard bound to this step's loss afterwards."""
-        prev = [(o, o.dynamic_topology) for o in self._topology_owners()]
-        prev_seg = getattr(self.model, "segment_build", False)
-        if self.dynamic:
-            self._set_dynamic_topology(True)
-        if self._topo_graph is not None:
-            self.model.segment_build = True
-        try:
-            return self.graph.replay()
-        finally:
-            if hasattr(self.opt, "guard"):
-                self.opt.guard = None
-            for o, was in prev:
-                o.dynamic_topology = was
-            if self._topo_graph is not None:
-                self.model.segment_build = prev_seg
+        with self._capture_state():
+            try:
+                return self.graph.replay()
+            finally:
+                if hasattr(self.opt, "guard"):
+                    self.opt.guard = None
 
     def _eager(self, data):
         """The eager body -- on the side stream of the capture's warm-up once there is one: autograd binds a parameter's
@@ -220,12 +202,7 @@ class GraphedTrainStep:
         per parameter on the host (35 parameters: 1.06 instead of 0.69 ms per step at case118v2 x 128)."""
         if self.side is None:
             return self._eager_body(data)
-        cur = torch.cuda.current_stream()
-        self.side.wait_stream(cur)
-        with torch.cuda.stream(self.side):
-            loss = self._eager_body(data)
-        cur.wait_stream(self.side)
-        return loss
+        return run_on(self.side, lambda: self._eager_body(data))
 
     def _snapshot(self):
         """Everything a training step mutates, so that the warm-up steps torch asks for before a capture leave no trace."""
@@ -257,22 +234,10 @@ class GraphedTrainStep:
         self.static = data.clone()
         if not self.dynamic:
             self.static.edge_index = data.edge_index               # identity matters: the model's adjacency cache keys on it
-        # dynamic: the clone IS the captured edge_index buffer.  `dynamic_topology` is raised on the model AND on every loss
-        # module that keeps an adjacency of its own (PowerImbalance: with its cache the replayed loss kept walking the
-        # capture-time topology) for the warm-up and the capture only: the captured launches rebuild from the
-        # buffer; forwards outside the graph (evaluation, the short last batch) keep the validated, cached build.
+        # (dynamic: the clone IS the captured edge_index buffer the captured launches rebuild the adjacency from)
         snap = self._snapshot()
         if self.side is None:
             self.side = torch.cuda.Stream()
-        side = self.side
-        prev = [(o, o.dynamic_topology) for o in self._topology_owners()]
-        prev_seg = getattr(self.model, "segment_build", False)
-        if self.dynamic:
-            self._set_dynamic_topology(True)
-        if self._topo_graph is not None:
-            # (like dynamic_topology: for the warm-up and the capture only.  Should the model ever decline the adjacency the
-            #  gather built, its own in-graph build of the collated list is the segmented one too)
-            self.model.segment_build = True
         guarded = self.dynamic and hasattr(self.opt, "guard")
         # a guarded update under data parallelism must be decided on a value EVERY rank sees: one rank's bad batch reaches the
         # others only as NaN gradients through the all-reduce -- their own losses are finite -- so the losses are summed across
@@ -280,42 +245,32 @@ class GraphedTrainStep:
         shared_guard = guarded and self.allreduce and dp.active()
         if shared_guard and self._guard_buf is None:
             self._guard_buf = torch.zeros((), dtype=torch.float32, device=data.x.device)
-        try:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                          # warm-up off the capture stream (allocator, adjacency cache)
-                for _ in range(2):
-                    self._eager_body(self.static)
-            torch.cuda.current_stream().wait_stream(side)
-            self._restore(snap)
-            self.opt.zero_grad(set_to_none=True)
-            box = {}
 
-            def fwd_bwd():
-                box["loss"] = self._fwd_bwd(self.static)
-                if guarded:
-                    # unverified batches: a bad one (ids out of range, edges across the claimed graph boundaries) reaches the
-                    # step as a NaN loss (pfn_graph_poison_if_bad); the captured update then SKIPS instead of turning every
-                    # parameter NaN for good (the reference would have raised before the step)
-                    if shared_guard:
-                        self._guard_buf.copy_(box["loss"])
-                        self.opt.guard = self._guard_buf
-                    else:
-                        self.opt.guard = box["loss"]
-                return box["loss"]
-            self.graph = dp.GraphedStep(fwd_bwd, self.opt.step, self.model, self.allreduce, mode=self.dp_mode,
-                                        extra=[self._guard_buf] if shared_guard else ()).capture()
+        def fwd_bwd():
+            loss = _fwd_bwd(self.model, self.loss_fn, self.opt, self.static, self.source)
+            if guarded:
+                # unverified batches: a bad one (ids out of range, edges across the claimed graph boundaries) reaches the step as
+                # a NaN loss (pfn_graph_poison_if_bad); the captured update then SKIPS instead of turning every parameter NaN for
+                # good (the reference would have raised before the step)
+                if shared_guard:
+                    self._guard_buf.copy_(loss)
+                    self.opt.guard = self._guard_buf
+                else:
+                    self.opt.guard = loss
+            return loss
+        try:
+            with self._capture_state():
+                warm_up(self.side, lambda: self._eager_body(self.static))
+                self._restore(snap)
+                self.opt.zero_grad(set_to_none=True)
+                self.graph = dp.GraphedStep(fwd_bwd, self.opt.step, self.model, self.allreduce, mode=self.dp_mode,
+                                            extra=[self._guard_buf] if shared_guard else ()).capture()
         finally:
             if guarded:
                 self.opt.guard = None
-            for o, was in prev:
-                o.dynamic_topology = was
-            if self._topo_graph is not None:
-                self.model.segment_build = prev_seg
         self.loss = self.graph.out
         self.key = self._hyper_key()
-        # static mode: the captured launches read the workspaces of the adjacencies built during the warm-up, whose only other
-        # owner is a one-entry cache -- a batch with another edge_index (evaluation, a short last batch) would evict and free them
-        self._held = [o._graphs._graph for o in self._topology_owners() if getattr(o, "_graphs", None) is not None]
+        self._held = held_adjacencies(self._owners())
         return self.loss                                           # the capture pass does not execute: caller replays
 
     def _same_shapes(self, data):
@@ -330,50 +285,46 @@ class GraphedTrainStep:
     def _compatible(self, data):
         return self._same_shapes(data) and (self.dynamic or data.edge_index is self.static.edge_index)
 
-    def step_indexed(self, dataset, idx):
-        """One training step on the samples `idx` (a device int64 tensor) of a device-resident dataset (`dataset.can_gather()`).
-        The captured graph contains the five row gathers that assemble the batch, so a step costs the host ONE 1-KiB device copy
-        (the indices) and ONE graph launch -- no collate, no per-field copies; every batch size met gets its own
-        captured step (the short last batch of an epoch no longer runs eager).  Returns (loss, len(batch)) like the loop needs."""
-        B = int(idx.numel())
-        child = self._children.get(B)
+    def _child(self, children, key, make, dynamic=False):
+        """The child step `children[key]`, made on first use: a step of its own (graph, captured inputs, hyper-parameter key)
+        whose captured body starts by pulling its batch from `source` into `_template`; `make()` returns (template, source)."""
+        child = children.get(key)
         if child is None:
-            child = GraphedTrainStep(self.model, self.loss_fn, self.opt, self.allreduce, self.dp_mode)
-            child._source = (dataset, idx.clone())
-            child._template = dataset.collate_indices(idx.tolist())   # shapes, edge_index / batch / ptr of this batch size
-            self._children[B] = child
-        child.allreduce = self.allreduce
-        child._source[1].copy_(idx)
-        return child(child._template), len(child._template)
+            child = children[key] = GraphedTrainStep(self.model, self.loss_fn, self.opt, False, self.dp_mode)
+            child._template, child.source = make()
+            child.dynamic = dynamic
+        return child
+
+    def _replay_from(self, buffer, non_blocking=False):
+        """A child's step on the samples `buffer` names: ONE copy into the captured buffer, ONE graph launch.  (loss, len(batch))."""
+        self.source.buffer.copy_(buffer, non_blocking=non_blocking)
+        return self(self._template), len(self._template)
+
+    def step_indexed(self, dataset, idx):
+        """One training step on the samples `idx` (a device int64 tensor) of a device-resident dataset (`dataset.can_gather()`):
+        the captured graph contains the five row gathers that assemble the batch, so a step costs the host ONE 1-KiB device copy
+        (the indices) and ONE graph launch.  Returns (loss, len(batch)) like the loop needs."""
+        def make():                                                # the template: shapes, edge_index / batch / ptr of this batch size
+            return dataset.collate_indices(idx.tolist()), BatchSource.indexed(dataset, idx)
+        child = self._child(self._children, int(idx.numel()), make)
+        child.allreduce = self.allreduce                           # (the only children that run under data parallelism)
+        return child._replay_from(idx)
 
     def topologies_supported(self, dataset, device=None) -> bool:
         """Does `train_epoch` drive this dataset through `step_topologies`?  per_sample_topology on, no data parallelism, no
-        mixed_slots, the model the only owner of an adjacency (a loss module that walks the grid itself keeps a build of its own
-        and passes no segment hint: today's dynamic path), a dataset whose `can_gather_topologies()` holds on `device`."""
+        mixed_slots, `captured.topologies_gatherable`, the dataset on `device`."""
         return bool(self.per_sample_topology and not self.allreduce and not self.mixed_slots
-                    and hasattr(self.model, "segment_build") and hasattr(getattr(self.model, "_graphs", None), "adopt")
-                    and self._topology_owners() == [self.model]
-                    and hasattr(dataset, "can_gather_topologies") and dataset.can_gather_topologies()
+                    and topologies_gatherable(self.model, self._owners(), dataset)
                     and (device is None or dataset.device == torch.device(device)))
 
     def step_topologies(self, dataset, idx):
-        """`step_indexed` for a split with one topology per sample (`dataset.can_gather_topologies()`): the captured graph holds
-        the five row gathers, the ONE call that collates the samples' edge lists and builds their adjacency (one workgroup per
-        graph), and the step in dynamic mode -- guarded update included, since the checks of such a build stay on the device.  Per
-        batch the host issues one index copy and one graph launch; `collate_indices` runs once per batch SIZE, for the template."""
-        from ..networks.MPN import GraphCSR
-        B = int(idx.numel())
-        child = self._topo_children.get(B)
-        if child is None:
-            child = GraphedTrainStep(self.model, self.loss_fn, self.opt, False, self.dp_mode)
-            child._source = (dataset, idx.clone())
-            child._template = dataset.collate_indices(idx.tolist())
-            n_of, e_of, _ = dataset.case_sizes()
-            child._topo_graph = GraphCSR.for_block(B * n_of[0], B * e_of[0], n_of[0], e_of[0], child._template.x.device)
-            child.dynamic = True
-            self._topo_children[B] = child
-        child._source[1].copy_(idx)
-        return child(child._template), len(child._template)
+        """`step_indexed` for a split with one topology per sample (`dataset.can_gather_topologies()`): the pull builds the batch's
+        adjacency too, and the step is in dynamic mode -- guarded update included, since the checks of such a build stay on the
+        device.  `collate_indices` runs once per batch SIZE, for the template."""
+        def make():
+            template = dataset.collate_indices(idx.tolist())
+            return template, BatchSource.topo(dataset, idx, template.x.device)
+        return self._child(self._topo_children, int(idx.numel()), make, dynamic=True)._replay_from(idx)
 
     def slots_supported(self, dataset, device=None) -> bool:
         """Does `train_epoch` drive this dataset through `step_slots`?  mixed_slots on, no data parallelism, a loss that takes the
@@ -382,41 +333,47 @@ class GraphedTrainStep:
                     and hasattr(dataset, "can_gather_slots") and dataset.can_gather_slots()
                     and (device is None or dataset.device == torch.device(device)))
 
-    def _slot_child(self, dataset, bucket):
-        """The child step of `bucket` (its template is built on first use), or None: the bucket would be one too many."""
-        child = self._slot_children.get(bucket)
-        if child is None:
-            if len(self._slot_children) >= self.max_slot_buckets:
-                return None
-            child = GraphedTrainStep(self.model, self.loss_fn, self.opt, False, self.dp_mode)
-            child._slots = True
-            child._template = dataset.slot_template(bucket, getattr(self.model, "segment_max_padding", 0.25))
-            child._source = (dataset, torch.zeros(child._template._slot_layout.n_slots, 2, dtype=torch.int32,
-                                                  device=child._template.x.device))
-            self._slot_children[bucket] = child
-        return child
-
-    def step_slots(self, dataset, indices, table: Optional[torch.Tensor] = None, fillers=None):
-        """One training step on the samples `indices` (host ints) of a mixed device-resident dataset, replayed from the hipGraph of
-        the batch's bucket (`segpack.bucket_of` of its per-case counts at `slot_granule`).  The captured graph starts with the one
-        launch that collates and packs the batch from the slot table (`dataset.gather_slots_into`), so a step costs the host the
-        O(graphs) slot table, ONE copy of it into the captured buffer and ONE graph launch.  `table`: the slot table already on the
-        device (train_epoch uploads an epoch's tables in one copy); otherwise it is built and copied here.  Returns (loss,
-        len(batch)), or None when the bucket would be one more than `max_slot_buckets`: the caller runs its eager path."""
+    def _slot_plan(self, dataset, indices, fillers=None):
+        """(the child step of the bucket of the batch `indices` -- `segpack.bucket_of` of its per-case counts at `slot_granule`; its
+        template is built on first use --, the batch's slot table on the host), or None: the bucket would be one too many."""
         from .. import segpack
         per_case = dataset.group_by_case(indices)
-        child = self._slot_child(dataset, segpack.bucket_of([int(p.shape[0]) for p in per_case], self.slot_granule))
-        if child is None:
+        bucket = segpack.bucket_of([int(p.shape[0]) for p in per_case], self.slot_granule)
+        if bucket not in self._slot_children and len(self._slot_children) >= self.max_slot_buckets:
             return None
-        if table is None:
-            host = segpack.slot_table(child._template._slot_layout, per_case, dataset.case_sizes()[2], fillers)
-            table = torch.from_numpy(host)
-        return self._replay_slots(child, table)
 
-    @staticmethod
-    def _replay_slots(child, table):
-        child._source[1].copy_(table, non_blocking=True)
-        return child(child._template), len(child._template)
+        def make():
+            template = dataset.slot_template(bucket, getattr(self.model, "segment_max_padding", 0.25))
+            return template, BatchSource.slots(dataset, template._slot_layout.n_slots, template.x.device)
+        child = self._child(self._slot_children, bucket, make)
+        return child, segpack.slot_table(child._template._slot_layout, per_case, dataset.case_sizes()[2], fillers)
+
+    def step_slots(self, dataset, indices, fillers=None):
+        """One training step on the samples `indices` (host ints) of a mixed device-resident dataset, replayed from the hipGraph of
+        the batch's bucket: a step costs the host the O(graphs) slot table, ONE copy of it into the captured buffer and ONE graph
+        launch.  Returns (loss, len(batch)), or None when the bucket would be one more than `max_slot_buckets`: the caller runs
+        its eager path."""
+        plan = self._slot_plan(dataset, indices, fillers)
+        return None if plan is None else plan[0]._replay_from(torch.from_numpy(plan[1]), non_blocking=True)
+
+    def slot_epoch(self, dataset, lists, device):
+        """`step_slots` over the batches `lists` of an epoch, as (loss, len(batch)) per batch, the epoch's slot tables uploaded in
+        ONE copy before the first replay.  A batch past the bucket cap runs what a mixed batch runs without mixed_slots, and is
+        counted in `slot_fallbacks`."""
+        lists = list(lists)
+        plans = [self._slot_plan(dataset, idx) for idx in lists]
+        tabs = [plan[1] for plan in plans if plan is not None]
+        dev_tab = torch.from_numpy(np.concatenate(tabs)).to(device, non_blocking=True) if tabs else None
+        row = 0
+        for idx, plan in zip(lists, plans):
+            if plan is None:
+                self.slot_fallbacks += 1
+                data = dataset.collate_indices(idx)
+                yield self(data), len(data)
+            else:
+                rows = plan[1].shape[0]
+                yield plan[0]._replay_from(dev_tab[row:row + rows], non_blocking=True)
+                row += rows
 
     def slot_buckets(self):
         """The buckets that have a child step, in the order they were met."""
@@ -473,9 +430,8 @@ class GraphedTrainStep:
             return self._eager(data)                               # e.g. the short last batch of an epoch
         if hasattr(self.opt, "sync_hyper"):
             self.opt.sync_hyper()                                  # a scheduler moved lr / betas: 20 bytes to the device
-        if self._source is None:
-            for k in ("x", "y", "pred_mask", "edge_attr") + (("edge_index",) if self.dynamic else ()):
-                getattr(self.static, k).copy_(getattr(data, k))
+        if self.source is None:
+            copy_batch(self.static, data, self.dynamic)
         # (graph forms: the captured loss tensor; the eager form: this step's)
         self.loss = self._replay_eager_form() if self.graph.form == "eager" else self.graph.replay()
         return self.loss
@@ -487,8 +443,7 @@ def train_epoch(model: nn.Module, loader, loss_fn: Callable, optimizer, device, 
     one hipGraph where that is safe.  Either way the running loss is accumulated on the device and read back ONCE per epoch
     (the reference's per-batch `loss.item()`, :77, is a host sync per step; the returned value is the same sum)."""
     model = model.to(device)
-    num_samples = 0
-    total = None
+    num_samples, total = 0, None
     model.train()
     if allreduce is None:
         allreduce = dp.world_size() > 1
@@ -500,70 +455,24 @@ def train_epoch(model: nn.Module, loader, loss_fn: Callable, optimizer, device, 
         graph._drop_all()                       # the replayed step contains (or not) the collective: capture again
         graph.allreduce = bool(allreduce)
     ds = getattr(loader, "dataset", None)
-    if (graph is not None and not progress and hasattr(loader, "index_batches") and hasattr(ds, "can_gather") and ds.can_gather()
+    resident = graph is not None and not progress                  # the captured step pulls its own batch: no collate here
+    if (resident and hasattr(loader, "index_batches") and hasattr(ds, "can_gather") and ds.can_gather()
             and ds.device == torch.device(device)):
-        # device-resident dataset: the captured step gathers its own batch -- per batch one index copy and one graph launch
-        for idx in loader.index_batches(device):
-            loss, n_keys = graph.step_indexed(ds, idx)
-            num_samples += n_keys
-            term = loss.detach().double() * n_keys
-            total = term if total is None else total + term
-        it = ()
-    elif (graph is not None and not progress and not allreduce and hasattr(loader, "index_batches")
-          and graph.topologies_supported(ds, device)):
-        # device-resident dataset with a topology per sample: the captured step gathers its batch and builds its adjacency from
-        # the dataset's edge block -- per batch one index copy and one graph launch (GraphedTrainStep.step_topologies)
-        for idx in loader.index_batches(device):
-            loss, n_keys = graph.step_topologies(ds, idx)
-            num_samples += n_keys
-            term = loss.detach().double() * n_keys
-            total = term if total is None else total + term
-        it = ()
-    elif (graph is not None and not progress and not allreduce and hasattr(loader, "_index_lists") and graph.mixed_slots
+        # device-resident dataset: per batch one index copy and one graph launch
+        steps = (graph.step_indexed(ds, idx) for idx in loader.index_batches(device))
+    elif resident and not allreduce and hasattr(loader, "index_batches") and graph.topologies_supported(ds, device):
+        # ... with a topology per sample: the captured step builds its adjacency from the dataset's edge block as well
+        steps = (graph.step_topologies(ds, idx) for idx in loader.index_batches(device))
+    elif (resident and not allreduce and hasattr(loader, "_index_lists") and graph.mixed_slots
           and graph.slots_supported(ds, device)):
-        # a mixed device-resident split: every batch is replayed from the hipGraph of its bucket (GraphedTrainStep.step_slots).
-        # The epoch's slot tables are built on the host -- O(graphs) per batch -- and uploaded in ONE copy; per batch one
-        # O(graphs) copy into the bucket's captured table and one graph launch.  No collate, no per-field copies.
-        from .. import segpack
-        lists = list(loader._index_lists())
-        lens = ds.case_sizes()[2]
-        flat, spans, rows = [], [], 0
-        for idx in lists:
-            per_case = ds.group_by_case(idx)
-            child = graph._slot_child(ds, segpack.bucket_of([int(p.shape[0]) for p in per_case], graph.slot_granule))
-            if child is None:
-                spans.append(None)
-                continue
-            tab = segpack.slot_table(child._template._slot_layout, per_case, lens)
-            spans.append((child, rows, rows + tab.shape[0]))
-            rows += tab.shape[0]
-            flat.append(tab)
-        dev_tab = torch.from_numpy(np.concatenate(flat)).to(device, non_blocking=True) if flat else None
-        for idx, span in zip(lists, spans):
-            if span is not None:
-                loss, n_keys = graph._replay_slots(span[0], dev_tab[span[1]:span[2]])
-            else:                               # the bucket cap: this batch runs what a mixed batch runs without mixed_slots
-                graph.slot_fallbacks += 1
-                data = ds.collate_indices(idx)
-                loss, n_keys = graph(data), len(data)
-            num_samples += n_keys
-            term = loss.detach().double() * n_keys
-            total = term if total is None else total + term
-        it = ()
-    for data in it:
-        data = data.to(device)
-        if graph is not None:
-            loss = graph(data)
-        else:
-            optimizer.zero_grad()
-            _announce_loss(loss_fn, model, data)
-            loss = _dispatch_loss(loss_fn, model(data), data)
-            _backward(loss_fn, loss)
-            if allreduce:
-                dp.allreduce_gradients(model)
-            _guarded_opt_step(optimizer, model, loss, allreduce)
-        num_samples += len(data)
-        term = loss.detach().double() * len(data)
+        # a mixed device-resident split: every batch is replayed from the hipGraph of its bucket
+        steps = graph.slot_epoch(ds, loader._index_lists(), device)
+    else:                                                          # collated batches: the loop of utils/training.py:55-77
+        steps = ((graph(data) if graph is not None else _eager_step(model, loss_fn, optimizer, data, allreduce), len(data))
+                 for data in (batch.to(device) for batch in it))
+    for loss, n_keys in steps:
+        num_samples += n_keys
+        term = loss.detach().double() * n_keys
         total = term if total is None else total + term
     skipped = getattr(optimizer, "skipped_steps", None)
     if skipped is not None and graph is not None and (graph.dynamic or graph._topo_children):
