@@ -13,7 +13,13 @@ are the test split (their values are already normalised: errors are then in norm
 results/<case>_{errors,masks,types}.npy -- the three files the reference writes, [S, n, 4] / [S, n, 4] / [S, n] -- and
 results/<case>_error_hist.npy [n, 4, nbins] with results/<case>_error_hist_edges.npy [4, nbins + 1]; `--save-predictions` adds
 results/<case>_predictions.npy.  `--graphed-eval` replays the per-batch body from a hipGraph.  No plots: the .npy files are what
-the reference's plotting half reads."""
+the reference's plotting half reads.
+
+`--branch-errors` adds the per-line analysis the reference left commented out (:186-223; utils/branch_analysis.py): the errors of the
+line currents, flows and losses the predicted voltages imply, from one more device pass over the finished tables.  It prints their
+report after the lines above and writes results/<case>_i_error_table.npy [S, e] (the reference's file name), _branch_errors.npy
+[S, e, 4] (I, P, Q, loss), _lines.npy [2, e], _branch_error_hist.npy and _branch_error_hist_edges.npy; `--save-flows` adds
+_branch_flows_pred.npy and _branch_flows_true.npy."""
 import os
 import sys
 
@@ -43,13 +49,15 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     run_id = _take(argv, "--run-id", default="synthetic")
     save_predictions = _take(argv, "--save-predictions", has_value=False, default=False)
+    branch_errors = _take(argv, "--branch-errors", has_value=False, default=False)
+    save_flows = _take(argv, "--save-flows", has_value=False, default=False)
     nbins = int(_take(argv, "--nbins", default=300))
     out_dir = _take(argv, "--results-dir", default="results")
     args = argument_parser(argv)
     if not torch.cuda.is_available():
         raise SystemExit("error_per_feature.py needs a HIP device: poweflownet_amd has no CPU fallback")
     device = torch.device("cuda")
-    xymean = xystd = None
+    xymean = xystd = edgemean = edgestd = None
     raw = os.path.join(args.data_dir, "raw", f"case{args.case}_node_features.npy")
     if os.path.exists(raw):
         params, kw = os.path.join(args.data_dir, "params", f"data_params_{run_id}.pt"), {}
@@ -57,7 +65,7 @@ def main(argv=None):
             p = torch.load(params, map_location="cpu")
             kw = {k: p[k] for k in ("xymean", "xystd", "edgemean", "edgestd")}
         testset = PowerFlowData(root=args.data_dir, case=args.case, split=[.5, .2, .3], task="test", device=device, **kw)
-        xymean, xystd = testset.xymean, testset.xystd
+        xymean, xystd, edgemean, edgestd = testset.xymean, testset.xystd, testset.edgemean, testset.edgestd
         nin, nout, ne = testset.get_data_dimensions()
     else:
         n = args.synthetic_samples
@@ -75,7 +83,7 @@ def main(argv=None):
     print(f"Model: {args.model}\nCase: {args.case}\nNumber of samples: {len(testset)}")
     graphed = getattr(args, "graphed_eval", None) is True           # (off unless asked for: one pass cannot repay the captures)
     res = bus_error_epoch(model, loader, device, xymean=xymean, xystd=xystd, graph=GraphedEvalStep(model) if graphed else None,
-                          keep_errors=True, keep_predictions=bool(save_predictions))
+                          keep_errors=True, keep_predictions=bool(save_predictions or branch_errors))
     if res.flags & 1:
         raise SystemExit("error_per_feature.py: a batch named a sample outside the table")
     for key, value in report_lines(res.moments, res.mask0, res.types0).items():
@@ -97,7 +105,34 @@ def main(argv=None):
     print(f"histograms: {nbins} bins per (bus, feature); {inside} of {S * hist.shape[0] * 4} scaled errors inside the range, "
           f"{int(outside[..., 0].sum())} below, {int(outside[..., 1].sum())} above, {int(outside[..., 2].sum())} NaN")
     print(f"wrote {out_dir}/{args.case}_{{errors,masks,types,error_hist,error_hist_edges{',predictions' if save_predictions else ''}}}.npy")
+    if branch_errors:
+        _branch_part(res, loader, xymean, xystd, edgemean, edgestd, bool(save_flows), nbins, path, out_dir, args.case)
     return 0
+
+
+def _branch_part(res, loader, xymean, xystd, edgemean, edgestd, save_flows, nbins, path, out_dir, case):
+    from poweflownet_amd.utils.branch_analysis import branch_errors_of, branch_report_lines
+    br = branch_errors_of(res, loader, xymean=xymean, xystd=xystd, edgemean=edgemean, edgestd=edgestd, keep_flows=save_flows)
+    if br.flags & 1:
+        print("branch errors: a line names a bus outside the grid; its rows are NaN and left out of the figures")
+    for key, value in branch_report_lines(br.moments).items():
+        print(f"{key}: {value}")
+    edges = histogram_edges(br.moments, nbins=nbins)
+    hist, outside = bus_error_histograms(br.errors, edges)
+    errors = br.errors.cpu().numpy()
+    np.save(path("i_error_table"), np.ascontiguousarray(errors[:, :, 0]))
+    np.save(path("branch_errors"), errors)
+    np.save(path("lines"), br.lines0.numpy())
+    np.save(path("branch_error_hist"), hist.cpu().numpy())
+    np.save(path("branch_error_hist_edges"), edges)
+    names = "i_error_table,branch_errors,lines,branch_error_hist,branch_error_hist_edges"
+    if save_flows:
+        np.save(path("branch_flows_pred"), br.flows_pred.cpu().numpy())
+        np.save(path("branch_flows_true"), br.flows_true.cpu().numpy())
+        names += ",branch_flows_pred,branch_flows_true"
+    print(f"branch histograms: {nbins} bins per (line, quantity); {int(hist.sum())} of {errors.size} errors inside the range, "
+          f"{int(outside[..., 0].sum())} below, {int(outside[..., 1].sum())} above, {int(outside[..., 2].sum())} NaN")
+    print(f"wrote {out_dir}/{case}_{{{names}}}.npy")
 
 
 if __name__ == "__main__":

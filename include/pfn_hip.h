@@ -465,6 +465,42 @@ int pfn_bus_errors_accumulate(const float* out, const float* y, const void* mask
 int pfn_bus_errors_histogram(const float* table, int64_t n_samples, int64_t n_bus, const float* scale, const double* edges, int nbins,
                              uint32_t* hist, uint32_t* outside, void* stream);
 
+/* ------------------------------------------------------------------------------------- per-line branch flows
+ * pfn_branch_flows (csrc/branch_flows.hip): the line currents and line flows that one or two finished bus tables imply, their error
+ * and its running moments per (line, quantity), in two launches and without a host sync (capturable).  The table the reference's
+ * error_per_feature.py:186-223 left commented out.
+ *   pred, truth  [n_samples, n_bus, 4] f32 rows (Vm, Va in degrees, P, Q); only Vm and Va are read.  A table whose `*_normalised`
+ *                flag is set is de-normalised first as v * std4[f] + mean4[f], product and sum rounded separately (the prediction
+ *                expression of pfn_bus_errors_accumulate; four HOST floats each, NULL: 1 / 0).  truth may be NULL: the flows of one
+ *                table only -- flows_true, err_table and moments must then be NULL too.
+ *   edge_index   DEVICE int64 local bus ids: [2, n_lines] for all samples (lines_per_sample == 0) or [n_samples, 2, n_lines].
+ *   edge_attr    f32 (r, x): [n_lines, 2] (attr_per_sample == 0) or [n_samples, n_lines, 2]; de-normalised with one fmaf per value,
+ *                fmaf(v, edge_std2[f], edge_mean2[f]) (two HOST floats each, NULL: 1 / 0), as pfn_power_imbalance does.
+ * Per (sample, stored line i = edge_index[0] -> j = edge_index[1]) four fp32 quantities, PowerImbalance.message's convention with
+ * no unit conversion:  e = Vm cos(Va pi/180), f = Vm sin(Va pi/180), d = r^2 + x^2, g = r/d, b = -x/d, de = e_i - e_j, df = f_i - f_j
+ *   0  I     sqrt(de^2 + df^2) / sqrt(d)                                        the current magnitude
+ *   1  P     g (e_i e_j - e_i^2 + f_i f_j - f_i^2) + b (f_i e_j - e_i f_j)      the message of the stored direction
+ *   2  Q     g (f_i e_j - e_i f_j) + b (-e_i e_j + e_i^2 - f_i f_j + f_i^2)
+ *   3  loss  g (de^2 + df^2) = r I^2, >= 0 whenever r >= 0
+ * (the reverse direction's message is -P - r I^2, -Q - x I^2).  r = x = 0: g and b are 0/0, so P, Q and loss are NaN as in
+ * pfn_power_imbalance; I is |dV| / 0.
+ *   flows_pred, flows_true, err_table   each optional, [n_samples, n_lines, 4] f32; err_table = flows_pred - flows_true, ONE fp32
+ *                subtraction of the two written values.
+ *   moments      optional double[n_lines][4][6] = {count, sum, sum |e|, sum e^2, min, max} of the error, accumulated INTO (cleared
+ *                by the caller, min = +inf and max = -inf); min / max ignore NaN, the sums propagate it.  Without err_table the
+ *                error table goes to `ws` (pfn_branch_flows_workspace_bytes(n_samples, n_lines, 1) bytes; PFN_ENOSPACE otherwise).
+ *   flags        bit 0 of flags[0] is set (a plain vector store) when a line names a bus outside [0, n_bus): that (sample, line)'s
+ *                values are NaN, it is left out of the moments, and the id is never followed.
+ * Buses up to pfn_branch_flows_lds_max_bus() keep a sample's rectangular voltages in LDS (one sincos per bus and table); beyond,
+ * they are formed per line end from global memory.  One owner per (line, quantity), a fixed work split and combine order, no
+ * float atomics: a call is a pure function of its inputs and of the moments it found.                                        */
+int64_t pfn_branch_flows_lds_max_bus(void);
+size_t pfn_branch_flows_workspace_bytes(int64_t n_samples, int64_t n_lines, int moments_without_err_table);
+int pfn_branch_flows(const float* pred, int pred_normalised, const float* truth, int truth_normalised, int64_t n_samples, int64_t n_bus,
+                     const float* std4, const float* mean4, const int64_t* edge_index, int lines_per_sample, int64_t n_lines,
+                     const float* edge_attr, int attr_per_sample, const float* edge_std2, const float* edge_mean2, float* flows_pred,
+                     float* flows_true, float* err_table, double* moments, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it
@@ -492,6 +528,7 @@ int pfn_bus_errors_histogram(const float* table, int64_t n_samples, int64_t n_bu
  *   PFN_FRONT_NO_THREAD_ROWS=1   inference front: the row-per-wave / block kernels instead of one row per thread
  *   PFN_NO_SERPENTINE=1     the row-streaming kernels (gemm_nt, LDS-resident walks / hops, the generic forward walk) all visit their rows
  *                           first to last (default: consecutive launches alternate, so a consumer starts with what its producer wrote last)
+ *   PFN_BRANCH_NO_LDS=1     pfn_branch_flows: the direct kernel (phasors per line end from global memory) for every size
  *   PFN_NT_CT=1|2           gemm_nt: quarters per wave
  *   PFN_NO_NT_ILF=1         gemm_nt, one-piece tiles at two quarters per wave: every tile flushed behind its own multiply (default: parked
  *                           and flushed inside the wave's next multiply, between its own MFMAs)

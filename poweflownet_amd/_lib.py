@@ -29,6 +29,7 @@ SYMBOLS = (
     "pfn_segpack_gather_slots", "pfn_mse_loss_rows", "pfn_masked_l2_loss_rows",
     "pfn_eval_metrics", "pfn_eval_accumulate",
     "pfn_bus_errors_accumulate", "pfn_bus_errors_histogram",
+    "pfn_branch_flows_lds_max_bus", "pfn_branch_flows_workspace_bytes", "pfn_branch_flows",
 )
 
 # enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
@@ -135,6 +136,10 @@ def load() -> C.CDLL:
         "pfn_bus_errors_accumulate": (C.c_int, [p, p, p, C.c_int, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), p, i64, p, p,
                                                 p, p, p]),
         "pfn_bus_errors_histogram": (C.c_int, [p, i64, i64, p, p, C.c_int, p, p, p]),
+        "pfn_branch_flows_lds_max_bus": (i64, []),
+        "pfn_branch_flows_workspace_bytes": (sz, [i64, i64, C.c_int]),
+        "pfn_branch_flows": (C.c_int, [p, C.c_int, p, C.c_int, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), p, C.c_int, i64,
+                                       p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), p, p, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -455,3 +455,90 @@ def bus_errors_histogram(table, edges, scale=None):
         L.check(L.load().pfn_bus_errors_histogram(table.data_ptr(), S, n_bus, L.ptr(scale), edges.data_ptr(), nbins, hist.data_ptr(),
                                                   outside.data_ptr(), L.stream_ptr()), "pfn_bus_errors_histogram")
     return hist, outside
+
+
+# ------------------------------------------------------------------------------------------ per-line branch flows
+BRANCH_QUANTITIES = ("I", "P", "Q", "loss")      # the four values per (sample, line): current magnitude, P and Q message, series loss
+
+
+def branch_moments(device, n_lines: int) -> torch.Tensor:
+    """The running moments of `branch_flows`, cleared: float64 [n_lines, 4, 6] (`BRANCH_QUANTITIES` x `BUS_MOMENTS`), min = +inf and
+    max = -inf.  Clear it again with `reset_bus_error_moments` -- outside a captured graph."""
+    return reset_bus_error_moments(torch.empty(int(n_lines), 4, 6, dtype=torch.float64, device=device))
+
+
+def branch_flows_lds_max_bus() -> int:
+    """The largest n_bus whose rectangular voltages `pfn_branch_flows` keeps in LDS; beyond it the direct kernel runs."""
+    return int(L.load().pfn_branch_flows_lds_max_bus())
+
+
+def _host_floats(v, count, what):
+    import ctypes as C
+    if v is None:
+        return None
+    v = [float(a) for a in (v.detach().cpu().reshape(-1).tolist() if torch.is_tensor(v) else v)]
+    if len(v) != count:
+        raise RuntimeError(f"branch_flows: {what} must hold {count} values")
+    return (C.c_float * count)(*v)
+
+
+def branch_flows(pred, edge_index, edge_attr, truth=None, pred_normalised=False, truth_normalised=False, std=None, mean=None,
+                 edge_std=None, edge_mean=None, flows_pred=False, flows_true=False, errors=True, moments=None, flags=None):
+    """The line currents and flows of finished bus tables in ONE call (`pfn_branch_flows`: a flows launch, and a moments launch when
+    `moments` is given).  `pred` / `truth`: float32 [S, n_bus, 4] rows (Vm, Va in degrees, P, Q); a `*_normalised` table is
+    de-normalised with the host floats `std` / `mean` (four each; None: 1 / 0).  `edge_index`: int64 local ids, [2, e] for all
+    samples or [S, 2, e]; `edge_attr`: float32 (r, x), [e, 2] or [S, e, 2], de-normalised with `edge_std` / `edge_mean` (two each).
+    `flows_pred` / `flows_true` / `errors`: True (allocate), False (leave out) or a float32 [S, e, 4] tensor to write; without
+    `truth` only `flows_pred` exists (then allocated by default).  `moments`: `branch_moments(device, e)`, accumulated into;
+    `flags`: device int32, bit 0 = a line named a bus outside [0, n_bus).  Returns (flows_pred, flows_true, errors, flags), the
+    `BRANCH_QUANTITIES` of every (sample, stored line i = edge_index[0] -> j = edge_index[1]).  No host sync; capturable."""
+    L.require_device(pred, truth, edge_index, edge_attr, moments, flags, what="branch_flows input")
+    pred = L.f32c(pred, "pred")
+    if pred.dim() != 3 or pred.shape[2] != 4:
+        raise RuntimeError(f"branch_flows: pred must be (S, n_bus, 4); got {tuple(pred.shape)}")
+    S, n_bus = int(pred.shape[0]), int(pred.shape[1])
+    if truth is not None:
+        truth = L.f32c(truth, "truth")
+        if truth.shape != pred.shape:
+            raise RuntimeError(f"branch_flows: truth {tuple(truth.shape)} against pred {tuple(pred.shape)}")
+    else:
+        if moments is not None or torch.is_tensor(flows_true) or torch.is_tensor(errors):
+            raise RuntimeError("branch_flows: moments, flows_true and errors need a truth table")
+        flows_pred, flows_true, errors = (flows_pred if torch.is_tensor(flows_pred) else True), False, False
+    if edge_index.dtype != torch.int64 or edge_index.dim() not in (2, 3) or edge_index.shape[-2] != 2:
+        raise RuntimeError(f"branch_flows: edge_index must be int64 (2, e) or (S, 2, e); got {edge_index.dtype} {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[-1])
+    edge_attr = L.f32c(edge_attr, "edge_attr")
+    if edge_attr.dim() not in (2, 3) or tuple(edge_attr.shape[-2:]) != (e, 2):
+        raise RuntimeError(f"branch_flows: edge_attr must be ({e}, 2) or (S, {e}, 2); got {tuple(edge_attr.shape)}")
+    for name, t in (("edge_index", edge_index), ("edge_attr", edge_attr)):
+        if t.dim() == 3 and t.shape[0] != S:
+            raise RuntimeError(f"branch_flows: per-sample {name} of {t.shape[0]} samples against tables of {S}")
+    edge_index = edge_index.contiguous()
+    dev = pred.device
+    outs = []
+    for name, want in (("flows_pred", flows_pred), ("flows_true", flows_true), ("errors", errors)):
+        if torch.is_tensor(want):
+            if want.dtype != torch.float32 or tuple(want.shape) != (S, e, 4) or not want.is_contiguous() or want.device != dev:
+                raise RuntimeError(f"branch_flows: {name} must be a contiguous float32 tensor of shape ({S}, {e}, 4) on {dev}")
+            outs.append(want)
+        else:
+            outs.append(torch.empty(S, e, 4, dtype=torch.float32, device=dev) if want else None)
+    ws = None
+    if moments is not None:
+        if moments.dtype != torch.float64 or moments.numel() != e * 24 or not moments.is_contiguous():
+            raise RuntimeError(f"branch_flows: moments must be a contiguous float64 tensor of {e} x 4 x 6 elements")
+        if outs[2] is None:
+            ws = torch.empty(S, e, 4, dtype=torch.float32, device=dev)
+    if flags is None:
+        flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif flags.dtype != torch.int32 or flags.numel() < 1:
+        raise RuntimeError("branch_flows: flags must be an int32 tensor")
+    with torch.cuda.device(dev):
+        L.check(L.load().pfn_branch_flows(pred.data_ptr(), int(bool(pred_normalised)), L.ptr(truth), int(bool(truth_normalised)), S, n_bus,
+                                          _host_floats(std, 4, "std"), _host_floats(mean, 4, "mean"), edge_index.data_ptr(),
+                                          int(edge_index.dim() == 3), e, edge_attr.data_ptr(), int(edge_attr.dim() == 3),
+                                          _host_floats(edge_std, 2, "edge_std"), _host_floats(edge_mean, 2, "edge_mean"),
+                                          L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), L.ptr(moments), flags.data_ptr(), L.ptr(ws),
+                                          0 if ws is None else ws.numel() * 4, L.stream_ptr()), "pfn_branch_flows")
+    return outs[0], outs[1], outs[2], flags

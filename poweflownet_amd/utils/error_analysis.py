@@ -22,7 +22,8 @@ _AT = {k: i for i, k in enumerate(BUS_MOMENTS)}
 class BusErrors:
     """What `bus_error_epoch` returns.  `errors` / `predictions`: [S, n, 4] float32 on the device or None; a row no batch wrote holds
     NaN.  `moments`: host float64 [n, 4, 2, 6] (group 0: predicted entries, group 1: given; `loss.BUS_MOMENTS`).  `flags`: bit 0 =
-    a batch named a row outside the table.  `mask0` / `types0`: sample 0's `pred_mask` [n, 4] and `bus_type` [n] on the host."""
+    a batch named a row outside the table.  `mask0` / `types0`: sample 0's `pred_mask` [n, 4] and `bus_type` [n] on the host.
+    `rows_by_index`: a table row is the sample's index in the dataset (else: its position in the loader's order)."""
     errors: Optional[torch.Tensor]
     predictions: Optional[torch.Tensor]
     moments: torch.Tensor
@@ -30,6 +31,7 @@ class BusErrors:
     flags: int
     mask0: torch.Tensor
     types0: torch.Tensor
+    rows_by_index: bool = False
 
 
 def _uniform_split(ds):
@@ -83,7 +85,8 @@ def bus_error_epoch(model, loader, device, xymean=None, xystd=None, graph: Optio
     num = int(step._pos)
     take = (lambda t: None if t is None else t.clone()) if step.rows_by_index else (lambda t: None if t is None else t[:num].clone())
     return BusErrors(errors=take(step._etab), predictions=take(step._ptab), moments=host[:-1].view(n_bus, 4, 2, 6).clone(),
-                     num_samples=num, flags=int(host[-1:].view(torch.int32)[0]), mask0=mask0, types0=types0)
+                     num_samples=num, flags=int(host[-1:].view(torch.int32)[0]), mask0=mask0, types0=types0,
+                     rows_by_index=bool(step.rows_by_index))
 
 
 def mask_scale(mask0) -> torch.Tensor:
@@ -95,8 +98,11 @@ def mask_scale(mask0) -> torch.Tensor:
 def histogram_edges(moments, scale=None, nbins: int = 300, multiplier=(0.8, 0.8, 0.4, 0.4)) -> np.ndarray:
     """The reference's bin range (:388-398) from the moments: per feature the min and max of the SCALED errors (error * scale[bus,
     feature] in float32; scale >= 0), each times the feature's multiplier (in float64), made symmetric about 0 on the larger
-    magnitude; `np.linspace(lo, hi, nbins + 1)`.  Returns float64 [4, nbins + 1]."""
+    magnitude; `np.linspace(lo, hi, nbins + 1)`.  Returns float64 [4, nbins + 1].  Moments of ONE group, [rows, 4, 6] (the branch
+    table's, utils/branch_analysis.py), are taken as they stand."""
     m = np.asarray(torch.as_tensor(moments).cpu().numpy() if torch.is_tensor(moments) else moments, dtype=np.float64)
+    if m.ndim == 3:
+        m = m[:, :, None, :]
     n = m.shape[0]
     sc = np.ones((n, 4), dtype=np.float32) if scale is None else np.asarray(torch.as_tensor(scale).cpu().numpy(), dtype=np.float32)
     seen = m[..., _AT["count"]] > 0                                                      # [n, 4, 2]
