@@ -501,6 +501,49 @@ int pfn_branch_flows(const float* pred, int pred_normalised, const float* truth,
                      const float* edge_attr, int attr_per_sample, const float* edge_std2, const float* edge_mean2, float* flows_pred,
                      float* flows_true, float* err_table, double* moments, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------- power-flow solver
+ * The classical-solver side of the reference -- pandapower's Newton-Raphson behind dataset_generator.py:142 and its DC power flow
+ * behind dc_error.py:120 -- for this project's network model, batched: ONE launch, one workgroup per sample, no host sync, no
+ * allocation (capturable).  The mismatch is exactly pfn_power_imbalance's dP_i, dQ_i: series admittance only (g = r / (r^2 + x^2),
+ * b = -x / (r^2 + x^2)), every stored line counted in both directions (parallel lines add), P and Q demand-positive per-unit, Va in
+ * degrees; no shunt, charging, tap or unit conversion.  Bus types: 0 slack (gives Vm, Va), 1 PV (Vm, P), 2 PQ (P, Q); exactly one
+ * slack.  Unknowns: Va at the non-slack buses, Vm at the PQ buses, m = (n_bus - 1) + n_pq.
+ * THE ONE EXCEPTION to "all floating point is fp32": the inputs and the table are fp64 (raw dataset files are).
+ *   edge_index   DEVICE int64 local bus ids: [2, n_lines] for all samples (lines_per_sample == 0) or [n_samples, 2, n_lines].
+ *   rx           f64 [n_samples, n_lines, 2] = (r, x) per sample.
+ *   bus_type     int32 [n_bus], shared by the samples.  n_pv, n_pq: its counts, HOST ints -- they decide m, the route and the LDS
+ *                size.  The kernel counts the device array itself: where it disagrees (or holds a type outside 0..2, or not exactly
+ *                one slack) nothing is solved, every status is -5 and bit 0 of flags[0] is set (a plain vector store).
+ *   spec         f64 [n_samples, n_bus, 4] = (Vm, Va, P, Q): only the entries the bus type gives are read.
+ *   mode 0 (AC)  Newton-Raphson in polar form from a flat start (Vm = 1 at PQ buses, Va = the slack's).  State, mismatch and the
+ *                convergence test are fp64; the Jacobian is assembled analytically and factorised in fp32 (LU, partial pivoting, ties
+ *                to the lowest row), the update is solved from that factor with an fp64 right-hand side.  Stops when
+ *                max(|dP|, |dQ|) over the equations < tol, or after max_iter Jacobian solves.
+ *   mode 1 (DC)  the same loop on the linear mismatch F(theta) = B' theta + P over the non-slack buses, B' the Laplacian of 1 / x:
+ *                iterative refinement of an fp32 factor under the same fp64 tol.  m = n_bus - 1.
+ *   table        f64 [n_samples, n_bus, 4], 32-byte aligned.  AC: (Vm, Va, P, Q) with the slack's P, Q and the PV buses' Q the
+ *                aggregated line sums, everything else as given or solved.  DC: Vm as given at slack and PV buses and 1 at PQ
+ *                buses, Va = theta, P as given with the slack's the aggregated line sum (lossless: minus the sum of the others),
+ *                Q NaN.  A failed sample's rows are NaN; it touches nothing of another sample.
+ *   status       int32 [n_samples]: >= 0 the number of Jacobian solves used; -1 not converged in max_iter; -2 singular (a pivot of
+ *                magnitude <= 1e-30 or NaN, e.g. a bus without a line); -3 non-finite mismatch; -4 a line names a bus outside
+ *                [0, n_bus) (never followed); -5 bus_type disagrees with n_pv / n_pq (see above).
+ *   residual     f64 [n_samples]: the last max |F| (NaN where none was formed).
+ *   route        0 auto, 1 LDS, 2 global.  LDS: the fp32 matrix (m rows of m | 1 floats) sits behind the sample's vectors in the
+ *                160 KiB of a compute unit -- up to m = 195 at 118 buses; route 1 beyond that is PFN_EINVAL.  Global: the matrix
+ *                lives in a per-sample slab of `ws`, same code, up to pfn_powerflow_max_unknowns() unknowns; beyond that PFN_EINVAL:
+ *                a sparse factorisation is needed.  pfn_powerflow_workspace_bytes(n_samples, n_bus, n_lines, n_pq, route) is what the
+ *                route needs in mode 0 (for mode 1 pass n_pq = 0: its m is n_bus - 1) -- 0 exactly when it is the LDS route, which is
+ *                how a caller learns what route 0 takes; too little is PFN_ENOSPACE.
+ * One owner per matrix row, sequential sums in stored line order, only max-reductions across threads, no float atomics: a
+ * sample's result is a pure function of its own inputs, bit for bit, whatever the batch around it.                          */
+int64_t pfn_powerflow_max_unknowns(void);
+size_t pfn_powerflow_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq, int route);
+int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                        const double* spec, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode, double tol,
+                        int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

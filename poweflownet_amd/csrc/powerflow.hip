@@ -1,0 +1,373 @@
+// Batched AC / DC power flow on the device (gfx950): pfn_powerflow_solve, ONE launch, one workgroup per sample.  The solver side of
+// the reference (dataset_generator.py's pp.runpp, dc_error.py's pp.rundcpp) for this project's network model: series admittance
+// only, every stored line counted in both directions, P and Q demand-positive per-unit, Va in degrees -- the mismatch is exactly
+// pfn_power_imbalance's dP_i, dQ_i (physics.hip), so the two check each other.
+//
+// Newton-Raphson in polar form from a flat start.  The state, the mismatch F and the convergence test are fp64; the matrix
+// A = d(line sums)/d(unknowns) = -dF/dx is assembled analytically, stored and factorised in fp32 (LU, partial pivoting, ties to the
+// lowest row) and A dx = F is solved from that factor with the right-hand side kept in fp64.  An fp32 factor costs convergence
+// rate only: the residual that decides is fp64.  mode 1 (DC) runs the same loop on F(theta) = B' theta + P, B' from 1 / x: the
+// loop is then iterative refinement of an fp32 factor (re-formed per pass: it is a constant) under the same fp64 tolerance.
+//
+// Unknowns / equations: theta of the non-slack buses in bus order (P equations), then Vm of the PQ buses in bus order (Q equations).
+// A bus row is gathered by scanning the stored line list -- n * e loads against m^3 / 3 multiply-adds -- which keeps stored order:
+// one owner per row, sequential sums, no float atomics, max-reductions only across threads.  A sample's result is a pure function
+// of its own inputs; nothing depends on the batch around it.
+//
+// The matrix is row-major with an ODD leading dimension ld = m | 1: the rank-1 update walks rows (lanes on consecutive columns, the
+// multiplier a broadcast), the pivot search and the back substitution walk columns (stride ld: odd, so coprime to the 32 banks a
+// dword access of a 32-lane half is spread over: no conflict).  LDS route: the matrix sits behind the sample's vectors in LDS;
+// global route: in a per-sample slab of the caller's workspace, same code.
+#include <algorithm>
+
+#include "pfn_internal.hpp"
+
+namespace pfn {
+
+constexpr int PF_LDS_CU = 160 * 1024;              // LDS of one compute unit
+constexpr int PF_LDS_RESERVE = 1024;               // (kept free of the dynamic region: the kernel's static words)
+constexpr int PF_MAX_UNKNOWNS = 1024;              // dense cap of the global route: 4 MiB per sample, 3.6e8 multiply-adds per factor
+constexpr int PF_SMALL_THREADS = 256, PF_BIG_THREADS = 1024;
+constexpr int PF_BIG_M = 90;                       // 4 m^2 beyond ~32 KiB: few workgroups per CU, so each gets 16 waves
+constexpr float PF_TINY_PIVOT = 1e-30f;            // |pivot| <= this (or NaN): singular
+constexpr double PF_RAD = 3.14159265358979323846 / 180.0;
+
+enum { PF_NOT_CONVERGED = -1, PF_SINGULAR = -2, PF_NON_FINITE = -3, PF_BAD_LINE = -4, PF_BAD_TYPES = -5 };
+
+__host__ __device__ inline int pf_ld(int m) { return m | 1; }
+// the sample's vectors: double vm, th, sp, sq [n], F [m]; int aidx, vidx [n]; rounded to 16 bytes
+__host__ __device__ inline size_t pf_vec_bytes(int n, int m) { return ((size_t)8 * (4 * (size_t)n + m) + (size_t)8 * n + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t pf_mat_floats(int m) { return ((size_t)m * pf_ld(m) + 3) & ~(size_t)3; }
+
+struct PfArgs {
+    const int64_t* edge_index;
+    const double* rx;
+    const int32_t* bus_type;
+    const double* spec;
+    double* table;
+    int32_t* status;
+    double* residual;
+    int32_t* flags;
+    float* slab;
+    double tol;
+    int n, e, m, n_pv, n_pq, mode, max_iter, lines_per_sample;
+};
+
+// max over the workgroup (max is exact: the order does not matter); every thread calls it
+__device__ __forceinline__ double pf_block_max(double v, double* red) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    double r = red[0];
+    for (int w = 1; w < nw; ++w) r = fmax(r, red[w]);
+    __syncthreads();
+    return r;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
+    __shared__ double s_red[16];
+    __shared__ float s_pval;
+    __shared__ int s_piv, s_ok, s_slack;
+    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
+    const int s = blockIdx.x;
+    const int n = a.n, e = a.e, m = a.m, ld = pf_ld(m);
+    const bool dc = a.mode == 1;
+    double* vm = reinterpret_cast<double*>(pf_smem);
+    double* th = vm + n;
+    double* sp = th + n;
+    double* sq = sp + n;
+    double* F = sq + n;
+    int* aidx = reinterpret_cast<int*>(F + m);
+    int* vidx = aidx + n;
+    float* A;
+    if constexpr (LDS) A = reinterpret_cast<float*>(pf_smem + pf_vec_bytes(n, m));
+    else A = a.slab + (size_t)s * pf_mat_floats(m);
+    const int64_t* ei = a.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
+    const double* rx = a.rx + (int64_t)s * 2 * e;
+    const double* spec = a.spec + (int64_t)s * 4 * n;
+    double* out = a.table + (int64_t)s * 4 * n;
+    const double nanv = __builtin_nan("");
+    int code = 0;                                   // (uniform over the workgroup wherever it is tested)
+    double res = nanv;
+
+    // ---- the lines name buses of the grid?  (an id outside [0, n) is never followed)
+    int bad = 0;
+    for (int k = t; k < e; k += nt) bad |= (uint64_t)ei[k] >= (uint64_t)n || (uint64_t)ei[e + k] >= (uint64_t)n;
+    // ---- unknown numbering; the host's n_pv / n_pq (they decided m, the route and the LDS size) against the device bus types
+    if (t == 0) {
+        int na = 0, nv = 0, ns = 0, npv = 0, npq = 0, odd = 0, slack = 0;
+        for (int i = 0; i < n; ++i) {
+            const int ty = a.bus_type[i];
+            int ia = -1, iv = -1;
+            if (ty == 0) { ++ns; slack = i; }
+            else if (ty == 1) { ++npv; ia = na++; }
+            else if (ty == 2) { ++npq; ia = na++; if (!dc) iv = (n - 1) + nv++; }
+            else odd = 1;
+            aidx[i] = ia;
+            vidx[i] = iv;
+        }
+        s_slack = slack;
+        s_ok = !odd && ns == 1 && npv == a.n_pv && npq == a.n_pq;
+    }
+    bad = __syncthreads_or(bad);
+    if (!s_ok) {
+        code = PF_BAD_TYPES;
+        if (t == 0) a.flags[0] = a.flags[0] | 1;    // (every writer stores the same bit over the same word)
+    } else if (bad) {
+        code = PF_BAD_LINE;
+    }
+
+    int it = 0;
+    if (code == 0) {
+        // ---- flat start
+        const double th0 = spec[4 * s_slack + 1] * PF_RAD;
+        for (int i = t; i < n; i += nt) {
+            vm[i] = a.bus_type[i] == 2 ? 1.0 : spec[4 * i];
+            th[i] = th0;
+        }
+        __syncthreads();
+        for (;; ++it) {
+            for (int k = t; k < m * ld; k += nt) A[k] = 0.f;
+            __syncthreads();
+            // ---- line sums, mismatch and matrix rows of bus i, its lines in stored order
+            for (int i = t; i < n; i += nt) {
+                const int ra = aidx[i], rv = vidx[i];
+                const double vi = vm[i], ti = th[i];
+                double sP = 0.0, sQ = 0.0, dPt = 0.0, dPv = 0.0, dQt = 0.0, dQv = 0.0;
+                for (int k = 0; k < e; ++k) {
+                    const int la = (int)ei[k], lb = (int)ei[e + k];
+                    if (la != i && lb != i) continue;
+                    const double r = rx[2 * k], x = rx[2 * k + 1];
+#pragma unroll 1
+                    for (int side = 0; side < 2; ++side) {       // the stored direction, then the reverse (a self-loop: both)
+                        if ((side ? lb : la) != i) continue;
+                        const int j = side ? la : lb;
+                        const int ca = aidx[j], cv = vidx[j];
+                        if (dc) {
+                            const double b = -1.0 / x;
+                            sP += b * (ti - th[j]);
+                            dPt += b;
+                            if (ra >= 0 && ca >= 0) A[ra * ld + ca] += (float)(-b);
+                            continue;
+                        }
+                        const double d = r * r + x * x, g = r / d, b = -x / d;
+                        const double vj = vm[j], vv = vi * vj;
+                        double sn, cs;
+                        sincos(ti - th[j], &sn, &cs);
+                        const double t1 = vv * cs - vi * vi, t2 = vv * sn;
+                        sP += g * t1 + b * t2;
+                        sQ += g * t2 - b * t1;
+                        const double pti = vv * (b * cs - g * sn), qti = vv * (g * cs + b * sn);
+                        dPt += pti;
+                        dPv += g * (vj * cs - 2.0 * vi) + b * vj * sn;
+                        dQt += qti;
+                        dQv += g * vj * sn - b * (vj * cs - 2.0 * vi);
+                        if (ra >= 0) {
+                            if (ca >= 0) A[ra * ld + ca] += (float)(-pti);
+                            if (cv >= 0) A[ra * ld + cv] += (float)(vi * (g * cs + b * sn));
+                        }
+                        if (rv >= 0) {
+                            if (ca >= 0) A[rv * ld + ca] += (float)(-qti);
+                            if (cv >= 0) A[rv * ld + cv] += (float)(vi * (g * sn - b * cs));
+                        }
+                    }
+                }
+                sp[i] = sP;
+                sq[i] = sQ;
+                if (ra >= 0) {
+                    F[ra] = spec[4 * i + 2] - sP;
+                    A[ra * ld + ra] += (float)dPt;
+                    if (rv >= 0) A[ra * ld + rv] += (float)dPv;
+                }
+                if (rv >= 0) {
+                    F[rv] = spec[4 * i + 3] - sQ;
+                    A[rv * ld + ra] += (float)dQt;
+                    A[rv * ld + rv] += (float)dQv;
+                }
+            }
+            __syncthreads();
+            // ---- max |F| in fp64; a non-finite entry counts as +inf
+            double mx = 0.0;
+            for (int k = t; k < m; k += nt) {
+                const double f = fabs(F[k]);
+                mx = fmax(mx, f < __builtin_inf() ? f : __builtin_inf());
+            }
+            res = pf_block_max(mx, s_red);
+            if (!(res < __builtin_inf())) { code = PF_NON_FINITE; break; }
+            if (res < a.tol) break;
+            if (it >= a.max_iter) { code = PF_NOT_CONVERGED; break; }
+            // ---- LU with partial pivoting, the right-hand side F eliminated along (fp64); L is not kept
+            for (int k = 0; k < m; ++k) {
+                if (wave == 0) {
+                    float best = -1.f;
+                    int bi = m;
+                    for (int i = k + lane; i < m; i += 64) {
+                        const float v = fabsf(A[i * ld + k]);
+                        if (v > best) { best = v; bi = i; }
+                    }
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const float ob = __shfl_xor(best, off);
+                        const int oi = __shfl_xor(bi, off);
+                        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+                    }
+                    if (lane == 0) { s_piv = bi; s_pval = best; }
+                }
+                __syncthreads();
+                const int p = s_piv;
+                if (!(s_pval > PF_TINY_PIVOT)) { code = PF_SINGULAR; break; }
+                if (p != k) {
+                    for (int j = k + t; j < m; j += nt) {
+                        const float u = A[k * ld + j];
+                        A[k * ld + j] = A[p * ld + j];
+                        A[p * ld + j] = u;
+                    }
+                    if (t == 0) {
+                        const double f = F[k];
+                        F[k] = F[p];
+                        F[p] = f;
+                    }
+                }
+                __syncthreads();
+                const float piv = A[k * ld + k];
+                for (int i = k + 1 + wave; i < m; i += nw) {
+                    const float l = A[i * ld + k] / piv;
+                    for (int j = k + 1 + lane; j < m; j += 64) A[i * ld + j] = fmaf(-l, A[k * ld + j], A[i * ld + j]);
+                    if (lane == 0) F[i] -= (double)l * F[k];
+                }
+                __syncthreads();
+            }
+            if (code) break;
+            // ---- back substitution by columns: after step k, F[k] / U[k][k] is x_k
+            for (int k = m - 1; k > 0; --k) {
+                const double xk = F[k] / (double)A[k * ld + k];
+                for (int i = t; i < k; i += nt) F[i] -= (double)A[i * ld + k] * xk;
+                __syncthreads();
+            }
+            for (int i = t; i < n; i += nt) {
+                const int ia = aidx[i], iv = vidx[i];
+                if (ia >= 0) th[i] += F[ia] / (double)A[ia * ld + ia];
+                if (iv >= 0) vm[i] += F[iv] / (double)A[iv * ld + iv];
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- the table: slack P, Q and PV Q are the aggregated line sums of the last pass; a failed sample's rows are NaN
+    for (int i = t; i < n; i += nt) {
+        double4 row = make_double4(nanv, nanv, nanv, nanv);
+        if (code == 0) {
+            const int ty = a.bus_type[i];
+            row.x = vm[i];
+            row.y = ty == 0 ? spec[4 * i + 1] : th[i] * (1.0 / PF_RAD);
+            row.z = ty == 0 ? sp[i] : spec[4 * i + 2];
+            row.w = dc ? nanv : (ty == 2 ? spec[4 * i + 3] : sq[i]);
+        }
+        *reinterpret_cast<double4*>(out + 4 * i) = row;
+    }
+    if (t == 0) {
+        a.status[s] = code ? code : it;
+        a.residual[s] = res;
+    }
+}
+
+static int pf_unknowns(int64_t n, int64_t n_pq, int mode) { return (int)((n - 1) + (mode == 1 ? 0 : n_pq)); }
+static bool pf_fits_lds(int n, int m) { return pf_vec_bytes(n, m) + pf_mat_floats(m) * 4 <= (size_t)(PF_LDS_CU - PF_LDS_RESERVE); }
+
+}  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+
+int64_t pfn_powerflow_max_unknowns(void) { return PF_MAX_UNKNOWNS; }
+
+size_t pfn_powerflow_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq, int route) {
+    (void)n_lines;
+    if (n_samples <= 0 || n_bus <= 0 || n_pq < 0 || n_pq >= n_bus || n_bus > PF_MAX_UNKNOWNS + 1) return 0;
+    const int m = pf_unknowns(n_bus, n_pq, 0);      // (mode 1: the caller passes n_pq = 0)
+    if (m > PF_MAX_UNKNOWNS || route == 1 || (route != 2 && pf_fits_lds((int)n_bus, m))) return 0;
+    return (size_t)n_samples * pf_mat_floats(m) * sizeof(float);
+}
+
+int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                        const double* spec, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode, double tol,
+                        int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
+                        size_t ws_bytes, void* stream) {
+    PFN_CHECK_ARG(n_samples >= 0 && n_bus >= 1 && n_lines >= 0 && n_samples < (1ll << 29) && n_lines < (1ll << 24) && n_bus < (1ll << 24),
+                  "pfn_powerflow_solve: bad sizes (%lld samples of %lld buses and %lld lines)", (long long)n_samples, (long long)n_bus,
+                  (long long)n_lines);
+    PFN_CHECK_ARG(n_pv >= 0 && n_pq >= 0 && n_pv + n_pq == n_bus - 1,
+                  "pfn_powerflow_solve: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses", (long long)n_pv,
+                  (long long)n_pq, (long long)n_bus);
+    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve: mode must be 0 (AC) or 1 (DC)");
+    PFN_CHECK_ARG(route >= 0 && route <= 2, "pfn_powerflow_solve: route must be 0 (auto), 1 (LDS) or 2 (global)");
+    PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "pfn_powerflow_solve: max_iter must be >= 0 and tol > 0");
+    const int64_t m64 = (n_bus - 1) + (mode == 1 ? 0 : n_pq);
+    PFN_CHECK_ARG(m64 <= PF_MAX_UNKNOWNS,
+                  "pfn_powerflow_solve: %lld unknowns per sample exceed the dense solver's %d; a sparse factorisation is needed",
+                  (long long)m64, PF_MAX_UNKNOWNS);
+    if (n_samples == 0) return PFN_OK;
+    PFN_CHECK_ARG(rx || n_lines == 0, "pfn_powerflow_solve: null rx");
+    PFN_CHECK_ARG(edge_index || n_lines == 0, "pfn_powerflow_solve: null edge_index");
+    PFN_CHECK_ARG(bus_type && spec && table && status && residual && flags, "pfn_powerflow_solve: null pointer");
+    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(table) & 31) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
+                      ((reinterpret_cast<uintptr_t>(spec) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(edge_index) |
+                        reinterpret_cast<uintptr_t>(residual)) & 7) == 0 &&
+                      ((reinterpret_cast<uintptr_t>(bus_type) | reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(flags)) & 3) == 0,
+                  "pfn_powerflow_solve: table must be 32-byte aligned, the workspace 16-byte, fp64 and int64 inputs 8-byte, int32 arrays 4-byte");
+    const int n = (int)n_bus, m = (int)m64;
+    const bool fits = pf_fits_lds(n, m);
+    PFN_CHECK_ARG(route != 1 || fits, "pfn_powerflow_solve: route 1 (LDS): %d unknowns of %d buses need %zu bytes of LDS, %d are there", m, n,
+                  pf_vec_bytes(n, m) + pf_mat_floats(m) * 4, PF_LDS_CU - PF_LDS_RESERVE);
+    const bool lds = route == 1 || (route == 0 && fits);
+    PfArgs a;
+    a.edge_index = edge_index;
+    a.rx = rx;
+    a.bus_type = bus_type;
+    a.spec = spec;
+    a.table = table;
+    a.status = status;
+    a.residual = residual;
+    a.flags = flags;
+    a.slab = nullptr;
+    a.tol = tol;
+    a.n = n;
+    a.e = (int)n_lines;
+    a.m = m;
+    a.n_pv = (int)n_pv;
+    a.n_pq = (int)n_pq;
+    a.mode = mode;
+    a.max_iter = max_iter;
+    a.lines_per_sample = lines_per_sample != 0;
+    if (!lds) {
+        const size_t need = (size_t)n_samples * pf_mat_floats(m) * sizeof(float);
+        if (need && (!ws || ws_bytes < need)) {
+            set_error("pfn_powerflow_solve: the global route needs a workspace of %zu bytes (got %zu)", need, ws ? ws_bytes : (size_t)0);
+            return PFN_ENOSPACE;
+        }
+        a.slab = static_cast<float*>(ws);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int threads = m > PF_BIG_M ? PF_BIG_THREADS : PF_SMALL_THREADS;
+    const size_t bytes = pf_vec_bytes(n, m) + (lds ? pf_mat_floats(m) * 4 : 0);
+    const double iters = 5.0, mm = (double)m;
+    ProfScope ps(mode == 1 ? "powerflow_dc" : "powerflow_ac",
+                 (double)n_samples * ((double)n_lines * (16.0 + (lines_per_sample ? 16.0 : 0.0)) + (double)n * 64.0),
+                 (double)n_samples * iters * (2.0 / 3.0 * mm * mm * mm + 2.0 * mm * mm), s);
+    if (lds) {
+        static std::atomic<uint64_t> raised{0};
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true>), PF_LDS_CU - PF_LDS_RESERVE, raised));
+        powerflow_kernel<true><<<(int)n_samples, threads, bytes, s>>>(a);
+    } else {
+        powerflow_kernel<false><<<(int)n_samples, threads, bytes, s>>>(a);
+    }
+    PFN_CHECK_LAUNCH();
+    return PFN_OK;
+}
+
+}  // extern "C"

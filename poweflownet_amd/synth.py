@@ -72,6 +72,34 @@ def make_batch(case: str, batch_size: int, seed: int = 0, hub_frac: float = 0.0,
                                  for b in range(batch_size)])
 
 
+def make_physical_inputs(n: int, e: int, num_samples: int, seed: int, load: float = 0.2):
+    """Inputs of `utils.powerflow.solve_power_flow` that a power-flow solution exists for: `make_topology(n, e)`'s grid with
+    `make_graph`'s bus types, per-unit, demand-positive.  Returns (edge_index [2, e] int64, bus_type [n] int64, rx [S, e, 2] float64,
+    spec [S, n, 4] float64 = (Vm, Va in degrees, P, Q) with the entries a bus type does not give left 0).  One
+    `np.random.default_rng(seed)` serves the samples one after the other, each drawing in this order: r ~ U(0.005, 0.03),
+    x ~ U(0.03, 0.15) per line; Vm ~ U(1.00, 1.05) at the slack and the PV buses; P ~ N(load, 0.1 load) and
+    Q ~ N(load / 4, 0.1 load / 4) at the PQ buses; P = -sum(P_pq) / n_pv * U(0.8, 1.2) at the PV buses; the slack's Va is 0.  The
+    reference generator's +-20 % / 10 % perturbations (dataset_generator.py) around a made-up base case."""
+    edge_index = make_topology(n, e)
+    bus_type = torch.full((n,), 2, dtype=torch.long)
+    bus_type[::3] = 1
+    bus_type[0] = 0
+    bt = bus_type.numpy()
+    fixed_v, pv, pq = np.flatnonzero(bt != 2), np.flatnonzero(bt == 1), np.flatnonzero(bt == 2)
+    rng = np.random.default_rng(seed)
+    rx = np.empty((num_samples, e, 2), dtype=np.float64)
+    spec = np.zeros((num_samples, n, 4), dtype=np.float64)
+    for s in range(num_samples):
+        rx[s, :, 0] = rng.uniform(0.005, 0.03, e)
+        rx[s, :, 1] = rng.uniform(0.03, 0.15, e)
+        spec[s, fixed_v, 0] = rng.uniform(1.00, 1.05, fixed_v.size)
+        spec[s, pq, 2] = rng.normal(load, 0.1 * load, pq.size)
+        spec[s, pq, 3] = rng.normal(load / 4, 0.1 * load / 4, pq.size)
+        if pv.size:
+            spec[s, pv, 2] = -spec[s, pq, 2].sum() / pv.size * rng.uniform(0.8, 1.2, pv.size)
+    return edge_index, bus_type, torch.from_numpy(rx), torch.from_numpy(spec)
+
+
 def make_dataset(case: str, num_samples: int, seed: int = 0):
     n, e = CASES[str(case)]
     topo = make_topology(n, e, 0)

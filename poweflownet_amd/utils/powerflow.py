@@ -1,0 +1,84 @@
+"""Batched AC / DC power flow on the device: `solve_power_flow` is ONE `pfn_powerflow_solve` launch (csrc/powerflow.hip), one
+workgroup per sample.  It stands where the reference calls pandapower -- `pp.runpp` in dataset_generator.py, `pp.rundcpp` in
+dc_error.py -- for this project's network model: series admittance only, every stored line in both directions, P and Q
+demand-positive per-unit, Va in degrees; no shunts, line charging, taps, Q-limits or unit conversion.  The mismatch it drives to zero
+is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  No CPU path."""
+from dataclasses import dataclass
+
+import torch
+
+from .. import _lib as L
+
+STATUS = {-1: "not converged in max_iter", -2: "singular Jacobian", -3: "non-finite mismatch", -4: "a line names a bus outside the grid",
+          -5: "bus_type disagrees with the counts the launch was sized for"}
+_MODES = {"ac": 0, "dc": 1}
+_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+
+
+@dataclass
+class PowerFlowResult:
+    """`table` [S, n, 4] float64 (Vm, Va in degrees, P, Q; NaN rows where the sample failed), `status` [S] int32 (>= 0: Jacobian
+    solves used; < 0: `STATUS`), `iterations` [S] int32 (the status where it is >= 0, else -1), `residual` [S] float64 (the last
+    max |F|), `flags` [1] int32 (bit 0: `bus_type` changed under the launch) -- all on the device, nothing read back; `route`: the
+    route that ran, "lds" or "global"."""
+    table: torch.Tensor
+    status: torch.Tensor
+    iterations: torch.Tensor
+    residual: torch.Tensor
+    flags: torch.Tensor
+    route: str
+
+
+def max_unknowns() -> int:
+    """The largest m = (n - 1) + n_pq the dense solver takes (global route); beyond it a sparse factorisation is needed."""
+    return int(L.load().pfn_powerflow_max_unknowns())
+
+
+def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max_iter=10, route="auto") -> PowerFlowResult:
+    """Solve S power-flow problems on one grid.  `bus_type` [n] (0 slack, 1 PV, 2 PQ; exactly one slack; shared by the samples),
+    `spec` [S, n, 4] float64 (Vm, Va, P, Q: the slack gives Vm and Va, a PV bus Vm and P, a PQ bus P and Q; the rest is ignored),
+    `edge_index` int64 local ids [2, e] or [S, 2, e], `rx` [S, e, 2] float64.  mode "ac": Newton-Raphson from a flat start, fp64
+    state and residual, fp32 LU of the analytic Jacobian; "dc": the linear B' theta = -P model (B' from 1 / x) refined to the same
+    fp64 tolerance, Q NaN.  It stops when max |mismatch| < `tol` or after `max_iter` Jacobian solves.  `route`: "auto", "lds" (the
+    matrix in LDS; RuntimeError where it does not fit) or "global" (in a workspace allocated here).
+
+    tol = 1e-8 and max_iter = 10 are what pandapower's Newton-Raphson (`pp.runpp(algorithm="nr")`, per-unit mismatch) is believed to
+    use; pandapower is not installed where this was written, so that could not be verified.
+
+    One host read (the counts of `bus_type`, which size the launch); no read-back of the results."""
+    L.require_device(bus_type, spec, edge_index, rx, what="solve_power_flow input")
+    if mode not in _MODES or route not in _ROUTES:
+        raise ValueError(f"solve_power_flow: mode must be one of {sorted(_MODES)} and route one of {sorted(_ROUTES)}")
+    if spec.dtype != torch.float64 or spec.dim() != 3 or spec.shape[2] != 4:
+        raise RuntimeError(f"solve_power_flow: spec must be float64 (S, n, 4); got {spec.dtype} {tuple(spec.shape)}")
+    S, n = int(spec.shape[0]), int(spec.shape[1])
+    if bus_type.dim() != 1 or bus_type.shape[0] != n or bus_type.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"solve_power_flow: bus_type must be an integer tensor of {n} entries; got {bus_type.dtype} {tuple(bus_type.shape)}")
+    if edge_index.dtype != torch.int64 or edge_index.dim() not in (2, 3) or edge_index.shape[-2] != 2:
+        raise RuntimeError(f"solve_power_flow: edge_index must be int64 (2, e) or (S, 2, e); got {edge_index.dtype} {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[-1])
+    if edge_index.dim() == 3 and edge_index.shape[0] != S:
+        raise RuntimeError(f"solve_power_flow: per-sample edge_index of {edge_index.shape[0]} samples against {S}")
+    if rx.dtype != torch.float64 or tuple(rx.shape) != (S, e, 2):
+        raise RuntimeError(f"solve_power_flow: rx must be float64 ({S}, {e}, 2); got {rx.dtype} {tuple(rx.shape)}")
+    dev = spec.device
+    bt = bus_type.to(torch.int32).contiguous()
+    counts = torch.bincount(bt.clamp(0, 3).long(), minlength=4).tolist()
+    if counts[0] != 1 or counts[3] != 0 or bool((bt < 0).any()):
+        raise RuntimeError(f"solve_power_flow: bus_type needs exactly one slack (0) and only types 0, 1, 2; got counts {counts}")
+    n_pv, n_pq = counts[1], counts[2]
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    lib = L.load()
+    table = torch.empty(S, n, 4, dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    residual = torch.empty(S, dtype=torch.float64, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = int(lib.pfn_powerflow_workspace_bytes(S, n, e, n_pq if mode == "ac" else 0, _ROUTES[route]))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with torch.cuda.device(dev):
+        L.check(lib.pfn_powerflow_solve(edge_index.data_ptr(), int(edge_index.dim() == 3), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(),
+                                        S, n, n_pv, n_pq, _MODES[mode], float(tol), int(max_iter), _ROUTES[route], table.data_ptr(),
+                                        status.data_ptr(), residual.data_ptr(), flags.data_ptr(), L.ptr(ws), need, L.stream_ptr()),
+                "pfn_powerflow_solve")
+    return PowerFlowResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
+                           residual=residual, flags=flags, route="global" if need else "lds")

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Batched power-flow solver: samples per second and mean Newton iterations of `solve_power_flow` (ONE `pfn_powerflow_solve` launch)
+at case14 and case118 x 4096 samples, AC and DC, on the LDS route and with the global route forced; beside it the float64 numpy
+yardstick of tests/powerflow_ref.py per sample on this host's CPU -- a dense np.linalg.solve Newton loop written for the tests,
+labelled as what it is: not pandapower, not a tuned CPU solver.  Not part of bench.py; no threshold (there is no predecessor).
+
+    python tools/powerflow_bench.py [--samples 4096] [--repeats 5] [--cpu-samples 16]
+
+Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
+max_iter 10 (the defaults).  One JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, HERE)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=4096)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--cpu-samples", type=int, default=16)
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("powerflow_bench.py needs a HIP device")
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    from tests import powerflow_ref as P
+    dev = torch.device("cuda:0")
+    res = {"device": torch.cuda.get_device_name(0), "samples": a.samples, "tol": 1e-8, "max_iter": 10, "cases": {}}
+    for case in ("14", "118"):
+        n, e = CASES[case]
+        ei, bt, rx, spec = make_physical_inputs(n, e, a.samples, seed=0)
+        d = [t.to(dev) for t in (bt, spec, ei, rx)]
+        out = {"buses": n, "lines": e, "unknowns_ac": (n - 1) + int((bt == 2).sum()), "unknowns_dc": n - 1}
+        for mode in ("ac", "dc"):
+            for route in ("auto", "global"):
+                per, last = [], None
+                for rep in range(a.repeats + 1):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    last = solve_power_flow(*d, mode=mode, route=route)
+                    torch.cuda.synchronize()
+                    if rep:
+                        per.append(time.perf_counter() - t0)
+                status = last.status.cpu().numpy()
+                ms = 1e3 * float(np.median(per))
+                out[f"{mode}_{last.route}"] = {"ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3),
+                                               "samples_per_s": round(a.samples / (ms * 1e-3)), "failed": int((status < 0).sum()),
+                                               "mean_iterations": round(float(status[status >= 0].mean()), 3)}
+        # the numpy yardstick, one sample at a time on the CPU
+        k = min(a.cpu_samples, a.samples)
+        ein, btn, rxn, specn = ei.numpy(), bt.numpy(), rx.numpy(), spec.numpy()
+        for name, fn in (("ac", lambda s: P.newton(btn, specn[s], ein, rxn[s], tol=1e-8, max_iter=10)),
+                         ("dc", lambda s: P.dc_solve(btn, specn[s], ein, rxn[s], norm=False))):
+            fn(0)
+            t0 = time.perf_counter()
+            for s in range(k):
+                fn(s)
+            ms = 1e3 * (time.perf_counter() - t0) / k
+            out[f"{name}_numpy_yardstick_cpu"] = {"ms_per_sample": round(ms, 3), "samples_per_s": round(1e3 / ms, 1), "samples_timed": k}
+        res["cases"][case] = out
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
