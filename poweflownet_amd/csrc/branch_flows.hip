@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "pfn_internal.hpp"
+#include "reduce.hpp"
 
 namespace pfn {
 
@@ -18,9 +19,7 @@ namespace pfn {
 // writes 16-byte rows.  Where 16 n_bus bytes do not fit the LDS of a compute unit (BF_LDS_MAX_BUS) the direct kernel forms the
 // phasors per line end from global memory.  Nothing here depends on the work split: every output element is a function of its
 // own inputs.
-constexpr int BF_LDS_CU = 160 * 1024;              // LDS of one compute unit
-constexpr int BF_LDS_RESERVE = 1024;               // (kept free of the dynamic region)
-constexpr int BF_LDS_MAX_BUS = (BF_LDS_CU - BF_LDS_RESERVE) / 16;       // 10176 buses
+constexpr int BF_LDS_MAX_BUS = (kLdsCuBytes - kLdsReserve) / 16;        // 10176 buses
 constexpr int BF_SMALL_THREADS = 256, BF_BIG_THREADS = 1024;
 constexpr int BF_BIG_LDS = 32 * 1024;              // a sample's phasors beyond this: few workgroups per CU, so each gets 16 waves
 
@@ -38,20 +37,13 @@ struct BfArgs {
     float std[2], mean[2], estd[2], emean[2];      // (Vm, Va) and (r, x)
 };
 
-// out * std + mean, product and sum rounded separately: be_prediction of bus_errors.hip, torch's `denormalize` bit for bit
-__device__ __forceinline__ float bf_denorm(float o, float sd, float mu) {
-#pragma clang fp contract(off)
-    const float p = o * sd;
-    return p + mu;
-}
-
 // (e, f) of one bus row; the angle as bus_of (physics.hip) forms it.  No contraction: the direct kernel inlines this into the
 // line expressions, where vm * c - ... would otherwise fuse and differ from the value the LDS kernel stores
 __device__ __forceinline__ float2 bf_phasor(const float* __restrict__ table, int64_t row, bool norm, const float* sd, const float* mu) {
 #pragma clang fp contract(off)
     const float2 v = *reinterpret_cast<const float2*>(table + 4 * row);
-    const float vm = norm ? bf_denorm(v.x, sd[0], mu[0]) : v.x;
-    const float va = (norm ? bf_denorm(v.y, sd[1], mu[1]) : v.y) * (3.14159265358979323846f / 180.0f);
+    const float vm = norm ? denorm(v.x, sd[0], mu[0]) : v.x;
+    const float va = (norm ? denorm(v.y, sd[1], mu[1]) : v.y) * (3.14159265358979323846f / 180.0f);
     float s, c;
     sincosf(va, &s, &c);
     return make_float2(vm * c, vm * s);
@@ -121,41 +113,25 @@ __global__ __launch_bounds__(BF_BIG_THREADS) void branch_flows_kernel(const BfAr
 }
 
 // ---------------------------------------------------------------------------------------------------- moments
-// The layout of bus_errors_accumulate_kernel over the finished error table: a workgroup owns BM_LX consecutive lines, its 256
-// threads are BM_LX line lanes x BM_SY sample slices; slice s walks the samples s, s + BM_SY, ... (16 lanes read 16 consecutive
-// 16-byte rows of ONE sample), keeps the 24 moments of its line in registers and hands them over through LDS, two quantities per
-// round; thread (line, value) adds the BM_SY slice partials in slice order and folds the result into the moments it found.  A
-// (sample, line) whose line names a bus outside [0, n_bus) is left out (its table row is NaN by construction, which must not reach
-// the sums): the ids are read again here, never followed.
-constexpr int BM_LX = 16, BM_SY = 16, BM_THREADS = BM_LX * BM_SY, BM_UNROLL = 4;
-constexpr int BM_VALUES = 12;                      // {count, sum e, sum |e|, sum e^2, min e, max e} x the two quantities of a round
-constexpr int BM_PART_LD = BM_THREADS + 1;         // (odd stride: the combine's lanes differ in the value index)
-
-__global__ __launch_bounds__(BM_THREADS) void branch_moments_kernel(const float* __restrict__ err, const int64_t* __restrict__ edge_index,
+// The moments engine of reduce.hpp over the finished error table, with a line as the owner: slice s walks the samples s,
+// s + MO_SLICES, ..., keeps the 24 moments of its line -- one accumulator per quantity -- in registers and hands them over two
+// quantities per round.  A (sample, line) whose line names a bus outside [0, n_bus) is left out (its table row is NaN by
+// construction, which must not reach the sums): the ids are read again here, never followed.
+__global__ __launch_bounds__(MO_THREADS) void branch_moments_kernel(const float* __restrict__ err, const int64_t* __restrict__ edge_index,
                                                                    int lines_per_sample, int n_samples, int n_lines, int n_bus,
                                                                    double* __restrict__ moments) {
-    __shared__ double part[BM_VALUES * BM_PART_LD];
-    const int t = threadIdx.x, ll = t & (BM_LX - 1), sl = t / BM_LX;
-    const int line = blockIdx.x * BM_LX + ll;
+    const int t = threadIdx.x, ll = t & (MO_OWNERS - 1), sl = t / MO_OWNERS;
+    const int line = blockIdx.x * MO_OWNERS + ll;
     const bool live = line < n_lines;
     const uint64_t nb = (uint64_t)n_bus;
-    const double inf = __builtin_inf();
-    int cnt[4];
-    double sum[4], sab[4], ssq[4], mn[4], mx[4];
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        cnt[f] = 0;
-        sum[f] = sab[f] = ssq[f] = 0.0;
-        mn[f] = inf;
-        mx[f] = -inf;
-    }
+    Moments6 mo[4];
     const bool shared_ok = live && !lines_per_sample && (uint64_t)edge_index[line] < nb && (uint64_t)edge_index[n_lines + line] < nb;
-    for (int s0 = sl; s0 < n_samples; s0 += BM_UNROLL * BM_SY) {
-        float4 v[BM_UNROLL];
-        bool on[BM_UNROLL];
+    for (int s0 = sl; s0 < n_samples; s0 += MO_UNROLL * MO_SLICES) {
+        float4 v[MO_UNROLL];
+        bool on[MO_UNROLL];
 #pragma unroll
-        for (int u = 0; u < BM_UNROLL; ++u) {       // every load of the trip is requested before the first row is consumed
-            const int s = s0 + u * BM_SY;
+        for (int u = 0; u < MO_UNROLL; ++u) {       // every load of the trip is requested before the first row is consumed
+            const int s = s0 + u * MO_SLICES;
             on[u] = live && s < n_samples;
             v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (on[u]) {
@@ -169,53 +145,15 @@ __global__ __launch_bounds__(BM_THREADS) void branch_moments_kernel(const float*
             }
         }
 #pragma unroll
-        for (int u = 0; u < BM_UNROLL; ++u) {
+        for (int u = 0; u < MO_UNROLL; ++u) {
             if (!on[u]) continue;
             const float ev[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
 #pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const double e = (double)ev[f];
-                cnt[f] += 1;
-                sum[f] += e;
-                sab[f] += fabs(e);
-                ssq[f] += e * e;
-                mn[f] = fmin(mn[f], e);             // fmin / fmax ignore a NaN operand
-                mx[f] = fmax(mx[f], e);
-            }
+            for (int f = 0; f < 4; ++f) mo[f].add((double)ev[f]);
         }
     }
-    // two quantities per round: the slices' partials through LDS, summed in slice order by the owner of (line, value)
-    const int cb = t / BM_VALUES, cv = t - cb * BM_VALUES;      // the combine's lane: line cb < 16, value cv (t < 192)
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (h) __syncthreads();
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const int f = 2 * h + g;
-            double* q = part + (g * 6) * BM_PART_LD + t;
-            q[0] = (double)cnt[f];
-            q[BM_PART_LD] = sum[f];
-            q[2 * BM_PART_LD] = sab[f];
-            q[3 * BM_PART_LD] = ssq[f];
-            q[4 * BM_PART_LD] = mn[f];
-            q[5 * BM_PART_LD] = mx[f];
-        }
-        __syncthreads();
-        const int cline = blockIdx.x * BM_LX + cb;
-        if (t < BM_LX * BM_VALUES && cline < n_lines) {
-            const int k = cv % 6;
-            const double* q = part + cv * BM_PART_LD + cb;
-            double a = q[0];
-#pragma unroll
-            for (int s = 1; s < BM_SY; ++s) {
-                const double w = q[s * BM_LX];
-                a = k < 4 ? a + w : (k == 4 ? fmin(a, w) : fmax(a, w));
-            }
-            double* m = moments + ((int64_t)cline * 4 + 2 * h) * 6 + cv;
-            const double was = *m;
-            *m = k < 4 ? was + a : (k == 4 ? fmin(was, a) : fmax(was, a));
-        }
-    }
+    for (int h = 0; h < 2; ++h) moments_round(mo[2 * h], mo[2 * h + 1], h, n_lines, 24, moments);      // two quantities per round
 }
 
 static bool bf_use_lds(int64_t n_bus) {
@@ -231,7 +169,7 @@ static int bf_launch(const BfArgs& a, hipStream_t s) {
     const int grid = std::max(1, std::min(a.n_samples, 8 * device_cus()));
     if (lds) {
         static std::atomic<uint64_t> raised{0};
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(branch_flows_kernel<TWO, true>), BF_LDS_CU - BF_LDS_RESERVE, raised));
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(branch_flows_kernel<TWO, true>), kLdsCuBytes - kLdsReserve, raised));
         branch_flows_kernel<TWO, true><<<grid, threads, bytes, s>>>(a);
     } else {
         branch_flows_kernel<TWO, false><<<grid, threads, 0, s>>>(a);
@@ -316,7 +254,7 @@ int pfn_branch_flows(const float* pred, int pred_normalised, const float* truth,
     }
     if (moments) {
         ProfScope ps("branch_moments", lines * (16.0 + (lines_per_sample ? 16.0 : 0.0)) + (double)n_lines * 384.0, lines * 32.0, s);
-        branch_moments_kernel<<<(int)((n_lines + BM_LX - 1) / BM_LX), BM_THREADS, 0, s>>>(err, edge_index, a.lines_per_sample, a.n_samples,
+        branch_moments_kernel<<<(int)((n_lines + MO_OWNERS - 1) / MO_OWNERS), MO_THREADS, 0, s>>>(err, edge_index, a.lines_per_sample, a.n_samples,
                                                                                           a.n_lines, a.n_bus, moments);
         PFN_CHECK_LAUNCH();
     }

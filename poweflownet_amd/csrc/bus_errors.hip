@@ -6,20 +6,14 @@
 #include <algorithm>
 
 #include "pfn_internal.hpp"
+#include "reduce.hpp"
 
 namespace pfn {
 
 // ------------------------------------------------------------------------------------------------- accumulate
-// A workgroup owns BE_BX consecutive buses; its 256 threads are BE_BX bus lanes x BE_SY sample slices.  Slice s walks the graphs
-// s, s + BE_SY, ... (16 lanes read 16 consecutive 16-byte rows of ONE sample: 256 contiguous bytes), keeps the 48 moments of its bus
-// in registers and hands them over through LDS, one feature per round; thread (bus, value) then adds the BE_SY slice partials in
-// slice order and folds the result into the moments it found.  The split depends on nothing but the constants below, so a launch
-// is a pure function of its inputs.  6470 buses x 64 graphs: 405 workgroups, 4 graphs per thread; 118 x 128: 8 workgroups, 8 graphs
-// per thread in two trips of BE_UNROLL.
-constexpr int BE_BX = 16, BE_SY = 16, BE_THREADS = BE_BX * BE_SY, BE_UNROLL = 4;
-constexpr int BE_VALUES = 12;                      // {count, sum e, sum |e|, sum e^2, min e, max e} x {mask != 0, mask == 0}
-constexpr int BE_PART_LD = BE_THREADS + 1;         // (odd stride: the combine's lanes differ in the value index)
-
+// The moments engine of reduce.hpp with a bus as the owner: slice s walks the graphs s, s + MO_SLICES, ..., keeps the 48 moments of
+// its bus -- 4 features x {mask != 0, mask == 0} -- in registers and hands them over one feature per round.  6470 buses x 64 graphs:
+// 405 workgroups, 4 graphs per thread; 118 x 128: 8 workgroups, 8 graphs per thread in two trips of MO_UNROLL.
 struct BusErrScale {
     float std[4], mean[4];
 };
@@ -35,48 +29,30 @@ __device__ __forceinline__ unsigned be_mask_bits(const void* m, int dtype, int64
     return (v.x != 0.f ? 1u : 0u) | (v.y != 0.f ? 2u : 0u) | (v.z != 0.f ? 4u : 0u) | (v.w != 0.f ? 8u : 0u);
 }
 
-// (out - y) * std and out * std + mean, every operation rounded on its own (eval.hip: hipcc contracts a * b + c also through the
-// _rn intrinsics) -- the expression of pfn_eval_metrics' de-normalised terms, and torch's `denormalize` bit for bit
+// (out - y) * std, every operation rounded on its own, as `denorm` -- the expression of pfn_eval_metrics' de-normalised terms
 __device__ __forceinline__ float be_error(float o, float y, float sd) {
 #pragma clang fp contract(off)
     const float d = o - y;
     return d * sd;
 }
-__device__ __forceinline__ float be_prediction(float o, float sd, float mu) {
-#pragma clang fp contract(off)
-    const float p = o * sd;
-    return p + mu;
-}
 
-__global__ __launch_bounds__(BE_THREADS) void bus_errors_accumulate_kernel(
+__global__ __launch_bounds__(MO_THREADS) void bus_errors_accumulate_kernel(
     const float* __restrict__ o, const float* __restrict__ y, const void* __restrict__ mask, int mask_dtype, int n_graphs, int n_bus,
     BusErrScale sc, const int64_t* __restrict__ sample_idx, int64_t table_rows, float* __restrict__ err_table,
     float* __restrict__ pred_table, double* __restrict__ moments, int32_t* __restrict__ flags) {
-    __shared__ double part[BE_VALUES * BE_PART_LD];
-    const int t = threadIdx.x, bl = t & (BE_BX - 1), sl = t / BE_BX;
-    const int bus = blockIdx.x * BE_BX + bl;
+    const int t = threadIdx.x, bl = t & (MO_OWNERS - 1), sl = t / MO_OWNERS;
+    const int bus = blockIdx.x * MO_OWNERS + bl;
     const bool live = bus < n_bus;
-    const double inf = __builtin_inf();
-    int cnt[4][2];
-    double sum[4][2], sab[4][2], ssq[4][2], mn[4][2], mx[4][2];
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            cnt[f][g] = 0;
-            sum[f][g] = sab[f][g] = ssq[f][g] = 0.0;
-            mn[f][g] = inf;
-            mx[f][g] = -inf;
-        }
+    Moments6 mo[4][2];                              // [feature][group 0: mask != 0 (predicted), group 1: mask == 0 (given)]
     bool bad_seen = false;
-    for (int g0 = sl; g0 < n_graphs; g0 += BE_UNROLL * BE_SY) {
-        float4 vo[BE_UNROLL], vy[BE_UNROLL];
-        unsigned mb[BE_UNROLL];
-        int64_t row[BE_UNROLL];
-        bool on[BE_UNROLL];
+    for (int g0 = sl; g0 < n_graphs; g0 += MO_UNROLL * MO_SLICES) {
+        float4 vo[MO_UNROLL], vy[MO_UNROLL];
+        unsigned mb[MO_UNROLL];
+        int64_t row[MO_UNROLL];
+        bool on[MO_UNROLL];
 #pragma unroll
-        for (int u = 0; u < BE_UNROLL; ++u) {      // every load of the trip is requested before the first row is consumed
-            const int g = g0 + u * BE_SY;
+        for (int u = 0; u < MO_UNROLL; ++u) {      // every load of the trip is requested before the first row is consumed
+            const int g = g0 + u * MO_SLICES;
             on[u] = live && g < n_graphs;
             row[u] = 0;
             vo[u] = vy[u] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -96,14 +72,14 @@ __global__ __launch_bounds__(BE_THREADS) void bus_errors_accumulate_kernel(
             }
         }
 #pragma unroll
-        for (int u = 0; u < BE_UNROLL; ++u) {
+        for (int u = 0; u < MO_UNROLL; ++u) {
             if (!on[u]) continue;
             const float ov[4] = {vo[u].x, vo[u].y, vo[u].z, vo[u].w}, yv[4] = {vy[u].x, vy[u].y, vy[u].z, vy[u].w};
             float ev[4], pv[4];
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
                 ev[f] = be_error(ov[f], yv[f], sc.std[f]);
-                pv[f] = be_prediction(ov[f], sc.std[f], sc.mean[f]);
+                pv[f] = denorm(ov[f], sc.std[f], sc.mean[f]);
             }
             if (err_table) st4(err_table + 4 * row[u], make_float4(ev[0], ev[1], ev[2], ev[3]));
             if (pred_table) st4(pred_table + 4 * row[u], make_float4(pv[0], pv[1], pv[2], pv[3]));
@@ -112,51 +88,13 @@ __global__ __launch_bounds__(BE_THREADS) void bus_errors_accumulate_kernel(
                 const double e = (double)ev[f];
                 const bool p = (mb[u] >> f) & 1u;
 #pragma unroll
-                for (int g = 0; g < 2; ++g) {       // group 0: mask != 0 (predicted), group 1: mask == 0 (given)
-                    const bool in = (g == 0) == p;
-                    // (branch-free: an entry of the other group adds 0 / offers +-inf, so a NaN poisons its own group only)
-                    cnt[f][g] += in ? 1 : 0;
-                    sum[f][g] += in ? e : 0.0;
-                    sab[f][g] += in ? fabs(e) : 0.0;
-                    ssq[f][g] += in ? e * e : 0.0;
-                    mn[f][g] = fmin(mn[f][g], in ? e : inf);        // fmin / fmax ignore a NaN operand
-                    mx[f][g] = fmax(mx[f][g], in ? e : -inf);
-                }
+                for (int g = 0; g < 2; ++g) mo[f][g].add_if((g == 0) == p, e);
             }
         }
     }
     if (bad_seen && bl == 0) flags[0] = flags[0] | 1;    // (every writer stores the same bit over the same word)
-    // one feature per round: the slices' partials through LDS, summed in slice order by the owner of (bus, value)
-    const int cb = t / BE_VALUES, cv = t - cb * BE_VALUES;      // the combine's lane: bus cb < 16, value cv (t < 192)
 #pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        if (f) __syncthreads();
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            double* q = part + (g * 6) * BE_PART_LD + t;
-            q[0] = (double)cnt[f][g];
-            q[BE_PART_LD] = sum[f][g];
-            q[2 * BE_PART_LD] = sab[f][g];
-            q[3 * BE_PART_LD] = ssq[f][g];
-            q[4 * BE_PART_LD] = mn[f][g];
-            q[5 * BE_PART_LD] = mx[f][g];
-        }
-        __syncthreads();
-        const int cbus = blockIdx.x * BE_BX + cb;
-        if (t < BE_BX * BE_VALUES && cbus < n_bus) {
-            const int k = cv % 6;
-            const double* q = part + cv * BE_PART_LD + cb;
-            double a = q[0];
-#pragma unroll
-            for (int s = 1; s < BE_SY; ++s) {
-                const double v = q[s * BE_BX];
-                a = k < 4 ? a + v : (k == 4 ? fmin(a, v) : fmax(a, v));
-            }
-            double* m = moments + ((int64_t)cbus * 4 + f) * BE_VALUES + cv;
-            const double was = *m;
-            *m = k < 4 ? was + a : (k == 4 ? fmin(was, a) : fmax(was, a));
-        }
-    }
+    for (int f = 0; f < 4; ++f) moments_round(mo[f][0], mo[f][1], f, n_bus, 48, moments);      // one feature per round
 }
 
 // -------------------------------------------------------------------------------------------------- histogram
@@ -165,8 +103,6 @@ __global__ __launch_bounds__(BE_THREADS) void bus_errors_accumulate_kernel(
 // 16 * tile contiguous bytes of a sample are one coalesced read of `tile` lanes -- and counts with integer LDS atomics, which are
 // order-free; then it writes its slab of `hist` / `outside`.  No global atomics.
 constexpr int BH_THREADS = 256, BH_UNROLL = 4, BH_MAX_TILE = 32, BH_MAX_BINS = 2048;
-constexpr int BH_LDS_CU = 160 * 1024;              // LDS of one compute unit
-constexpr int BH_LDS_RESERVE = 1024;               // (kept free of the dynamic region)
 
 __host__ __device__ inline size_t bh_lds_bytes(int tile, int nbins) {
     return (size_t)4 * (nbins + 1) * sizeof(double) + (size_t)tile * 4 * (nbins + 3) * sizeof(uint32_t);
@@ -175,7 +111,7 @@ __host__ __device__ inline size_t bh_lds_bytes(int tile, int nbins) {
 // loop is load -> compare -> LDS atomic), else the largest that fits at all.  300 bins: 8 buses (48.4 KB with the 9.6 KB of edges:
 // three workgroups per CU; 16 buses + edges = 87.2 KB would be alone on its CU); 2048 bins: 2 buses (131 KB).
 static int bh_tile(int nbins) {
-    for (int budget : {BH_LDS_CU / 2, BH_LDS_CU - BH_LDS_RESERVE})
+    for (int budget : {kLdsCuBytes / 2, kLdsCuBytes - kLdsReserve})
         for (int tile = BH_MAX_TILE; tile >= 1; tile >>= 1)
             if ((int64_t)bh_lds_bytes(tile, nbins) <= budget) return tile;
     return 0;
@@ -280,11 +216,11 @@ int pfn_bus_errors_accumulate(const float* out, const float* y, const void* mask
         sc.mean[f] = mean4 ? mean4[f] : 0.f;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nb = (int)((n_bus + BE_BX - 1) / BE_BX);
+    const int nb = (int)((n_bus + MO_OWNERS - 1) / MO_OWNERS);
     const double rows = (double)n_graphs * (double)n_bus;
     ProfScope ps("bus_errors_accumulate", rows * (32.0 + (mask_dtype == 0 ? 32.0 : 16.0) + (err_table ? 16.0 : 0.0) + (pred_table ? 16.0 : 0.0)) +
                                               (double)n_bus * 768.0, rows * 64.0, s);
-    bus_errors_accumulate_kernel<<<nb, BE_THREADS, 0, s>>>(out, y, mask, mask_dtype, (int)n_graphs, (int)n_bus, sc, sample_idx, table_rows,
+    bus_errors_accumulate_kernel<<<nb, MO_THREADS, 0, s>>>(out, y, mask, mask_dtype, (int)n_graphs, (int)n_bus, sc, sample_idx, table_rows,
                                                            err_table, pred_table, moments, flags);
     PFN_CHECK_LAUNCH();
     return PFN_OK;
@@ -304,7 +240,7 @@ int pfn_bus_errors_histogram(const float* table, int64_t n_samples, int64_t n_bu
     const int tile = bh_tile(nbins);
     PFN_CHECK_ARG(tile >= 1, "pfn_bus_errors_histogram: %d bins do not fit the LDS of a compute unit", nbins);
     static std::atomic<uint64_t> raised{0};
-    PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bus_errors_histogram_kernel), BH_LDS_CU - BH_LDS_RESERVE, raised));
+    PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(bus_errors_histogram_kernel), kLdsCuBytes - kLdsReserve, raised));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int nb = (int)((n_bus + tile - 1) / tile);
     ProfScope ps("bus_errors_histogram", (double)n_samples * n_bus * 16.0 + (double)n_bus * 4.0 * (nbins + 3) * 4.0,

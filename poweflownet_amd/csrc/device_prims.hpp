@@ -62,9 +62,37 @@ __device__ __forceinline__ void dma_1k(const char* g, float* lds_dst) {
 }
 // Drain of everything the wave has in flight in vector memory, hidden from hipcc's own wait-count bookkeeping: the hand-issued
 // loads, DMAs and stores above and below are invisible to it, so it would not place this wait itself.  On gfx950 vmcnt counts
-// stores too: behind a write-through store it means "the payload has left the XCD" (the loss hand-offs of ea_seg.hip and
-// util_kernels.hip, guarded by their #error for other targets).
+// stores too: behind a write-through store it means "the payload has left the XCD" (handoff_drained_publish below).
 __device__ __forceinline__ void vmem_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ----------------------------------------------------------------------- the last-arriver hand-off
+// Every block publishes a payload, takes a ticket on a counter and learns whether it is the LAST to arrive; the last one reads all
+// payloads (in block order: reduce.hpp) and re-arms the counter with a plain store of 0.  Two flavours, both kept:
+//   FENCED   plain payload stores by the thread that then calls handoff_fenced_publish (__threadfence, ACQ_REL ticket); every
+//            thread of the last block calls handoff_fenced_consume (__threadfence) before it reads.  The language memory model
+//            promises this form.  A __threadfence is an L2 write-back + L1 invalidate, ~3.5 us each on this multi-XCD part.
+//   DRAINED  the payload is stored WRITE-THROUGH (agent_store), the stores are drained (vmem_drain), then a RELAXED ticket is
+//            taken; the last block reads with agent_load (served by L2 / memory, never by its L1).  This is the "write-through
+//            payload -> asm vmcnt(0) -> flag, agent-scope loads on the consumer" form MI355X_MICROARCH.md lists as valid ON gfx950
+//            (vmcnt covers stores there; the language memory model does not promise it) -- hence the one target guard below, and
+//            tests/test_gpu_parity.py::test_mse_loss_handoff_stress.  CONTRACT: the drain covers the calling WAVE only, so every
+//            payload store must have been issued by the wave that calls handoff_drained_publish (any lane of it, any time before).
+template <typename T>
+__device__ __forceinline__ void agent_store(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ T agent_load(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ bool handoff_fenced_publish(int* counter) {
+    __threadfence();
+    return __hip_atomic_fetch_add(counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+}
+__device__ __forceinline__ void handoff_fenced_consume() { __threadfence(); }
+__device__ __forceinline__ bool handoff_drained_publish(int* counter) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
+#error "the drained last-arriver hand-off relies on gfx950 semantics (write-through stores drained by s_waitcnt vmcnt(0))"
+#endif
+    vmem_drain();
+    return __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
+}
 
 // --------------------------------------------------------------------------- hand-managed VMEM
 // In the steady state of the GEMM kernels EVERY vector-memory instruction of a wave is inline asm, invisible to hipcc's waitcnt

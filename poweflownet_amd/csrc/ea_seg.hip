@@ -1308,11 +1308,9 @@ void ea_seg_bwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
         }
     }
     if (LOSS && wave == 0 && sc.q == max(0, sc.nq - 2)) {
-        // the loss: the last of the partial-owning blocks to get here sums the partials in BLOCK order (deterministic).  Same
-        // hand-off as mse_kernel (util_kernels.hip): write-through partial, drained, then the ticket; agent-scope loads on the consumer
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "the loss hand-off relies on gfx950 semantics (write-through stores drained by s_waitcnt vmcnt(0))"
-#endif
+        // the loss: the last of the partial-owning blocks to get here sums the partials in BLOCK order (deterministic).  The
+        // drained hand-off of device_prims.hpp (its explanation and target guard), kept in its own words: through agent_store /
+        // handoff_drained_publish / agent_load this kernel's register allocation comes out different
         int last = 0;
         if (lane == 0) {
             vmem_drain();

@@ -66,7 +66,7 @@ __device__ __forceinline__ void eval_family(const float* S, const float* cntc, f
 }
 
 // One thread per row (grid-stride past 256 x 256 rows), 16-byte loads, 25 accumulators; wave butterflies, a fixed LDS combine of the
-// four waves, then mse_kernel's hand-off (util_kernels.hip): partials stored write-through and drained before the ticket, the last
+// four waves, then the drained hand-off (device_prims.hpp): partials stored write-through and drained before the ticket, the last
 // arriver reads them with agent-scope loads, sums them in an order that depends on the grid only, writes the terms, updates the
 // epoch accumulators and re-arms the ticket.
 __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restrict__ o, const float* __restrict__ y,
@@ -130,24 +130,16 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
     }
     __syncthreads();
     if (wv == 0) {
-        // the hand-off of mse_kernel: write-through payload -> drain -> ticket; agent-scope loads on the consumer.  Valid ON
-        // gfx950 (vmcnt covers stores there) -- hence the same target guard.  All 26 stores are lanes of ONE wave: the drain below
-        // covers every one of them before lane 0 takes the ticket.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "eval_metrics_kernel's last-arriver hand-off relies on gfx950 semantics (write-through stores drained before the ticket)"
-#endif
+        // the drained hand-off (device_prims.hpp).  Its contract holds: all 26 stores are lanes of wave 0, whose lane 0 drains and
+        // takes the ticket.
         if (t < kEvalSlots) {
             float v;
             if (t < kEvalFloatSlots) v = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
             else v = __int_as_float(((__float_as_int(red[0][t]) + __float_as_int(red[1][t])) + __float_as_int(red[2][t])) +
                                     __float_as_int(red[3][t]));
-            __hip_atomic_store(w->part + t * 256 + blockIdx.x, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            agent_store(w->part + t * 256 + blockIdx.x, v);
         }
-        vmem_drain();
-        if (t == 0) {
-            const int tk = __hip_atomic_fetch_add(&w->counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = tk == (int)gridDim.x - 1;
-        }
+        if (t == 0) s_last = handoff_drained_publish(&w->counter);
     }
     __syncthreads();
     if (!s_last) return;
@@ -162,10 +154,10 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
                 const int b = lane + 64 * j;
                 if (b < nb) {
                     const float* p = w->part + (4 * g) * 256 + b;
-                    a.x += __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    a.y += __hip_atomic_load(p + 256, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    a.z += __hip_atomic_load(p + 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    a.w += __hip_atomic_load(p + 768, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    a.x += agent_load(p);
+                    a.y += agent_load(p + 256);
+                    a.z += agent_load(p + 512);
+                    a.w += agent_load(p + 768);
                 }
             }
             a = wave_sum4(a);
@@ -176,8 +168,8 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
             for (int j = 0; j < 4; ++j) {
                 const int b = lane + 64 * j;
                 if (b < nb) {
-                    k1 += __float_as_int(__hip_atomic_load(w->part + 24 * 256 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                    k0 += __float_as_int(__hip_atomic_load(w->part + 25 * 256 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                    k1 += __float_as_int(agent_load(w->part + 24 * 256 + b));
+                    k0 += __float_as_int(agent_load(w->part + 25 * 256 + b));
                 }
             }
             k1 = wave_sum_int(k1);

@@ -62,6 +62,8 @@ const char* diag_env(const char* name);
 // no result depends on it.
 int next_sweep_direction();
 int ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& done);
+constexpr int kLdsCuBytes = 160 * 1024;            // LDS of one compute unit
+constexpr int kLdsReserve = 1024;                  // (kept free of a kernel's dynamic region: its static words)
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline int ld_of(int f) { return (int)round_up(f, 4); }
@@ -597,6 +599,14 @@ int launch_export_edge_gates(const GraphView& g, const float* P, const float* Q,
 int launch_export_row_gates(int64_t n, int h, int ld, const float* y, int cm, uint8_t* out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------- dropout RNG
+// out * std + mean, product and sum rounded separately (hipcc contracts a * b + c also through the _rn intrinsics): torch's
+// `denormalize` bit for bit
+__device__ __forceinline__ float denorm(float o, float sd, float mu) {
+#pragma clang fp contract(off)
+    const float p = o * sd;
+    return p + mu;
+}
+
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter-based, so the mask of a
 // forward pass is a pure function of (seed, offset, layer, element) -- nothing is stored, any kernel can re-derive it.
 //   key     = { seed[31:0], seed[63:32] ^ offset[63:32] }

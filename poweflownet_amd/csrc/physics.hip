@@ -11,6 +11,7 @@
 // collects from the rows where k is the source (its own dP, dQ) and from the rows where k is the destination (the
 // source's dP, dQ).  No atomics, edge-id order, an ordered last-arriver sum for the scalar.
 #include "pfn_internal.hpp"
+#include "reduce.hpp"
 
 namespace pfn {
 
@@ -44,8 +45,6 @@ __global__ __launch_bounds__(256) void power_imbalance_fwd_kernel(int n, int e_s
                                                                   const float* __restrict__ ea, const PiStats st,
                                                                   float* __restrict__ dpq, PiHeader* __restrict__ hd,
                                                                   float* __restrict__ loss) {
-    __shared__ float red[256];
-    __shared__ int s_last;
     float acc = 0.f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const Bus bi = bus_of(x, i, st);
@@ -63,31 +62,8 @@ __global__ __launch_bounds__(256) void power_imbalance_fwd_kernel(int n, int e_s
         dpq[2 * i + 1] = dq;
         acc += dp * dp + dq * dq;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        hd->partial[blockIdx.x] = red[0];
-        __threadfence();
-        const int t = __hip_atomic_fetch_add(&hd->counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    red[threadIdx.x] = threadIdx.x < gridDim.x ? __hip_atomic_load(&hd->partial[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        loss[0] = red[0] / (float)n;    // n == 0: NaN, torch's mean of nothing
-        hd->counter = 0;
-    }
+    float total = 0.f;                  // (the fenced hand-off, device_prims.hpp)
+    if (grid_sum_ordered<false>(acc, hd->partial, &hd->counter, total) && threadIdx.x == 0) loss[0] = total / (float)n;    // n == 0: NaN, torch's mean of nothing
 }
 
 // d loss / d x[k][:]:  loss = (1/N) sum_i (dP_i^2 + dQ_i^2)

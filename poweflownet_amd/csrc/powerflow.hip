@@ -24,8 +24,6 @@
 
 namespace pfn {
 
-constexpr int PF_LDS_CU = 160 * 1024;              // LDS of one compute unit
-constexpr int PF_LDS_RESERVE = 1024;               // (kept free of the dynamic region: the kernel's static words)
 constexpr int PF_MAX_UNKNOWNS = 1024;              // dense cap of the global route: 4 MiB per sample, 3.6e8 multiply-adds per factor
 constexpr int PF_SMALL_THREADS = 256, PF_BIG_THREADS = 1024;
 constexpr int PF_BIG_M = 90;                       // 4 m^2 beyond ~32 KiB: few workgroups per CU, so each gets 16 waves
@@ -276,7 +274,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
 }
 
 static int pf_unknowns(int64_t n, int64_t n_pq, int mode) { return (int)((n - 1) + (mode == 1 ? 0 : n_pq)); }
-static bool pf_fits_lds(int n, int m) { return pf_vec_bytes(n, m) + pf_mat_floats(m) * 4 <= (size_t)(PF_LDS_CU - PF_LDS_RESERVE); }
+static bool pf_fits_lds(int n, int m) { return pf_vec_bytes(n, m) + pf_mat_floats(m) * 4 <= (size_t)(kLdsCuBytes - kLdsReserve); }
 
 }  // namespace pfn
 
@@ -323,7 +321,7 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
     const int n = (int)n_bus, m = (int)m64;
     const bool fits = pf_fits_lds(n, m);
     PFN_CHECK_ARG(route != 1 || fits, "pfn_powerflow_solve: route 1 (LDS): %d unknowns of %d buses need %zu bytes of LDS, %d are there", m, n,
-                  pf_vec_bytes(n, m) + pf_mat_floats(m) * 4, PF_LDS_CU - PF_LDS_RESERVE);
+                  pf_vec_bytes(n, m) + pf_mat_floats(m) * 4, kLdsCuBytes - kLdsReserve);
     const bool lds = route == 1 || (route == 0 && fits);
     PfArgs a;
     a.edge_index = edge_index;
@@ -361,7 +359,7 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
                  (double)n_samples * iters * (2.0 / 3.0 * mm * mm * mm + 2.0 * mm * mm), s);
     if (lds) {
         static std::atomic<uint64_t> raised{0};
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true>), PF_LDS_CU - PF_LDS_RESERVE, raised));
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
         powerflow_kernel<true><<<(int)n_samples, threads, bytes, s>>>(a);
     } else {
         powerflow_kernel<false><<<(int)n_samples, threads, bytes, s>>>(a);

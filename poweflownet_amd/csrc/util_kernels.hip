@@ -3,20 +3,13 @@
 #include <algorithm>
 
 #include "pfn_internal.hpp"
+#include "reduce.hpp"
 
 namespace pfn {
 
 // ---- Masked_L2_loss (utils/custom_loss_functions.py:10-46): two masked means of (out - y)^2.  Kernel 1 reduces
-// (sum, count) of both sets with an ordered last-arriver combine and writes the loss and the totals; kernel 2 turns the
-// totals into the two gradient scales.
-struct MaskedL2Ws {
-    float s1[256], s0[256];
-    int c1[256], c0[256];
-    float tot_s1, tot_s0;
-    int tot_c1, tot_c0;
-    int pad_[3];
-    int counter;   // byte 4124
-};
+// (sum, count) of both sets with an ordered last-arriver combine (reduce.hpp masked_l2_combine: MaskedL2Ws) and writes the loss and
+// the totals; kernel 2 turns the totals into the two gradient scales.
 __device__ __forceinline__ float mask_value(const void* m, int dtype, int64_t i) {
     return dtype == 0 ? (float)static_cast<const int64_t*>(m)[i] : static_cast<const float*>(m)[i];
 }
@@ -24,9 +17,6 @@ __global__ __launch_bounds__(256) void masked_l2_reduce_kernel(const float* __re
                                                                const void* __restrict__ mask, int mask_dtype, int64_t n,
                                                                int regularize, float regcoeff, MaskedL2Ws* __restrict__ w,
                                                                float* __restrict__ loss) {
-    __shared__ float rs1[256], rs0[256];
-    __shared__ int rc1[256], rc0[256];
-    __shared__ int s_last;
     float a1 = 0.f, a0 = 0.f;
     int k1 = 0, k0 = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -34,38 +24,11 @@ __global__ __launch_bounds__(256) void masked_l2_reduce_kernel(const float* __re
         if (m != 0.f) { a1 = fmaf(d, d, a1); ++k1; }                 // mask.type(bool)
         if (1.f - m != 0.f) { a0 = fmaf(d, d, a0); ++k0; }           // (1 - mask).type(bool)
     }
-    const int t = threadIdx.x;
-    rs1[t] = a1; rs0[t] = a0; rc1[t] = k1; rc0[t] = k0;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) { rs1[t] += rs1[t + off]; rs0[t] += rs0[t + off]; rc1[t] += rc1[t + off]; rc0[t] += rc0[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        w->s1[blockIdx.x] = rs1[0]; w->s0[blockIdx.x] = rs0[0]; w->c1[blockIdx.x] = rc1[0]; w->c0[blockIdx.x] = rc0[0];
-        __threadfence();
-        const int tk = __hip_atomic_fetch_add(&w->counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = tk == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    const bool in = t < (int)gridDim.x;
-    rs1[t] = in ? __hip_atomic_load(&w->s1[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    rs0[t] = in ? __hip_atomic_load(&w->s0[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    rc1[t] = in ? __hip_atomic_load(&w->c1[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    rc0[t] = in ? __hip_atomic_load(&w->c0[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) { rs1[t] += rs1[t + off]; rs0[t] += rs0[t + off]; rc1[t] += rc1[t + off]; rc0[t] += rc0[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        w->tot_s1 = rs1[0]; w->tot_s0 = rs0[0]; w->tot_c1 = rc1[0]; w->tot_c0 = rc0[0];
-        float l = rs1[0] / (float)rc1[0];                            // 0/0 = NaN: torch's mean of an empty selection
-        if (regularize) l += regcoeff * (rs0[0] / (float)rc0[0]);
+    if (!masked_l2_combine(a1, a0, k1, k0, w)) return;
+    if (threadIdx.x == 0) {
+        float l = w->tot_s1 / (float)w->tot_c1;                      // 0/0 = NaN: torch's mean of an empty selection
+        if (regularize) l += regcoeff * (w->tot_s0 / (float)w->tot_c0);
         loss[0] = l;
-        w->counter = 0;
     }
 }
 __global__ __launch_bounds__(256) void masked_l2_grad_kernel(const float* __restrict__ o, const float* __restrict__ y,
@@ -87,47 +50,15 @@ __global__ __launch_bounds__(256) void masked_l2_grad_kernel(const float* __rest
 __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ o, const float* __restrict__ y, int64_t n,
                                                   float inv_n, float* __restrict__ grad, float* __restrict__ partial,
                                                   int* __restrict__ counter, float* __restrict__ loss) {
-    __shared__ float red[256];
-    __shared__ int s_last;
     float acc = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float d = o[i] - y[i];
         acc = fmaf(d, d, acc);
         if (grad) grad[i] = 2.f * d * inv_n;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        // hand-off to the last arriver without __threadfence() (an L2 write-back + L1 invalidate, ~3.5 us each on this
-        // multi-XCD part, and the kernel had two): the partial is stored WRITE-THROUGH (agent-scope atomic store), the
-        // store is drained (vmem_drain), then the ticket is taken; the last arriver reads the partials with agent-scope atomic loads
-        // (served by L2 / memory, never by its L1).  This is the "write-through payload -> asm vmcnt(0) -> flag, agent-scope loads on
-        // the consumer" form MI355X_MICROARCH.md lists as valid ON gfx950 (vmcnt covers stores there; the language memory model does not
-        // promise it) -- hence the target guard below, and tests/test_gpu_parity.py::test_mse_loss_handoff_stress.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
-#error "mse_kernel's last-arriver hand-off relies on gfx950 semantics (write-through stores drained by s_waitcnt vmcnt(0))"
-#endif
-        __hip_atomic_store(partial + blockIdx.x, red[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        vmem_drain();
-        const int t = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    red[threadIdx.x] = threadIdx.x < gridDim.x ? __hip_atomic_load(partial + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        loss[0] = red[0] * inv_n;
-        *counter = 0;
-    }
+    // (the drained hand-off, device_prims.hpp: no __threadfence on either side of the ticket; the kernel had two)
+    float total = 0.f;
+    if (grid_sum_ordered<true>(acc, partial, counter, total) && threadIdx.x == 0) loss[0] = total * inv_n;
 }
 
 // one block per CU at most: every block ends with one atomic on the arrival counter (64 blocks of 1024 threads were tried for
@@ -377,9 +308,6 @@ __global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const float* __re
                                                                const void* __restrict__ mask, int mask_dtype,
                                                                const int* __restrict__ valid, int64_t n_rows, int regularize,
                                                                float regcoeff, MaskedL2Ws* __restrict__ w, float* __restrict__ loss) {
-    __shared__ float rs1[256], rs0[256];
-    __shared__ int rc1[256], rc0[256];
-    __shared__ int s_last;
     float a1 = 0.f, a0 = 0.f;
     int k1 = 0, k0 = 0;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * blockDim.x) {
@@ -393,45 +321,18 @@ __global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const float* __re
             if (MASKED && 1.f - m != 0.f) { a0 = fmaf(d[e], d[e], a0); ++k0; }
         }
     }
-    const int t = threadIdx.x;
-    rs1[t] = a1; rs0[t] = a0; rc1[t] = k1; rc0[t] = k0;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) { rs1[t] += rs1[t + off]; rs0[t] += rs0[t + off]; rc1[t] += rc1[t + off]; rc0[t] += rc0[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        w->s1[blockIdx.x] = rs1[0]; w->s0[blockIdx.x] = rs0[0]; w->c1[blockIdx.x] = rc1[0]; w->c0[blockIdx.x] = rc0[0];
-        __threadfence();
-        const int tk = __hip_atomic_fetch_add(&w->counter, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = tk == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    const bool in = t < (int)gridDim.x;
-    rs1[t] = in ? __hip_atomic_load(&w->s1[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    rs0[t] = in ? __hip_atomic_load(&w->s0[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-    rc1[t] = in ? __hip_atomic_load(&w->c1[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    rc0[t] = in ? __hip_atomic_load(&w->c0[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (t < off) { rs1[t] += rs1[t + off]; rs0[t] += rs0[t + off]; rc1[t] += rc1[t + off]; rc0[t] += rc0[t + off]; }
-        __syncthreads();
-    }
-    if (t == 0) {
-        w->tot_s1 = rs1[0]; w->tot_s0 = rs0[0]; w->tot_c1 = rc1[0]; w->tot_c0 = rc0[0];
+    if (!masked_l2_combine(a1, a0, k1, k0, w)) return;
+    if (threadIdx.x == 0) {
         float l = 0.f;                                                   // no valid row at all: the loss of nothing is 0 here
-        if (rc1[0] + rc0[0] > 0) {
+        if (w->tot_c1 + w->tot_c0 > 0) {
             if (MASKED) {
-                l = rs1[0] / (float)rc1[0];                              // (an empty set of a non-empty batch: NaN, as above)
-                if (regularize) l += regcoeff * (rs0[0] / (float)rc0[0]);
+                l = w->tot_s1 / (float)w->tot_c1;                        // (an empty set of a non-empty batch: NaN, as above)
+                if (regularize) l += regcoeff * (w->tot_s0 / (float)w->tot_c0);
             } else {
-                l = rs1[0] * __fdiv_rn(1.0f, (float)rc1[0]);             // mse_kernel: sum * inv_n, inv_n = 1 / count rounded once
+                l = w->tot_s1 * __fdiv_rn(1.0f, (float)w->tot_c1);       // mse_kernel: sum * inv_n, inv_n = 1 / count rounded once
             }
         }
         loss[0] = l;
-        w->counter = 0;
     }
 }
 

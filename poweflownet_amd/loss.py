@@ -12,7 +12,7 @@ import torch.nn as nn
 from . import _lib as L
 
 
-MASKED_L2_WS_FLOATS = 1032     # struct MaskedL2Ws (csrc/util_kernels.hip): 4128 bytes
+MASKED_L2_WS_FLOATS = 1032     # struct MaskedL2Ws (csrc/reduce.hpp): 4128 bytes
 
 _ONE = {}     # per device: the constant 1 used as the unit loss gradient (immutable after creation)
 
@@ -306,7 +306,6 @@ def eval_metrics(out, y, mask, x=None, std=None, weight=1.0, first_unweighted=Fa
     slots): acc[k] += w * terms[k] on the device, w = 1 on the first batch when `first_unweighted`.  `mixed_out` (needs `x`):
     receives out * mask + x * (1 - mask).  `workspace`: a `_Workspace(L.EVAL_WS_FLOATS)` of the caller (a throw-away one
     otherwise).  No host sync; capturable."""
-    import ctypes as C
     L.require_device(out, y, mask, x, acc, mixed_out, terms, what="eval_metrics input")
     out, y = L.f32c(out, "out"), L.f32c(y, "y")
     n = out.shape[0]
@@ -330,11 +329,7 @@ def eval_metrics(out, y, mask, x=None, std=None, weight=1.0, first_unweighted=Fa
         terms = torch.empty(len(L.EVAL_TERMS), dtype=torch.float32, device=out.device)
     elif terms.dtype != torch.float32 or terms.numel() != len(L.EVAL_TERMS) or not terms.is_contiguous():
         raise RuntimeError(f"eval_metrics: terms must be a contiguous float32 tensor of {len(L.EVAL_TERMS)} elements")
-    if std is not None:
-        std = [float(v) for v in std]
-        if len(std) != 4:
-            raise RuntimeError("eval_metrics: std must hold four values")
-        std = (C.c_float * 4)(*std)
+    std = _host_floats(std, 4, "eval_metrics: std must hold four values")
     ws = (workspace or _Workspace(L.EVAL_WS_FLOATS)).on(out.device)
     with torch.cuda.device(out.device):
         L.check(L.load().pfn_eval_metrics(out.data_ptr(), y.data_ptr(), L.ptr(x), mask.data_ptr(), code, n, std, float(weight),
@@ -358,6 +353,7 @@ def eval_accumulate(loss, acc, weight=1.0, first_unweighted=False):
 
 # ------------------------------------------------------------------------------------------ per-bus error analysis
 BUS_MOMENTS = ("count", "sum", "sum_abs", "sum_sq", "min", "max")      # the six values per (bus, feature, mask group)
+MOMENT_AT = {k: i for i, k in enumerate(BUS_MOMENTS)}                   # ... and where each sits in the last axis
 
 
 def bus_error_moments(device, n_bus: int) -> torch.Tensor:
@@ -373,14 +369,15 @@ def reset_bus_error_moments(moments: torch.Tensor) -> torch.Tensor:
     return moments
 
 
-def _host4(v, what):
+def _host_floats(v, count, complaint):
+    """`count` host floats (a sequence or a tensor; None stays None) as a C float array; RuntimeError(`complaint`) on another length."""
     import ctypes as C
     if v is None:
         return None
-    v = [float(a) for a in v]
-    if len(v) != 4:
-        raise RuntimeError(f"bus_errors_accumulate: {what} must hold four values")
-    return (C.c_float * 4)(*v)
+    v = [float(a) for a in (v.detach().cpu().reshape(-1).tolist() if torch.is_tensor(v) else v)]
+    if len(v) != count:
+        raise RuntimeError(complaint)
+    return (C.c_float * count)(*v)
 
 
 def bus_errors_accumulate(out, y, mask, n_bus, sample_idx, moments, flags, std=None, mean=None, err_table=None, pred_table=None,
@@ -425,7 +422,8 @@ def bus_errors_accumulate(out, y, mask, n_bus, sample_idx, moments, flags, std=N
         raise RuntimeError("bus_errors_accumulate: flags must be an int32 tensor")
     with torch.cuda.device(out.device):
         L.check(L.load().pfn_bus_errors_accumulate(out.data_ptr(), y.data_ptr(), mask.data_ptr(), code, n_graphs, n_bus,
-                                                   _host4(std, "std"), _host4(mean, "mean"),
+                                                   _host_floats(std, 4, "bus_errors_accumulate: std must hold four values"),
+                                                   _host_floats(mean, 4, "bus_errors_accumulate: mean must hold four values"),
                                                    sample_idx.data_ptr() if rows is not None else None, rows if rows is not None else 0, L.ptr(err_table), L.ptr(pred_table),
                                                    moments.data_ptr(), flags.data_ptr(), L.stream_ptr()), "pfn_bus_errors_accumulate")
 
@@ -470,16 +468,6 @@ def branch_moments(device, n_lines: int) -> torch.Tensor:
 def branch_flows_lds_max_bus() -> int:
     """The largest n_bus whose rectangular voltages `pfn_branch_flows` keeps in LDS; beyond it the direct kernel runs."""
     return int(L.load().pfn_branch_flows_lds_max_bus())
-
-
-def _host_floats(v, count, what):
-    import ctypes as C
-    if v is None:
-        return None
-    v = [float(a) for a in (v.detach().cpu().reshape(-1).tolist() if torch.is_tensor(v) else v)]
-    if len(v) != count:
-        raise RuntimeError(f"branch_flows: {what} must hold {count} values")
-    return (C.c_float * count)(*v)
 
 
 def branch_flows(pred, edge_index, edge_attr, truth=None, pred_normalised=False, truth_normalised=False, std=None, mean=None,
@@ -534,11 +522,12 @@ def branch_flows(pred, edge_index, edge_attr, truth=None, pred_normalised=False,
         flags = torch.zeros(1, dtype=torch.int32, device=dev)
     elif flags.dtype != torch.int32 or flags.numel() < 1:
         raise RuntimeError("branch_flows: flags must be an int32 tensor")
+    std, mean, edge_std, edge_mean = (_host_floats(v, count, f"branch_flows: {what} must hold {count} values")
+                                      for v, count, what in ((std, 4, "std"), (mean, 4, "mean"), (edge_std, 2, "edge_std"), (edge_mean, 2, "edge_mean")))
     with torch.cuda.device(dev):
         L.check(L.load().pfn_branch_flows(pred.data_ptr(), int(bool(pred_normalised)), L.ptr(truth), int(bool(truth_normalised)), S, n_bus,
-                                          _host_floats(std, 4, "std"), _host_floats(mean, 4, "mean"), edge_index.data_ptr(),
-                                          int(edge_index.dim() == 3), e, edge_attr.data_ptr(), int(edge_attr.dim() == 3),
-                                          _host_floats(edge_std, 2, "edge_std"), _host_floats(edge_mean, 2, "edge_mean"),
+                                          std, mean, edge_index.data_ptr(),
+                                          int(edge_index.dim() == 3), e, edge_attr.data_ptr(), int(edge_attr.dim() == 3), edge_std, edge_mean,
                                           L.ptr(outs[0]), L.ptr(outs[1]), L.ptr(outs[2]), L.ptr(moments), flags.data_ptr(), L.ptr(ws),
                                           0 if ws is None else ws.numel() * 4, L.stream_ptr()), "pfn_branch_flows")
     return outs[0], outs[1], outs[2], flags

@@ -11,12 +11,11 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..loss import BUS_MOMENTS, branch_flows, branch_moments
-from .error_analysis import bus_error_epoch
-from .evaluation import GraphedEvalStep, _std4
+from ..loss import MOMENT_AT as _AT, branch_flows, branch_moments
+from .error_analysis import abs_mean_std, bus_error_epoch
+from .evaluation import GraphedEvalStep, _mean4, _std4
 
 QUANTITIES = ("Line Current", "Active Flow", "Reactive Flow", "Active Loss")
-_AT = {k: i for i, k in enumerate(BUS_MOMENTS)}
 
 
 @dataclass
@@ -95,7 +94,7 @@ def branch_errors_of(bus, loader, xymean=None, xystd=None, edgemean=None, edgest
         raise ValueError(f"branch_error_epoch: the pass saw {bus.num_samples} of the split's {len(ds)} samples; every sample is needed once")
     y, ei, ea = _split_tables(ds, bus.predictions.device)
     std4 = _std4(xystd)
-    mean4 = None if xymean is None else [float(v) for v in torch.as_tensor(xymean, dtype=torch.float32).detach().cpu().reshape(-1, 4)[0].tolist()]
+    mean4 = _mean4(xymean)
     esd, emu = _edge_stats(edgemean, edgestd)
     e = int(ei.shape[-1])
     state = torch.empty(e * 24 + 1, dtype=torch.float64, device=bus.predictions.device)      # moments + the flags word: ONE read-back
@@ -119,10 +118,7 @@ def branch_report_lines(moments) -> dict:
     out = {}
     with np.errstate(invalid="ignore", divide="ignore"):                                 # (an empty table: the mean of nothing, NaN)
         def abs_figures(q):
-            cnt = m[:, q, _AT["count"]].sum()
-            mean = m[:, q, _AT["sum_abs"]].sum() / cnt
-            msq = m[:, q, _AT["sum_sq"]].sum() / cnt
-            return float(mean), float(np.sqrt(max(msq - mean * mean, 0.0)))
+            return abs_mean_std(m[:, q, _AT["count"]].sum(), m[:, q, _AT["sum_abs"]].sum(), m[:, q, _AT["sum_sq"]].sum())
         out["i_error_table mean"], out["i_error_table std"] = abs_figures(0)
         for q, name in enumerate(QUANTITIES):
             out[f"Absolute Average of {name}"], out[f"Absolute Standard Deviation of {name}"] = abs_figures(q)

@@ -10,12 +10,11 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..loss import BUS_MOMENTS, bus_errors_histogram
-from .evaluation import GraphedEvalStep, _std4, _step_for
+from ..loss import MOMENT_AT as _AT, bus_errors_histogram
+from .evaluation import GraphedEvalStep, _mean4, _std4, _step_for
 
 FEATURES = ("Voltage Magnitude", "Voltage Angle", "Active Power", "Reactive Power")
 GIVEN_FACTOR = np.float32(0.00001)     # the reference's `masks[masks == 0] = 0.00001` (:258): given entries are scaled, not dropped
-_AT = {k: i for i, k in enumerate(BUS_MOMENTS)}
 
 
 @dataclass
@@ -73,8 +72,7 @@ def bus_error_epoch(model, loader, device, xymean=None, xystd=None, graph: Optio
     (ValueError otherwise)."""
     mask0, types0, n_bus, rows = _uniform_split(getattr(loader, "dataset", None))
     std4 = _std4(xystd)
-    mean4 = None if xymean is None else [float(v) for v in
-                                         torch.as_tensor(xymean, dtype=torch.float32).detach().cpu().reshape(-1, 4)[0].tolist()]
+    mean4 = _mean4(xymean)
     extras = (None if std4 is None else tuple(std4), None if mean4 is None else tuple(mean4), bool(keep_errors),
               bool(keep_predictions), rows, n_bus)
     step = _step_for(graph, model) if graph is not None else GraphedEvalStep(model)
@@ -137,20 +135,22 @@ def _figures(m, factor, pred_rows, rows) -> dict:
         return _figures_of(tot, factor, pred_rows, rows)
 
 
+def abs_mean_std(count, sum_abs, sum_sq):
+    """Mean and population standard deviation of |e| from the summed moments (count, sum |e|, sum e^2) -- of e itself when given its
+    plain sum.  One-pass variance in float64: mean of squares minus squared mean, clamped at 0."""
+    mean = sum_abs / count
+    msq = sum_sq / count
+    return float(mean), float(np.sqrt(max(msq - mean * mean, 0.0)))
+
+
 def _figures_of(tot, factor, pred_rows, rows) -> dict:
     out = {}
     for f, name in enumerate(FEATURES):
         r = pred_rows[f]
-        cnt = tot[r, f, _AT["count"]].sum()
-        mean = (tot[r, f, _AT["sum_abs"]] * factor[r, f]).sum() / cnt
-        msq = (tot[r, f, _AT["sum_sq"]] * factor[r, f] ** 2).sum() / cnt
-        out[f"Absolute Average of {name}"] = float(mean)
-        out[f"Absolute Standard Deviation of {name}"] = float(np.sqrt(max(msq - mean * mean, 0.0)))
-    cnt = tot[rows, :, _AT["count"]].sum()
-    mean = (tot[rows, :, _AT["sum"]] * factor[rows]).sum() / cnt
-    msq = (tot[rows, :, _AT["sum_sq"]] * factor[rows] ** 2).sum() / cnt
-    out["Average of all errors"] = float(mean)
-    out["Standard Deviation of all errors"] = float(np.sqrt(max(msq - mean * mean, 0.0)))
+        out[f"Absolute Average of {name}"], out[f"Absolute Standard Deviation of {name}"] = abs_mean_std(
+            tot[r, f, _AT["count"]].sum(), (tot[r, f, _AT["sum_abs"]] * factor[r, f]).sum(), (tot[r, f, _AT["sum_sq"]] * factor[r, f] ** 2).sum())
+    out["Average of all errors"], out["Standard Deviation of all errors"] = abs_mean_std(
+        tot[rows, :, _AT["count"]].sum(), (tot[rows, :, _AT["sum"]] * factor[rows]).sum(), (tot[rows, :, _AT["sum_sq"]] * factor[rows] ** 2).sum())
     return out
 
 

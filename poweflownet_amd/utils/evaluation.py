@@ -131,6 +131,13 @@ def _std4(xystd):
     return [float(v) for v in (t + 1e-7).tolist()]
 
 
+def _mean4(xymean):
+    """The four means `denormalize` adds, as host floats."""
+    if xymean is None:
+        return None
+    return [float(v) for v in torch.as_tensor(xymean, dtype=torch.float32).detach().cpu().reshape(-1, 4)[0].tolist()]
+
+
 # ------------------------------------------------------------------------------------------------ the step
 class _Child:
     """One captured per-batch body: its input tensors, (indexed modes) their BatchSource, the graph and the adjacencies it reads."""

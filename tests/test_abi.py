@@ -132,10 +132,11 @@ def test_every_environment_switch_of_the_library_is_documented():
 
 def test_every_hand_managed_device_primitive_is_spelled_once():
     """csrc/device_prims.hpp defines the primitives whose correctness is an ISA fact (LDS-only barrier, LDS-DMA, hidden drain,
-    write-through store, vector typedefs) once, with their hazard notes.  No other file of csrc/ spells their instruction text --
-    comments included -- or brings back one of the prefixed copies that were folded into it."""
+    write-through store, vector typedefs, the two last-arriver hand-offs) once, with their hazard notes.  No other file of csrc/
+    spells their instruction text -- comments included -- or brings back one of the prefixed copies that were folded into it; the
+    ordered reductions above the hand-offs exist once, in csrc/reduce.hpp; and ONE file carries the gfx950 target guard."""
     import glob
-    texts = ("global_load_lds", r"lgkmcnt(0)\n\ts_barrier", "sc1", "ext_vector_type", '"s_waitcnt vmcnt(0)" ::: "memory"')
+    texts = ("global_load_lds", r"lgkmcnt(0)\n\ts_barrier", "sc1", "ext_vector_type", '"s_waitcnt vmcnt(0)" ::: "memory"', "__threadfence()")
     gone = ("bh_lds_barrier", "seg_lds_barrier", "seg_dma_1k", "seg_dma_wait", "dma_wait", "sg_st4_wt", "st4f", "ld4f", "sg_ld4",
             "sg_st4", "sg_add4", "sg_fma4", "sg_relu4", "sg_wave_sum4", "slh_sel4", "f4wt_")
     gone_re = re.compile(r"\b(" + "|".join(gone) + r")\b")
@@ -143,18 +144,27 @@ def test_every_hand_managed_device_primitive_is_spelled_once():
     twin_re = re.compile(r"__forceinline__\s+\w+\s+\w+_(ld4|st4|fma4|mul4|add4|sel4|relu4|wave_sum4|st4_wt|lds_barrier|dma_1k)\s*\(")
     once = ("void lds_barrier(", "void dma_1k(", "void vmem_drain(", "void st4_wt(", "float4 wave_sum4(", "float4 ld4(", "void st4(",
             "float4 fma4(", "float4 mul4(", "float4 add4(", "float4 sel4(", "float4 relu4(", "void vload_x4(", "void vstore_x4(",
-            "void vstore_x4_sv(", "void vstore_x4_sv_masked(", "void wait_a(", "#define PFN_OPAQUE(", "#define PFN_XDL_SETTLE(")
+            "void vstore_x4_sv(", "void vstore_x4_sv_masked(", "void wait_a(", "#define PFN_OPAQUE(", "#define PFN_XDL_SETTLE(",
+            "void agent_store(", "T agent_load(", "bool handoff_fenced_publish(", "void handoff_fenced_consume(",
+            "bool handoff_drained_publish(")
+    # ... and the shared text above them, each in the one header that owns it
+    once_in = {"reduce.hpp": ("void block_tree_256(", "bool grid_sum_ordered(", "bool masked_l2_combine(", "struct Moments6 {",
+                              "void moments_round("),
+               "pfn_internal.hpp": ("float denorm(", "constexpr int kLdsCuBytes", "constexpr int kLdsReserve")}
     csrc = os.path.join(ROOT, "poweflownet_amd", "csrc")
     header = open(os.path.join(csrc, "device_prims.hpp")).read()
     for t in texts:
         assert t in header, t
     files = [f for f in glob.glob(os.path.join(csrc, "*")) if f.endswith((".hip", ".hpp", ".cpp"))]
     assert len(files) >= 15
-    seen = dict.fromkeys(once, 0)
+    seen = dict.fromkeys(once + sum(once_in.values(), ()), 0)
+    guarded = []
     for f in files:
         text = open(f).read()
-        for d in once:
+        for d in seen:
             seen[d] += text.count(d)
+        if "relies on gfx950 semantics" in text:
+            guarded.append(os.path.basename(f))
         assert not gone_re.search(text), (f, gone_re.search(text).group(0))
         assert not twin_re.search(text), (f, twin_re.search(text).group(0))
         if os.path.basename(f) == "device_prims.hpp":
@@ -164,6 +174,11 @@ def test_every_hand_managed_device_primitive_is_spelled_once():
     assert all(n == 1 for n in seen.values()), seen
     for d in once:
         assert d in header, d
+    assert guarded == ["device_prims.hpp"], guarded
+    for name, defs in once_in.items():
+        text = open(os.path.join(csrc, name)).read()
+        for d in defs:
+            assert d in text, (name, d)
 
 
 def test_isa_of_the_async_operand_fragments_is_hazard_free():
