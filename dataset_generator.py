@@ -7,12 +7,19 @@ a made-up per-unit base on the synthetic grid of the case's size) and are solved
 reference's `continue` -- and counted.
 
     python dataset_generator.py --case 118 --samples 2000 --root data
+    python dataset_generator.py --case 118 --samples 2000 --root data -r 1 -a 1
 
     <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]
     <root>/raw/case<case>_edge_features.npy   (S, e, 4) float64 [from, to, r, x]
 
-Per-unit, demand-positive, the network model of `PowerImbalance` (no shunts, taps, line charging or Q-limits).  The reference's
-topology perturbation (-r / -a) is not here.  Needs a HIP device: there is no CPU solver in this package."""
+-r / -a, the reference's topology perturbation (utils/data_utils.py:12-59): every sample loses r random lines -- drawn again, up to
+20 times, while a bus is left unsupplied -- and gains a lines between random bus pairs, each with the parameters of a random
+existing line.  The draw is `perturb_topology` (csrc/topology.hip, one workgroup per sample, in front of the solver's launch); a
+sample without a connected draw is dropped and counted.  The files are then named case<case>perturbed<r>r<a>a_*, the reference's
+naming, and hold e - r + a lines per sample: `PowerFlowData(case="118perturbed1r1a")` and train.py --case 118perturbed1r1a load them.
+
+Per-unit, demand-positive, the network model of `PowerImbalance` (no shunts, taps, line charging or Q-limits).  Needs a HIP device:
+there is no CPU solver in this package."""
 import argparse
 import os
 import sys
@@ -23,17 +30,18 @@ GENERATOR_CASES = ("14", "118", "118v2")
 
 
 def write_raw(root, case, bus_type, edge_index, rx, tables):
-    """Write solved tables [S, n, 4] with their line parameters [S, e, 2] in the reference's raw layout; returns the two paths."""
+    """Write solved tables [S, n, 4] with their line parameters [S, e, 2] and lines -- [2, e] for all samples or [S, 2, e] -- in the
+    reference's raw layout; returns the two paths."""
     bus_type, edge_index = np.asarray(bus_type), np.asarray(edge_index)
     rx, tables = np.asarray(rx, dtype=np.float64), np.asarray(tables, dtype=np.float64)
-    S, n, e = tables.shape[0], tables.shape[1], edge_index.shape[1]
-    assert tables.shape == (S, n, 4) and rx.shape == (S, e, 2) and edge_index.shape == (2, e) and bus_type.shape == (n,)
+    S, n, e = tables.shape[0], tables.shape[1], edge_index.shape[-1]
+    assert tables.shape == (S, n, 4) and rx.shape == (S, e, 2) and edge_index.shape in ((2, e), (S, 2, e)) and bus_type.shape == (n,)
     node = np.empty((S, n, 6), dtype=np.float64)
     node[:, :, 0] = np.arange(n)
     node[:, :, 1] = bus_type
     node[:, :, 2:] = tables
     edge = np.empty((S, e, 4), dtype=np.float64)
-    edge[:, :, :2] = edge_index.T
+    edge[:, :, :2] = edge_index.T if edge_index.ndim == 2 else edge_index.transpose(0, 2, 1)
     edge[:, :, 2:] = rx
     os.makedirs(os.path.join(root, "raw"), exist_ok=True)
     paths = (os.path.join(root, "raw", f"case{case}_node_features.npy"), os.path.join(root, "raw", f"case{case}_edge_features.npy"))
@@ -42,31 +50,59 @@ def write_raw(root, case, bus_type, edge_index, rx, tables):
     return paths
 
 
-def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10, device="cuda:0", max_rounds=64):
-    """(bus_type [n], edge_index [2, e], rx [S, e, 2], tables [S, n, 4], redrawn): `samples` converged samples, host arrays."""
+def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10, device="cuda:0", max_rounds=64, remove=0, add=0,
+             counts=None):
+    """(bus_type [n], edge_index, rx [S, e, 2], tables [S, n, 4], redrawn): `samples` converged samples, host arrays.  `edge_index`
+    is the grid's [2, e]; with `remove` or `add` above 0 it is [S, 2, e - remove + add], one perturbed line list per sample, and
+    rx holds the parameters of those lines.  `counts` (a dict, optional) receives "disconnected": the samples dropped because no
+    connected draw was found, and "drawn": all samples drawn."""
     import torch
     from poweflownet_amd.synth import CASES, make_physical_inputs
     from poweflownet_amd.utils.powerflow import solve_power_flow
+    from poweflownet_amd.utils.topology import perturb_topology
     if samples < 1:
         raise ValueError("dataset_generator: --samples must be at least 1")
+    if remove < 0 or add < 0:
+        raise ValueError(f"dataset_generator: cannot remove {remove} and add {add} lines")
     n, e = CASES[str(case)]
-    keep_rx, keep_t, have, redrawn = [], [], 0, 0
+    perturbed = remove > 0 or add > 0
+    keep_ei, keep_rx, keep_t, have, redrawn, drawn, disconnected = [], [], [], 0, 0, 0, 0
     for rnd in range(max_rounds):
         if have >= samples:
             break
         want = min(batch, samples - have)
         ei, bt, rx, spec = make_physical_inputs(n, e, want, seed * 1_000_003 + rnd, load)
-        res = solve_power_flow(bt.to(device), spec.to(device), ei.to(device), rx.to(device), tol=tol, max_iter=max_iter)
-        ok = (res.status >= 0).cpu().numpy()
+        d_ei, d_rx, d_spec = ei.to(device), rx.to(device), spec.to(device)
+        if perturbed:
+            # sample numbers run on over the rounds: no draw repeats.  An added line has the parameters of the line it copies
+            topo = perturb_topology(d_ei, n, num_samples=want, remove=remove, add=add, seed=seed, first_sample=drawn)
+            connected = topo.status >= 1
+            if bool((topo.status == -4).any()):
+                raise RuntimeError("dataset_generator: the base grid names a bus outside the grid")
+            d_ei = topo.edge_index[connected]
+            d_rx = torch.gather(d_rx, 1, topo.source.long().clamp(min=0)[:, :, None].expand(-1, -1, 2))[connected]
+            d_spec = d_spec[connected]
+            disconnected += want - int(d_ei.shape[0])
+        drawn += want
+        if d_spec.shape[0] == 0:
+            continue
+        res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
+        ok = res.status >= 0
         if int(res.flags.item()) != 0:
             raise RuntimeError("dataset_generator: the solver flagged its bus types")
-        keep_rx.append(rx.numpy()[ok])
+        if perturbed:
+            keep_ei.append(d_ei[ok].cpu().numpy())
+        ok = ok.cpu().numpy()
+        keep_rx.append(d_rx.cpu().numpy()[ok])
         keep_t.append(res.table.cpu().numpy()[ok])
         have += int(ok.sum())
         redrawn += int((~ok).sum())
+    if counts is not None:
+        counts.update(disconnected=disconnected, drawn=drawn)
     if have < samples:
         raise RuntimeError(f"dataset_generator: only {have} of {samples} samples converged in {max_rounds} rounds (load {load})")
-    return bt.numpy(), ei.numpy(), np.concatenate(keep_rx)[:samples], np.concatenate(keep_t)[:samples], redrawn
+    lines = np.concatenate(keep_ei)[:samples] if perturbed else ei.numpy()
+    return bt.numpy(), lines, np.concatenate(keep_rx)[:samples], np.concatenate(keep_t)[:samples], redrawn
 
 
 def main(argv=None):
@@ -77,14 +113,23 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch", type=int, default=4096, help="samples per device launch")
     ap.add_argument("--load", type=float, default=0.2, help="mean active demand of a PQ bus, per-unit")
+    ap.add_argument("-r", "--num_lines_to_remove", type=int, default=0, help="lines every sample loses (redrawn while a bus is unsupplied)")
+    ap.add_argument("-a", "--num_lines_to_add", type=int, default=0, help="lines every sample gains, each a copy of a random line")
     a = ap.parse_args(argv)
+    r, add = a.num_lines_to_remove, a.num_lines_to_add
+    if r < 0 or add < 0:
+        ap.error("-r and -a must be at least 0")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("dataset_generator.py needs a HIP device: poweflownet_amd has no CPU solver")
-    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load)
-    paths = write_raw(a.root, a.case, bt, ei, rx, tables)
+    counts = {}
+    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load, remove=r, add=add, counts=counts)
+    name = f"{a.case}perturbed{r}r{add}a" if r > 0 or add > 0 else a.case
+    paths = write_raw(a.root, name, bt, ei, rx, tables)
+    if r > 0 or add > 0:
+        print(f"Left a bus unsupplied in every draw and dropped: {counts['disconnected']}")
     print(f"Failed to converge and drawn again: {redrawn}")
-    print(f"wrote {a.samples} samples of case{a.case} ({tables.shape[1]} buses, {ei.shape[1]} lines): {paths[0]}, {paths[1]}")
+    print(f"wrote {a.samples} samples of case{name} ({tables.shape[1]} buses, {ei.shape[-1]} lines): {paths[0]}, {paths[1]}")
     return 0
 
 

@@ -544,6 +544,43 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
                         int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* --------------------------------------------------------------------------- topology perturbation
+ * The reference's perturb_topology (utils/data_utils.py:12-59, behind dataset_generator.py -r / -a) drawn per sample on the device:
+ * remove n_remove random lines, start over while a bus is left unsupplied, then add n_add lines between random bus pairs, each a copy
+ * of a random existing line.  ONE launch, one workgroup per sample, the sample's state in LDS; no host sync, no allocation
+ * (capturable), no atomic on global memory, no floating point.  What the solver's [n_samples, 2, e] line lists are made of.
+ * THE DRAWING RULE (tests/topology_ref.py transcribes it in numpy and is held to it bit for bit).  Random words are Philox4x32-10
+ * with key {seed[31:0], seed[63:32]} and counter {item, attempt, sample, stream}, sample = first_sample + s the GLOBAL sample
+ * number: a sample's draw depends on (seed, sample) only, never on its batch.
+ *   removal      stream 0; for attempt = 0 .. max_attempts - 1: base line j gets the key word 0 of philox({j, attempt, sample, 0});
+ *                the n_remove lines with the smallest (key, j), compared lexicographically, are removed (a uniform subset, ties to
+ *                the lower index); the draw is accepted when every bus is reachable from `root` over the kept lines -- the
+ *                reference's unsupplied_buses == 0, checked before any line is added, as there.  The first accepted attempt ends it.
+ *   addition     stream 1, attempt word 0; for k < n_add, w = philox({k, 0, sample, 1}): from = w0 mod n_bus,
+ *                to = (from + 1 + w1 mod (n_bus - 1)) mod n_bus (never from; a duplicate of an existing line is allowed, as in the
+ *                reference), source line = w2 mod n_lines.  The modulo bias is at most n / 2^32 (n = n_bus, n_lines).
+ *   edge_index   DEVICE int64 [2, n_lines], the base list (local bus ids).
+ *   edge_index_out  int64 [n_samples, 2, e_out], e_out = n_lines - n_remove + n_add for every sample: the kept base lines in base
+ *                order (a stable compaction), then the added lines in draw order.
+ *   source       int32 [n_samples, e_out]: the base line that output line j is, or whose parameters it copies.
+ *   status       int32 [n_samples]: >= 1 the attempts used; -1 no connected draw in max_attempts (the reference gives up there);
+ *                -4 a base line names a bus outside [0, n_bus) -- checked before any id is followed, hence for every sample; the
+ *                solver's code.  Where status < 0 that sample's edge_index_out and source rows are all -1.
+ * PFN_EINVAL, nothing launched: n_remove < 0, n_add < 0, n_remove > n_lines; n_lines - n_remove < n_bus - 1 (no such draw is
+ * connected); n_add > 0 with n_bus < 2; root outside [0, n_bus); max_attempts outside [1, 1024]; first_sample < 0 or
+ * first_sample + n_samples > 2^32; a shape whose state (8 n_lines + 4 n_remove + n_lines + n_bus bytes with 16-bit ids, up to
+ * n_bus = 65536; 12 n_lines + ... beyond) exceeds the 159 KiB of LDS a workgroup may take -- 6470rte's (6470, 9005) needs 88 KB.
+ *
+ * pfn_topology_unsupplied: count[s] = the number of buses NOT reachable from `root` over the lines of sample s -- [2, n_lines]
+ * for all samples (lines_per_sample == 0) or [n_samples, 2, n_lines] -- or -4 where a line of that sample names a bus outside
+ * [0, n_bus).  The same reach routine: the check a stored dataset can be held to.  PFN_EINVAL: root outside [0, n_bus), a shape
+ * beyond the LDS budget (4 n_lines + n_bus bytes with 16-bit ids).                                                              */
+int pfn_topology_perturb(const int64_t* edge_index, int64_t n_lines, int64_t n_bus, int64_t n_samples, int64_t first_sample,
+                         int64_t n_remove, int64_t n_add, uint64_t seed, int64_t root, int max_attempts, int64_t* edge_index_out,
+                         int32_t* source, int32_t* status, void* stream);
+int pfn_topology_unsupplied(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, int64_t n_samples, int64_t n_bus,
+                            int64_t root, int32_t* count, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it
