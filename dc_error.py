@@ -15,14 +15,11 @@ import sys
 import numpy as np
 
 
-def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, device="cuda:0", split=(.5, .2, .3)):
-    """Per-sample losses (host float64 array) of the DC solve against the test split of `root`'s case; failed solves raise."""
-    import torch
+def load_test_split(root, case, samples=None, split=(.5, .2, .3)):
+    """(the normalised test split, its raw node rows [S, n, 6], its raw edge rows [S, e, 4]) of `root`'s case, the raw rows cut to the
+    first `samples`: every sample's own solver inputs, as the files hold them (speedup_evaluator.py reads them the same way)."""
     from poweflownet_amd.datasets import PowerFlowData
-    from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
-    from poweflownet_amd.utils.powerflow import solve_power_flow
     testset = PowerFlowData(root=root, case=case, split=list(split), task="test")
-    mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     pair = testset._raw_pairs()[0]
     edge, node = np.load(pair[0]), np.load(pair[1])
     lens = [int(len(node) * f) for f in split]
@@ -32,6 +29,26 @@ def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, devic
         node, edge = node[:samples], edge[:samples]
     if (node[:, :, 1] != node[:1, :, 1]).any():
         raise RuntimeError("dc_error: the bus types differ between the samples")
+    return testset, node, edge
+
+
+def solver_inputs(node, edge, device, rows=slice(None)):
+    """(spec = the truth table [S, n, 4] float64, edge_index [S, 2, e] int64, rx [S, e, 2] float64) of raw rows, on `device`."""
+    import torch
+    truth = torch.from_numpy(node[rows, :, 2:].astype(np.float64)).to(device)
+    ei = torch.from_numpy(edge[rows, :, :2].astype(np.int64).transpose(0, 2, 1).copy()).to(device)
+    rx = torch.from_numpy(edge[rows, :, 2:].astype(np.float64).copy()).to(device)
+    return truth, ei, rx
+
+
+def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, device="cuda:0", split=(.5, .2, .3)):
+    """Per-sample losses (host float64 array) of the DC solve against the test split of `root`'s case; failed solves raise."""
+    import torch
+    from poweflownet_amd.datasets import PowerFlowData
+    from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    testset, node, edge = load_test_split(root, case, samples, split)
+    mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     mask = torch.tensor(PowerFlowData.bus_type_mask)[bus_type.cpu()].clone()
     mask[:, 0] = 0
@@ -40,9 +57,7 @@ def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, devic
     loss_fn = Masked_L2_loss(regularize=False)
     out = []
     for s0 in range(0, len(node), batch):
-        truth = torch.from_numpy(node[s0:s0 + batch, :, 2:].astype(np.float64)).to(device)
-        ei = torch.from_numpy(edge[s0:s0 + batch, :, :2].astype(np.int64).transpose(0, 2, 1).copy()).to(device)
-        rx = torch.from_numpy(edge[s0:s0 + batch, :, 2:].astype(np.float64).copy()).to(device)
+        truth, ei, rx = solver_inputs(node, edge, device, slice(s0, s0 + batch))
         res = solve_power_flow(bus_type, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter)
         if int((res.status < 0).sum()) or int(res.flags.item()):
             raise RuntimeError(f"dc_error: {int((res.status < 0).sum())} DC solves failed (statuses {sorted(set(res.status.tolist()))})")

@@ -535,10 +535,37 @@ int pfn_branch_flows(const float* pred, int pred_normalised, const float* truth,
  *                a sparse factorisation is needed.  pfn_powerflow_workspace_bytes(n_samples, n_bus, n_lines, n_pq, route) is what the
  *                route needs in mode 0 (for mode 1 pass n_pq = 0: its m is n_bus - 1) -- 0 exactly when it is the LDS route, which is
  *                how a caller learns what route 0 takes; too little is PFN_ENOSPACE.
+ * pfn_powerflow_solve_init: everything above, plus a warm start and the fast-decoupled modes; pfn_powerflow_solve is this call with
+ * init = NULL and accepts modes 0 and 1 only, its results unchanged bit for bit.
+ *   init         DEVICE f64 [n_samples, n_bus, 2] = (Vm, Va in degrees), 8-byte aligned, or NULL for the flat start.  Read: Va at the
+ *                non-slack buses and Vm at the PQ buses (mode 1: Va only -- its Vm is no unknown); the slack's Vm / Va and a PV bus's
+ *                Vm always come from `spec`, whatever `init` holds there.  A non-finite entry that is read gives that sample status
+ *                -3, NaN rows and a NaN residual, and touches no other sample.  A start whose max |F| < tol returns status 0 (nothing
+ *                is solved) with the table finished from it.
+ *   mode 2 (fdxb), mode 3 (fdbx)  the fast-decoupled iterations.  State, mismatch and convergence test are mode 0's fp64 code.  B'
+ *                (order n_bus - 1, the angle buses) and B'' (order n_pq, the PQ buses) are Laplacians over the stored lines, parallel
+ *                lines adding: XB takes B' from 1 / x and B'' from -b = x / (r^2 + x^2), BX swaps the two.  Both are built ONCE per
+ *                sample in fp32, inverted in place once (Gauss-Jordan without pivoting: symmetric and diagonally dominant for x > 0)
+ *                and stay resident together; a half-iteration is a mat-vec with the explicit inverse, fp64 sums:
+ *                theta -= B'^-1 (dP / Vm) over the angle buses, then Vm -= B''^-1 (dQ / Vm) over the PQ buses, alternating, the P
+ *                half first (the sign is that of the demand-positive mismatch).  The mismatch is re-formed and tested after every
+ *                half-iteration; max_iter and a status >= 0 count HALF-iterations.  n_pq == 0: only the P half runs.  Statuses -1
+ *                ... -5 as above; -2: a pivot of either matrix.  n_bus - 1 <= pfn_powerflow_max_unknowns().
+ *   route        modes 2, 3: LDS when the vectors (40 n + 16 m bytes, m = n_bus - 1 + n_pq: F / Vm sits behind F) plus BOTH
+ *                matrices, each with its odd leading dimension, fit the same 160 KiB - 1 KiB; otherwise per-sample slabs of `ws`
+ *                holding the two.  256 or 1024 threads by the rule of modes 0 / 1 applied to the larger of the two orders.
+ *                pfn_powerflow_workspace_bytes_mode(n_samples, n_bus, n_lines, n_pq, mode, route) is pfn_powerflow_workspace_bytes
+ *                with the mode it is asked about (n_pq = the real count in every mode; modes 0 and 1 answer as the function above
+ *                does): 0 exactly on the LDS route.
  * One owner per matrix row, sequential sums in stored line order, only max-reductions across threads, no float atomics: a
  * sample's result is a pure function of its own inputs, bit for bit, whatever the batch around it.                          */
 int64_t pfn_powerflow_max_unknowns(void);
 size_t pfn_powerflow_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq, int route);
+size_t pfn_powerflow_workspace_bytes_mode(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq, int mode, int route);
+int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                             const double* spec, const double* init, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode,
+                             double tol, int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags,
+                             void* ws, size_t ws_bytes, void* stream);
 int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
                         const double* spec, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode, double tol,
                         int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,

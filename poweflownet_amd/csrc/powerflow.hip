@@ -18,6 +18,14 @@
 // multiplier a broadcast), the pivot search and the back substitution walk columns (stride ld: odd, so coprime to the 32 banks a
 // dword access of a 32-lane half is spread over: no conflict).  LDS route: the matrix sits behind the sample's vectors in LDS;
 // global route: in a per-sample slab of the caller's workspace, same code.
+//
+// pfn_powerflow_solve_init adds a warm start (the state begins at the caller's Vm / Va instead of the flat start) and the two
+// fast-decoupled iterations, modes 2 (XB) and 3 (BX): the same fp64 state, mismatch and convergence test, but the update comes from
+// two CONSTANT matrices -- B' over the angle buses, B'' over the PQ buses, both Laplacians of the stored lines -- that are built once
+// per sample in fp32, inverted in place once (Gauss-Jordan, no pivoting: they are symmetric and diagonally dominant for x > 0, and the
+// elimination keeps that) and stay resident together; a half-iteration is then a mat-vec, theta -= B'^-1 (dP / Vm) or
+// Vm -= B''^-1 (dQ / Vm), one owner per row, with no sequential chain and one barrier.  The FD template instantiation carries that
+// code; the Newton / DC instantiation does not pay registers for it.
 #include <algorithm>
 
 #include "pfn_internal.hpp"
@@ -36,6 +44,7 @@ __host__ __device__ inline int pf_ld(int m) { return m | 1; }
 // the sample's vectors: double vm, th, sp, sq [n], F [m]; int aidx, vidx [n]; rounded to 16 bytes
 __host__ __device__ inline size_t pf_vec_bytes(int n, int m) { return ((size_t)8 * (4 * (size_t)n + m) + (size_t)8 * n + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t pf_mat_floats(int m) { return ((size_t)m * pf_ld(m) + 3) & ~(size_t)3; }
+__host__ __device__ inline size_t pf_fd_extra_bytes(int m) { return ((size_t)8 * m + 15) & ~(size_t)15; }      // modes 2, 3: F / Vm [m]
 
 struct PfArgs {
     const int64_t* edge_index;
@@ -47,6 +56,7 @@ struct PfArgs {
     double* residual;
     int32_t* flags;
     float* slab;
+    const double* init;                             // [S, n, 2] = (Vm, Va in degrees) or null: the flat start
     double tol;
     int n, e, m, n_pv, n_pq, mode, max_iter, lines_per_sample;
 };
@@ -64,7 +74,31 @@ __device__ __forceinline__ double pf_block_max(double v, double* red) {
     return r;
 }
 
-template <bool LDS>
+// B (mm x mm, leading dimension ld) becomes its inverse, in place: Gauss-Jordan without pivoting, two barriers per column.  Every
+// thread calls it; false (uniform: all threads read the same pivot) when a pivot is tiny or NaN.
+__device__ __forceinline__ bool pf_invert_in_place(float* B, int mm, int ld) {
+    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
+    for (int k = 0; k < mm; ++k) {
+        const float p = B[k * ld + k];              // (written last before the barrier that ended step k - 1)
+        if (!(fabsf(p) > PF_TINY_PIVOT)) return false;
+        const float pinv = 1.f / p;
+        for (int j = t; j < mm; j += nt)
+            if (j != k) B[k * ld + j] *= pinv;
+        __syncthreads();
+        for (int i = wave; i < mm; i += nw) {
+            if (i == k) continue;
+            const float f = B[i * ld + k];
+            for (int j = lane; j < mm; j += 64)
+                if (j != k) B[i * ld + j] = fmaf(-f, B[k * ld + j], B[i * ld + j]);
+            if (lane == 0) B[i * ld + k] = -f * pinv;
+        }
+        if (t == 0) B[k * ld + k] = pinv;
+        __syncthreads();
+    }
+    return true;
+}
+
+template <bool LDS, bool FD>
 __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
     __shared__ double s_red[16];
@@ -73,7 +107,8 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
     const int s = blockIdx.x;
     const int n = a.n, e = a.e, m = a.m, ld = pf_ld(m);
-    const bool dc = a.mode == 1;
+    const bool dc = !FD && a.mode == 1;
+    const int mp = n - 1, mq = a.n_pq, ldp = pf_ld(mp), ldq = pf_ld(mq);      // FD: B' [mp x mp], B'' [mq x mq] behind it
     double* vm = reinterpret_cast<double*>(pf_smem);
     double* th = vm + n;
     double* sp = th + n;
@@ -81,9 +116,12 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     double* F = sq + n;
     int* aidx = reinterpret_cast<int*>(F + m);
     int* vidx = aidx + n;
+    double* G = reinterpret_cast<double*>(pf_smem + pf_vec_bytes(n, m));      // FD only: F / Vm [m]
     float* A;
-    if constexpr (LDS) A = reinterpret_cast<float*>(pf_smem + pf_vec_bytes(n, m));
-    else A = a.slab + (size_t)s * pf_mat_floats(m);
+    if constexpr (LDS) A = reinterpret_cast<float*>(pf_smem + pf_vec_bytes(n, m) + (FD ? pf_fd_extra_bytes(m) : 0));
+    else A = a.slab + (size_t)s * (FD ? pf_mat_floats(mp) + pf_mat_floats(mq) : pf_mat_floats(m));
+    float* Bq = A + pf_mat_floats(mp);
+    const double* init = a.init ? a.init + (int64_t)s * 2 * n : nullptr;
     const int64_t* ei = a.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
     const double* rx = a.rx + (int64_t)s * 2 * e;
     const double* spec = a.spec + (int64_t)s * 4 * n;
@@ -121,16 +159,29 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
 
     int it = 0;
     if (code == 0) {
-        // ---- flat start
+        // ---- flat start, or the caller's: Va at the non-slack buses, Vm at the PQ buses (mode 1: Va only -- its Vm is no unknown)
         const double th0 = spec[4 * s_slack + 1] * PF_RAD;
+        int wild = 0;
         for (int i = t; i < n; i += nt) {
-            vm[i] = a.bus_type[i] == 2 ? 1.0 : spec[4 * i];
-            th[i] = th0;
+            const int ty = a.bus_type[i];
+            double v = ty == 2 ? 1.0 : spec[4 * i], ang = th0;
+            if (init) {
+                if (ty == 2 && !dc) v = init[2 * i];
+                if (ty != 0) ang = init[2 * i + 1] * PF_RAD;
+                wild |= !(fabs(v) < __builtin_inf()) || !(fabs(ang) < __builtin_inf());
+            }
+            vm[i] = v;
+            th[i] = ang;
         }
-        __syncthreads();
+        if (__syncthreads_or(wild)) code = PF_NON_FINITE;
+    }
+    if (code == 0) {
+        int half = 0;                               // FD: 0 the P half comes next, 1 the Q half
         for (;; ++it) {
-            for (int k = t; k < m * ld; k += nt) A[k] = 0.f;
-            __syncthreads();
+            if constexpr (!FD) {
+                for (int k = t; k < m * ld; k += nt) A[k] = 0.f;
+                __syncthreads();
+            }
             // ---- line sums, mismatch and matrix rows of bus i, its lines in stored order
             for (int i = t; i < n; i += nt) {
                 const int ra = aidx[i], rv = vidx[i];
@@ -159,6 +210,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
                         const double t1 = vv * cs - vi * vi, t2 = vv * sn;
                         sP += g * t1 + b * t2;
                         sQ += g * t2 - b * t1;
+                        if constexpr (FD) continue;
                         const double pti = vv * (b * cs - g * sn), qti = vv * (g * cs + b * sn);
                         dPt += pti;
                         dPv += g * (vj * cs - 2.0 * vi) + b * vj * sn;
@@ -176,6 +228,17 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
                 }
                 sp[i] = sP;
                 sq[i] = sQ;
+                if constexpr (FD) {
+                    if (ra >= 0) {
+                        F[ra] = spec[4 * i + 2] - sP;
+                        G[ra] = F[ra] / vi;
+                    }
+                    if (rv >= 0) {
+                        F[rv] = spec[4 * i + 3] - sQ;
+                        G[rv] = F[rv] / vi;
+                    }
+                    continue;
+                }
                 if (ra >= 0) {
                     F[ra] = spec[4 * i + 2] - sP;
                     A[ra * ld + ra] += (float)dPt;
@@ -198,6 +261,55 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
             if (!(res < __builtin_inf())) { code = PF_NON_FINITE; break; }
             if (res < a.tol) break;
             if (it >= a.max_iter) { code = PF_NOT_CONVERGED; break; }
+            if constexpr (FD) {
+                if (it == 0) {
+                    // ---- B' and B'', once: Laplacians of the stored lines (parallel lines add, a self-loop cancels), bus i's rows
+                    //      by bus i in stored order, the diagonal summed in fp64 and added last; then inverted in place
+                    const bool xb = a.mode == 2;
+                    for (int k = t; k < (int)(pf_mat_floats(mp) + pf_mat_floats(mq)); k += nt) A[k] = 0.f;
+                    __syncthreads();
+                    for (int i = t; i < n; i += nt) {
+                        const int ra = aidx[i], rv = vidx[i];
+                        double dp = 0.0, dq = 0.0;
+                        for (int k = 0; k < e; ++k) {
+                            const int la = (int)ei[k], lb = (int)ei[e + k];
+                            if (la != i && lb != i) continue;
+                            const double r = rx[2 * k], x = rx[2 * k + 1];
+                            const double w1 = 1.0 / x, w2 = x / (r * r + x * x);
+                            const double wp = xb ? w1 : w2, wq = xb ? w2 : w1;
+#pragma unroll 1
+                            for (int side = 0; side < 2; ++side) {
+                                if ((side ? lb : la) != i) continue;
+                                const int j = side ? la : lb;
+                                const int ca = aidx[j], cv = vidx[j];
+                                dp += wp;
+                                dq += wq;
+                                if (ra >= 0 && ca >= 0) A[ra * ldp + ca] += (float)(-wp);
+                                if (rv >= 0 && cv >= 0) Bq[(rv - mp) * ldq + (cv - mp)] += (float)(-wq);
+                            }
+                        }
+                        if (ra >= 0) A[ra * ldp + ra] += (float)dp;
+                        if (rv >= 0) Bq[(rv - mp) * ldq + (rv - mp)] += (float)dq;
+                    }
+                    __syncthreads();
+                    if (!pf_invert_in_place(A, mp, ldp) || !pf_invert_in_place(Bq, mq, ldq)) { code = PF_SINGULAR; break; }
+                }
+                // ---- one half-iteration: a mat-vec with the resident inverse, row by its owner, fp64 sum in column order
+                for (int i = t; i < n; i += nt) {
+                    const int r = half ? vidx[i] - mp : aidx[i];
+                    if (r < 0) continue;
+                    const float* row = half ? Bq + r * ldq : A + r * ldp;
+                    const double* g = half ? G + mp : G;
+                    const int cols = half ? mq : mp;
+                    double acc = 0.0;
+                    for (int c = 0; c < cols; ++c) acc += (double)row[c] * g[c];
+                    if (half) vm[i] -= acc;
+                    else th[i] -= acc;
+                }
+                __syncthreads();
+                half = mq ? !half : 0;
+                continue;
+            }
             // ---- LU with partial pivoting, the right-hand side F eliminated along (fp64); L is not kept
             for (int k = 0; k < m; ++k) {
                 if (wave == 0) {
@@ -275,6 +387,13 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
 
 static int pf_unknowns(int64_t n, int64_t n_pq, int mode) { return (int)((n - 1) + (mode == 1 ? 0 : n_pq)); }
 static bool pf_fits_lds(int n, int m) { return pf_vec_bytes(n, m) + pf_mat_floats(m) * 4 <= (size_t)(kLdsCuBytes - kLdsReserve); }
+// modes 2, 3: the vectors (with F / Vm behind them) and BOTH matrices, resident together
+static size_t pf_fd_mat_floats(int n, int n_pq) { return pf_mat_floats(n - 1) + pf_mat_floats(n_pq); }
+static size_t pf_fd_lds_bytes(int n, int n_pq) {
+    const int m = (n - 1) + n_pq;
+    return pf_vec_bytes(n, m) + pf_fd_extra_bytes(m) + pf_fd_mat_floats(n, n_pq) * 4;
+}
+static bool pf_fd_fits_lds(int n, int n_pq) { return pf_fd_lds_bytes(n, n_pq) <= (size_t)(kLdsCuBytes - kLdsReserve); }
 
 }  // namespace pfn
 
@@ -292,36 +411,46 @@ size_t pfn_powerflow_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n
     return (size_t)n_samples * pf_mat_floats(m) * sizeof(float);
 }
 
-int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
-                        const double* spec, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode, double tol,
-                        int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
-                        size_t ws_bytes, void* stream) {
+size_t pfn_powerflow_workspace_bytes_mode(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq, int mode, int route) {
+    if (mode == 0) return pfn_powerflow_workspace_bytes(n_samples, n_bus, n_lines, n_pq, route);
+    if (mode < 0 || mode > 3 || n_samples <= 0 || n_bus <= 0 || n_pq < 0 || n_pq >= n_bus || n_bus > PF_MAX_UNKNOWNS + 1) return 0;
+    if (mode == 1) return pfn_powerflow_workspace_bytes(n_samples, n_bus, n_lines, 0, route);       // its m is n_bus - 1
+    if (route == 1 || (route != 2 && pf_fd_fits_lds((int)n_bus, (int)n_pq))) return 0;
+    return (size_t)n_samples * pf_fd_mat_floats((int)n_bus, (int)n_pq) * sizeof(float);
+}
+
+int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                             const double* spec, const double* init, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode,
+                             double tol, int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags,
+                             void* ws, size_t ws_bytes, void* stream) {
     PFN_CHECK_ARG(n_samples >= 0 && n_bus >= 1 && n_lines >= 0 && n_samples < (1ll << 29) && n_lines < (1ll << 24) && n_bus < (1ll << 24),
                   "pfn_powerflow_solve: bad sizes (%lld samples of %lld buses and %lld lines)", (long long)n_samples, (long long)n_bus,
                   (long long)n_lines);
     PFN_CHECK_ARG(n_pv >= 0 && n_pq >= 0 && n_pv + n_pq == n_bus - 1,
                   "pfn_powerflow_solve: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses", (long long)n_pv,
                   (long long)n_pq, (long long)n_bus);
-    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve: mode must be 0 (AC) or 1 (DC)");
+    PFN_CHECK_ARG(mode >= 0 && mode <= 3, "pfn_powerflow_solve: mode must be 0 (AC), 1 (DC), 2 (fast-decoupled XB) or 3 (fast-decoupled BX)");
     PFN_CHECK_ARG(route >= 0 && route <= 2, "pfn_powerflow_solve: route must be 0 (auto), 1 (LDS) or 2 (global)");
     PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "pfn_powerflow_solve: max_iter must be >= 0 and tol > 0");
-    const int64_t m64 = (n_bus - 1) + (mode == 1 ? 0 : n_pq);
-    PFN_CHECK_ARG(m64 <= PF_MAX_UNKNOWNS,
+    const bool fd = mode >= 2;
+    const int64_t m64 = (n_bus - 1) + (mode == 1 ? 0 : n_pq);      // equations; modes 2, 3 hold no matrix of that order: their larger one is n_bus - 1
+    PFN_CHECK_ARG((fd ? n_bus - 1 : m64) <= PF_MAX_UNKNOWNS,
                   "pfn_powerflow_solve: %lld unknowns per sample exceed the dense solver's %d; a sparse factorisation is needed",
-                  (long long)m64, PF_MAX_UNKNOWNS);
+                  (long long)(fd ? n_bus - 1 : m64), PF_MAX_UNKNOWNS);
     if (n_samples == 0) return PFN_OK;
     PFN_CHECK_ARG(rx || n_lines == 0, "pfn_powerflow_solve: null rx");
     PFN_CHECK_ARG(edge_index || n_lines == 0, "pfn_powerflow_solve: null edge_index");
     PFN_CHECK_ARG(bus_type && spec && table && status && residual && flags, "pfn_powerflow_solve: null pointer");
     PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(table) & 31) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
                       ((reinterpret_cast<uintptr_t>(spec) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(edge_index) |
-                        reinterpret_cast<uintptr_t>(residual)) & 7) == 0 &&
+                        reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(init)) & 7) == 0 &&
                       ((reinterpret_cast<uintptr_t>(bus_type) | reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(flags)) & 3) == 0,
                   "pfn_powerflow_solve: table must be 32-byte aligned, the workspace 16-byte, fp64 and int64 inputs 8-byte, int32 arrays 4-byte");
     const int n = (int)n_bus, m = (int)m64;
-    const bool fits = pf_fits_lds(n, m);
+    const size_t lds_need = fd ? pf_fd_lds_bytes(n, (int)n_pq) : pf_vec_bytes(n, m) + pf_mat_floats(m) * 4;
+    const bool fits = fd ? pf_fd_fits_lds(n, (int)n_pq) : pf_fits_lds(n, m);
     PFN_CHECK_ARG(route != 1 || fits, "pfn_powerflow_solve: route 1 (LDS): %d unknowns of %d buses need %zu bytes of LDS, %d are there", m, n,
-                  pf_vec_bytes(n, m) + pf_mat_floats(m) * 4, kLdsCuBytes - kLdsReserve);
+                  lds_need, kLdsCuBytes - kLdsReserve);
     const bool lds = route == 1 || (route == 0 && fits);
     PfArgs a;
     a.edge_index = edge_index;
@@ -333,6 +462,7 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
     a.residual = residual;
     a.flags = flags;
     a.slab = nullptr;
+    a.init = init;
     a.tol = tol;
     a.n = n;
     a.e = (int)n_lines;
@@ -342,8 +472,9 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
     a.mode = mode;
     a.max_iter = max_iter;
     a.lines_per_sample = lines_per_sample != 0;
+    const size_t mat_floats = fd ? pf_fd_mat_floats(n, (int)n_pq) : pf_mat_floats(m);
     if (!lds) {
-        const size_t need = (size_t)n_samples * pf_mat_floats(m) * sizeof(float);
+        const size_t need = (size_t)n_samples * mat_floats * sizeof(float);
         if (need && (!ws || ws_bytes < need)) {
             set_error("pfn_powerflow_solve: the global route needs a workspace of %zu bytes (got %zu)", need, ws ? ws_bytes : (size_t)0);
             return PFN_ENOSPACE;
@@ -351,21 +482,37 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
         a.slab = static_cast<float*>(ws);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int threads = m > PF_BIG_M ? PF_BIG_THREADS : PF_SMALL_THREADS;
-    const size_t bytes = pf_vec_bytes(n, m) + (lds ? pf_mat_floats(m) * 4 : 0);
-    const double iters = 5.0, mm = (double)m;
-    ProfScope ps(mode == 1 ? "powerflow_dc" : "powerflow_ac",
-                 (double)n_samples * ((double)n_lines * (16.0 + (lines_per_sample ? 16.0 : 0.0)) + (double)n * 64.0),
-                 (double)n_samples * iters * (2.0 / 3.0 * mm * mm * mm + 2.0 * mm * mm), s);
-    if (lds) {
-        static std::atomic<uint64_t> raised{0};
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-        powerflow_kernel<true><<<(int)n_samples, threads, bytes, s>>>(a);
+    const int big = fd ? std::max(n - 1, (int)n_pq) : m;            // the rule of the one matrix, applied to the larger of the two
+    const int threads = big > PF_BIG_M ? PF_BIG_THREADS : PF_SMALL_THREADS;
+    const size_t bytes = pf_vec_bytes(n, m) + (fd ? pf_fd_extra_bytes(m) : 0) + (lds ? mat_floats * 4 : 0);
+    const double iters = 5.0, mm = (double)m, mp = (double)(n - 1), mq = (double)n_pq;
+    static const char* const names[4] = {"powerflow_ac", "powerflow_dc", "powerflow_fdxb", "powerflow_fdbx"};
+    ProfScope ps(names[mode], (double)n_samples * ((double)n_lines * (16.0 + (lines_per_sample ? 16.0 : 0.0)) + (double)n * 64.0 + (init ? (double)n * 16.0 : 0.0)),
+                 fd ? (double)n_samples * (2.0 * (mp * mp * mp + mq * mq * mq) + 20.0 * (mp * mp + mq * mq))
+                    : (double)n_samples * iters * (2.0 / 3.0 * mm * mm * mm + 2.0 * mm * mm), s);
+    static std::atomic<uint64_t> raised{0}, raised_fd{0};
+    if (lds && !fd) {
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true, false>), kLdsCuBytes - kLdsReserve, raised));
+        powerflow_kernel<true, false><<<(int)n_samples, threads, bytes, s>>>(a);
+    } else if (lds) {
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(powerflow_kernel<true, true>), kLdsCuBytes - kLdsReserve, raised_fd));
+        powerflow_kernel<true, true><<<(int)n_samples, threads, bytes, s>>>(a);
+    } else if (!fd) {
+        powerflow_kernel<false, false><<<(int)n_samples, threads, bytes, s>>>(a);
     } else {
-        powerflow_kernel<false><<<(int)n_samples, threads, bytes, s>>>(a);
+        powerflow_kernel<false, true><<<(int)n_samples, threads, bytes, s>>>(a);
     }
     PFN_CHECK_LAUNCH();
     return PFN_OK;
+}
+
+int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                        const double* spec, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, int mode, double tol,
+                        int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
+                        size_t ws_bytes, void* stream) {
+    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve: mode must be 0 (AC) or 1 (DC)");
+    return pfn_powerflow_solve_init(edge_index, lines_per_sample, n_lines, rx, bus_type, spec, nullptr, n_samples, n_bus, n_pv, n_pq, mode,
+                                    tol, max_iter, route, table, status, residual, flags, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

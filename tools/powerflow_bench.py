@@ -3,6 +3,9 @@
 at case14 and case118 x 4096 samples, AC and DC, on the LDS route and with the global route forced; beside it the float64 numpy
 yardstick of tests/powerflow_ref.py per sample on this host's CPU -- a dense np.linalg.solve Newton loop written for the tests,
 labelled as what it is: not pandapower, not a tuned CPU solver.  Not part of bench.py; no threshold (there is no predecessor).
+After those rows: the fast-decoupled modes (`fdxb`, `fdbx`; max_iter 60 half-iterations, LDS route and global route forced) and
+warm starts (`*_warm`: Newton and both fast-decoupled modes started from Newton's solution plus N(0, 1e-3) noise in Vm and radians,
+the start a good prediction would give).
 
     python tools/powerflow_bench.py [--samples 4096] [--repeats 5] [--cpu-samples 16]
 
@@ -54,6 +57,27 @@ def main():
                 out[f"{mode}_{last.route}"] = {"ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3),
                                                "samples_per_s": round(a.samples / (ms * 1e-3)), "failed": int((status < 0).sum()),
                                                "mean_iterations": round(float(status[status >= 0].mean()), 3)}
+        # the fast-decoupled modes, and warm starts from the solution plus noise
+        solved = solve_power_flow(*d, mode="ac").table
+        near = solved[:, :, :2] + torch.randn(a.samples, n, 2, dtype=torch.float64, device=dev,
+                                              generator=torch.Generator(device=dev).manual_seed(0)) * torch.tensor([1e-3, 1e-3 * 180.0 / np.pi], dtype=torch.float64, device=dev)
+        for name, mode, route, init in (("fdxb", "fdxb", "auto", None), ("fdxb", "fdxb", "global", None), ("fdbx", "fdbx", "auto", None),
+                                        ("fdbx", "fdbx", "global", None), ("ac_warm", "ac", "auto", near), ("fdxb_warm", "fdxb", "auto", near),
+                                        ("fdbx_warm", "fdbx", "auto", near)):
+            per, last = [], None
+            for rep in range(a.repeats + 1):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                last = solve_power_flow(*d, mode=mode, route=route, init=init, max_iter=10 if mode == "ac" else 60)
+                torch.cuda.synchronize()
+                if rep:
+                    per.append(time.perf_counter() - t0)
+            status = last.status.cpu().numpy()
+            ms = 1e3 * float(np.median(per))
+            out[f"{name}_{last.route}"] = {"ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3),
+                                           "samples_per_s": round(a.samples / (ms * 1e-3)), "failed": int((status < 0).sum()),
+                                           "mean_iterations": round(float(status[status >= 0].mean()), 3),
+                                           "max_iterations": int(status.max())}
         # the numpy yardstick, one sample at a time on the CPU
         k = min(a.cpu_samples, a.samples)
         ein, btn, rxn, specn = ei.numpy(), bt.numpy(), rx.numpy(), spec.numpy()
