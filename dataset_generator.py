@@ -4,10 +4,14 @@ written as the raw files `PowerFlowData` (and train.py --data-dir) load unchange
 calls pp.runpp per sample; here the problems come from `synth.make_physical_inputs` (the same +-20 % / 10 % perturbation style around
 a made-up per-unit base on the synthetic grid of the case's size) and are solved in device batches by `solve_power_flow`
 (csrc/powerflow.hip: Newton-Raphson, one workgroup per sample).  A sample whose status is negative is drawn again -- the
-reference's `continue` -- and counted.
+reference's `continue` -- and counted.  A case with more unknowns than the dense solver takes (6470rte: 10782) goes through the
+sparse route (csrc/powerflow_sparse.hip): its plan is built once and serves every device batch and redraw; --route sparse forces
+that route at any size.  With -r / -a every sample has its own topology, which the sparse route does not take: at such a size the
+solver's refusal stands.
 
     python dataset_generator.py --case 118 --samples 2000 --root data
     python dataset_generator.py --case 118 --samples 2000 --root data -r 1 -a 1
+    python dataset_generator.py --case 6470rte --samples 256 --root data
 
     <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]
     <root>/raw/case<case>_edge_features.npy   (S, e, 4) float64 [from, to, r, x]
@@ -26,7 +30,8 @@ import sys
 
 import numpy as np
 
-GENERATOR_CASES = ("14", "118", "118v2")
+GENERATOR_CASES = ("14", "118", "118v2", "6470rte")
+SPARSE_BATCH = 1024              # samples per launch on the sparse route: a 6470-bus sample holds 5.4 MB of workspace (5.5 GB)
 
 
 def write_raw(root, case, bus_type, edge_index, rx, tables):
@@ -51,21 +56,34 @@ def write_raw(root, case, bus_type, edge_index, rx, tables):
 
 
 def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10, device="cuda:0", max_rounds=64, remove=0, add=0,
-             counts=None):
+             counts=None, route="auto"):
     """(bus_type [n], edge_index, rx [S, e, 2], tables [S, n, 4], redrawn): `samples` converged samples, host arrays.  `edge_index`
     is the grid's [2, e]; with `remove` or `add` above 0 it is [S, 2, e - remove + add], one perturbed line list per sample, and
     rx holds the parameters of those lines.  `counts` (a dict, optional) receives "disconnected": the samples dropped because no
-    connected draw was found, and "drawn": all samples drawn."""
+    connected draw was found, "drawn": all samples drawn, and "route": the solver route that ran.  `route`: "auto" (the sparse
+    route where the case has more unknowns than the dense solver takes and one topology) or "sparse"."""
     import torch
     from poweflownet_amd.synth import CASES, make_physical_inputs
-    from poweflownet_amd.utils.powerflow import solve_power_flow
+    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
     from poweflownet_amd.utils.topology import perturb_topology
+    if route not in ("auto", "sparse"):
+        raise ValueError(f"dataset_generator: route must be 'auto' or 'sparse', not {route!r}")
     if samples < 1:
         raise ValueError("dataset_generator: --samples must be at least 1")
     if remove < 0 or add < 0:
         raise ValueError(f"dataset_generator: cannot remove {remove} and add {add} lines")
     n, e = CASES[str(case)]
     perturbed = remove > 0 or add > 0
+    if route == "sparse" and perturbed:
+        raise ValueError("dataset_generator: the sparse route takes one topology; it does not go with -r / -a")
+    plan = None
+    # the route is decided from the grid alone, before a sample is drawn: a draw of no samples gives the lines and the bus types
+    ei0, bt0, _, _ = make_physical_inputs(n, e, 0, seed * 1_000_003, load)
+    if route == "auto" and not perturbed and (n - 1) + int((bt0 == 2).sum()) > max_unknowns():
+        route = "sparse"
+    if route == "sparse":
+        batch = min(batch, SPARSE_BATCH)
+        plan = sparse_plan(bt0.to(device), ei0.to(device))       # one grid: built and uploaded once, it serves every batch and redraw
     keep_ei, keep_rx, keep_t, have, redrawn, drawn, disconnected = [], [], [], 0, 0, 0, 0
     for rnd in range(max_rounds):
         if have >= samples:
@@ -86,7 +104,7 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         drawn += want
         if d_spec.shape[0] == 0:
             continue
-        res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
+        res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter, route=route, plan=plan)
         ok = res.status >= 0
         if int(res.flags.item()) != 0:
             raise RuntimeError("dataset_generator: the solver flagged its bus types")
@@ -98,7 +116,7 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         have += int(ok.sum())
         redrawn += int((~ok).sum())
     if counts is not None:
-        counts.update(disconnected=disconnected, drawn=drawn)
+        counts.update(disconnected=disconnected, drawn=drawn, route=route)
     if have < samples:
         raise RuntimeError(f"dataset_generator: only {have} of {samples} samples converged in {max_rounds} rounds (load {load})")
     lines = np.concatenate(keep_ei)[:samples] if perturbed else ei.numpy()
@@ -115,6 +133,8 @@ def main(argv=None):
     ap.add_argument("--load", type=float, default=0.2, help="mean active demand of a PQ bus, per-unit")
     ap.add_argument("-r", "--num_lines_to_remove", type=int, default=0, help="lines every sample loses (redrawn while a bus is unsupplied)")
     ap.add_argument("-a", "--num_lines_to_add", type=int, default=0, help="lines every sample gains, each a copy of a random line")
+    ap.add_argument("--route", default="auto", choices=("auto", "sparse"),
+                    help="solver route: auto takes the sparse one where the case exceeds the dense solver; sparse forces it")
     a = ap.parse_args(argv)
     r, add = a.num_lines_to_remove, a.num_lines_to_add
     if r < 0 or add < 0:
@@ -123,12 +143,14 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("dataset_generator.py needs a HIP device: poweflownet_amd has no CPU solver")
     counts = {}
-    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load, remove=r, add=add, counts=counts)
+    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load, remove=r, add=add, counts=counts, route=a.route)
     name = f"{a.case}perturbed{r}r{add}a" if r > 0 or add > 0 else a.case
     paths = write_raw(a.root, name, bt, ei, rx, tables)
     if r > 0 or add > 0:
         print(f"Left a bus unsupplied in every draw and dropped: {counts['disconnected']}")
     print(f"Failed to converge and drawn again: {redrawn}")
+    if counts["route"] == "sparse":
+        print("Solved on the sparse route")
     print(f"wrote {a.samples} samples of case{name} ({tables.shape[1]} buses, {ei.shape[-1]} lines): {paths[0]}, {paths[1]}")
     return 0
 

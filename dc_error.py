@@ -41,13 +41,23 @@ def solver_inputs(node, edge, device, rows=slice(None)):
     return truth, ei, rx
 
 
-def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, device="cuda:0", split=(.5, .2, .3)):
-    """Per-sample losses (host float64 array) of the DC solve against the test split of `root`'s case; failed solves raise."""
+def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, device="cuda:0", split=(.5, .2, .3), route="auto"):
+    """Per-sample losses (host float64 array) of the DC solve against the test split of `root`'s case; failed solves raise.  `route`:
+    "auto" -- the sparse route (one plan for the whole split) where the case has more buses than the dense solver takes and its
+    samples share one line list -- or "sparse"."""
     import torch
     from poweflownet_amd.datasets import PowerFlowData
     from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
-    from poweflownet_amd.utils.powerflow import solve_power_flow
+    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
+    if route not in ("auto", "sparse"):
+        raise ValueError(f"dc_error: route must be 'auto' or 'sparse', not {route!r}")
     testset, node, edge = load_test_split(root, case, samples, split)
+    one_topology = bool((edge[:, :, :2] == edge[:1, :, :2]).all())
+    if route == "auto" and one_topology and node.shape[1] - 1 > max_unknowns():
+        route = "sparse"
+    if route == "sparse" and not one_topology:
+        raise RuntimeError("dc_error: the sparse route takes one line list for all samples; this set has one per sample")
+    plan = None
     mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     mask = torch.tensor(PowerFlowData.bus_type_mask)[bus_type.cpu()].clone()
@@ -58,7 +68,10 @@ def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, devic
     out = []
     for s0 in range(0, len(node), batch):
         truth, ei, rx = solver_inputs(node, edge, device, slice(s0, s0 + batch))
-        res = solve_power_flow(bus_type, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter)
+        if route == "sparse":
+            ei = ei[0].contiguous()
+            plan = plan or sparse_plan(bus_type, ei, "dc")
+        res = solve_power_flow(bus_type, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter, route=route, plan=plan)
         if int((res.status < 0).sum()) or int(res.flags.item()):
             raise RuntimeError(f"dc_error: {int((res.status < 0).sum())} DC solves failed (statuses {sorted(set(res.status.tolist()))})")
         dc = res.table.clone()
@@ -84,11 +97,13 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=None, help="only the first N samples of the test split")
     ap.add_argument("--batch", type=int, default=4096, help="samples per device launch")
     ap.add_argument("--split", type=float, nargs=3, default=[.5, .2, .3], help="train / val / test fractions (the reference's .5 .2 .3)")
+    ap.add_argument("--route", default="auto", choices=("auto", "sparse"),
+                    help="solver route: auto takes the sparse one where the case exceeds the dense solver; sparse forces it")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("dc_error.py needs a HIP device: poweflownet_amd has no CPU solver")
-    losses = dc_losses(a.data_dir, a.case, a.samples, a.batch, split=tuple(a.split))
+    losses = dc_losses(a.data_dir, a.case, a.samples, a.batch, split=tuple(a.split), route=a.route)
     print(f"Case {a.case} done: {len(losses)} samples")
     for line in statistics_lines(losses):
         print(line)

@@ -571,6 +571,37 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
                         int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------- sparse power-flow route
+ * The same Newton / DC loop beyond pfn_powerflow_max_unknowns() (csrc/powerflow_sparse.hip), for ONE line list [2, n_lines] shared by
+ * the samples: a static minimum-degree order and the filled pattern under it are planned once per grid on the host, the fp32
+ * factor is sparse, left-looking by columns, not pivoted.  Modes 0 (AC) and 1 (DC) only.
+ * pfn_powerflow_sparse_plan (csrc/powerflow_plan.cpp; HOST arrays in, HOST blob out, no device call): edge_index int64 [2, n_lines],
+ *   bus_type int32 [n_bus].  pfn_powerflow_sparse_plan_bytes is the blob's size (0 on error); the blob is relocatable -- 32 int32
+ *   header words (magic, version, n, e, m, mode, slab positions, nnz(L), the multiply-adds of one factor as lo / hi words, ...), then
+ *   the sections csrc/powerflow_plan.hpp lists, by byte offset.  Unknowns: theta of the non-slack buses and Vm of the PQ buses (mode
+ *   1: theta only) in a minimum-degree order of the bus graph (parallel lines collapse, ties to the lowest bus id: the plan is a pure
+ *   function of its inputs), a bus's theta directly before its Vm.  PFN_EINVAL, nothing written: a line that names a bus outside
+ *   [0, n_bus), not exactly one slack, a bus type outside 0, 1, 2, a plan whose offsets do not fit int32.  A bus without a line is no
+ *   error: it is a zero pivot at solve time.
+ * pfn_powerflow_solve_sparse: ONE launch, one workgroup per sample, no host sync, no allocation (capturable).  edge_index, rx,
+ *   bus_type, spec, init, table, status, residual, flags, tol, max_iter as in pfn_powerflow_solve_init with lines_per_sample = 0;
+ *   plan_header: the first 32 words of the blob on the HOST (sizes the launch); plan_dev: the whole blob on the DEVICE, 16-byte
+ *   aligned; ws: pfn_powerflow_sparse_workspace_bytes(n_samples, plan_header) bytes (state, right-hand side and the factor's slab per
+ *   sample), too little is PFN_ENOSPACE; threads: 0 (64 lanes per sample, 256 once the plan's longest column exceeds 128), or 64 /
+ *   256 to force one.  PFN_EINVAL: a plan for another n_bus / n_lines / mode; a plan with 32-bit row ids (m > 65535) or whose
+ *   work vector (4 m bytes) does not fit LDS.  Statuses as above, and -6: the device line list or
+ *   bus types are not the ones the plan was built from (-5 with flag bit 0 for the types, as on the dense route).  Results are a pure
+ *   function of the sample's inputs and the plan, bit for bit, whatever the batch.                                            */
+#define PFN_POWERFLOW_STALE_PLAN (-6)
+size_t pfn_powerflow_sparse_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode);
+int pfn_powerflow_sparse_plan(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode, void* plan,
+                              size_t plan_bytes);
+size_t pfn_powerflow_sparse_workspace_bytes(int64_t n_samples, const void* plan_header);
+int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                               const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
+                               const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
+                               double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* --------------------------------------------------------------------------- topology perturbation
  * The reference's perturb_topology (utils/data_utils.py:12-59, behind dataset_generator.py -r / -a) drawn per sample on the device:
  * remove n_remove random lines, start over while a bus is left unsupplied, then add n_add lines between random bus pairs, each a copy

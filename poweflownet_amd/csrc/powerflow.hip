@@ -435,7 +435,7 @@ int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, in
     const bool fd = mode >= 2;
     const int64_t m64 = (n_bus - 1) + (mode == 1 ? 0 : n_pq);      // equations; modes 2, 3 hold no matrix of that order: their larger one is n_bus - 1
     PFN_CHECK_ARG((fd ? n_bus - 1 : m64) <= PF_MAX_UNKNOWNS,
-                  "pfn_powerflow_solve: %lld unknowns per sample exceed the dense solver's %d; a sparse factorisation is needed",
+                  "pfn_powerflow_solve: %lld unknowns per sample exceed the dense solver's %d; a sparse factorisation is needed (pfn_powerflow_solve_sparse, route \"sparse\")",
                   (long long)(fd ? n_bus - 1 : m64), PF_MAX_UNKNOWNS);
     if (n_samples == 0) return PFN_OK;
     PFN_CHECK_ARG(rx || n_lines == 0, "pfn_powerflow_solve: null rx");

@@ -3,6 +3,8 @@
 dc_error.py -- for this project's network model: series admittance only, every stored line in both directions, P and Q
 demand-positive per-unit, Va in degrees; no shunts, line charging, taps, Q-limits or unit conversion.  The mismatch it drives to zero
 is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  No CPU path."""
+import ctypes as C
+import time
 from dataclasses import dataclass
 
 import torch
@@ -10,9 +12,11 @@ import torch
 from .. import _lib as L
 
 STATUS = {-1: "not converged in max_iter", -2: "singular Jacobian", -3: "non-finite mismatch", -4: "a line names a bus outside the grid",
-          -5: "bus_type disagrees with the counts the launch was sized for"}
+          -5: "bus_type disagrees with the counts the launch was sized for",
+          -6: "the sparse plan was built from another line list or other bus types"}
 _MODES = {"ac": 0, "dc": 1, "fdxb": 2, "fdbx": 3}
-_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+_ROUTES = {"auto": 0, "lds": 1, "global": 2, "sparse": 3}
+_PLAN_HEADER_WORDS = 32          # csrc/powerflow_plan.hpp: n, e, m, mode at words 2..5, slab positions 6, nnz(L) 7, multiply-adds 8 / 9
 
 
 @dataclass
@@ -20,7 +24,7 @@ class PowerFlowResult:
     """`table` [S, n, 4] float64 (Vm, Va in degrees, P, Q; NaN rows where the sample failed), `status` [S] int32 (>= 0: Jacobian
     solves used -- half-iterations in the fast-decoupled modes; < 0: `STATUS`), `iterations` [S] int32 (the status where it is >= 0, else -1), `residual` [S] float64 (the last
     max |F|), `flags` [1] int32 (bit 0: `bus_type` changed under the launch) -- all on the device, nothing read back; `route`: the
-    route that ran, "lds" or "global"."""
+    route that ran, "lds", "global" or "sparse"."""
     table: torch.Tensor
     status: torch.Tensor
     iterations: torch.Tensor
@@ -34,7 +38,52 @@ def max_unknowns() -> int:
     return int(L.load().pfn_powerflow_max_unknowns())
 
 
-def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max_iter=10, route="auto", init=None) -> PowerFlowResult:
+@dataclass
+class SparsePlan:
+    """The symbolic half of the sparse route for ONE grid (csrc/powerflow_plan.cpp): `blob` the plan on the device (uint8), `header`
+    its first 32 int32 words on the host, and what a report needs -- `n`, `e`, `m` unknowns, `mode`, `nnz` slab positions per sample,
+    `nnz_l` = nnz(L), `madds` multiply-adds of one factorisation, `max_col` the longest L column, `bytes` of the plan, `build_s` the
+    host time it took."""
+    blob: torch.Tensor
+    header: object
+    n: int
+    e: int
+    m: int
+    mode: str
+    nnz: int
+    nnz_l: int
+    madds: int
+    max_col: int
+    bytes: int
+    build_s: float
+
+
+def sparse_plan(bus_type, edge_index, mode="ac") -> SparsePlan:
+    """Plan the sparse route for the grid (`bus_type` [n], `edge_index` int64 [2, e]; device or host tensors): one host read of the
+    two, a minimum-degree order and the filled pattern built by the library on the host, one upload.  Reuse the plan for every solve
+    on that grid and mode ("ac" or "dc")."""
+    if mode not in ("ac", "dc"):
+        raise ValueError("sparse_plan: mode must be 'ac' or 'dc'; the fast-decoupled modes are dense only")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64 or bus_type.dim() != 1:
+        raise RuntimeError(f"sparse_plan: edge_index must be int64 (2, e) and bus_type (n,); got {tuple(edge_index.shape)} and {tuple(bus_type.shape)}")
+    dev = edge_index.device if edge_index.is_cuda else bus_type.device
+    ei = edge_index.detach().cpu().contiguous()
+    bt = bus_type.detach().to(torch.int32).cpu().contiguous()
+    lib = L.load()
+    e, n = int(ei.shape[1]), int(bt.shape[0])
+    t0 = time.perf_counter()
+    need = int(lib.pfn_powerflow_sparse_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode]))
+    if need == 0:
+        raise RuntimeError(f"sparse_plan failed: {lib.pfn_last_error().decode('utf-8', 'replace')}")
+    host = torch.empty(need, dtype=torch.uint8)
+    L.check(lib.pfn_powerflow_sparse_plan(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode], host.data_ptr(), need), "pfn_powerflow_sparse_plan")
+    build_s = time.perf_counter() - t0
+    h = (C.c_int32 * _PLAN_HEADER_WORDS).from_buffer_copy(host[:4 * _PLAN_HEADER_WORDS].numpy().tobytes())
+    return SparsePlan(blob=host.to(dev), header=h, n=n, e=e, m=int(h[4]), mode=mode, nnz=int(h[6]), nnz_l=int(h[7]),
+                      madds=(int(h[9]) << 32) | (int(h[8]) & 0xffffffff), max_col=int(h[11]), bytes=need, build_s=build_s)
+
+
+def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max_iter=10, route="auto", init=None, plan=None) -> PowerFlowResult:
     """Solve S power-flow problems on one grid.  `bus_type` [n] (0 slack, 1 PV, 2 PQ; exactly one slack; shared by the samples),
     `spec` [S, n, 4] float64 (Vm, Va, P, Q: the slack gives Vm and Va, a PV bus Vm and P, a PQ bus P and Q; the rest is ignored),
     `edge_index` int64 local ids [2, e] or [S, 2, e], `rx` [S, e, 2] float64.  mode "ac": Newton-Raphson from a flat start, fp64
@@ -57,7 +106,18 @@ def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max
     tol = 1e-8 and max_iter = 10 are what pandapower's Newton-Raphson (`pp.runpp(algorithm="nr")`, per-unit mismatch) is believed to
     use; pandapower is not installed where this was written, so that could not be verified.
 
+    route "sparse": the same loop beyond `max_unknowns()` -- a sparse fp32 factor under a static minimum-degree order, no pivoting
+    (csrc/powerflow_sparse.hip), modes "ac" and "dc", one `[2, e]` line list for all samples.  `plan`: a `sparse_plan(bus_type,
+    edge_index, mode)` to reuse; None builds one here (a host read of the grid and a host computation: build it once per grid).  A
+    plan for another n, e or mode raises; one for other lines of the same size gives status -6.  "auto" never takes this route.
+
     One host read (the counts of `bus_type`, which size the launch); no read-back of the results."""
+    return _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, 0)
+
+
+def _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, threads) -> PowerFlowResult:
+    """`solve_power_flow` with the sparse route's workgroup size exposed (`threads`: 0 the library's choice, 64 or 256): what
+    tools/powerflow_bench.py and the tests measure the two sizes with."""
     L.require_device(bus_type, spec, edge_index, rx, what="solve_power_flow input")
     if mode not in _MODES or route not in _ROUTES:
         raise ValueError(f"solve_power_flow: mode must be one of {sorted(_MODES)} and route one of {sorted(_ROUTES)}")
@@ -90,6 +150,30 @@ def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max
     status = torch.empty(S, dtype=torch.int32, device=dev)
     residual = torch.empty(S, dtype=torch.float64, device=dev)
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    if route == "sparse":
+        if mode not in ("ac", "dc"):
+            raise ValueError(f"solve_power_flow: route 'sparse' has no mode {mode!r}: the fast-decoupled inverses are dense")
+        if edge_index.dim() == 3:
+            raise RuntimeError("solve_power_flow: route 'sparse' takes one (2, e) line list for all samples: a plan belongs to one topology")
+        if plan is None:
+            plan = sparse_plan(bt, edge_index, mode)
+        if not isinstance(plan, SparsePlan) or (plan.n, plan.e, plan.mode) != (n, e, mode):
+            raise RuntimeError(f"solve_power_flow: the plan is for (n, e, mode) = {(plan.n, plan.e, plan.mode) if isinstance(plan, SparsePlan) else plan!r}; "
+                               f"the call has {(n, e, mode)}")
+        if plan.blob.device != dev:
+            raise RuntimeError(f"solve_power_flow: the plan lives on {plan.blob.device}, the inputs on {dev}")
+        need = int(lib.pfn_powerflow_sparse_workspace_bytes(S, C.addressof(plan.header))) if S else 0
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.pfn_powerflow_solve_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), S, n,
+                                                   _MODES[mode], float(tol), int(max_iter), C.addressof(plan.header), plan.blob.data_ptr(),
+                                                   int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(), flags.data_ptr(),
+                                                   ws.data_ptr(), need, L.stream_ptr()),
+                    "pfn_powerflow_solve_sparse")
+        return PowerFlowResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
+                               residual=residual, flags=flags, route="sparse")
+    if plan is not None:
+        raise ValueError("solve_power_flow: a plan goes with route='sparse' only")
     need = int(lib.pfn_powerflow_workspace_bytes_mode(S, n, e, n_pq, _MODES[mode], _ROUTES[route]))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
     with torch.cuda.device(dev):

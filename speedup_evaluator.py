@@ -17,7 +17,11 @@ solves used (mean and max over the converged samples; half-iterations in the fas
 max_iter 10 for NR and DC, 60 half-iterations for the fast-decoupled rows.  The checkpoint is models/model_<run-id>.pt (normalised
 with `<data-dir>/params/data_params_<run-id>.pt` where it exists); without `--run-id` the model keeps its random initialisation and
 the output says so -- the "from the prediction" rows then show what a bad start costs, not what a trained model saves.  The
-solver inputs are read as dc_error.py reads them.  No plots."""
+solver inputs are read as dc_error.py reads them.  No plots.
+
+A case with more unknowns than the dense solver takes (6470rte) runs its NR and DC rows on the sparse route
+(csrc/powerflow_sparse.hip; one plan per mode, built before the timing); the fast-decoupled rows print `n/a (dense only)`: their
+inverses are dense."""
 import os
 import sys
 
@@ -59,7 +63,7 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     from poweflownet_amd.data import DataLoader
     from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
     from poweflownet_amd.utils.error_analysis import bus_error_epoch
-    from poweflownet_amd.utils.powerflow import solve_power_flow
+    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
     testset, node, edge = dc_error.load_test_split(root, case, samples, tuple(split))
     if xy is not None:
         testset = type(testset)(root=root, case=case, split=list(split), task="test", xymean=xy[0], xystd=xy[1], edgemean=xy[2], edgestd=xy[3])
@@ -68,6 +72,14 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     spec, ei, rx = dc_error.solver_inputs(node, edge, device)
+    # beyond the dense solver: the sparse route, one line list for all samples and one plan per mode
+    sparse = (node.shape[1] - 1) + int((node[0, :, 1] == 2).sum()) > max_unknowns()
+    plans = {}
+    if sparse:
+        if not bool((edge[:, :, :2] == edge[:1, :, :2]).all()):
+            raise RuntimeError("speedup_evaluator: a case beyond the dense solver needs one line list for all samples (the sparse route)")
+        ei = ei[0].contiguous()
+        plans = {mode: sparse_plan(bus_type, ei, mode) for mode in ("ac", "dc")}
     # ---- the model: the de-normalised prediction table of the whole split (rows in file order), then its forward alone
     loader = DataLoader(testset, batch_size=batch_size, shuffle=False)
     pred = bus_error_epoch(model, loader, device, xymean=testset.xymean, xystd=testset.xystd, keep_errors=False, keep_predictions=True)
@@ -86,7 +98,11 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     for name, mode, start in (("nr", "ac", None), ("nr_result_init", "ac", init), ("fdxb", "fdxb", None), ("fdbx", "fdbx", None),
                               ("fdxb_result_init", "fdxb", init), ("fdbx_result_init", "fdbx", init), ("dc", "dc", None)):
         iters = FD_ITERS if mode.startswith("fd") else NR_ITERS
-        sec, res = device_seconds(lambda: solve_power_flow(bus_type, spec, ei, rx, mode=mode, tol=TOL, max_iter=iters, init=start))
+        if sparse and mode.startswith("fd"):
+            rows[name] = None                                  # n/a: dense only
+            continue
+        kw = {"route": "sparse", "plan": plans[mode]} if sparse else {}
+        sec, res = device_seconds(lambda: solve_power_flow(bus_type, spec, ei, rx, mode=mode, tol=TOL, max_iter=iters, init=start, **kw))
         status = res.status.cpu().numpy()
         ok = status[status >= 0]
         rows[name] = {"seconds_per_sample": sec / S, "solves_mean": float(ok.mean()) if len(ok) else float("nan"),
@@ -107,6 +123,8 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
 def report(rows):
     def solver(name):
         r = rows[name]
+        if r is None:
+            return [f"{name}: n/a (dense only)"]
         return [f"{name}: {r['seconds_per_sample']}",
                 f"{name} solves: mean {r['solves_mean']:.3f} max {r['solves_max']} failures {r['failures']}"]
     lines = ["", "", "===========================================", "Results with auto_init:", ""]

@@ -8,6 +8,12 @@ warm starts (`*_warm`: Newton and both fast-decoupled modes started from Newton'
 the start a good prediction would give).
 
     python tools/powerflow_bench.py [--samples 4096] [--repeats 5] [--cpu-samples 16]
+    python tools/powerflow_bench.py --route sparse [--case 118 --case 130,200 --case 600,835 --case 6470rte] [--samples 4096]
+
+`--route sparse`: the sparse route (csrc/powerflow_sparse.hip) per `--case` column (a case name or "n,e"; default 118, 130,200,
+600,835 and 6470rte): the plan's fill, multiply-adds per factor, size and HOST build time, then ms and ms per sample of the solve
+with 64 and with 256 threads per sample and what the default takes, the mean and maximum solve count, and -- where the shape is
+under the dense cap -- the dense global route beside it.  6470rte runs 64 samples and `--big-samples` (default 512).
 
 Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
 max_iter 10 (the defaults).  One JSON line."""
@@ -23,15 +29,71 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, HERE)
 
 
+def _timed(fn, repeats):
+    import torch
+    per, last = [], None
+    for rep in range(repeats + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        last = fn()
+        torch.cuda.synchronize()
+        if rep:
+            per.append(time.perf_counter() - t0)
+    return per, last
+
+
+def sparse_rows(a):
+    """The `--route sparse` table: one column per case."""
+    import torch
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils import powerflow as PF
+    from poweflownet_amd.utils.powerflow import max_unknowns, sparse_plan
+    dev = torch.device("cuda:0")
+    res = {"device": torch.cuda.get_device_name(0), "route": "sparse", "tol": 1e-8, "max_iter": 10, "cases": {}}
+    for case in a.case or ["118", "130,200", "600,835", "6470rte"]:
+        n, e = CASES[case] if case in CASES else tuple(int(v) for v in case.split(","))
+        big = n > 2000
+        for samples in ([64, a.big_samples] if big else [a.samples]):
+            ei, bt, rx, spec = make_physical_inputs(n, e, samples, seed=0)
+            d = [t.to(dev) for t in (bt, spec, ei, rx)]
+            out = {"buses": n, "lines": e, "samples": samples}
+            for mode in ("ac", "dc"):
+                plan = sparse_plan(d[0], d[2], mode)
+                out[f"{mode}_plan"] = {"unknowns": plan.m, "nnz_l": plan.nnz_l, "slab_positions": plan.nnz, "longest_column": plan.max_col,
+                                       "multiply_adds_per_factor": plan.madds, "plan_bytes": plan.bytes,
+                                       "factor_bytes_per_sample": 4 * plan.nnz, "host_build_ms": round(1e3 * plan.build_s, 2)}
+                runs = [("sparse_64", "sparse", 64), ("sparse_256", "sparse", 256), ("sparse_default", "sparse", 0)]
+                if plan.m <= max_unknowns():
+                    runs.append(("dense_global", "global", 0))
+                for name, route, threads in runs:
+                    per, last = _timed(lambda: PF._solve(*d, mode, 1e-8, 10, route, None, plan if route == "sparse" else None, threads),
+                                       1 if big else a.repeats)
+                    status = last.status.cpu().numpy()
+                    ms = 1e3 * float(np.median(per))
+                    ok = status[status >= 0]
+                    out[f"{mode}_{name}"] = {"ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3),
+                                             "ms_per_sample": round(ms / samples, 5), "failed": int((status < 0).sum()),
+                                             "mean_iterations": round(float(ok.mean()), 3) if len(ok) else None,
+                                             "max_iterations": int(ok.max()) if len(ok) else None}
+            res["cases"][f"{case}x{samples}"] = out
+            print(json.dumps({f"{case}x{samples}": out}), flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cpu-samples", type=int, default=16)
+    ap.add_argument("--route", default=None, choices=("sparse",), help="the sparse route's table instead of the dense rows")
+    ap.add_argument("--case", action="append", default=None, help="with --route sparse: a case name or n,e (repeatable)")
+    ap.add_argument("--big-samples", type=int, default=512, help="with --route sparse: the large batch of a case beyond 2000 buses")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("powerflow_bench.py needs a HIP device")
+    if a.route == "sparse":
+        return sparse_rows(a)
     from poweflownet_amd.synth import CASES, make_physical_inputs
     from poweflownet_amd.utils.powerflow import solve_power_flow
     from tests import powerflow_ref as P
