@@ -574,7 +574,7 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
 /* ----------------------------------------------------------------------- sparse power-flow route
  * The same Newton / DC loop beyond pfn_powerflow_max_unknowns() (csrc/powerflow_sparse.hip), for ONE line list [2, n_lines] shared by
  * the samples: a static minimum-degree order and the filled pattern under it are planned once per grid on the host, the fp32
- * factor is sparse, left-looking by columns, not pivoted.  Modes 0 (AC) and 1 (DC) only.
+ * factor is sparse, left-looking by columns, not pivoted.  Modes 0 (AC) and 1 (DC); the fast-decoupled modes follow below.
  * pfn_powerflow_sparse_plan (csrc/powerflow_plan.cpp; HOST arrays in, HOST blob out, no device call): edge_index int64 [2, n_lines],
  *   bus_type int32 [n_bus].  pfn_powerflow_sparse_plan_bytes is the blob's size (0 on error); the blob is relocatable -- 32 int32
  *   header words (magic, version, n, e, m, mode, slab positions, nnz(L), the multiply-adds of one factor as lo / hi words, ...), then
@@ -601,6 +601,30 @@ int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const
                                const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
                                const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
                                double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------- sparse power-flow route, fast-decoupled modes
+ * Modes 2 (fdxb) and 3 (fdbx) of pfn_powerflow_solve_init beyond pfn_powerflow_max_unknowns() (csrc/powerflow_sparse_fd.hip): B'
+ * over the n_bus - 1 angle buses and B'' over the PQ buses are constant, so each is assembled and factored ONCE per sample (sparse,
+ * fp32, left-looking, not pivoted) and a half-iteration is one mismatch walk and one pair of fp64 substitutions.  Half-iterations,
+ * their count in `status`, the stopping rule, the warm start and the table are those of the dense fast-decoupled route.
+ * pfn_powerflow_sparse_fd_plan (HOST arrays in, HOST blob out): ONE plan serves both variants -- an outer header of 32 int32 words
+ *   (a magic of its own, n, e, m_p = n_bus - 1 in the usual words, m_q = the number of PQ buses in word 15, slab positions, nnz(L),
+ *   multiply-adds and bytes as TOTALS over both halves, the longer of the two longest columns) and two embedded sub-plans at the
+ *   byte offsets in words 16 and 17 -- P, byte for byte the mode-1 plan, and Q over the bus graph induced on the PQ buses under its
+ *   own minimum-degree order (csrc/powerflow_plan.hpp).  pfn_powerflow_sparse_fd_plan_bytes is its size (0 on error).  PFN_EINVAL,
+ *   nothing written: pfn_powerflow_sparse_plan's cases and a blob that is too small.  A grid without a PQ bus is valid (m_q = 0).
+ * pfn_powerflow_solve_sparse_fd: ONE launch, one workgroup per sample, no host sync, no allocation (capturable); the arguments of
+ *   pfn_powerflow_solve_sparse with mode 2 or 3, plan_header the outer header on the HOST, ws of
+ *   pfn_powerflow_sparse_fd_workspace_bytes(n_samples, plan_header) bytes.  max_iter counts half-iterations.  Statuses as there:
+ *   -2 a tiny or NaN pivot in either matrix, -5 (flag bit 0) bus types that disagree with either half, -6 another line list.   */
+size_t pfn_powerflow_sparse_fd_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus);
+int pfn_powerflow_sparse_fd_plan(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, void* plan,
+                                 size_t plan_bytes);
+size_t pfn_powerflow_sparse_fd_workspace_bytes(int64_t n_samples, const void* plan_header);
+int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                                  const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
+                                  const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
+                                  double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------- topology perturbation
  * The reference's perturb_topology (utils/data_utils.py:12-59, behind dataset_generator.py -r / -a) drawn per sample on the device:

@@ -33,6 +33,7 @@ SYMBOLS = (
     "pfn_powerflow_max_unknowns", "pfn_powerflow_workspace_bytes", "pfn_powerflow_solve",
     "pfn_powerflow_workspace_bytes_mode", "pfn_powerflow_solve_init",
     "pfn_powerflow_sparse_plan_bytes", "pfn_powerflow_sparse_plan", "pfn_powerflow_sparse_workspace_bytes", "pfn_powerflow_solve_sparse",
+    "pfn_powerflow_sparse_fd_plan_bytes", "pfn_powerflow_sparse_fd_plan", "pfn_powerflow_sparse_fd_workspace_bytes", "pfn_powerflow_solve_sparse_fd",
     "pfn_topology_perturb", "pfn_topology_unsupplied",
 )
 
@@ -156,6 +157,11 @@ def load() -> C.CDLL:
         "pfn_powerflow_sparse_workspace_bytes": (sz, [i64, p]),
         "pfn_powerflow_solve_sparse": (C.c_int, [p, i64, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int, p, p, p, p, p,
                                                  sz, p]),
+        "pfn_powerflow_sparse_fd_plan_bytes": (sz, [p, i64, p, i64]),
+        "pfn_powerflow_sparse_fd_plan": (C.c_int, [p, i64, p, i64, p, sz]),
+        "pfn_powerflow_sparse_fd_workspace_bytes": (sz, [i64, p]),
+        "pfn_powerflow_solve_sparse_fd": (C.c_int, [p, i64, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int, p, p, p, p, p,
+                                                    sz, p]),
         "pfn_topology_perturb": (C.c_int, [p, i64, i64, i64, i64, i64, i64, C.c_uint64, i64, C.c_int, p, p, p, p]),
         "pfn_topology_unsupplied": (C.c_int, [p, C.c_int, i64, i64, i64, i64, p, p]),
     }

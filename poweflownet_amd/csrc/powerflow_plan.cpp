@@ -28,45 +28,51 @@ namespace {
 int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 // plan null: nothing is written, *bytes_out gets the size.  Returns PFN_OK or PFN_EINVAL (text set).
-int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int mode, void* plan, size_t plan_bytes, size_t* bytes_out) {
+// mode 0 / 1: the public plans.  PLAN_PQ (internal, the Q half of a fast-decoupled plan): the PQ buses alone carry an unknown, one
+// each; the slack AND the PV buses are left out of the bus graph; the header says mode 1 (one unknown per bus) and `order` has m entries.
+constexpr int PLAN_PQ = 2;
+int build_plan(const char* who, const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int mode, void* plan, size_t plan_bytes,
+               size_t* bytes_out) {
     if (!(n >= 1 && e >= 0 && n < (1ll << 24) && e < (1ll << 24))) {
-        set_error("pfn_powerflow_sparse_plan: bad sizes (%lld buses, %lld lines)", (long long)n, (long long)e);
+        set_error("%s: bad sizes (%lld buses, %lld lines)", who, (long long)n, (long long)e);
         return PFN_EINVAL;
     }
-    if (mode != 0 && mode != 1) {
-        set_error("pfn_powerflow_sparse_plan: mode must be 0 (AC) or 1 (DC)");
+    if (mode != 0 && mode != 1 && mode != PLAN_PQ) {
+        set_error("%s: mode must be 0 (AC) or 1 (DC)", who);
         return PFN_EINVAL;
     }
     if (!bt || (!ei && e)) {
-        set_error("pfn_powerflow_sparse_plan: null pointer");
+        set_error("%s: null pointer", who);
         return PFN_EINVAL;
     }
     int64_t n_slack = 0, slack = 0;
     for (int64_t i = 0; i < n; ++i) {
         if (bt[i] < 0 || bt[i] > 2) {
-            set_error("pfn_powerflow_sparse_plan: bus %lld has type %d; only 0 (slack), 1 (PV) and 2 (PQ) exist", (long long)i, (int)bt[i]);
+            set_error("%s: bus %lld has type %d; only 0 (slack), 1 (PV) and 2 (PQ) exist", who, (long long)i, (int)bt[i]);
             return PFN_EINVAL;
         }
         if (bt[i] == 0) { ++n_slack; slack = i; }
     }
     if (n_slack != 1) {
-        set_error("pfn_powerflow_sparse_plan: %lld slack buses; exactly one is needed", (long long)n_slack);
+        set_error("%s: %lld slack buses; exactly one is needed", who, (long long)n_slack);
         return PFN_EINVAL;
     }
     for (int64_t k = 0; k < e; ++k) {
         if ((uint64_t)ei[k] >= (uint64_t)n || (uint64_t)ei[e + k] >= (uint64_t)n) {
-            set_error("pfn_powerflow_sparse_plan: line %lld names a bus outside [0, %lld)", (long long)k, (long long)n);
+            set_error("%s: line %lld names a bus outside [0, %lld)", who, (long long)k, (long long)n);
             return PFN_EINVAL;
         }
     }
     const int N = (int)n, E = (int)e;
-    const bool dc = mode == 1;
+    const bool dc = mode != 0;
+    // the buses that carry an unknown: all but the slack; PLAN_PQ: the PQ buses alone
+    auto in_graph = [&](int i) { return mode == PLAN_PQ ? bt[i] == 2 : i != slack; };
 
-    // ---- minimum degree on the bus graph without the slack
+    // ---- minimum degree on the bus graph induced on those buses
     std::vector<std::vector<int>> nb(N);
     for (int k = 0; k < E; ++k) {
         const int a = (int)ei[k], b = (int)ei[e + k];
-        if (a == b || a == slack || b == slack) continue;
+        if (a == b || !in_graph(a) || !in_graph(b)) continue;
         nb[a].push_back(b);
         nb[b].push_back(a);
     }
@@ -74,7 +80,7 @@ int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int m
     for (int i = 0; i < N; ++i) {
         std::sort(nb[i].begin(), nb[i].end());
         nb[i].erase(std::unique(nb[i].begin(), nb[i].end()), nb[i].end());
-        if (i != slack) heap.insert({(int)nb[i].size(), i});
+        if (in_graph(i)) heap.insert({(int)nb[i].size(), i});
     }
     std::vector<int> order, where(N, -1);           // where[bus] = its place in the order
     order.reserve(N);
@@ -97,7 +103,7 @@ int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int m
         }
         lower[where[v]].swap(nv);
     }
-    const int NB = (int)order.size();                // N - 1
+    const int NB = (int)order.size();                // N - 1; PLAN_PQ: the number of PQ buses
     // ---- unknown numbering in that order; upper[place] = earlier places whose L structure holds this bus (ascending by construction)
     std::vector<int> ua(N, -1), uv(N, -1);
     int64_t m64 = 0;
@@ -149,14 +155,14 @@ int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int m
     const int64_t o_adj = place_section(8ll * n_adj), o_adjpos = place_section(16ll * n_adj), o_buspos = place_section(16ll * N);
     const int64_t total = off;
     if (total >= (1ll << 31) || nnz >= (1ll << 31)) {
-        set_error("pfn_powerflow_sparse_plan: a filled pattern of %lld entries (a plan of %lld bytes) does not fit 32-bit offsets",
+        set_error("%s: a filled pattern of %lld entries (a plan of %lld bytes) does not fit 32-bit offsets", who,
                   (long long)nnz, (long long)total);
         return PFN_EINVAL;
     }
     if (bytes_out) *bytes_out = (size_t)total;
     if (!plan) return PFN_OK;
     if (plan_bytes < (size_t)total) {
-        set_error("pfn_powerflow_sparse_plan: the plan needs %lld bytes (got %zu)", (long long)total, plan_bytes);
+        set_error("%s: the plan needs %lld bytes (got %zu)", who, (long long)total, plan_bytes);
         return PFN_EINVAL;
     }
     unsigned char* base = static_cast<unsigned char*>(plan);
@@ -167,7 +173,7 @@ int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int m
     H[PFP_H_N] = N;
     H[PFP_H_E] = E;
     H[PFP_H_M] = M;
-    H[PFP_H_MODE] = mode;
+    H[PFP_H_MODE] = dc ? 1 : 0;
     H[PFP_H_NNZ] = (int32_t)nnz;
     H[PFP_H_NNZ_L] = (int32_t)nnz_l;
     H[PFP_H_MADDS_LO] = (int32_t)(uint32_t)(madds & 0xffffffffll);
@@ -265,7 +271,7 @@ int build_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, int m
         }
     }
     if (missing) {                                   // (cannot happen: every line's block is in the pattern by construction)
-        set_error("pfn_powerflow_sparse_plan: internal error, a Jacobian entry has no place in the filled pattern");
+        set_error("%s: internal error, a Jacobian entry has no place in the filled pattern", who);
         std::memset(base, 0, (size_t)total);
         return PFN_EINVAL;
     }
@@ -280,7 +286,8 @@ extern "C" {
 //  buses, once per grid -- and neither keeps anything behind)
 size_t pfn_powerflow_sparse_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode) {
     size_t bytes = 0;
-    return build_plan(edge_index, n_lines, bus_type, n_bus, mode, nullptr, 0, &bytes) == PFN_OK ? bytes : 0;
+    if (mode != 0 && mode != 1) mode = -1;          // (the internal kinds are not reachable from here)
+    return build_plan("pfn_powerflow_sparse_plan", edge_index, n_lines, bus_type, n_bus, mode, nullptr, 0, &bytes) == PFN_OK ? bytes : 0;
 }
 
 int pfn_powerflow_sparse_plan(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode, void* plan,
@@ -289,7 +296,78 @@ int pfn_powerflow_sparse_plan(const int64_t* edge_index, int64_t n_lines, const 
         set_error("pfn_powerflow_sparse_plan: null plan");
         return PFN_EINVAL;
     }
-    return build_plan(edge_index, n_lines, bus_type, n_bus, mode, plan, plan_bytes, nullptr);
+    if (mode != 0 && mode != 1) mode = -1;
+    return build_plan("pfn_powerflow_sparse_plan", edge_index, n_lines, bus_type, n_bus, mode, plan, plan_bytes, nullptr);
+}
+
+// The fast-decoupled plan (layout: powerflow_plan.hpp): an outer header, then two complete sub-plans -- P, B' over the angle buses
+// (byte for byte the mode-1 plan), and Q, B'' over the PQ buses.  Each sizing call runs both eliminations.
+static int build_fd_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, void* plan, size_t plan_bytes, size_t* bytes_out) {
+    const char* who = "pfn_powerflow_sparse_fd_plan";
+    size_t bytes_p = 0, bytes_q = 0;
+    if (build_plan(who, ei, e, bt, n, 1, nullptr, 0, &bytes_p) != PFN_OK) return PFN_EINVAL;
+    if (build_plan(who, ei, e, bt, n, PLAN_PQ, nullptr, 0, &bytes_q) != PFN_OK) return PFN_EINVAL;
+    const int64_t off_p = (int64_t)PFP_HEADER_WORDS * 4, off_q = off_p + align16((int64_t)bytes_p), total = off_q + align16((int64_t)bytes_q);
+    if (total >= (1ll << 31)) {
+        set_error("%s: a plan of %lld bytes does not fit 32-bit offsets", who, (long long)total);
+        return PFN_EINVAL;
+    }
+    if (bytes_out) *bytes_out = (size_t)total;
+    if (!plan) return PFN_OK;
+    if (plan_bytes < (size_t)total) {
+        set_error("%s: the plan needs %lld bytes (got %zu)", who, (long long)total, plan_bytes);
+        return PFN_EINVAL;
+    }
+    unsigned char* base = static_cast<unsigned char*>(plan);
+    std::memset(base, 0, (size_t)total);
+    if (build_plan(who, ei, e, bt, n, 1, base + off_p, bytes_p, nullptr) != PFN_OK ||
+        build_plan(who, ei, e, bt, n, PLAN_PQ, base + off_q, bytes_q, nullptr) != PFN_OK) {
+        std::memset(base, 0, (size_t)total);
+        return PFN_EINVAL;
+    }
+    int32_t* H = reinterpret_cast<int32_t*>(base);
+    const int32_t* P = reinterpret_cast<const int32_t*>(base + off_p);
+    const int32_t* Q = reinterpret_cast<const int32_t*>(base + off_q);
+    auto madds_of = [](const int32_t* h) { return ((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]; };
+    const int64_t madds = madds_of(P) + madds_of(Q), nnz = (int64_t)P[PFP_H_NNZ] + Q[PFP_H_NNZ];
+    if (nnz >= (1ll << 31)) {
+        set_error("%s: filled patterns of %lld entries do not fit 32-bit offsets", who, (long long)nnz);
+        std::memset(base, 0, (size_t)total);
+        return PFN_EINVAL;
+    }
+    H[PFP_H_MAGIC] = PFD_MAGIC;
+    H[PFP_H_VERSION] = PFP_VERSION;
+    H[PFP_H_N] = P[PFP_H_N];
+    H[PFP_H_E] = P[PFP_H_E];
+    H[PFP_H_M] = P[PFP_H_M];
+    H[PFP_H_MODE] = PFD_MODE;
+    H[PFP_H_NNZ] = (int32_t)nnz;
+    H[PFP_H_NNZ_L] = P[PFP_H_NNZ_L] + Q[PFP_H_NNZ_L];
+    H[PFP_H_MADDS_LO] = (int32_t)(uint32_t)(madds & 0xffffffffll);
+    H[PFP_H_MADDS_HI] = (int32_t)(madds >> 32);
+    H[PFP_H_IDX16] = P[PFP_H_IDX16] && Q[PFP_H_IDX16];
+    H[PFP_H_MAX_COL] = std::max(P[PFP_H_MAX_COL], Q[PFP_H_MAX_COL]);
+    H[PFP_H_N_ADJ] = P[PFP_H_N_ADJ];
+    H[PFP_H_BYTES] = (int32_t)total;
+    H[PFP_H_SLACK] = P[PFP_H_SLACK];
+    H[PFD_H_M_Q] = Q[PFP_H_M];
+    H[PFD_H_OFF_P] = (int32_t)off_p;
+    H[PFD_H_OFF_Q] = (int32_t)off_q;
+    return PFN_OK;
+}
+
+size_t pfn_powerflow_sparse_fd_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus) {
+    size_t bytes = 0;
+    return build_fd_plan(edge_index, n_lines, bus_type, n_bus, nullptr, 0, &bytes) == PFN_OK ? bytes : 0;
+}
+
+int pfn_powerflow_sparse_fd_plan(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, void* plan,
+                                 size_t plan_bytes) {
+    if (!plan) {
+        set_error("pfn_powerflow_sparse_fd_plan: null plan");
+        return PFN_EINVAL;
+    }
+    return build_fd_plan(edge_index, n_lines, bus_type, n_bus, plan, plan_bytes, nullptr);
 }
 
 }  // extern "C"

@@ -11,6 +11,19 @@
 //   adjpos  int32 [n_adj][4]     slab positions of the entries that line end adds to: (theta_i, theta_j), (theta_i, Vm_j),
 //                                (Vm_i, theta_j), (Vm_i, Vm_j) as (row, column); -1 where a row or a column is no unknown
 //   buspos  int32 [n][4]         the same for the bus's own 2 x 2 diagonal block
+//
+// The fast-decoupled plan (pfn_powerflow_sparse_fd_plan, read by powerflow_sparse_fd.hip and tests/powerflow_sparse_fd_ref.py) is ONE blob too:
+// an OUTER header of PFP_HEADER_WORDS words in the positions above with PFD_MAGIC, mode PFD_MODE, n, e, slack and n_adj as above,
+// M = m_p = n - 1 (the order of B'), PFD_H_M_Q = m_q = the number of PQ buses (the order of B''), NNZ / NNZ_L / MADDS / BYTES
+// totals over both halves (BYTES: the whole blob), MAX_COL the larger half's, IDX16 set when both halves have 16-bit rows; its
+// section-offset words are unused but for PFD_H_OFF_P and PFD_H_OFF_Q, the BYTE offsets of two embedded sub-plans.  Each sub-plan
+// is a complete plan as described above -- its own header (PFP_MAGIC, mode 1, its own M, NNZ, ... and BYTES), then its sections at
+// offsets FROM THE SUB-PLAN'S START -- for a matrix with one unknown per bus: uv is all -1 and only the first of the four adjpos /
+// buspos positions is used.
+//   P  B' over the n - 1 non-slack buses: byte for byte the mode-1 plan of the grid;
+//   Q  B'' over the PQ buses: the bus graph induced on them (the slack and the PV buses left out), its own minimum-degree order
+//      (`order` has m_q entries), ua[i] = -1 at every bus that is not PQ.  m_q = 0 is valid: empty sections.
+// The launch and the workspace are sized from the outer header alone.
 #pragma once
 #include <stdint.h>
 
@@ -19,6 +32,9 @@ namespace pfn {
 constexpr int32_t PFP_MAGIC = 0x50465350;          // "PSFP"
 constexpr int32_t PFP_VERSION = 1;
 constexpr int PFP_HEADER_WORDS = 32;
+constexpr int32_t PFD_MAGIC = 0x44465350;          // "PSFD"
+constexpr int32_t PFD_MODE = 2;
+enum { PFD_H_M_Q = 15, PFD_H_OFF_P = 16, PFD_H_OFF_Q = 17 };
 enum {
     PFP_H_MAGIC = 0, PFP_H_VERSION, PFP_H_N, PFP_H_E, PFP_H_M, PFP_H_MODE,
     PFP_H_NNZ,                                      // slab positions per sample: U parts, diagonals and L parts

@@ -20,12 +20,13 @@
 // crosses threads.  The metadata of up to 64 columns (where their L parts begin and end) is loaded by the lanes at once and handed
 // round with wave shuffles, and a thread's first element of the next L column is requested before the current step's barrier (an
 // LDS-only barrier, device_prims.hpp): a k-step then waits for an LDS round trip and a barrier, not for three dependent loads.
+// Steps (3) and (4) are powerflow_sparse_core.hpp's, shared with the fast-decoupled kernel (powerflow_sparse_fd.hip).
 #include "pfn_internal.hpp"
 #include "powerflow_plan.hpp"
+#include "powerflow_sparse_core.hpp"
 
 namespace pfn {
 
-constexpr float PFS_TINY_PIVOT = 1e-30f;           // (powerflow.hip PF_TINY_PIVOT)
 constexpr double PFS_RAD = 3.14159265358979323846 / 180.0;
 constexpr int PFS_F_LDS_BYTES = 80 * 1024;         // w + F in LDS up to here (two workgroups per compute unit at least)
 enum { PFS_NOT_CONVERGED = -1, PFS_SINGULAR = -2, PFS_NON_FINITE = -3, PFS_BAD_TYPES = -5, PFS_STALE_PLAN = -6 };
@@ -56,23 +57,10 @@ __host__ __device__ inline size_t pfs_w_bytes(int m) { return ((size_t)4 * m + 1
 __host__ __device__ inline size_t pfs_lds_bytes(int m) { return pfs_w_bytes(m) + (pfs_f_in_lds(m) ? (size_t)8 * m : 0) + 16; }
 
 template <int THREADS>
-__device__ __forceinline__ double pfs_block_max(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) r = fmax(r, red[w]);
-    __syncthreads();
-    return r;
-}
-
-template <int THREADS>
 __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pfs_smem[];
     __shared__ double s_red[THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63;
+    const int t = threadIdx.x;
     constexpr int nt = THREADS;
     const int s = blockIdx.x;
     const int n = a.n, e = a.e, m = a.m, nnz = a.nnz;
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
     const int4* adjpos = reinterpret_cast<const int4*>(pb + H[PFP_H_OFF_ADJPOS]);
     const int4* buspos = reinterpret_cast<const int4*>(pb + H[PFP_H_OFF_BUSPOS]);
     const int slack = H[PFP_H_SLACK];
-    auto row_of = [&](int pos) -> int { return (int)row16[pos]; };
+    const PfcMatrix A{colptr, diag, row16, m};
 
     double* vm = reinterpret_cast<double*>(a.ws + (size_t)s * a.ws_stride);
     double* th = vm + n;
@@ -205,93 +193,14 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
                 const double f = fabs(F[k]);
                 mx = fmax(mx, f < __builtin_inf() ? f : __builtin_inf());
             }
-            res = pfs_block_max<THREADS>(mx, s_red);
+            res = pfc_block_max<THREADS>(mx, s_red);
             if (!(res < __builtin_inf())) { code = PFS_NON_FINITE; break; }
             if (res < a.tol) break;
             if (it >= a.max_iter) { code = PFS_NOT_CONVERGED; break; }
-            // ---- (3) left-looking factorisation in plan order
-            for (int j = 0; j < m; ++j) {
-                const int c0 = colptr[j], dg = diag[j], c1 = colptr[j + 1];
-                for (int i = c0 + t; i < c1; i += nt) w[row_of(i)] = slab[i];
-                __syncthreads();
-                for (int p0 = c0; p0 < dg; p0 += 64) {
-                    const int cnt = min(64, dg - p0);
-                    int myk = 0, myb = 0, mye = 0;
-                    if (lane < cnt) {
-                        myk = row_of(p0 + lane);
-                        myb = diag[myk] + 1;
-                        mye = colptr[myk + 1];
-                    }
-                    // the thread's first element of L(:, k) is requested one step ahead: L is final in the slab (its column's barrier
-                    // is long past) and the k-steps' barrier orders LDS only, so the load stays in flight across it
-                    int k = __shfl(myk, 0), lb = __shfl(myb, 0), le = __shfl(mye, 0), r0 = 0;
-                    float l0 = 0.f;
-                    if (lb + t < le) {
-                        r0 = row_of(lb + t);
-                        l0 = slab[lb + t];
-                    }
-                    for (int q = 0; q < cnt; ++q) {
-                        const int kc = k, lbc = lb, lec = le, rc = r0;
-                        const float lc = l0;
-                        if (q + 1 < cnt) {
-                            k = __shfl(myk, q + 1);
-                            lb = __shfl(myb, q + 1);
-                            le = __shfl(mye, q + 1);
-                            if (lb + t < le) {
-                                r0 = row_of(lb + t);
-                                l0 = slab[lb + t];
-                            }
-                        }
-                        const float ukj = w[kc];     // final: every earlier step that could reach row k is behind a barrier
-                        if (lbc + t < lec) w[rc] = fmaf(-lc, ukj, w[rc]);
-                        for (int i = lbc + t + nt; i < lec; i += nt) {
-                            const int r = row_of(i);
-                            w[r] = fmaf(-slab[i], ukj, w[r]);
-                        }
-                        lds_barrier();               // (w only: no thread reads another's global writes before the column's last barrier)
-                    }
-                }
-                const float piv = w[j];
-                if (!(fabsf(piv) > PFS_TINY_PIVOT)) { code = PFS_SINGULAR; break; }
-                const float pinv = 1.f / piv;
-                for (int i = c0 + t; i < c1; i += nt) {
-                    const float v = w[row_of(i)];
-                    slab[i] = i > dg ? v * pinv : v;
-                }
-                __syncthreads();
-            }
-            if (code) break;
+            // ---- (3) left-looking factorisation in plan order (powerflow_sparse_core.hpp)
+            if (!pfc_factor<THREADS>(A, slab, w)) { code = PFS_SINGULAR; break; }
             // ---- (4) L y = F, then U dx = y, by columns: after its step F[j] is final (the backward one leaves U_jj dx_j)
-            for (int j0 = 0; j0 < m; j0 += 64) {
-                const int cnt = min(64, m - j0);
-                int myb = 0, mye = 0;
-                if (lane < cnt) {
-                    myb = diag[j0 + lane] + 1;
-                    mye = colptr[j0 + lane + 1];
-                }
-                for (int q = 0; q < cnt; ++q) {
-                    const int lb = __shfl(myb, q), le = __shfl(mye, q);
-                    if (lb >= le) continue;          // (uniform: nothing is written, the next step reads what a barrier already covers)
-                    const double yj = F[j0 + q];
-                    for (int i = lb + t; i < le; i += nt) F[row_of(i)] -= (double)slab[i] * yj;
-                    __syncthreads();
-                }
-            }
-            for (int j1 = m; j1 > 0; j1 -= 64) {
-                const int cnt = min(64, j1);
-                int myb = 0, mye = 0;
-                if (lane < cnt) {
-                    myb = colptr[j1 - 1 - lane];
-                    mye = diag[j1 - 1 - lane];
-                }
-                for (int q = 0; q < cnt; ++q) {
-                    const int ub = __shfl(myb, q), ue = __shfl(mye, q);
-                    if (ub >= ue) continue;
-                    const double xj = F[j1 - 1 - q] / (double)slab[ue];
-                    for (int i = ub + t; i < ue; i += nt) F[row_of(i)] -= (double)slab[i] * xj;
-                    __syncthreads();
-                }
-            }
+            pfc_substitute<THREADS>(A, slab, F);
             // ---- (5) x += dx
             for (int i = t; i < n; i += nt) {
                 const int ia = ua[i], iv = uv[i];
@@ -348,7 +257,7 @@ int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const
     const int32_t* h = static_cast<const int32_t*>(plan_header);
     PFN_TRY(pfs_check_header(h, "pfn_powerflow_solve_sparse"));
     PFN_CHECK_ARG(n_samples >= 0 && n_samples < (1ll << 29), "pfn_powerflow_solve_sparse: bad sample count %lld", (long long)n_samples);
-    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve_sparse: mode must be 0 (AC) or 1 (DC); the fast-decoupled modes are dense only");
+    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve_sparse: mode must be 0 (AC) or 1 (DC); the fast-decoupled modes 2 and 3 are pfn_powerflow_solve_sparse_fd's");
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines && h[PFP_H_MODE] == mode,
                   "pfn_powerflow_solve_sparse: the plan is for %d buses, %d lines, mode %d; the call has %lld, %lld, mode %d", (int)h[PFP_H_N],
                   (int)h[PFP_H_E], (int)h[PFP_H_MODE], (long long)n_bus, (long long)n_lines, mode);

@@ -17,6 +17,7 @@ STATUS = {-1: "not converged in max_iter", -2: "singular Jacobian", -3: "non-fin
 _MODES = {"ac": 0, "dc": 1, "fdxb": 2, "fdbx": 3}
 _ROUTES = {"auto": 0, "lds": 1, "global": 2, "sparse": 3}
 _PLAN_HEADER_WORDS = 32          # csrc/powerflow_plan.hpp: n, e, m, mode at words 2..5, slab positions 6, nnz(L) 7, multiply-adds 8 / 9
+_FD_PLAN_MODES = ("fd", "fdxb", "fdbx")      # one plan serves both variants: only the weights differ
 
 
 @dataclass
@@ -43,7 +44,9 @@ class SparsePlan:
     """The symbolic half of the sparse route for ONE grid (csrc/powerflow_plan.cpp): `blob` the plan on the device (uint8), `header`
     its first 32 int32 words on the host, and what a report needs -- `n`, `e`, `m` unknowns, `mode`, `nnz` slab positions per sample,
     `nnz_l` = nnz(L), `madds` multiply-adds of one factorisation, `max_col` the longest L column, `bytes` of the plan, `build_s` the
-    host time it took."""
+    host time it took.  mode "fd" (the fast-decoupled plan: B' and B'' side by side): `m` is the order of B' (n - 1), `m_q` that of
+    B'' (the PQ buses; 0 in the other modes), `nnz`, `nnz_l`, `madds` and `bytes` are totals over both, `max_col` the larger half's,
+    and `halves` holds (m, nnz, nnz_l, madds, max_col) of each half, P first."""
     blob: torch.Tensor
     header: object
     n: int
@@ -56,14 +59,18 @@ class SparsePlan:
     max_col: int
     bytes: int
     build_s: float
+    m_q: int = 0
+    halves: tuple = ()
 
 
 def sparse_plan(bus_type, edge_index, mode="ac") -> SparsePlan:
     """Plan the sparse route for the grid (`bus_type` [n], `edge_index` int64 [2, e]; device or host tensors): one host read of the
     two, a minimum-degree order and the filled pattern built by the library on the host, one upload.  Reuse the plan for every solve
-    on that grid and mode ("ac" or "dc")."""
-    if mode not in ("ac", "dc"):
-        raise ValueError("sparse_plan: mode must be 'ac' or 'dc'; the fast-decoupled modes are dense only")
+    on that grid and mode ("ac" or "dc").  mode "fd" (also spelled "fdxb" or "fdbx"; the plan's `mode` is "fd" either way): the
+    fast-decoupled plan, the symbolic factorisations of B' and B'' in one blob, for `solve_power_flow(mode="fdxb" | "fdbx")`."""
+    if mode not in ("ac", "dc") + _FD_PLAN_MODES:
+        raise ValueError("sparse_plan: mode must be 'ac', 'dc' or 'fd' ('fdxb' and 'fdbx' are spellings of 'fd')")
+    fd = mode in _FD_PLAN_MODES
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64 or bus_type.dim() != 1:
         raise RuntimeError(f"sparse_plan: edge_index must be int64 (2, e) and bus_type (n,); got {tuple(edge_index.shape)} and {tuple(bus_type.shape)}")
     dev = edge_index.device if edge_index.is_cuda else bus_type.device
@@ -72,15 +79,28 @@ def sparse_plan(bus_type, edge_index, mode="ac") -> SparsePlan:
     lib = L.load()
     e, n = int(ei.shape[1]), int(bt.shape[0])
     t0 = time.perf_counter()
-    need = int(lib.pfn_powerflow_sparse_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode]))
+    if fd:
+        need = int(lib.pfn_powerflow_sparse_fd_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n))
+    else:
+        need = int(lib.pfn_powerflow_sparse_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode]))
     if need == 0:
         raise RuntimeError(f"sparse_plan failed: {lib.pfn_last_error().decode('utf-8', 'replace')}")
     host = torch.empty(need, dtype=torch.uint8)
-    L.check(lib.pfn_powerflow_sparse_plan(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode], host.data_ptr(), need), "pfn_powerflow_sparse_plan")
+    if fd:
+        L.check(lib.pfn_powerflow_sparse_fd_plan(ei.data_ptr(), e, bt.data_ptr(), n, host.data_ptr(), need), "pfn_powerflow_sparse_fd_plan")
+    else:
+        L.check(lib.pfn_powerflow_sparse_plan(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode], host.data_ptr(), need), "pfn_powerflow_sparse_plan")
     build_s = time.perf_counter() - t0
-    h = (C.c_int32 * _PLAN_HEADER_WORDS).from_buffer_copy(host[:4 * _PLAN_HEADER_WORDS].numpy().tobytes())
-    return SparsePlan(blob=host.to(dev), header=h, n=n, e=e, m=int(h[4]), mode=mode, nnz=int(h[6]), nnz_l=int(h[7]),
-                      madds=(int(h[9]) << 32) | (int(h[8]) & 0xffffffff), max_col=int(h[11]), bytes=need, build_s=build_s)
+
+    def header(at):
+        return (C.c_int32 * _PLAN_HEADER_WORDS).from_buffer_copy(host[at:at + 4 * _PLAN_HEADER_WORDS].numpy().tobytes())
+
+    def madds(w):
+        return (int(w[9]) << 32) | (int(w[8]) & 0xffffffff)
+    h = header(0)
+    halves = tuple((int(w[4]), int(w[6]), int(w[7]), madds(w), int(w[11])) for w in (header(int(h[16])), header(int(h[17])))) if fd else ()
+    return SparsePlan(blob=host.to(dev), header=h, n=n, e=e, m=int(h[4]), mode="fd" if fd else mode, nnz=int(h[6]), nnz_l=int(h[7]),
+                      madds=madds(h), max_col=int(h[11]), bytes=need, build_s=build_s, m_q=int(h[15]) if fd else 0, halves=halves)
 
 
 def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max_iter=10, route="auto", init=None, plan=None) -> PowerFlowResult:
@@ -110,6 +130,9 @@ def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max
     (csrc/powerflow_sparse.hip), modes "ac" and "dc", one `[2, e]` line list for all samples.  `plan`: a `sparse_plan(bus_type,
     edge_index, mode)` to reuse; None builds one here (a host read of the grid and a host computation: build it once per grid).  A
     plan for another n, e or mode raises; one for other lines of the same size gives status -6.  "auto" never takes this route.
+    Modes "fdxb" / "fdbx" on this route (csrc/powerflow_sparse_fd.hip) keep the sparse fp32 FACTORS of B' and B'' -- factored once
+    per sample -- where the dense route keeps their inverses; same half-iterations, `init`, `tol` and `max_iter`.  They need
+    `plan=sparse_plan(bus_type, edge_index, "fd")` (one plan serves both variants); without a plan they are dense only: ValueError.
 
     One host read (the counts of `bus_type`, which size the launch); no read-back of the results."""
     return _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, 0)
@@ -151,25 +174,29 @@ def _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, pla
     residual = torch.empty(S, dtype=torch.float64, device=dev)
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     if route == "sparse":
-        if mode not in ("ac", "dc"):
-            raise ValueError(f"solve_power_flow: route 'sparse' has no mode {mode!r}: the fast-decoupled inverses are dense")
+        fd = mode in ("fdxb", "fdbx")
+        if fd and plan is None:
+            raise ValueError(f"solve_power_flow: route 'sparse' with mode {mode!r}: pass plan=sparse_plan(bus_type, edge_index, 'fd'); "
+                             "without a plan the fast-decoupled modes are dense only")
         if edge_index.dim() == 3:
             raise RuntimeError("solve_power_flow: route 'sparse' takes one (2, e) line list for all samples: a plan belongs to one topology")
         if plan is None:
             plan = sparse_plan(bt, edge_index, mode)
-        if not isinstance(plan, SparsePlan) or (plan.n, plan.e, plan.mode) != (n, e, mode):
+        if not isinstance(plan, SparsePlan) or (plan.n, plan.e, plan.mode) != (n, e, "fd" if fd else mode):
             raise RuntimeError(f"solve_power_flow: the plan is for (n, e, mode) = {(plan.n, plan.e, plan.mode) if isinstance(plan, SparsePlan) else plan!r}; "
                                f"the call has {(n, e, mode)}")
         if plan.blob.device != dev:
             raise RuntimeError(f"solve_power_flow: the plan lives on {plan.blob.device}, the inputs on {dev}")
-        need = int(lib.pfn_powerflow_sparse_workspace_bytes(S, C.addressof(plan.header))) if S else 0
+        sizer, launch, what = ((lib.pfn_powerflow_sparse_fd_workspace_bytes, lib.pfn_powerflow_solve_sparse_fd, "pfn_powerflow_solve_sparse_fd") if fd
+                               else (lib.pfn_powerflow_sparse_workspace_bytes, lib.pfn_powerflow_solve_sparse, "pfn_powerflow_solve_sparse"))
+        need = int(sizer(S, C.addressof(plan.header))) if S else 0
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            L.check(lib.pfn_powerflow_solve_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), S, n,
-                                                   _MODES[mode], float(tol), int(max_iter), C.addressof(plan.header), plan.blob.data_ptr(),
-                                                   int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(), flags.data_ptr(),
-                                                   ws.data_ptr(), need, L.stream_ptr()),
-                    "pfn_powerflow_solve_sparse")
+            L.check(launch(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), S, n,
+                           _MODES[mode], float(tol), int(max_iter), C.addressof(plan.header), plan.blob.data_ptr(),
+                           int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(), flags.data_ptr(),
+                           ws.data_ptr(), need, L.stream_ptr()),
+                    what)
         return PowerFlowResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
                                residual=residual, flags=flags, route="sparse")
     if plan is not None:

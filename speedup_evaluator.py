@@ -10,7 +10,7 @@ time in a commented-out block; here every row is one batched `solve_power_flow` 
     `Loss result_init` (Masked_L2 of the normalised NR-from-prediction table against the normalised NR-flat table, the samples'
     prediction mask).
 
-    python speedup_evaluator.py --case 118 --data-dir data [--run-id <id>] [--samples 1000] [--split .5 .2 .3] [--cfg_json configs/standard.json]
+    python speedup_evaluator.py --case 118 --data-dir data [--run-id <id>] [--samples 1000] [--split .5 .2 .3] [--route sparse] [--cfg_json configs/standard.json]
 
 Per method: seconds per sample -- DEVICE time around the call from HIP events, one warm-up call excluded, median of 5 --, the
 solves used (mean and max over the converged samples; half-iterations in the fast-decoupled rows) and the failures.  tol 1e-8;
@@ -19,9 +19,10 @@ with `<data-dir>/params/data_params_<run-id>.pt` where it exists); without `--ru
 the output says so -- the "from the prediction" rows then show what a bad start costs, not what a trained model saves.  The
 solver inputs are read as dc_error.py reads them.  No plots.
 
-A case with more unknowns than the dense solver takes (6470rte) runs its NR and DC rows on the sparse route
-(csrc/powerflow_sparse.hip; one plan per mode, built before the timing); the fast-decoupled rows print `n/a (dense only)`: their
-inverses are dense."""
+A case with more unknowns than the dense solver takes (6470rte) runs every solver row on the sparse route (csrc/powerflow_sparse.hip
+for NR and DC, csrc/powerflow_sparse_fd.hip for the fast-decoupled rows, which keep the sparse factors of B' and B'' instead of
+their dense inverses); `--route sparse` forces that route at any size.  One plan per kind -- "ac", "dc" and one "fd" plan for the
+four fast-decoupled rows -- is built once, before the timing."""
 import os
 import sys
 
@@ -54,10 +55,13 @@ def device_seconds(fn, repeats=REPEATS):
     return float(np.median(times)), out
 
 
-def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, xy=None, split=(.5, .2, .3)):
+def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, xy=None, split=(.5, .2, .3), route="auto"):
     """The rows as a dict: name -> {"seconds_per_sample", "solves_mean", "solves_max", "failures"} for the solver rows,
     "GNN" -> {"seconds_per_sample"}, and the two losses.  `xy`: (xymean, xystd, edgemean, edgestd) saved with the run, None: the
-    split's own.  `split`: the train / val / test fractions (they must cover the set, as `PowerFlowData` demands)."""
+    split's own.  `split`: the train / val / test fractions (they must cover the set, as `PowerFlowData` demands).  `route`: "auto"
+    (the sparse route where the case is beyond the dense solver) or "sparse"; "route" in the result says which ran."""
+    if route not in ("auto", "sparse"):
+        raise ValueError(f"speedup_evaluator: route must be 'auto' or 'sparse', not {route!r}")
     import torch
     import dc_error
     from poweflownet_amd.data import DataLoader
@@ -73,13 +77,14 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     spec, ei, rx = dc_error.solver_inputs(node, edge, device)
     # beyond the dense solver: the sparse route, one line list for all samples and one plan per mode
-    sparse = (node.shape[1] - 1) + int((node[0, :, 1] == 2).sum()) > max_unknowns()
+    sparse = route == "sparse" or (node.shape[1] - 1) + int((node[0, :, 1] == 2).sum()) > max_unknowns()
     plans = {}
     if sparse:
         if not bool((edge[:, :, :2] == edge[:1, :, :2]).all()):
-            raise RuntimeError("speedup_evaluator: a case beyond the dense solver needs one line list for all samples (the sparse route)")
+            raise RuntimeError("speedup_evaluator: the sparse route needs one line list for all samples")
         ei = ei[0].contiguous()
-        plans = {mode: sparse_plan(bus_type, ei, mode) for mode in ("ac", "dc")}
+        plans = {mode: sparse_plan(bus_type, ei, mode) for mode in ("ac", "dc", "fd")}
+        plans["fdxb"] = plans["fdbx"] = plans["fd"]
     # ---- the model: the de-normalised prediction table of the whole split (rows in file order), then its forward alone
     loader = DataLoader(testset, batch_size=batch_size, shuffle=False)
     pred = bus_error_epoch(model, loader, device, xymean=testset.xymean, xystd=testset.xystd, keep_errors=False, keep_predictions=True)
@@ -98,9 +103,6 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     for name, mode, start in (("nr", "ac", None), ("nr_result_init", "ac", init), ("fdxb", "fdxb", None), ("fdbx", "fdbx", None),
                               ("fdxb_result_init", "fdxb", init), ("fdbx_result_init", "fdbx", init), ("dc", "dc", None)):
         iters = FD_ITERS if mode.startswith("fd") else NR_ITERS
-        if sparse and mode.startswith("fd"):
-            rows[name] = None                                  # n/a: dense only
-            continue
         kw = {"route": "sparse", "plan": plans[mode]} if sparse else {}
         sec, res = device_seconds(lambda: solve_power_flow(bus_type, spec, ei, rx, mode=mode, tol=TOL, max_iter=iters, init=start, **kw))
         status = res.status.cpu().numpy()
@@ -117,14 +119,13 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     losses = [float(loss_fn(a[s], b[s], mask)) for s in range(S) if both[s]]
     rows["loss_result_init"] = float(np.mean(losses)) if losses else float("nan")
     rows["samples"] = S
+    rows["route"] = "sparse" if sparse else "dense"
     return rows
 
 
 def report(rows):
     def solver(name):
         r = rows[name]
-        if r is None:
-            return [f"{name}: n/a (dense only)"]
         return [f"{name}: {r['seconds_per_sample']}",
                 f"{name} solves: mean {r['solves_mean']:.3f} max {r['solves_max']} failures {r['failures']}"]
     lines = ["", "", "===========================================", "Results with auto_init:", ""]
@@ -144,6 +145,7 @@ def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     run_id = _take(argv, "--run-id")
     samples = int(_take(argv, "--samples", default=1000))
+    route = _take(argv, "--route", default="auto")
     split = (.5, .2, .3)
     if "--split" in argv:
         i = argv.index("--split")
@@ -170,8 +172,10 @@ def main(argv=None):
             xy = tuple(p[k] for k in ("xymean", "xystd", "edgemean", "edgestd"))
     else:
         print("no --run-id: the model keeps its RANDOM initialisation; the rows that start from its prediction show a bad start")
-    rows = evaluate(args.data_dir, args.case, model, samples, device, args.batch_size, xy, split)
+    rows = evaluate(args.data_dir, args.case, model, samples, device, args.batch_size, xy, split, route)
     print(f"Number of samples: {rows['samples']}")
+    if rows["route"] == "sparse":
+        print("Solved on the sparse route")
     for line in report(rows):
         print(line)
     return 0

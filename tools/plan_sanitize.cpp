@@ -1,6 +1,7 @@
 // Stand-alone AddressSanitizer / UBSan check of the sparse power-flow plan builder (csrc/powerflow_plan.cpp): its own main, linked
 // against the builder's translation unit alone (tools/plan_sanitize.sh), no GPU and no Python.  Random trees plus chords with
-// parallel lines and self-pairs at several sizes, both modes, an exact-size and a too-small buffer, and the error paths.
+// parallel lines and self-pairs at several sizes, both modes and the fast-decoupled plan, an exact-size and a too-small buffer, and
+// the error paths.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -57,8 +58,27 @@ int main() {
             CHECK(pfn_powerflow_sparse_plan(ei.data(), e, bt.data(), n, mode, blob.data(), need - 1) == PFN_EINVAL);
             printf("n %d e %d mode %d: plan of %zu bytes\n", n, e, mode, need);
         }
+        {                                                                                         // the fast-decoupled plan: two sub-plans in one blob
+            const size_t need = pfn_powerflow_sparse_fd_plan_bytes(ei.data(), e, bt.data(), n);
+            CHECK(need > 0);
+            std::vector<unsigned char> blob(need), again(need);
+            CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, bt.data(), n, blob.data(), need) == PFN_OK);
+            CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, bt.data(), n, again.data(), need) == PFN_OK);
+            CHECK(blob == again);
+            CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, bt.data(), n, blob.data(), need - 1) == PFN_EINVAL);
+            std::vector<int32_t> no_pq(bt);                                                       // an empty Q half
+            for (int i = 1; i < n; ++i) no_pq[i] = 1;
+            const size_t need0 = pfn_powerflow_sparse_fd_plan_bytes(ei.data(), e, no_pq.data(), n);
+            CHECK(need0 > 0 && need0 <= need);
+            std::vector<unsigned char> blob0(need0);
+            CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, no_pq.data(), n, blob0.data(), need0) == PFN_OK);
+            printf("n %d e %d fd: plan of %zu bytes (%zu without a PQ bus)\n", n, e, need, need0);
+        }
         if (e > 0) {
             std::vector<unsigned char> blob(1 << 16);
+            ei[e - 1] = n;
+            CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, bt.data(), n, blob.data(), blob.size()) == PFN_EINVAL);
+            CHECK(pfn_powerflow_sparse_fd_plan_bytes(ei.data(), e, bt.data(), n) == 0);
             ei[e - 1] = n;
             CHECK(pfn_powerflow_sparse_plan(ei.data(), e, bt.data(), n, 0, blob.data(), blob.size()) == PFN_EINVAL);
             ei[e - 1] = -1;

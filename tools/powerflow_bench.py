@@ -9,11 +9,16 @@ the start a good prediction would give).
 
     python tools/powerflow_bench.py [--samples 4096] [--repeats 5] [--cpu-samples 16]
     python tools/powerflow_bench.py --route sparse [--case 118 --case 130,200 --case 600,835 --case 6470rte] [--samples 4096]
+    python tools/powerflow_bench.py --route sparse --mode fdxb [--mode fdbx] [--case ...]
 
 `--route sparse`: the sparse route (csrc/powerflow_sparse.hip) per `--case` column (a case name or "n,e"; default 118, 130,200,
 600,835 and 6470rte): the plan's fill, multiply-adds per factor, size and HOST build time, then ms and ms per sample of the solve
 with 64 and with 256 threads per sample and what the default takes, the mean and maximum solve count, and -- where the shape is
 under the dense cap -- the dense global route beside it.  6470rte runs 64 samples and `--big-samples` (default 512).
+`--mode` (repeatable; default ac and dc): `fdxb` / `fdbx` are the fast-decoupled modes on that route (csrc/powerflow_sparse_fd.hip):
+one "fd" plan, reported per half (B' and B'': unknowns, fill, multiply-adds of the one-time factor, longest column), its host build
+time, then the same timing rows with max_iter 60 HALF-iterations (mean and maximum count), and `factor_only`: the same launch with
+max_iter 0, which assembles and factors both matrices and forms one mismatch -- the one-time share of the solve.
 
 Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
 max_iter 10 (the defaults).  One JSON line."""
@@ -57,16 +62,23 @@ def sparse_rows(a):
             ei, bt, rx, spec = make_physical_inputs(n, e, samples, seed=0)
             d = [t.to(dev) for t in (bt, spec, ei, rx)]
             out = {"buses": n, "lines": e, "samples": samples}
-            for mode in ("ac", "dc"):
+            for mode in a.mode or ["ac", "dc"]:
+                fd = mode.startswith("fd")
+                iters = 60 if fd else 10
                 plan = sparse_plan(d[0], d[2], mode)
                 out[f"{mode}_plan"] = {"unknowns": plan.m, "nnz_l": plan.nnz_l, "slab_positions": plan.nnz, "longest_column": plan.max_col,
                                        "multiply_adds_per_factor": plan.madds, "plan_bytes": plan.bytes,
                                        "factor_bytes_per_sample": 4 * plan.nnz, "host_build_ms": round(1e3 * plan.build_s, 2)}
-                runs = [("sparse_64", "sparse", 64), ("sparse_256", "sparse", 256), ("sparse_default", "sparse", 0)]
-                if plan.m <= max_unknowns():
-                    runs.append(("dense_global", "global", 0))
-                for name, route, threads in runs:
-                    per, last = _timed(lambda: PF._solve(*d, mode, 1e-8, 10, route, None, plan if route == "sparse" else None, threads),
+                if fd:
+                    out[f"{mode}_plan"]["halves"] = {name: {"unknowns": m, "slab_positions": nnz, "nnz_l": nnz_l, "multiply_adds_of_the_factor": madds,
+                                                            "longest_column": col} for name, (m, nnz, nnz_l, madds, col) in zip(("B'", "B''"), plan.halves)}
+                runs = [("sparse_64", "sparse", 64, iters), ("sparse_256", "sparse", 256, iters), ("sparse_default", "sparse", 0, iters)]
+                if fd:
+                    runs.append(("factor_only", "sparse", 0, 0))
+                if plan.m + plan.m_q <= max_unknowns():
+                    runs.append(("dense_global", "global", 0, iters))
+                for name, route, threads, max_iter in runs:
+                    per, last = _timed(lambda: PF._solve(*d, mode, 1e-8, max_iter, route, None, plan if route == "sparse" else None, threads),
                                        1 if big else a.repeats)
                     status = last.status.cpu().numpy()
                     ms = 1e3 * float(np.median(per))
@@ -88,6 +100,8 @@ def main():
     ap.add_argument("--route", default=None, choices=("sparse",), help="the sparse route's table instead of the dense rows")
     ap.add_argument("--case", action="append", default=None, help="with --route sparse: a case name or n,e (repeatable)")
     ap.add_argument("--big-samples", type=int, default=512, help="with --route sparse: the large batch of a case beyond 2000 buses")
+    ap.add_argument("--mode", action="append", default=None, choices=("ac", "dc", "fdxb", "fdbx"),
+                    help="with --route sparse: the modes to run (repeatable; default ac and dc)")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
