@@ -26,19 +26,18 @@
 // elimination keeps that) and stay resident together; a half-iteration is then a mat-vec, theta -= B'^-1 (dP / Vm) or
 // Vm -= B''^-1 (dQ / Vm), one owner per row, with no sequential chain and one barrier.  The FD template instantiation carries that
 // code; the Newton / DC instantiation does not pay registers for it.
+//
+// What this kernel shares with the sparse routes -- the status codes, the start state, the line-end terms, the stopping rule, the
+// table write-back, the argument checks -- is powerflow_common.hpp's.
 #include <algorithm>
 
-#include "pfn_internal.hpp"
+#include "powerflow_common.hpp"
 
 namespace pfn {
 
 constexpr int PF_MAX_UNKNOWNS = 1024;              // dense cap of the global route: 4 MiB per sample, 3.6e8 multiply-adds per factor
 constexpr int PF_SMALL_THREADS = 256, PF_BIG_THREADS = 1024;
 constexpr int PF_BIG_M = 90;                       // 4 m^2 beyond ~32 KiB: few workgroups per CU, so each gets 16 waves
-constexpr float PF_TINY_PIVOT = 1e-30f;            // |pivot| <= this (or NaN): singular
-constexpr double PF_RAD = 3.14159265358979323846 / 180.0;
-
-enum { PF_NOT_CONVERGED = -1, PF_SINGULAR = -2, PF_NON_FINITE = -3, PF_BAD_LINE = -4, PF_BAD_TYPES = -5 };
 
 __host__ __device__ inline int pf_ld(int m) { return m | 1; }
 // the sample's vectors: double vm, th, sp, sq [n], F [m]; int aidx, vidx [n]; rounded to 16 bytes
@@ -47,32 +46,9 @@ __host__ __device__ inline size_t pf_mat_floats(int m) { return ((size_t)m * pf_
 __host__ __device__ inline size_t pf_fd_extra_bytes(int m) { return ((size_t)8 * m + 15) & ~(size_t)15; }      // modes 2, 3: F / Vm [m]
 
 struct PfArgs {
-    const int64_t* edge_index;
-    const double* rx;
-    const int32_t* bus_type;
-    const double* spec;
-    double* table;
-    int32_t* status;
-    double* residual;
-    int32_t* flags;
-    float* slab;
-    const double* init;                             // [S, n, 2] = (Vm, Va in degrees) or null: the flat start
-    double tol;
-    int n, e, m, n_pv, n_pq, mode, max_iter, lines_per_sample;
+    PfProblem p;                                    // (p.ws: the global route's fp32 slabs)
+    int m, n_pv, n_pq, mode, lines_per_sample;
 };
-
-// max over the workgroup (max is exact: the order does not matter); every thread calls it
-__device__ __forceinline__ double pf_block_max(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    double r = red[0];
-    for (int w = 1; w < nw; ++w) r = fmax(r, red[w]);
-    __syncthreads();
-    return r;
-}
 
 // B (mm x mm, leading dimension ld) becomes its inverse, in place: Gauss-Jordan without pivoting, two barriers per column.  Every
 // thread calls it; false (uniform: all threads read the same pivot) when a pivot is tiny or NaN.
@@ -106,7 +82,8 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     __shared__ int s_piv, s_ok, s_slack;
     const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
     const int s = blockIdx.x;
-    const int n = a.n, e = a.e, m = a.m, ld = pf_ld(m);
+    const PfProblem& p = a.p;
+    const int n = p.n, e = p.e, m = a.m, ld = pf_ld(m);
     const bool dc = !FD && a.mode == 1;
     const int mp = n - 1, mq = a.n_pq, ldp = pf_ld(mp), ldq = pf_ld(mq);      // FD: B' [mp x mp], B'' [mq x mq] behind it
     double* vm = reinterpret_cast<double*>(pf_smem);
@@ -119,16 +96,14 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     double* G = reinterpret_cast<double*>(pf_smem + pf_vec_bytes(n, m));      // FD only: F / Vm [m]
     float* A;
     if constexpr (LDS) A = reinterpret_cast<float*>(pf_smem + pf_vec_bytes(n, m) + (FD ? pf_fd_extra_bytes(m) : 0));
-    else A = a.slab + (size_t)s * (FD ? pf_mat_floats(mp) + pf_mat_floats(mq) : pf_mat_floats(m));
+    else A = static_cast<float*>(p.ws) + (size_t)s * (FD ? pf_mat_floats(mp) + pf_mat_floats(mq) : pf_mat_floats(m));
     float* Bq = A + pf_mat_floats(mp);
-    const double* init = a.init ? a.init + (int64_t)s * 2 * n : nullptr;
-    const int64_t* ei = a.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
-    const double* rx = a.rx + (int64_t)s * 2 * e;
-    const double* spec = a.spec + (int64_t)s * 4 * n;
-    double* out = a.table + (int64_t)s * 4 * n;
-    const double nanv = __builtin_nan("");
+    const PfSample sm = pf_sample(p, s);
+    const int64_t* ei = p.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
+    const double* rx = sm.rx;
+    const double* spec = sm.spec;
     int code = 0;                                   // (uniform over the workgroup wherever it is tested)
-    double res = nanv;
+    double res = __builtin_nan("");
 
     // ---- the lines name buses of the grid?  (an id outside [0, n) is never followed)
     int bad = 0;
@@ -137,7 +112,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     if (t == 0) {
         int na = 0, nv = 0, ns = 0, npv = 0, npq = 0, odd = 0, slack = 0;
         for (int i = 0; i < n; ++i) {
-            const int ty = a.bus_type[i];
+            const int ty = p.bus_type[i];
             int ia = -1, iv = -1;
             if (ty == 0) { ++ns; slack = i; }
             else if (ty == 1) { ++npv; ia = na++; }
@@ -152,29 +127,13 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     bad = __syncthreads_or(bad);
     if (!s_ok) {
         code = PF_BAD_TYPES;
-        if (t == 0) a.flags[0] = a.flags[0] | 1;    // (every writer stores the same bit over the same word)
+        if (t == 0) p.flags[0] = p.flags[0] | 1;    // (every writer stores the same bit over the same word)
     } else if (bad) {
         code = PF_BAD_LINE;
     }
 
     int it = 0;
-    if (code == 0) {
-        // ---- flat start, or the caller's: Va at the non-slack buses, Vm at the PQ buses (mode 1: Va only -- its Vm is no unknown)
-        const double th0 = spec[4 * s_slack + 1] * PF_RAD;
-        int wild = 0;
-        for (int i = t; i < n; i += nt) {
-            const int ty = a.bus_type[i];
-            double v = ty == 2 ? 1.0 : spec[4 * i], ang = th0;
-            if (init) {
-                if (ty == 2 && !dc) v = init[2 * i];
-                if (ty != 0) ang = init[2 * i + 1] * PF_RAD;
-                wild |= !(fabs(v) < __builtin_inf()) || !(fabs(ang) < __builtin_inf());
-            }
-            vm[i] = v;
-            th[i] = ang;
-        }
-        if (__syncthreads_or(wild)) code = PF_NON_FINITE;
-    }
+    if (code == 0 && pf_start_state(p, sm, s_slack, dc, nt, vm, th)) code = PF_NON_FINITE;
     if (code == 0) {
         int half = 0;                               // FD: 0 the P half comes next, 1 the Q half
         for (;; ++it) {
@@ -197,32 +156,25 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
                         const int j = side ? la : lb;
                         const int ca = aidx[j], cv = vidx[j];
                         if (dc) {
-                            const double b = -1.0 / x;
-                            sP += b * (ti - th[j]);
+                            const double b = pf_dc_end(x, ti, th[j], sP);
                             dPt += b;
                             if (ra >= 0 && ca >= 0) A[ra * ld + ca] += (float)(-b);
                             continue;
                         }
-                        const double d = r * r + x * x, g = r / d, b = -x / d;
-                        const double vj = vm[j], vv = vi * vj;
-                        double sn, cs;
-                        sincos(ti - th[j], &sn, &cs);
-                        const double t1 = vv * cs - vi * vi, t2 = vv * sn;
-                        sP += g * t1 + b * t2;
-                        sQ += g * t2 - b * t1;
+                        const PfEnd end = pf_ac_end(r, x, vi, ti, vm[j], th[j], sP, sQ);
                         if constexpr (FD) continue;
-                        const double pti = vv * (b * cs - g * sn), qti = vv * (g * cs + b * sn);
-                        dPt += pti;
-                        dPv += g * (vj * cs - 2.0 * vi) + b * vj * sn;
-                        dQt += qti;
-                        dQv += g * vj * sn - b * (vj * cs - 2.0 * vi);
+                        const PfEndJac J = pf_ac_end_jac(end, vi);
+                        dPt += J.pti;
+                        dPv += J.pvi;
+                        dQt += J.qti;
+                        dQv += J.qvi;
                         if (ra >= 0) {
-                            if (ca >= 0) A[ra * ld + ca] += (float)(-pti);
-                            if (cv >= 0) A[ra * ld + cv] += (float)(vi * (g * cs + b * sn));
+                            if (ca >= 0) A[ra * ld + ca] += (float)(-J.pti);
+                            if (cv >= 0) A[ra * ld + cv] += (float)J.pvj;
                         }
                         if (rv >= 0) {
-                            if (ca >= 0) A[rv * ld + ca] += (float)(-qti);
-                            if (cv >= 0) A[rv * ld + cv] += (float)(vi * (g * sn - b * cs));
+                            if (ca >= 0) A[rv * ld + ca] += (float)(-J.qti);
+                            if (cv >= 0) A[rv * ld + cv] += (float)J.qvj;
                         }
                     }
                 }
@@ -253,14 +205,11 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
             __syncthreads();
             // ---- max |F| in fp64; a non-finite entry counts as +inf
             double mx = 0.0;
-            for (int k = t; k < m; k += nt) {
-                const double f = fabs(F[k]);
-                mx = fmax(mx, f < __builtin_inf() ? f : __builtin_inf());
-            }
-            res = pf_block_max(mx, s_red);
-            if (!(res < __builtin_inf())) { code = PF_NON_FINITE; break; }
-            if (res < a.tol) break;
-            if (it >= a.max_iter) { code = PF_NOT_CONVERGED; break; }
+            for (int k = t; k < m; k += nt) mx = fmax(mx, pf_abs_clamped(F[k]));
+            res = pf_block_max(mx, s_red, nw);
+            const int stop = pf_stop(res, p.tol, it, p.max_iter);
+            if (stop < 0) { code = stop; break; }
+            if (stop) break;
             if constexpr (FD) {
                 if (it == 0) {
                     // ---- B' and B'', once: Laplacians of the stored lines (parallel lines add, a self-loop cancels), bus i's rows
@@ -367,22 +316,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
         }
     }
 
-    // ---- the table: slack P, Q and PV Q are the aggregated line sums of the last pass; a failed sample's rows are NaN
-    for (int i = t; i < n; i += nt) {
-        double4 row = make_double4(nanv, nanv, nanv, nanv);
-        if (code == 0) {
-            const int ty = a.bus_type[i];
-            row.x = vm[i];
-            row.y = ty == 0 ? spec[4 * i + 1] : th[i] * (1.0 / PF_RAD);
-            row.z = ty == 0 ? sp[i] : spec[4 * i + 2];
-            row.w = dc ? nanv : (ty == 2 ? spec[4 * i + 3] : sq[i]);
-        }
-        *reinterpret_cast<double4*>(out + 4 * i) = row;
-    }
-    if (t == 0) {
-        a.status[s] = code ? code : it;
-        a.residual[s] = res;
-    }
+    pf_write_back(p, sm, s, dc, nt, code, it, res, vm, th, sp, sq);
 }
 
 static int pf_unknowns(int64_t n, int64_t n_pq, int mode) { return (int)((n - 1) + (mode == 1 ? 0 : n_pq)); }
@@ -431,47 +365,21 @@ int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, in
                   (long long)n_pq, (long long)n_bus);
     PFN_CHECK_ARG(mode >= 0 && mode <= 3, "pfn_powerflow_solve: mode must be 0 (AC), 1 (DC), 2 (fast-decoupled XB) or 3 (fast-decoupled BX)");
     PFN_CHECK_ARG(route >= 0 && route <= 2, "pfn_powerflow_solve: route must be 0 (auto), 1 (LDS) or 2 (global)");
-    PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "pfn_powerflow_solve: max_iter must be >= 0 and tol > 0");
     const bool fd = mode >= 2;
     const int64_t m64 = (n_bus - 1) + (mode == 1 ? 0 : n_pq);      // equations; modes 2, 3 hold no matrix of that order: their larger one is n_bus - 1
     PFN_CHECK_ARG((fd ? n_bus - 1 : m64) <= PF_MAX_UNKNOWNS,
                   "pfn_powerflow_solve: %lld unknowns per sample exceed the dense solver's %d; a sparse factorisation is needed (pfn_powerflow_solve_sparse, route \"sparse\")",
                   (long long)(fd ? n_bus - 1 : m64), PF_MAX_UNKNOWNS);
-    if (n_samples == 0) return PFN_OK;
-    PFN_CHECK_ARG(rx || n_lines == 0, "pfn_powerflow_solve: null rx");
-    PFN_CHECK_ARG(edge_index || n_lines == 0, "pfn_powerflow_solve: null edge_index");
-    PFN_CHECK_ARG(bus_type && spec && table && status && residual && flags, "pfn_powerflow_solve: null pointer");
-    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(table) & 31) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(spec) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(edge_index) |
-                        reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(init)) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(bus_type) | reinterpret_cast<uintptr_t>(status) | reinterpret_cast<uintptr_t>(flags)) & 3) == 0,
-                  "pfn_powerflow_solve: table must be 32-byte aligned, the workspace 16-byte, fp64 and int64 inputs 8-byte, int32 arrays 4-byte");
     const int n = (int)n_bus, m = (int)m64;
+    PfArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, (int)n_lines, max_iter},
+             m, (int)n_pv, (int)n_pq, mode, lines_per_sample != 0};
+    PFN_TRY(pf_check_call("pfn_powerflow_solve", a.p, n_samples, nullptr, "the workspace 16-byte"));
+    if (n_samples == 0) return PFN_OK;
     const size_t lds_need = fd ? pf_fd_lds_bytes(n, (int)n_pq) : pf_vec_bytes(n, m) + pf_mat_floats(m) * 4;
     const bool fits = fd ? pf_fd_fits_lds(n, (int)n_pq) : pf_fits_lds(n, m);
     PFN_CHECK_ARG(route != 1 || fits, "pfn_powerflow_solve: route 1 (LDS): %d unknowns of %d buses need %zu bytes of LDS, %d are there", m, n,
                   lds_need, kLdsCuBytes - kLdsReserve);
     const bool lds = route == 1 || (route == 0 && fits);
-    PfArgs a;
-    a.edge_index = edge_index;
-    a.rx = rx;
-    a.bus_type = bus_type;
-    a.spec = spec;
-    a.table = table;
-    a.status = status;
-    a.residual = residual;
-    a.flags = flags;
-    a.slab = nullptr;
-    a.init = init;
-    a.tol = tol;
-    a.n = n;
-    a.e = (int)n_lines;
-    a.m = m;
-    a.n_pv = (int)n_pv;
-    a.n_pq = (int)n_pq;
-    a.mode = mode;
-    a.max_iter = max_iter;
-    a.lines_per_sample = lines_per_sample != 0;
     const size_t mat_floats = fd ? pf_fd_mat_floats(n, (int)n_pq) : pf_mat_floats(m);
     if (!lds) {
         const size_t need = (size_t)n_samples * mat_floats * sizeof(float);
@@ -479,7 +387,6 @@ int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, in
             set_error("pfn_powerflow_solve: the global route needs a workspace of %zu bytes (got %zu)", need, ws ? ws_bytes : (size_t)0);
             return PFN_ENOSPACE;
         }
-        a.slab = static_cast<float*>(ws);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int big = fd ? std::max(n - 1, (int)n_pq) : m;            // the rule of the one matrix, applied to the larger of the two

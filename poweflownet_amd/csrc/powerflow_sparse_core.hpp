@@ -1,37 +1,14 @@
 // The numeric core of a sparse power-flow kernel as workgroup-wide device functions over one planned matrix (powerflow_plan.hpp):
-// the left-looking column factorisation in fp32, the forward and backward substitutions on an fp64 right-hand side, and the
-// block-wide max.  Two kernels share them: the Newton / DC kernel (powerflow_sparse.hip), which factors and substitutes once per
+// the left-looking column factorisation in fp32 and the forward and backward substitutions on an fp64 right-hand side (the matrix
+// view PfcMatrix, the pivot threshold and everything a kernel does around them are powerflow_common.hpp's).  Two kernels share them: the Newton / DC kernel (powerflow_sparse.hip), which factors and substitutes once per
 // pass, and the fast-decoupled kernel (powerflow_sparse_fd.hip), which factors two matrices once and substitutes many times.
 //
 // Every function is called by ALL threads of the workgroup with the same arguments; every loop bound comes from the plan, so every
 // barrier inside is reached by all of them.  One owner per target per step; no float atomics.
 #pragma once
-#include "pfn_internal.hpp"
+#include "powerflow_common.hpp"
 
 namespace pfn {
-
-constexpr float PFC_TINY_PIVOT = 1e-30f;           // (powerflow.hip PF_TINY_PIVOT)
-
-// one planned matrix: the sections of a (sub-)plan the numeric loops read, and its order
-struct PfcMatrix {
-    const int32_t* colptr;
-    const int32_t* diag;
-    const uint16_t* row;
-    int m;
-};
-
-template <int THREADS>
-__device__ __forceinline__ double pfc_block_max(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = red[0];
-#pragma unroll
-    for (int w = 1; w < THREADS / 64; ++w) r = fmax(r, red[w]);
-    __syncthreads();
-    return r;
-}
 
 // slab (global, this sample's) holds A at the planned positions on entry, U (with its diagonal) and the L parts times 1 / pivot on
 // exit.  w: m floats of LDS.  Returns false -- for all threads alike -- at a pivot that is tiny or NaN; the slab is then half done.
@@ -86,7 +63,7 @@ __device__ __forceinline__ bool pfc_factor(const PfcMatrix A, float* slab, float
             }
         }
         const float piv = w[j];
-        if (!(fabsf(piv) > PFC_TINY_PIVOT)) return false;
+        if (!(fabsf(piv) > PF_TINY_PIVOT)) return false;
         const float pinv = 1.f / piv;
         for (int i = c0 + t; i < c1; i += nt) {
             const float v = w[row[i]];

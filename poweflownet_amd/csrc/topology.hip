@@ -26,7 +26,7 @@
 namespace pfn {
 
 constexpr int TP_MAX_ATTEMPTS = 1024;
-enum { TP_NO_DRAW = -1, TP_BAD_LINE = -4 };        // (-4: powerflow.hip's PF_BAD_LINE)
+enum { TP_NO_DRAW = -1, TP_BAD_LINE = -4 };        // (-4: powerflow_common.hpp's PF_BAD_LINE)
 
 struct TpArgs {
     const int64_t* edge_index;   // [2, e] base list (perturb) / [2, e] or [S, 2, e] (unsupplied)

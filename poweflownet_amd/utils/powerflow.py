@@ -11,6 +11,7 @@ import torch
 
 from .. import _lib as L
 
+# the texts of csrc/powerflow_common.hpp's status enum (PF_NOT_CONVERGED ... PF_STALE_PLAN), which every route's kernel writes
 STATUS = {-1: "not converged in max_iter", -2: "singular Jacobian", -3: "non-finite mismatch", -4: "a line names a bus outside the grid",
           -5: "bus_type disagrees with the counts the launch was sized for",
           -6: "the sparse plan was built from another line list or other bus types"}

@@ -11,10 +11,8 @@ with tests/branch_ref.py's C_BOUND, EPS and per-line scales as they stand) and t
 Worst ratios measured on an MI355X (bound 1; each test prints its own): residual 0.85 at (14, 20, 64), 3.4e-4 at m = 115 and m = 195;
 distance to the yardstick's solution 5.8e-3; DC 0.022 / 7.3e-4; PowerImbalance of the solved table 8.5e-12 against a bound of 3.6e-7
 (flat start 0.48).  3-4 Jacobian solves everywhere, 2 in DC mode.  DESIGN.md section 7h."""
-import contextlib
 import ctypes as C
 import functools
-import io
 
 import numpy as np
 import pytest
@@ -23,16 +21,11 @@ import torch
 from poweflownet_amd import _lib as L
 from poweflownet_amd.synth import make_physical_inputs, make_topology
 from poweflownet_amd.utils.powerflow import solve_power_flow
-from tests import branch_ref as R
 from tests import powerflow_ref as P
+from tests.powerflow_checks import DEV, TOL, _check_given, _dev, _distance, _imbalance_bound, _residual_ratio, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL, MAX_ITER = 1e-10, 10
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+MAX_ITER = 10
 
 
 class _Case:
@@ -75,16 +68,9 @@ def _check_ac(case, res, what):
     assert table.shape == (case.S, case.n, 4) and table.dtype == np.float64 and int(res.flags.item()) == 0
     assert ((status >= 1) & (status <= MAX_ITER)).all(), (what, status)
     assert torch.equal(res.iterations, res.status) and bool((res.residual < TOL).all())
-    worst_f = worst_x = 0.0
-    for s in range(case.S):
-        dp, dq = P.mismatch(table[s], case.ei, case.rx[s])
-        bound = TOL + 64 * P.EPS64 * P.scale(table[s], case.ei, case.rx[s])
-        worst_f = max(worst_f, float((np.maximum(np.abs(dp), np.abs(dq)) / bound).max()))
-        dx = max(np.abs(table[s, :, 0] - case.ref[s, :, 0]).max(), np.abs(table[s, :, 1] - case.ref[s, :, 1]).max() * P.RAD)
-        worst_x = max(worst_x, float(dx / (2 * TOL * case.inv_norm[s])))
-        # what is given comes back as given
-        assert np.array_equal(table[s][case.bt != 2, 0], case.spec[s][case.bt != 2, 0]) and np.array_equal(table[s][case.bt != 0, 2], case.spec[s][case.bt != 0, 2])
-        assert np.array_equal(table[s][case.bt == 2, 3], case.spec[s][case.bt == 2, 3]) and np.array_equal(table[s][case.bt == 0, 1], case.spec[s][case.bt == 0, 1])
+    worst_f = _residual_ratio(case, table)
+    worst_x = max(float(_distance(table[s], case.ref[s]) / (2 * TOL * case.inv_norm[s])) for s in range(case.S))
+    _check_given(case, table)
     print(f"{what}: route {res.route}, solves {status.min()}..{status.max()} (mean {status.mean():.2f}), worst |mismatch| / bound {worst_f:.3g}, "
           f"worst |x - yardstick| / (2 tol ||J^-1||) {worst_x:.3g}")
     assert worst_f <= 1.0 and worst_x <= 1.0, (what, worst_f, worst_x)
@@ -224,20 +210,6 @@ def test_dc_mode(n, e, S, route):
 
 
 # ------------------------------------------------------------------------------- closed loop: the physics kernel
-def _imbalance_bound(table32, ei, rx):
-    """mean over (sample, bus) of 2 (C_BOUND EPS sum of the per-line scales at the bus + EPS (|P_i| + |Q_i|))^2: every line message
-    the physics kernel forms in fp32 is within C_BOUND EPS scale of its exact value (tests/branch_ref.py: the bound the branch-flow
-    kernel is held to for the same expressions), P_i and Q_i carry their own fp32 rounding, and dP^2 + dQ^2 has two such terms."""
-    S, n = table32.shape[:2]
-    _, scales = R.flows(table32, ei, rx)                                       # [S, e, 4]; column 1 = the P / Q scale of the line
-    at_bus = np.zeros((S, n))
-    for s in range(S):
-        np.add.at(at_bus[s], ei[0], scales[s, :, 1])
-        np.add.at(at_bus[s], ei[1], scales[s, :, 1])
-    t = table32.astype(np.float64)
-    return float(np.mean(2 * (R.C_BOUND * R.EPS * at_bus + R.EPS * (np.abs(t[:, :, 2]) + np.abs(t[:, :, 3]))) ** 2))
-
-
 def test_power_imbalance_of_the_solved_table_is_rounding():
     from poweflownet_amd.utils.custom_loss_functions import PowerImbalance
     case = _case(14, 20, 64)
@@ -258,13 +230,6 @@ def test_power_imbalance_of_the_solved_table_is_rounding():
 
 
 # ------------------------------------------------------------------------------------------------------ end to end
-def _run(main, argv):
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        assert main(list(argv)) == 0
-    return out.getvalue()
-
-
 def test_generator_dataset_report_and_dc_error(tmp_path):
     import dataset_generator
     import dc_error

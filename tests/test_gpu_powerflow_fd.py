@@ -11,10 +11,8 @@ that stay local, capture, and speedup_evaluator.py end to end.
 Worst ratios measured on an MI355X (bound 1; each test prints its own): residual 0.985 (fdxb) / 0.982 (fdbx) -- a linearly converging
 iteration stops just under tol --, distance to the Newton yardstick's solution 0.066 / 0.058; half-iterations 14-35 (fdxb) and 13-23
 (fdbx) at the shapes with PQ buses, every range equal to the float64 yardstick's.  DESIGN.md section 7j has the table."""
-import contextlib
 import ctypes as C
 import functools
-import io
 
 import numpy as np
 import pytest
@@ -25,10 +23,10 @@ from poweflownet_amd.synth import make_topology
 from poweflownet_amd.utils.powerflow import solve_power_flow
 from tests import powerflow_fd_ref as FD
 from tests import powerflow_ref as P
-from tests.test_gpu_powerflow import TOL, _case, _dev
+from tests.powerflow_checks import DEV, TOL, _dev, _run
+from tests.test_gpu_powerflow import _case
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 MODES = {"ac": 0, "fdxb": 2, "fdbx": 3}
 FD_MODES = ("fdxb", "fdbx")
 YARDSTICK_CAP = 200                                            # the yardstick's own limit while its worst count is measured
@@ -334,13 +332,6 @@ def test_a_solve_is_capturable(mode, warm):
 
 
 # ------------------------------------------------------------------------------------------------------ end to end
-def _run(main, argv):
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        assert main(list(argv)) == 0
-    return out.getvalue()
-
-
 def test_speedup_evaluator(tmp_path):
     import re
     import dataset_generator

@@ -11,9 +11,7 @@ Worst ratios measured on an MI355X (bound 1; each test prints its own): residual
 m = 1832, 3.9e-4 at m = 10782; distance to the yardstick's solution 1.2e-2, to the dense route's 7.4e-3; DC 0.039 / 3.6e-5;
 PowerImbalance of the generated set 1.1e-12 against a bound of 2.9e-7.  3-4 solves (5 at 6470, in 1.9 s), 2 in DC mode.  DESIGN.md
 section 7k."""
-import contextlib
 import functools
-import io
 import time
 
 import numpy as np
@@ -23,16 +21,11 @@ import torch
 from poweflownet_amd.synth import make_physical_inputs
 from poweflownet_amd.utils import powerflow as PF
 from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
-from tests import branch_ref as R
 from tests import powerflow_ref as P
+from tests.powerflow_checks import DEV, TOL, _check_given, _dev, _distance, _imbalance_bound, _residual_ratio, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL, MAX_ITER = 1e-10, 10
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+MAX_ITER = 10
 
 
 class _Case:
@@ -78,22 +71,6 @@ def _case(n, e, S, seed=1, load=0.2):
     return _Case(n, e, S, seed, load)
 
 
-def _residual_ratio(case, table):
-    worst = 0.0
-    for s in range(table.shape[0]):
-        dp, dq = P.mismatch(table[s], case.ei, case.rx[s])
-        bound = TOL + 64 * P.EPS64 * P.scale(table[s], case.ei, case.rx[s])
-        worst = max(worst, float((np.maximum(np.abs(dp), np.abs(dq)) / bound).max()))
-    return worst
-
-
-def _check_given(case, table):
-    """what is given comes back as given, bit for bit"""
-    for s in range(table.shape[0]):
-        assert np.array_equal(table[s][case.bt != 2, 0], case.spec[s][case.bt != 2, 0]) and np.array_equal(table[s][case.bt != 0, 2], case.spec[s][case.bt != 0, 2])
-        assert np.array_equal(table[s][case.bt == 2, 3], case.spec[s][case.bt == 2, 3]) and np.array_equal(table[s][case.bt == 0, 1], case.spec[s][case.bt == 0, 1])
-
-
 # ------------------------------------------------------------------------------------------------- accuracy
 @pytest.mark.parametrize("n,e,S", [(5, 6, 3), (14, 20, 8), (70, 100, 4), (118, 186, 4)])
 def test_residual_and_solution_against_the_yardstick_and_the_dense_route(n, e, S):
@@ -110,8 +87,7 @@ def test_residual_and_solution_against_the_yardstick_and_the_dense_route(n, e, S
     worst_f, worst_x, worst_d = _residual_ratio(case, table), 0.0, 0.0
     for s in range(S):
         for other, which in ((case.ref[s], "yardstick"), (dense_table[s], "dense")):
-            dx = max(np.abs(table[s, :, 0] - other[:, 0]).max(), np.abs(table[s, :, 1] - other[:, 1]).max() * P.RAD)
-            ratio = float(dx / (2 * TOL * case.inv_norm[s]))
+            ratio = float(_distance(table[s], other) / (2 * TOL * case.inv_norm[s]))
             if which == "dense":
                 worst_d = max(worst_d, ratio)
             else:
@@ -260,19 +236,6 @@ def test_one_sample_of_the_workload_size():
 
 
 # ------------------------------------------------------------------------------------------------------ end to end
-def _imbalance_bound(table32, ei, rx):
-    """mean over (sample, bus) of 2 (C_BOUND EPS sum of the per-line scales at the bus + EPS (|P_i| + |Q_i|))^2: the bound
-    DESIGN 7h holds PowerImbalance of a solved table to (every fp32 line message within C_BOUND EPS scale of its exact value)."""
-    S, n = table32.shape[:2]
-    _, scales = R.flows(table32, ei, rx)
-    at_bus = np.zeros((S, n))
-    for s in range(S):
-        np.add.at(at_bus[s], ei[0], scales[s, :, 1])
-        np.add.at(at_bus[s], ei[1], scales[s, :, 1])
-    t = table32.astype(np.float64)
-    return float(np.mean(2 * (R.C_BOUND * R.EPS * at_bus + R.EPS * (np.abs(t[:, :, 2]) + np.abs(t[:, :, 3]))) ** 2))
-
-
 def test_generator_with_the_route_forced_writes_a_balanced_set(tmp_path):
     import dataset_generator
     from poweflownet_amd.data import DataLoader
@@ -281,10 +244,8 @@ def test_generator_with_the_route_forced_writes_a_balanced_set(tmp_path):
     from poweflownet_amd.utils.custom_loss_functions import PowerImbalance
     from poweflownet_amd.utils.evaluation import evaluate_report
     root, split = str(tmp_path / "solved"), [.5, .25, .25]
-    out = io.StringIO()
-    with contextlib.redirect_stdout(out):
-        assert dataset_generator.main(["--case", "14", "--samples", "16", "--root", root, "--route", "sparse"]) == 0
-    assert "Failed to converge and drawn again: 0" in out.getvalue() and "Solved on the sparse route" in out.getvalue()
+    text = _run(dataset_generator.main, ["--case", "14", "--samples", "16", "--root", root, "--route", "sparse"])
+    assert "Failed to converge and drawn again: 0" in text and "Solved on the sparse route" in text
     node, edge = np.load(tmp_path / "solved" / "raw" / "case14_node_features.npy"), np.load(tmp_path / "solved" / "raw" / "case14_edge_features.npy")
     assert node.shape == (16, 14, 6) and edge.shape == (16, 20, 4) and np.isfinite(node).all()
     ds = PowerFlowData(root=root, case="14", split=split, task="test", device=DEV)

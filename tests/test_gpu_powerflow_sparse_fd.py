@@ -19,9 +19,7 @@ linearly: the last residual lands just under tol); worst distance to the yardsti
 route's 5.4e-6, to sparse Newton's at (1100, 1530) 4.6e-4.  Workload size: the float64 yardstick on the host (B' and B'' inverted
 once, mat-vecs after that) takes 43 half-iterations of fdxb at tol 1e-8 on (6470, 9005), inside 100, and the device takes 43 in
 0.21 s (the test: 0.64 s), so neither case of the (2000, 2784) fallback arose."""
-import contextlib
 import functools
-import io
 import re
 import time
 
@@ -36,15 +34,11 @@ from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, spar
 from tests import powerflow_fd_ref as FD
 from tests import powerflow_ref as P
 from tests import powerflow_sparse_fd_ref as SF
+from tests.powerflow_checks import DEV, TOL, _check_given, _dev, _distance, _residual_ratio, _run
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-TOL, MAX_ITER = 1e-10, 60
+MAX_ITER = 60
 VARIANT = {"fdxb": "xb", "fdbx": "bx"}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
 class _Case:
@@ -94,27 +88,6 @@ class _Case:
 @functools.lru_cache(maxsize=None)
 def _case(n, e, S, seed=1, load=0.2, kind=None):
     return _Case(n, e, S, seed, load, kind)
-
-
-def _residual_ratio(case, table, tol=TOL):
-    worst = 0.0
-    for s in range(table.shape[0]):
-        dp, dq = P.mismatch(table[s], case.ei, case.rx[s])
-        bound = tol + 64 * P.EPS64 * P.scale(table[s], case.ei, case.rx[s])
-        worst = max(worst, float((np.maximum(np.abs(dp), np.abs(dq)) / bound).max()))
-    return worst
-
-
-def _distance(a, b):
-    """max over buses of |dVm| and |dVa| in radians"""
-    return max(np.abs(a[:, 0] - b[:, 0]).max(), np.abs(a[:, 1] - b[:, 1]).max() * P.RAD)
-
-
-def _check_given(case, table):
-    """what is given comes back as given, bit for bit"""
-    for s in range(table.shape[0]):
-        assert np.array_equal(table[s][case.bt != 2, 0], case.spec[s][case.bt != 2, 0]) and np.array_equal(table[s][case.bt != 0, 2], case.spec[s][case.bt != 0, 2])
-        assert np.array_equal(table[s][case.bt == 2, 3], case.spec[s][case.bt == 2, 3]) and np.array_equal(table[s][case.bt == 0, 1], case.spec[s][case.bt == 0, 1])
 
 
 def _check_accuracy(case, mode, res, dense=True):
@@ -379,17 +352,11 @@ def test_one_sample_of_the_workload_size():
 def test_speedup_evaluator_on_the_sparse_route(tmp_path):
     import dataset_generator
     import speedup_evaluator
-
-    def run(main, argv):
-        out = io.StringIO()
-        with contextlib.redirect_stdout(out):
-            assert main(list(argv)) == 0
-        return out.getvalue()
     root = str(tmp_path / "solved")
-    run(dataset_generator.main, ["--case", "14", "--samples", "32", "--root", root])
+    _run(dataset_generator.main, ["--case", "14", "--samples", "32", "--root", root])
     torch.manual_seed(0)
-    text = run(speedup_evaluator.main, ["--case", "14", "--data-dir", root, "--split", "0.5", "0.25", "0.25", "--hidden_dim", "32",
-                                       "--n_gnn_layers", "3", "--K", "2", "--route", "sparse"])
+    text = _run(speedup_evaluator.main, ["--case", "14", "--data-dir", root, "--split", "0.5", "0.25", "0.25", "--hidden_dim", "32",
+                                        "--n_gnn_layers", "3", "--K", "2", "--route", "sparse"])
     print(text)
     assert "n/a" not in text and "Number of samples: 8" in text and "Solved on the sparse route" in text
     value = {}
