@@ -358,13 +358,13 @@ void ea_seg_fwd_kernel(int n, int rows_pb, int trows, int cap, const int* __rest
 // ------------------------------------------------------------------------------------------------ forward, layer 0
 // The network's FRONT (mask_embd + residual, networks/MPN.py:533-537) and the whole first EdgeAggregation edge stage in ONE launch
 // for batches of small graphs -- what front.hip's row-per-wave kernel and the generic edge walk did as two (18.8 + 9.2 us at
-// case118v2 x 128).  Layer 0's node "GEMM" has K = 4: no matrix core, just the front's fma chains.  Block = (whole graph(s), one
+// case118v2 x 128).  Layer 0's node "GEMM" has K = 4: no matrix core, just the front's chains (front_chains.hpp).  Block = (whole graph(s), one
 // 32-column quarter), as everywhere in this file:
 //   * every wave takes rows of the block round-robin, ONE ROW PER WAVE with front_fwd_wave_body's lane = four-unit chunk layout,
-//     weight slices in registers, the same fma chains and the same xor-butterfly row sum -> x0 carries the bits of the front
+//     weight slices in registers, front_chains.hpp's units and the same xor-butterfly row sum -> x0 carries the bits of the front
 //     kernel (all four quarter-blocks of a graph compute it: 2 kFLOP per row; the block of quarter 0 stores x0 and maskf);
 //   * the lanes whose chunk lies in the block's quarter store their me_h units (the backward front reads them), form P | Q of
-//     their chunk from x0 (the front's chains), drop them into the LDS tiles and store them (ea_seg_bwd reads them);
+//     their chunk from x0 (pq_unit), drop them into the LDS tiles and store them (ea_seg_bwd reads them);
 //   * the walk over the incoming edges runs on the tiles exactly as in ea_seg_fwd_kernel (edge attributes through the edge ids:
 //     the slot-ordered copy is written by the pack blocks of this very launch).
 // The weight re-layout ("pack") blocks of the forward pass ride behind the graph blocks, as they did behind the front's.
@@ -449,8 +449,8 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
         s_me[3 * tid + 2] = make_float4(w3_, 0.f, 0.f, 0.f);
     }
     lds_barrier();
-    // ---- x0 = x + bb + Wb relu(Wa mask + ba): FOUR THREADS PER ROW.  The chunk sums a[c] (four hidden units each, an fma chain
-    // from zero) are added in the order of the row-per-wave kernel's xor butterfly (wave_sum4, lane 0's tree:
+    // ---- x0 = x + bb + Wb relu(Wa mask + ba): FOUR THREADS PER ROW.  The chunk sums a[c] (four hidden units each, a chain of
+    // front_chains.hpp's me_unit / wb_step from zero) are added in the order of the row-per-wave kernel's xor butterfly (wave_sum4, lane 0's tree:
     // s[c] = a[c] + a[c + 32]; t = s[c] + s[c + 16]; u = t[c] + t[c + 8]; v = u[c] + u[c + 4]; w = v[c] + v[c + 2]; w[0] + w[1]), so
     // x0 carries the bits that kernel stores: thread p of a row forms v[p], two quad shuffles finish the tree.  (As a butterfly
     // per row in every one of a graph's four blocks the LDS crossbar was the whole kernel: 24 ds_bpermute per row.)
@@ -471,11 +471,7 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
                         const int u = 4 * c + i;
                         if (u < h) {
                             const float4 ra = s_me[3 * u], rb = s_me[3 * u + 1], rc = s_me[3 * u + 2];
-                            float v = rb.x;
-                            v = fmaf(ra.x, m.x, v); v = fmaf(ra.y, m.y, v); v = fmaf(ra.z, m.z, v); v = fmaf(ra.w, m.w, v);
-                            v = fmaxf(v, 0.f);
-                            acc.x = fmaf(rb.y, v, acc.x); acc.y = fmaf(rb.z, v, acc.y);
-                            acc.z = fmaf(rb.w, v, acc.z); acc.w = fmaf(rc.x, v, acc.w);
+                            acc = wb_step(acc, make_float4(rb.y, rb.z, rb.w, rc.x), me_unit(ra, rb.x, m));
                         }
                     }
                 }
@@ -506,13 +502,7 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
         const int lr = tid >> 2;
         const bool on = lr < rows;
         const int row = r0 + min(lr, rows - 1);
-        float4 m;
-        if (f.mask_dtype == 0) {
-            const int64_t* mp = static_cast<const int64_t*>(f.mask) + (size_t)row * 4;
-            m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
-        } else {
-            m = ld4(static_cast<const float*>(f.mask) + (size_t)row * 4);
-        }
+        const float4 m = mask_row4(f.mask, f.mask_dtype, row);
         const float4 xi = ld4(f.x + (size_t)row * 4);
         if (tid < 64) {   // pattern k = tid >> 2: bit j set = mask entry j is 1
             const int k = tid >> 2;
@@ -525,7 +515,7 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
         float4 s4;
         if (b0 && b1 && b2 && b3) s4 = s_tab[(m.x != 0.f ? 1 : 0) | (m.y != 0.f ? 2 : 0) | (m.z != 0.f ? 4 : 0) | (m.w != 0.f ? 8 : 0)];
         else s4 = x0_tree(m);      // (the four threads of a row hold the same mask: the quad takes this branch together)
-        const float4 o = make_float4(xi.x + (s4.x + bb4.x), xi.y + (s4.y + bb4.y), xi.z + (s4.z + bb4.z), xi.w + (s4.w + bb4.w));
+        const float4 o = x0_row(xi, s4, bb4);
         int c1 = 0, c0 = 0;
         if (on && pq == 0) {
             s_x0[lr] = o;
@@ -551,7 +541,7 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
     }
     lds_barrier();
     if (f.mask_counts && by == 0 && tid < 2) f.mask_counts[2 * bx + tid] = s_cnt[tid];
-    // ---- me_h, P | Q of the block's chunks: item = (row, chunk), the row-per-wave kernel's fma chains
+    // ---- me_h, P | Q of the block's chunks: item = (row, chunk), the row-per-wave kernel's me_unit / pq_unit (front_chains.hpp)
     for (int it = tid; it < rows * sc.cw; it += SG_THREADS) {
         const int lr = it / sc.cw, lc = it - lr * sc.cw;
         const int tcw = seg_tcol(sc, lc), gc = seg_gcol(sc, lc), row = r0 + lr;
@@ -561,15 +551,8 @@ void front_seg_fwd_kernel(const FrontFwdArgs f, const PackArgs pa, int nseg_x, i
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float* w14 = wv + i * 14;
-            float v = w14[4];
-            v = fmaf(w14[0], m.x, v); v = fmaf(w14[1], m.y, v); v = fmaf(w14[2], m.z, v); v = fmaf(w14[3], m.w, v);
-            hv[i] = fmaxf(v, 0.f);
-            float pa_ = w14[13];
-            pa_ = fmaf(w14[5], o.x, pa_); pa_ = fmaf(w14[6], o.y, pa_); pa_ = fmaf(w14[7], o.z, pa_); pa_ = fmaf(w14[8], o.w, pa_);
-            float qb = 0.f;
-            qb = fmaf(w14[9], o.x, qb); qb = fmaf(w14[10], o.y, qb); qb = fmaf(w14[11], o.z, qb); qb = fmaf(w14[12], o.w, qb);
-            pv[i] = pa_;
-            qv[i] = qb;
+            hv[i] = me_unit(make_float4(w14[0], w14[1], w14[2], w14[3]), w14[4], m);
+            pq_unit(make_float4(w14[5], w14[6], w14[7], w14[8]), make_float4(w14[9], w14[10], w14[11], w14[12]), w14[13], o, pv[i], qv[i]);
         }
         if (f.me_h) st4_wt(f.me_h + (size_t)row * ld + gc, make_float4(hv[0], hv[1], hv[2], hv[3]));
         const float4 p4 = make_float4(pv[0], pv[1], pv[2], pv[3]), q4 = make_float4(qv[0], qv[1], qv[2], qv[3]);

@@ -678,8 +678,9 @@ __device__ __forceinline__ float dot4(float4 a, float4 b) { return fmaf(a.w, b.w
 // (behind it these loads were one more serial round trip; a load cannot move across __syncthreads by itself)
 struct EdgeRowHead { float4 p4; int beg, end, b4, b4n; };
 // FLY (EdgeFwdArgs::x0): the first layer behind the 4-wide front.  `P` and `Q` are both the N x 4 array x0; the head carries the
-// row's x0 and the walk forms P[row] = b1 + W1i x0[row], Q[src] = W1j x0[src] per chunk with the fma chains of front.hip (same
-// operands, same order: the bits the front would have stored) from weights staged behind the residue weights in LDS.
+// row's x0 and the walk forms P[row] = b1 + W1i x0[row], Q[src] = W1j x0[src] per chunk with front_chains.hpp's chain (chain4_t:
+// four units at once from the transposed weights; same operands, same order: the bits the front would have stored) from weights
+// staged behind the residue weights in LDS.
 template <bool MASK, bool FLY = false>
 __device__ __forceinline__ EdgeRowHead edge_row_head(int row, int col, const int* __restrict__ rowptr, const float* __restrict__ P,
                                                      int ld, const int* __restrict__ rp4) {
@@ -690,13 +691,6 @@ __device__ __forceinline__ EdgeRowHead edge_row_head(int row, int col, const int
     hd.b4 = MASK ? rp4[row] : 0;
     hd.b4n = MASK ? rp4[row + 1] : 0;
     return hd;
-}
-// the front's chains (front.hip): p = b1 + sum_f W1[u][f] x[f], q = sum_f W1[u][4 + f] x[f], f ascending, one fma per term
-__device__ __forceinline__ float4 fly_chain(float4 x, float4 w0, float4 w1, float4 w2, float4 w3, float4 acc) {
-    acc = fma4(x.x, w0, acc);
-    acc = fma4(x.y, w1, acc);
-    acc = fma4(x.z, w2, acc);
-    return fma4(x.w, w3, acc);
 }
 // stages wi [4][ld] | wj [4][ld] | b1 [ld] (zero past H) for the FLY walks
 __device__ __forceinline__ void stage_fly_weights(float* wf, const float* __restrict__ w1, const float* __restrict__ b1, int ld, int h,
@@ -717,7 +711,7 @@ __device__ __forceinline__ float4 edge_sum_chunk(int row, int col, int e_stored,
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (FLY) {
         const float* wf = we + fe * ld;          // wi [4][ld] | wj [4][ld] | b1 [ld]
-        p4 = fly_chain(hd.p4, ld4(wf + col), ld4(wf + ld + col), ld4(wf + 2 * ld + col), ld4(wf + 3 * ld + col), ld4(wf + 8 * ld + col));
+        p4 = chain4_t(hd.p4, ld4(wf + col), ld4(wf + ld + col), ld4(wf + 2 * ld + col), ld4(wf + 3 * ld + col), ld4(wf + 8 * ld + col));
         wj0 = ld4(wf + 4 * ld + col); wj1 = ld4(wf + 5 * ld + col); wj2 = ld4(wf + 6 * ld + col); wj3 = ld4(wf + 7 * ld + col);
     }
     // this (row, chunk)'s run of mask dwords (EdgeFwdArgs::mask): one dword per trip of four slots
@@ -747,7 +741,7 @@ __device__ __forceinline__ float4 edge_sum_chunk(int row, int col, int e_stored,
             }
             if (FLY) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) q_[u] = fly_chain(q_[u], wj0, wj1, wj2, wj3, zero4);
+                for (int u = 0; u < 4; ++u) q_[u] = chain4_t(q_[u], wj0, wj1, wj2, wj3, zero4);
             }
             unsigned mword = 0u;
 #pragma unroll
@@ -970,7 +964,7 @@ __global__ __launch_bounds__(ER_THREADS, 4) void edge_rows_fwd_kernel(int n, int
         float4 wj0, wj1, wj2, wj3;
         const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
         if (FLY) {
-            p4 = fly_chain(er_tile[row], s_w2[lc], s_w2[nchunk + lc], s_w2[2 * nchunk + lc], s_w2[3 * nchunk + lc], s_w2[8 * nchunk + lc]);
+            p4 = chain4_t(er_tile[row], s_w2[lc], s_w2[nchunk + lc], s_w2[2 * nchunk + lc], s_w2[3 * nchunk + lc], s_w2[8 * nchunk + lc]);
             wj0 = s_w2[4 * nchunk + lc]; wj1 = s_w2[5 * nchunk + lc]; wj2 = s_w2[6 * nchunk + lc]; wj3 = s_w2[7 * nchunk + lc];
         } else {
             p4 = ld4(P + (size_t)(r0 + row) * ld + 4 * lc);
@@ -990,7 +984,7 @@ __global__ __launch_bounds__(ER_THREADS, 4) void edge_rows_fwd_kernel(int n, int
                 }
                 float4 q_[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) q_[u] = FLY ? fly_chain(er_tile[s_[u]], wj0, wj1, wj2, wj3, zero4) : er_tile[s_[u] * nchunk + lc];
+                for (int u = 0; u < 4; ++u) q_[u] = FLY ? chain4_t(er_tile[s_[u]], wj0, wj1, wj2, wj3, zero4) : er_tile[s_[u] * nchunk + lc];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     float4 v = add4(p4, q_[u]);
@@ -1004,7 +998,7 @@ __global__ __launch_bounds__(ER_THREADS, 4) void edge_rows_fwd_kernel(int n, int
                 int id = eid[p];
                 id = id >= e_stored ? id - e_stored : id;
                 const float2 a2 = *reinterpret_cast<const float2*>(ea + (size_t)id * 2);
-                float4 v = add4(p4, FLY ? fly_chain(er_tile[nbr[p] - r0], wj0, wj1, wj2, wj3, zero4) : er_tile[(nbr[p] - r0) * nchunk + lc]);
+                float4 v = add4(p4, FLY ? chain4_t(er_tile[nbr[p] - r0], wj0, wj1, wj2, wj3, zero4) : er_tile[(nbr[p] - r0) * nchunk + lc]);
                 v = fma4(a2.x, w0, v);
                 v = fma4(a2.y, w1v, v);
                 acc = add4(acc, relu4(v));

@@ -22,15 +22,6 @@ struct EvalStd {
     float s[4];
 };
 
-__device__ __forceinline__ float4 eval_mask_row(const void* m, int dtype, int64_t r) {
-    if (dtype == 0) {
-        const longlong2* p = reinterpret_cast<const longlong2*>(static_cast<const int64_t*>(m) + 4 * r);
-        const longlong2 a = p[0], b = p[1];
-        return make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
-    }
-    return ld4(static_cast<const float*>(m) + 4 * r);
-}
-
 // Products and sums that must round ONE operation at a time (bit for bit torch's separate kernels / the host's double arithmetic):
 // contraction into an fma is switched off for these bodies -- hipcc contracts a plain a * b + c, also when it is written with
 // the _rn intrinsics.
@@ -83,7 +74,7 @@ __global__ __launch_bounds__(256) void eval_metrics_kernel(const float* __restri
     float s1 = 0.f, s0 = 0.f, sq = 0.f;
     int c1 = 0, c0 = 0;
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const float4 vo = ld4(o + 4 * r), vy = ld4(y + 4 * r), vm = eval_mask_row(mask, mask_dtype, r);
+        const float4 vo = ld4(o + 4 * r), vy = ld4(y + 4 * r), vm = mask_row4(mask, mask_dtype, r);
         const float ov[4] = {vo.x, vo.y, vo.z, vo.w}, yv[4] = {vy.x, vy.y, vy.z, vy.w}, mv[4] = {vm.x, vm.y, vm.z, vm.w};
         float mix[4] = {0.f, 0.f, 0.f, 0.f};
         if (mixed) {

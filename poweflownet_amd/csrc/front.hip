@@ -13,6 +13,9 @@
 // leaves the matrix cores idle and every launch pays its fixed cost.  Here a thread owns (node row, 4 hidden units): the
 // H-wide outputs are 4 + 8 FMAs per element straight from registers, the 4-wide ones a dot product over H reduced through
 // LDS in a fixed order (deterministic).  ~30 MFLOP in total: one launch of a few microseconds per direction.
+// The arithmetic itself -- the hidden unit, the Wb step, the residual, the P | Q unit, the g0 step, dh, the clamped weight slice, the
+// mask row, the block row sum -- is front_chains.hpp's: every body below, ea_seg.hip's front_seg_fwd_kernel and edge.hip's FLY walks
+// call the same functions, which is what makes their results the same bits.  What a body owns is its thread mapping and its tree.
 #include <stdlib.h>
 #include <string.h>
 
@@ -43,52 +46,33 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
     const int n = a.n, h = a.h, ldw1 = a.ldw1;
     const int r = threadIdx.x / nchunk, c = threadIdx.x - r * nchunk;
     const bool lane_on = r < rows_pb;
-    // this thread's units 4c .. 4c+3 of every weight (zero past H: the pad columns then come out as exact zeros)
-    float rwa[4][4], rba[4], rwb[4][4], rw1[4][8], rb1[4];
-    // (unconditional loads from a clamped unit, zeroed by a select afterwards: `ok ? load : 0` compiles to an exec-masked
-    //  branch with an immediate wait per load -- 72 serialized round trips to L2, 40 us)
+    // this thread's units 4c .. 4c+3 of every weight (front_chains.hpp: clamped loads + select, zero past H)
+    float4 rwa[4], rwb[4], rw1i[4], rw1j[4];
+    float rba[4], rb1[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int u = 4 * c + i, uc = min(u, h - 1);
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
         const bool ok = lane_on && u < h;
-        const float vba = a.ba[uc], vb1 = a.b1[uc];
-        rba[i] = ok ? vba : 0.f;
-        rb1[i] = ok ? vb1 : 0.f;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float va = a.wa[(size_t)uc * 4 + f], vb = a.wb[(size_t)f * h + uc];
-            rwa[i][f] = ok ? va : 0.f;
-            rwb[i][f] = ok ? vb : 0.f;
-        }
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const float v1 = a.w1[(size_t)uc * ldw1 + f];
-            rw1[i][f] = ok ? v1 : 0.f;
-        }
+        rba[i] = unit_val(a.ba, uc, ok);
+        rb1[i] = unit_val(a.b1, uc, ok);
+        rwa[i] = unit_row4(a.wa + (size_t)uc * 4, ok);
+        rwb[i] = unit_col4(a.wb, h, uc, ok);
+        rw1i[i] = unit_row4(a.w1 + (size_t)uc * ldw1, ok);
+        rw1j[i] = unit_row4(a.w1 + (size_t)uc * ldw1 + 4, ok);
     }
     const float4 bb4 = make_float4(a.bb[0], a.bb[1], a.bb[2], a.bb[3]);
     for (int row0 = bid * rows_pb; row0 < n; row0 += nblk * rows_pb) {
         const int row = row0 + r;
         const bool on = lane_on && row < n;
         if (on) {
-            float4 m;                                   // pred_mask.float() (networks/MPN.py:533)
-            if (a.mask_dtype == 0) {
-                const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
-                m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
-            } else {
-                m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
-            }
+            const float4 m = mask_row4(a.mask, a.mask_dtype, row);
             if (c == 0) st4_wt(a.maskf + (size_t)row * 4, m);
             float hv[4];
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // this chunk's share of me_h Wb^T
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float v = rba[i];
-                v = fmaf(rwa[i][0], m.x, v); v = fmaf(rwa[i][1], m.y, v); v = fmaf(rwa[i][2], m.z, v); v = fmaf(rwa[i][3], m.w, v);
-                v = fmaxf(v, 0.f);
-                hv[i] = v;
-                acc.x = fmaf(rwb[i][0], v, acc.x); acc.y = fmaf(rwb[i][1], v, acc.y);
-                acc.z = fmaf(rwb[i][2], v, acc.z); acc.w = fmaf(rwb[i][3], v, acc.w);
+                hv[i] = me_unit(rwa[i], rba[i], m);
+                acc = wb_step(acc, rwb[i], hv[i]);
             }
             if (a.me_h) st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));   // (null: no backward follows)
             part[r * nchunk + c] = acc;
@@ -98,7 +82,7 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
         if (on && c == 0) {
             const float4 s = part[r * nchunk];
             const float4 xi = ld4(a.x + (size_t)row * 4);   // (requested at the top of the trip instead: no gain at 128 graphs, 4-8 % slower at 2048)
-            const float4 o = make_float4(xi.x + (s.x + bb4.x), xi.y + (s.y + bb4.y), xi.z + (s.z + bb4.z), xi.w + (s.w + bb4.w));
+            const float4 o = x0_row(xi, s, bb4);
             vec[r] = o;
             st4_wt(a.x0 + (size_t)row * 4, o);
         }
@@ -107,14 +91,7 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdArgs& a, int bid, i
             const float4 v = vec[r];
             float p[4], q[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float pa = rb1[i];
-                pa = fmaf(rw1[i][0], v.x, pa); pa = fmaf(rw1[i][1], v.y, pa); pa = fmaf(rw1[i][2], v.z, pa); pa = fmaf(rw1[i][3], v.w, pa);
-                float qb = 0.f;
-                qb = fmaf(rw1[i][4], v.x, qb); qb = fmaf(rw1[i][5], v.y, qb); qb = fmaf(rw1[i][6], v.z, qb); qb = fmaf(rw1[i][7], v.w, qb);
-                p[i] = pa;
-                q[i] = qb;
-            }
+            for (int i = 0; i < 4; ++i) pq_unit(rw1i[i], rw1j[i], rb1[i], v, p[i], q[i]);
             st4_wt(a.P + (size_t)row * ld + 4 * c, make_float4(p[0], p[1], p[2], p[3]));
             st4_wt(a.Q + (size_t)row * ld + 4 * c, make_float4(q[0], q[1], q[2], q[3]));
         }
@@ -130,35 +107,23 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
     const int n = a.n, h = a.h, ldw1 = a.ldw1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane;
     const bool lane_on = c < nchunk;
-    float rwa[4][4], rba[4], rwb[4][4], rw1[4][8], rb1[4];
+    float4 rwa[4], rwb[4], rw1i[4], rw1j[4];
+    float rba[4], rb1[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // unconditional clamped loads + select (see front_fwd_body)
-        const int u = 4 * c + i, uc = min(u, h - 1);
+    for (int i = 0; i < 4; ++i) {
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
         const bool ok = lane_on && u < h;
-        const float vba = a.ba[uc], vb1 = a.b1[uc];
-        rba[i] = ok ? vba : 0.f;
-        rb1[i] = ok ? vb1 : 0.f;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float va = a.wa[(size_t)uc * 4 + f], vb = a.wb[(size_t)f * h + uc];
-            rwa[i][f] = ok ? va : 0.f;
-            rwb[i][f] = ok ? vb : 0.f;
-        }
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const float v1 = a.w1[(size_t)uc * ldw1 + f];
-            rw1[i][f] = ok ? v1 : 0.f;
-        }
+        rba[i] = unit_val(a.ba, uc, ok);
+        rb1[i] = unit_val(a.b1, uc, ok);
+        rwa[i] = unit_row4(a.wa + (size_t)uc * 4, ok);
+        rwb[i] = unit_col4(a.wb, h, uc, ok);
+        rw1i[i] = unit_row4(a.w1 + (size_t)uc * ldw1, ok);
+        rw1j[i] = unit_row4(a.w1 + (size_t)uc * ldw1 + 4, ok);
     }
     const float4 bb4 = make_float4(a.bb[0], a.bb[1], a.bb[2], a.bb[3]);
     const int wpb = blockDim.x >> 6;
-    auto load_row = [&](int row, float4& m, float4& xi) {   // pred_mask.float() (networks/MPN.py:533) and x: every lane reads the same bytes
-        if (a.mask_dtype == 0) {
-            const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
-            m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
-        } else {
-            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
-        }
+    auto load_row = [&](int row, float4& m, float4& xi) {   // the mask row and x: every lane reads the same bytes
+        m = mask_row4(a.mask, a.mask_dtype, row);
         xi = ld4(a.x + (size_t)row * 4);
     };
     float4 m_n = make_float4(0.f, 0.f, 0.f, 0.f), xi_n = m_n;
@@ -171,16 +136,12 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);   // this chunk's share of me_h Wb^T (zero in lanes past the row)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float v = rba[i];
-            v = fmaf(rwa[i][0], m.x, v); v = fmaf(rwa[i][1], m.y, v); v = fmaf(rwa[i][2], m.z, v); v = fmaf(rwa[i][3], m.w, v);
-            v = fmaxf(v, 0.f);
-            hv[i] = v;
-            acc.x = fmaf(rwb[i][0], v, acc.x); acc.y = fmaf(rwb[i][1], v, acc.y);
-            acc.z = fmaf(rwb[i][2], v, acc.z); acc.w = fmaf(rwb[i][3], v, acc.w);
+            hv[i] = me_unit(rwa[i], rba[i], m);
+            acc = wb_step(acc, rwb[i], hv[i]);
         }
         if (lane_on && a.me_h) st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
         const float4 s4 = wave_sum4(acc);            // fixed butterfly: every lane ends with the same, deterministic sum
-        const float4 o = make_float4(xi.x + (s4.x + bb4.x), xi.y + (s4.y + bb4.y), xi.z + (s4.z + bb4.z), xi.w + (s4.w + bb4.w));
+        const float4 o = x0_row(xi, s4, bb4);
         if (lane == 0) {
             st4_wt(a.maskf + (size_t)row * 4, m);
             st4_wt(a.x0 + (size_t)row * 4, o);
@@ -188,14 +149,7 @@ __device__ __forceinline__ void front_fwd_wave_body(const FrontFwdArgs& a, int b
         if (lane_on && a.P) {
             float pv[4], qv[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float pa = rb1[i];
-                pa = fmaf(rw1[i][0], o.x, pa); pa = fmaf(rw1[i][1], o.y, pa); pa = fmaf(rw1[i][2], o.z, pa); pa = fmaf(rw1[i][3], o.w, pa);
-                float qb = 0.f;
-                qb = fmaf(rw1[i][4], o.x, qb); qb = fmaf(rw1[i][5], o.y, qb); qb = fmaf(rw1[i][6], o.z, qb); qb = fmaf(rw1[i][7], o.w, qb);
-                pv[i] = pa;
-                qv[i] = qb;
-            }
+            for (int i = 0; i < 4; ++i) pq_unit(rw1i[i], rw1j[i], rb1[i], o, pv[i], qv[i]);
             st4_wt(a.P + (size_t)row * ld + 4 * c, make_float4(pv[0], pv[1], pv[2], pv[3]));
             st4_wt(a.Q + (size_t)row * ld + 4 * c, make_float4(qv[0], qv[1], qv[2], qv[3]));
         }
@@ -217,27 +171,16 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
     typedef const float __attribute__((address_space(4))) * cptr;
     const cptr wa = (cptr)a.wa, ba = (cptr)a.ba, wb = (cptr)a.wb;
     for (int row = bid * 256 + (int)threadIdx.x; row < n; row += nblk * 256) {
-        float4 m;                                   // pred_mask.float() (networks/MPN.py:533)
-        if (a.mask_dtype == 0) {
-            const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
-            m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
-        } else {
-            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
-        }
+        const float4 m = mask_row4(a.mask, a.mask_dtype, row);
         const float4 xi = ld4(a.x + (size_t)row * 4);
         float4 sub[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) sub[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         // (units past H: the block kernel multiplies zeroed weights there, i.e. adds exact zeros -- skipped here)
-#define PFN_FRONT_UNIT(u_)                                                                                                      \
-    {                                                                                                                           \
-        float v = ba[u_];                                                                                                       \
-        v = fmaf(wa[4 * (u_)], m.x, v); v = fmaf(wa[4 * (u_) + 1], m.y, v); v = fmaf(wa[4 * (u_) + 2], m.z, v);                 \
-        v = fmaf(wa[4 * (u_) + 3], m.w, v);                                                                                     \
-        v = fmaxf(v, 0.f);                                                                                                      \
-        acc.x = fmaf(wb[u_], v, acc.x); acc.y = fmaf(wb[h + (u_)], v, acc.y);                                                   \
-        acc.z = fmaf(wb[2 * h + (u_)], v, acc.z); acc.w = fmaf(wb[3 * h + (u_)], v, acc.w);                                     \
-    }
+        const auto unit = [&](int u, float4 acc) -> float4 {   // one hidden unit into its chunk's sum: the block kernel's two calls
+            const float v = me_unit(make_float4(wa[4 * u], wa[4 * u + 1], wa[4 * u + 2], wa[4 * u + 3]), ba[u], m);
+            return wb_step(acc, make_float4(wb[u], wb[h + u], wb[2 * h + u], wb[3 * h + u]), v);
+        };
         const int nfull8 = (h >> 2) & ~7;           // chunks that come in branch-free groups of eight whole chunks (a branch per
         int k0 = 0;                                 // unit made every scalar weight load wait for the one before it: 41 us)
         for (; k0 < nfull8; k0 += 8) {
@@ -245,7 +188,7 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
             for (int j = 0; j < 8; ++j) {
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) PFN_FRONT_UNIT(4 * (k0 + j) + i)
+                for (int i = 0; i < 4; ++i) acc = unit(4 * (k0 + j) + i, acc);
                 sub[j].x += acc.x; sub[j].y += acc.y; sub[j].z += acc.z; sub[j].w += acc.w;
             }
         }
@@ -258,11 +201,10 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
             for (int i = 0; i < 4; ++i) {
                 const int u = 4 * k + i;
                 if (u >= h) break;
-                PFN_FRONT_UNIT(u)
+                acc = unit(u, acc);
             }
             sub[j].x += acc.x; sub[j].y += acc.y; sub[j].z += acc.z; sub[j].w += acc.w;
         }
-#undef PFN_FRONT_UNIT
         float4 t = sub[0];
 #pragma unroll
         for (int j = 1; j < 8; ++j) {
@@ -270,7 +212,7 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
             t.x += sub[j].x; t.y += sub[j].y; t.z += sub[j].z; t.w += sub[j].w;
         }
         st4_wt(a.maskf + (size_t)row * 4, m);
-        st4_wt(a.x0 + (size_t)row * 4, make_float4(xi.x + (t.x + bb4.x), xi.y + (t.y + bb4.y), xi.z + (t.z + bb4.z), xi.w + (t.w + bb4.w)));
+        st4_wt(a.x0 + (size_t)row * 4, x0_row(xi, t, bb4));
     }
 }
 
@@ -279,41 +221,26 @@ __device__ __forceinline__ void front_fwd_thread_body(const FrontFwdArgs& a, int
 // Training beyond the latency regime with P | Q formed in the edge walk: the one H-wide tensor left to write is mask_embd's hidden
 // layer (kept for the backward pass).  Its workgroups need no reduction and no barrier -- thread (row group slot, chunk) keeps its
 // chunk's slices of Wa and ba in registers and walks rows, a row group's chunks are one contiguous 528-byte store -- while x0 and
-// maskf come from front_fwd_thread_body in OTHER workgroups of the same launch (independent work; same fma chains as the block
-// kernel, so the same bits).  6470rte x 64: 82 us for what the block kernel did in 159 us of barrier-separated phases.
+// maskf come from front_fwd_thread_body in OTHER workgroups of the same launch (independent work; the block kernel's me_unit, so
+// the same bits).  6470rte x 64: 82 us for what the block kernel did in 159 us of barrier-separated phases.
 __device__ __forceinline__ void front_meh_body(const FrontFwdArgs& a, int bid, int nblk, int ld, int nchunk) {
     const int n = a.n, h = a.h;
     const int rows_pb = 256 / nchunk;
     const int r = threadIdx.x / nchunk, c = threadIdx.x - r * nchunk;
     if (r >= rows_pb) return;
-    float rwa[4][4], rba[4];
+    float4 rwa[4];
+    float rba[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // (unconditional clamped loads + select, see front_fwd_body)
-        const int u = 4 * c + i, uc = min(u, h - 1);
-        const bool ok = u < h;
-        const float vba = a.ba[uc];
-        rba[i] = ok ? vba : 0.f;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float va = a.wa[(size_t)uc * 4 + f];
-            rwa[i][f] = ok ? va : 0.f;
-        }
+    for (int i = 0; i < 4; ++i) {
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
+        rba[i] = unit_val(a.ba, uc, u < h);
+        rwa[i] = unit_row4(a.wa + (size_t)uc * 4, u < h);
     }
     for (int row = bid * rows_pb + r; row < n; row += nblk * rows_pb) {
-        float4 m;
-        if (a.mask_dtype == 0) {
-            const int64_t* mp = static_cast<const int64_t*>(a.mask) + (size_t)row * 4;
-            m = make_float4((float)mp[0], (float)mp[1], (float)mp[2], (float)mp[3]);
-        } else {
-            m = ld4(static_cast<const float*>(a.mask) + (size_t)row * 4);
-        }
+        const float4 m = mask_row4(a.mask, a.mask_dtype, row);
         float hv[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float v = rba[i];
-            v = fmaf(rwa[i][0], m.x, v); v = fmaf(rwa[i][1], m.y, v); v = fmaf(rwa[i][2], m.z, v); v = fmaf(rwa[i][3], m.w, v);
-            hv[i] = fmaxf(v, 0.f);
-        }
+        for (int i = 0; i < 4; ++i) hv[i] = me_unit(rwa[i], rba[i], m);
         st4_wt(a.me_h + (size_t)row * ld + 4 * c, make_float4(hv[0], hv[1], hv[2], hv[3]));
     }
 }
@@ -352,21 +279,14 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
     float4* vec = fl + (size_t)rows_pb * nchunk;
     const int r = threadIdx.x / nchunk, c = threadIdx.x - r * nchunk;
     const bool lane_on = r < rows_pb;
-    float rwb[4][4], rw1[4][8];
+    float4 rwb[4], rw1i[4], rw1j[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {   // unconditional clamped loads + select (see front_fwd_kernel)
-        const int u = 4 * c + i, uc = min(u, h - 1);
+    for (int i = 0; i < 4; ++i) {
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
         const bool ok = lane_on && u < h;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float vb = wb[(size_t)f * h + uc];
-            rwb[i][f] = ok ? vb : 0.f;
-        }
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const float v1 = w1[(size_t)uc * ldw1 + f];
-            rw1[i][f] = ok ? v1 : 0.f;
-        }
+        rwb[i] = unit_col4(wb, h, uc, ok);
+        rw1i[i] = unit_row4(w1 + (size_t)uc * ldw1, ok);
+        rw1j[i] = unit_row4(w1 + (size_t)uc * ldw1 + 4, ok);
     }
     for (int row0 = blockIdx.x * rows_pb; row0 < n; row0 += gridDim.x * rows_pb) {
         const int row = row0 + r;
@@ -378,12 +298,7 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
             const float pv[4] = {p4.x, p4.y, p4.z, p4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                acc.x = fmaf(pv[i], rw1[i][0], acc.x); acc.y = fmaf(pv[i], rw1[i][1], acc.y);
-                acc.z = fmaf(pv[i], rw1[i][2], acc.z); acc.w = fmaf(pv[i], rw1[i][3], acc.w);
-                acc.x = fmaf(qv[i], rw1[i][4], acc.x); acc.y = fmaf(qv[i], rw1[i][5], acc.y);
-                acc.z = fmaf(qv[i], rw1[i][6], acc.z); acc.w = fmaf(qv[i], rw1[i][7], acc.w);
-            }
+            for (int i = 0; i < 4; ++i) acc = g0_step(acc, pv[i], qv[i], rw1i[i], rw1j[i]);
             part[r * nchunk + c] = acc;
         }
         __syncthreads();
@@ -399,11 +314,7 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(int n, int h, int ld, in
             const float yv[4] = {y.x, y.y, y.z, y.w};
             float o[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v = 0.f;
-                v = fmaf(g.x, rwb[i][0], v); v = fmaf(g.y, rwb[i][1], v); v = fmaf(g.z, rwb[i][2], v); v = fmaf(g.w, rwb[i][3], v);
-                o[i] = yv[i] > 0.f ? v : 0.f;
-            }
+            for (int i = 0; i < 4; ++i) o[i] = dh_unit(g, rwb[i], yv[i]);
             st4_wt(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
@@ -417,21 +328,14 @@ __global__ __launch_bounds__(256) void front_bwd_wave_kernel(int n, int h, int l
                                                              float* __restrict__ dh) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane;
     const bool lane_on = c < nchunk;
-    float rwb[4][4], rw1[4][8];
+    float4 rwb[4], rw1i[4], rw1j[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int u = 4 * c + i, uc = min(u, h - 1);
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
         const bool ok = lane_on && u < h;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float vb = wb[(size_t)f * h + uc];
-            rwb[i][f] = ok ? vb : 0.f;
-        }
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            const float v1 = w1[(size_t)uc * ldw1 + f];
-            rw1[i][f] = ok ? v1 : 0.f;
-        }
+        rwb[i] = unit_col4(wb, h, uc, ok);
+        rw1i[i] = unit_row4(w1 + (size_t)uc * ldw1, ok);
+        rw1j[i] = unit_row4(w1 + (size_t)uc * ldw1 + 4, ok);
     }
     const int wpb = blockDim.x >> 6, cc = lane_on ? c : 0;   // (lanes past the row re-read chunk 0: zero weights, nothing stored)
     const int step = gridDim.x * wpb, row_first = blockIdx.x * wpb + wave;
@@ -451,23 +355,14 @@ __global__ __launch_bounds__(256) void front_bwd_wave_kernel(int n, int h, int l
         const float pv[4] = {p4.x, p4.y, p4.z, p4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            acc.x = fmaf(pv[i], rw1[i][0], acc.x); acc.y = fmaf(pv[i], rw1[i][1], acc.y);
-            acc.z = fmaf(pv[i], rw1[i][2], acc.z); acc.w = fmaf(pv[i], rw1[i][3], acc.w);
-            acc.x = fmaf(qv[i], rw1[i][4], acc.x); acc.y = fmaf(qv[i], rw1[i][5], acc.y);
-            acc.z = fmaf(qv[i], rw1[i][6], acc.z); acc.w = fmaf(qv[i], rw1[i][7], acc.w);
-        }
+        for (int i = 0; i < 4; ++i) acc = g0_step(acc, pv[i], qv[i], rw1i[i], rw1j[i]);
         const float4 g = wave_sum4(acc);
         if (lane == 0) st4_wt(g0 + (size_t)row * 4, g);
         if (lane_on) {
             const float yv[4] = {y.x, y.y, y.z, y.w};
             float o[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float v = 0.f;
-                v = fmaf(g.x, rwb[i][0], v); v = fmaf(g.y, rwb[i][1], v); v = fmaf(g.z, rwb[i][2], v); v = fmaf(g.w, rwb[i][3], v);
-                o[i] = yv[i] > 0.f ? v : 0.f;
-            }
+            for (int i = 0; i < 4; ++i) o[i] = dh_unit(g, rwb[i], yv[i]);
             st4_wt(dh + (size_t)row * ld + 4 * c, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
@@ -597,7 +492,7 @@ int launch_front_fwd_pack(const FrontFwdArgs& f, const PackJob* jobs, int njobs,
     return PFN_OK;
 }
 
-// P | Q of the first EdgeAggregation layer written out after the fact, with the front's own fma chains (bit-identical to what the
+// P | Q of the first EdgeAggregation layer written out after the fact, with the front's own pq_unit (bit-identical to what the
 // front stores and to what the edge stage forms on the fly): for the callers that need the rows in memory when the forward pass
 // skipped them -- a backward pass that was asked for edge-attribute gradients, the gate export.  Thread = (row, chunk).
 __global__ __launch_bounds__(256) void front_pq_kernel(int n, int h, int ld, int nchunk, int ldw1, const float* __restrict__ x0,
@@ -610,12 +505,10 @@ __global__ __launch_bounds__(256) void front_pq_kernel(int n, int h, int ld, int
     float p[4], q[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int u = 4 * c + i, uc = min(u, h - 1);
+        const int u = 4 * c + i, uc = unit_clamp(u, h);
         const float* w = w1 + (size_t)uc * ldw1;
-        float pa = b1[uc];
-        pa = fmaf(w[0], v.x, pa); pa = fmaf(w[1], v.y, pa); pa = fmaf(w[2], v.z, pa); pa = fmaf(w[3], v.w, pa);
-        float qb = 0.f;
-        qb = fmaf(w[4], v.x, qb); qb = fmaf(w[5], v.y, qb); qb = fmaf(w[6], v.z, qb); qb = fmaf(w[7], v.w, qb);
+        float pa, qb;
+        pq_unit(make_float4(w[0], w[1], w[2], w[3]), make_float4(w[4], w[5], w[6], w[7]), b1[uc], v, pa, qb);
         p[i] = u < h ? pa : 0.f;
         q[i] = u < h ? qb : 0.f;
     }
@@ -634,34 +527,12 @@ int launch_front_pq(int n, int h, int ldw1, const float* x0, const float* w1, co
 // ---- the backward front beyond the latency regime when mask_embd's hidden layer was NOT stored (FrontFwdArgs::me_h null in a
 // training forward: model.hip Route::meh_recompute).  me_h is four fmas per element away from the 16-byte mask row, and dh, which
 // the block kernel above writes, has ONE reader: the weight-gradient pair (dh, maskf).  So this kernel recomputes me_h (the
-// forward's chain: the same gate bits), forms g0 and dh as above, and accumulates mask_embd's four weight gradients itself
+// forward's me_unit: the same gate bits), forms g0 and dh as above, and accumulates mask_embd's four weight gradients itself
 //     dWb[f][u] += g0[row][f] me_h[row][u]   dbb[f] += g0[row][f]   dWa[u][f] += dh[row][u] mask[row][f]   dba[u] += dh[row][u]
 // per thread over the rows it visits, per workgroup over its row slots in slot order, per launch over the workgroups in a
 // second kernel in workgroup order (fixed order throughout: deterministic).  Neither me_h nor dh touches memory: the forward front
 // writes 32 bytes per row, this kernel reads dP and dQ and writes 16 bytes per row, and two N x H pairs leave the weight-gradient
 // launch.  Partial sums per workgroup: [9][ld] floats (dWb f = 0..3, dWa f = 0..3, dba) + dbb[4].
-// row_sum (pfn_internal.hpp) on that barrier: same two-level order, same result
-__device__ __forceinline__ void row_sum_lb(float4* part, int r, int c, int nchunk, bool on) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on && c < 8) {
-        for (int k = c; k < nchunk; k += 8) {
-            const float4 p = part[r * nchunk + k];
-            s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-        }
-    }
-    lds_barrier();
-    if (on && c < 8) part[r * nchunk + c] = s;
-    lds_barrier();
-    if (on && c == 0) {
-        float4 t = part[r * nchunk];
-        const int m = nchunk < 8 ? nchunk : 8;
-        for (int k = 1; k < m; ++k) {
-            const float4 p = part[r * nchunk + k];
-            t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
-        }
-        part[r * nchunk] = t;
-    }
-}
 constexpr int FWG_SLOTS = 9;
 __host__ __device__ inline int fwg_stride(int ld) { return FWG_SLOTS * ld + 4; }
 __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld, int nchunk, int rows_pb, int ldw1,
@@ -683,7 +554,7 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
     // VGPRs -- three workgroups per CU, too few loads in flight: 187 us for half the bytes of the 183-us kernel above), Wa's and ba's
     // too.  Zero past H: the pad units then contribute exact zeros.
     for (int k = threadIdx.x; k < nchunk * 4; k += blockDim.x) {
-        const int u = k, uc = min(u, h - 1);
+        const int u = k, uc = unit_clamp(u, h);
         const bool ok = u < h;
         const float* w = w1 + (size_t)uc * ldw1;
         const int kc = k >> 2, ki = k & 3;           // unit k = 4 kc + ki -> plane-major [ki][kc]: a row's chunk-lanes read consecutive float4s
@@ -729,17 +600,11 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
             const float pv[4] = {p4.x, p4.y, p4.z, p4.w}, qv[4] = {q4.x, q4.y, q4.z, q4.w};
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 wi = s_w1[(2 * i) * nchunk + c], wj = s_w1[(2 * i + 1) * nchunk + c];
-                acc.x = fmaf(pv[i], wi.x, acc.x); acc.y = fmaf(pv[i], wi.y, acc.y);
-                acc.z = fmaf(pv[i], wi.z, acc.z); acc.w = fmaf(pv[i], wi.w, acc.w);
-                acc.x = fmaf(qv[i], wj.x, acc.x); acc.y = fmaf(qv[i], wj.y, acc.y);
-                acc.z = fmaf(qv[i], wj.z, acc.z); acc.w = fmaf(qv[i], wj.w, acc.w);
-            }
+            for (int i = 0; i < 4; ++i) acc = g0_step(acc, pv[i], qv[i], s_w1[(2 * i) * nchunk + c], s_w1[(2 * i + 1) * nchunk + c]);
             part[r * nchunk + c] = acc;
         }
         lds_barrier();
-        row_sum_lb(part, r, c, nchunk, on);
+        row_sum<true>(part, r, c, nchunk, on);   // (on lds_barrier: the next row group's loads stay in flight)
         if (on && c == 0) {
             const float4 s = part[r * nchunk];
             vec[r] = s;
@@ -751,22 +616,17 @@ __global__ __launch_bounds__(256) void front_bwd_wg_kernel(int n, int h, int ld,
             const float gv[4] = {g.x, g.y, g.z, g.w}, mv[4] = {m.x, m.y, m.z, m.w};
             const float4 b4 = s_ba[c];
             const float rba[4] = {b4.x, b4.y, b4.z, b4.w};
-            float rwb[4][4], rwa[4][4];
+            float4 rwb[4], rwa[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float4 w = s_wb[i * nchunk + c], a4 = s_wa[i * nchunk + c];
-                rwb[i][0] = w.x; rwb[i][1] = w.y; rwb[i][2] = w.z; rwb[i][3] = w.w;
-                rwa[i][0] = a4.x; rwa[i][1] = a4.y; rwa[i][2] = a4.z; rwa[i][3] = a4.w;
+                rwb[i] = s_wb[i * nchunk + c];
+                rwa[i] = s_wa[i * nchunk + c];
             }
             if (c == 0) { abb.x += g.x; abb.y += g.y; abb.z += g.z; abb.w += g.w; }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                float y = rba[i];                    // mask_embd's hidden unit, the forward's chain (front_fwd_body / front_meh_body)
-                y = fmaf(rwa[i][0], m.x, y); y = fmaf(rwa[i][1], m.y, y); y = fmaf(rwa[i][2], m.z, y); y = fmaf(rwa[i][3], m.w, y);
-                y = fmaxf(y, 0.f);
-                float v = 0.f;
-                v = fmaf(g.x, rwb[i][0], v); v = fmaf(g.y, rwb[i][1], v); v = fmaf(g.z, rwb[i][2], v); v = fmaf(g.w, rwb[i][3], v);
-                const float d = y > 0.f ? v : 0.f;   // dh[row][4c + i]
+                const float y = me_unit(rwa[i], rba[i], m);   // mask_embd's hidden unit: the forward's chain, the same gate bits
+                const float d = dh_unit(g, rwb[i], y);        // dh[row][4c + i]
                 aba[i] += d;
 #pragma unroll
                 for (int f = 0; f < 4; ++f) {

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(const PackArgs a) {
     if (a.mask_count > 0) {   // the rider: pred_mask.float() (networks/MPN.py:533), spread over every block of the launch
         const int64_t nthr = (int64_t)gridDim.x * gridDim.y * blockDim.x;
         for (int64_t i = ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < a.mask_count; i += nthr)
-            a.maskf[i] = a.mask_dtype == 0 ? (float)static_cast<const int64_t*>(a.mask)[i] : static_cast<const float*>(a.mask)[i];
+            a.maskf[i] = mask_elem(a.mask, a.mask_dtype, i);
     }
     slot_ea_body(a.slot_ea, ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x,
                  (int64_t)gridDim.x * gridDim.y * blockDim.x);

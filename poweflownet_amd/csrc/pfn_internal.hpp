@@ -8,6 +8,7 @@
 
 #include "../../include/pfn_hip.h"
 #include "device_prims.hpp"
+#include "front_chains.hpp"
 
 namespace pfn {
 
@@ -313,31 +314,6 @@ bool big_hops_fit(int seg, int n, int64_t e_stored);
 int launch_big_graph_hops(const GraphView& g, const FusedHopsArgs& a, hipStream_t s);
 
 // S[i] = sum_{e -> i} relu(P[i] + Q[src(e)] + sum_f a_e[f] * W1[:, 2Fi + f])
-// Sum of a row's nchunk float4 partials in a FIXED order, in two levels (a single thread walking all 33 was a chain of 33
-// dependent LDS reads, ~1 us per row group): lanes c < 8 each add the partials c, c + 8, c + 16, ... in that order, then lane 0
-// adds the eight sub-sums in lane order.  Called by every thread of the block (two barriers inside); result in part[r * nchunk].
-__device__ __forceinline__ void row_sum(float4* part, int r, int c, int nchunk, bool on) {
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (on && c < 8) {
-        for (int k = c; k < nchunk; k += 8) {
-            const float4 p = part[r * nchunk + k];
-            s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-        }
-    }
-    __syncthreads();
-    if (on && c < 8) part[r * nchunk + c] = s;
-    __syncthreads();
-    if (on && c == 0) {
-        float4 t = part[r * nchunk];
-        const int m = nchunk < 8 ? nchunk : 8;
-        for (int k = 1; k < m; ++k) {
-            const float4 p = part[r * nchunk + k];
-            t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
-        }
-        part[r * nchunk] = t;
-    }
-}
-
 // ReLU masks of the edge stage: one byte per (incoming edge, float4 column chunk), bit i = pre-activation of column 4c + i > 0.
 // Written by the forward walk when a backward pass will follow, read by the backward walks INSTEAD of recomputing
 // P[dst] + Q[src] + a_e We: they then gather dS rows only (a third of the gathers).  Layout: destination row i owns
@@ -367,7 +343,7 @@ struct EdgeFwdArgs {
     int seg = 0;                     // > 0: the batch is a union of graphs of this many nodes (pfn_graph_segments): big batches of
                                      // small graphs take edge_rows_fwd_kernel (the graph's Q rows LDS-resident)
     // first layer behind the 4-wide front (Fi = 4, Fe = 2): P and Q null, the walk forms P[i] = b1 + W1i x0[i] and Q[j] = W1j x0[j]
-    // from the 16-byte x0 rows itself, with the front's fma chains (front.hip) -- 2 N H floats neither written nor read back
+    // from the 16-byte x0 rows itself, with the front's chain (front_chains.hpp) -- 2 N H floats neither written nor read back
     const float* x0 = nullptr;
     const float* b1 = nullptr;
 };

@@ -48,15 +48,7 @@ __global__ __launch_bounds__(256) void segpack_rows_kernel(SegPackArgs a) {
             if (ok) {
                 a.src_of[r] = t;
                 st4(a.x_pad + (size_t)r * 4, ld4(a.x + (size_t)t * 4));
-                float4 m;
-                if (a.mask_dtype == 0) {
-                    const longlong2* mp = static_cast<const longlong2*>(a.mask) + (size_t)t * 2;
-                    const longlong2 m0 = mp[0], m1 = mp[1];
-                    m = make_float4((float)m0.x, (float)m0.y, (float)m1.x, (float)m1.y);
-                } else {
-                    m = ld4(static_cast<const float*>(a.mask) + (size_t)t * 4);
-                }
-                st4(a.mask_pad + (size_t)r * 4, m);
+                st4(a.mask_pad + (size_t)r * 4, mask_row4(a.mask, a.mask_dtype, t));
             }
         }
         if (t < a.n_pad) {

@@ -10,9 +10,6 @@ namespace pfn {
 // ---- Masked_L2_loss (utils/custom_loss_functions.py:10-46): two masked means of (out - y)^2.  Kernel 1 reduces
 // (sum, count) of both sets with an ordered last-arriver combine (reduce.hpp masked_l2_combine: MaskedL2Ws) and writes the loss and
 // the totals; kernel 2 turns the totals into the two gradient scales.
-__device__ __forceinline__ float mask_value(const void* m, int dtype, int64_t i) {
-    return dtype == 0 ? (float)static_cast<const int64_t*>(m)[i] : static_cast<const float*>(m)[i];
-}
 __global__ __launch_bounds__(256) void masked_l2_reduce_kernel(const float* __restrict__ o, const float* __restrict__ y,
                                                                const void* __restrict__ mask, int mask_dtype, int64_t n,
                                                                int regularize, float regcoeff, MaskedL2Ws* __restrict__ w,
@@ -20,7 +17,7 @@ __global__ __launch_bounds__(256) void masked_l2_reduce_kernel(const float* __re
     float a1 = 0.f, a0 = 0.f;
     int k1 = 0, k0 = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float d = o[i] - y[i], m = mask_value(mask, mask_dtype, i);
+        const float d = o[i] - y[i], m = mask_elem(mask, mask_dtype, i);
         if (m != 0.f) { a1 = fmaf(d, d, a1); ++k1; }                 // mask.type(bool)
         if (1.f - m != 0.f) { a0 = fmaf(d, d, a0); ++k0; }           // (1 - mask).type(bool)
     }
@@ -37,7 +34,7 @@ __global__ __launch_bounds__(256) void masked_l2_grad_kernel(const float* __rest
                                                              float* __restrict__ grad) {
     const float g1 = 2.f / (float)w->tot_c1, g0 = regularize ? 2.f * regcoeff / (float)w->tot_c0 : 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float d = o[i] - y[i], m = mask_value(mask, mask_dtype, i);
+        const float d = o[i] - y[i], m = mask_elem(mask, mask_dtype, i);
         float g = 0.f;
         if (m != 0.f) g += g1 * d;
         if (regularize && 1.f - m != 0.f) g += g0 * d;
@@ -316,7 +313,7 @@ __global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const float* __re
         const float d[4] = {vo.x - vy.x, vo.y - vy.y, vo.z - vy.z, vo.w - vy.w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float m = MASKED ? mask_value(mask, mask_dtype, r * 4 + e) : 1.f;
+            const float m = MASKED ? mask_elem(mask, mask_dtype, r * 4 + e) : 1.f;
             if (m != 0.f) { a1 = fmaf(d[e], d[e], a1); ++k1; }
             if (MASKED && 1.f - m != 0.f) { a0 = fmaf(d[e], d[e], a0); ++k0; }
         }
@@ -352,7 +349,7 @@ __global__ __launch_bounds__(256) void loss_rows_grad_kernel(const float* __rest
             for (int e = 0; e < 4; ++e) {
                 const float d = dd[e];
                 if (MASKED) {
-                    const float m = mask_value(mask, mask_dtype, r * 4 + e);
+                    const float m = mask_elem(mask, mask_dtype, r * 4 + e);
                     float g = 0.f;
                     if (m != 0.f) g += g1 * d;
                     if (regularize && 1.f - m != 0.f) g += g0 * d;

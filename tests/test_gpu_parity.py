@@ -1067,6 +1067,113 @@ torch.save(res, sys.argv[1])
             assert torch.equal(res["default"][key], res["fly"][key]), f"{key}: recomputed mask_embd hidden layer"
 
 
+# One child process per front route (the switches are read once per process); every child runs the same four small cases.
+_FRONT_CHAIN_ROUTES = (("seg_front", {}),
+                       ("wave", {"PFN_NO_SEG_FRONT": "1"}),
+                       ("beyond", {"PFN_FRONT_BLOCK_ROWS": "1", "PFN_NO_SEG_EA": "1"}),
+                       ("store_meh", {"PFN_FRONT_BLOCK_ROWS": "1", "PFN_NO_SEG_EA": "1", "PFN_FRONT_STORE_MEH": "1"}),
+                       ("block", {"PFN_FRONT_BLOCK_ROWS": "1", "PFN_NO_SEG_EA": "1", "PFN_FRONT_NO_THREAD_ROWS": "1"}),
+                       ("stored_pq", {"PFN_FRONT_BLOCK_ROWS": "1", "PFN_NO_SEG_EA": "1", "PFN_NO_L0_FLY": "1"}))
+_FRONT_CHAIN_CASES = tuple(f"h{h}.{mk}" for h in (6, 129) for mk in ("int64", "float32"))
+_FRONT_CHAIN_KEYS = ("out", "nograd", "gates_me", "gates0", "gx", "g")
+_FRONT_CHAIN_CHILD = """
+import sys, torch
+sys.path.insert(0, {root!r})
+from poweflownet_amd.networks.MPN import MaskEmbdMultiMPN
+from poweflownet_amd.synth import make_batch
+res = {{}}
+for h in (6, 129):
+    torch.manual_seed(11)
+    m = MaskEmbdMultiMPN(4, 2, 4, h, 3, 2, 0.0).to("cuda:0").eval()
+    for mk in ("int64", "float32"):
+        d = make_batch("118", 3, seed=4).to("cuda:0")          # 354 rows
+        if mk == "float32":
+            d.pred_mask = d.pred_mask.float()
+            d.pred_mask[5, 1] = 0.5                            # one non-binary row: front_seg_fwd_kernel's per-row tree
+        d.x.requires_grad_(True)
+        out = m(d)
+        g = m.export_gates()
+        res[f"h{{h}}.{{mk}}.gates_me"], res[f"h{{h}}.{{mk}}.gates0"] = g["mask_embd"].cpu(), g["edge"][0].cpu()
+        torch.nn.MSELoss()(out, d.y).backward()
+        res[f"h{{h}}.{{mk}}.out"], res[f"h{{h}}.{{mk}}.gx"], res[f"h{{h}}.{{mk}}.g"] = out.detach().cpu(), d.x.grad.cpu(), m.flat_grad().cpu()
+        m.zero_grad(set_to_none=True)
+        with torch.no_grad():
+            res[f"h{{h}}.{{mk}}.nograd"] = m(d).cpu()
+torch.save(res, sys.argv[1])
+"""
+
+
+def _front_chain_children(tmp_path):
+    import subprocess
+    import sys
+    script = _FRONT_CHAIN_CHILD.format(root=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    # (the six children run side by side: each is mostly its import of torch)
+    procs = [(tag, subprocess.Popen([sys.executable, "-c", script, str(tmp_path / f"{tag}.pt")], env=dict(os.environ, **env)))
+             for tag, env in _FRONT_CHAIN_ROUTES]
+    try:
+        for tag, proc in procs:
+            assert proc.wait(timeout=300) == 0, f"the child of route {tag} failed"
+    finally:
+        for _, proc in procs:
+            if proc.poll() is None:
+                proc.kill()
+    return {tag: torch.load(str(tmp_path / f"{tag}.pt")) for tag, _ in _FRONT_CHAIN_ROUTES}
+
+
+def test_front_chains_give_the_same_bits_on_every_route_at_small_shapes(tmp_path):
+    """csrc/front_chains.hpp holds the front's arithmetic once -- mask row, clamped weight slice, hidden unit, Wb step, residual,
+    P | Q unit, g0 step, dh unit, the two-level row sum -- and every front route calls it.  The cross-route tests above run
+    H = 129 at >= 35,400 rows; this one pins the shared functions where they can go wrong cheaply: 3 x 118 = 354 rows (a multiple
+    of neither the 4 rows per block of the row-per-wave kernels nor the 7-row group of the block kernels at H = 129: every
+    kernel ends on a ragged trip), hidden_dim 6 (h % 4 != 0, h < 8: the clamp min(u, h - 1), exact-zero pad units, nchunk = 2)
+    and 129 (nchunk = 33: the second level of row_sum, idle lanes 33..63, the c + 32 leg of front_seg_fwd_kernel's tree), int64
+    and float32 masks, the float one with a non-binary row (front_seg_fwd_kernel's per-row tree next to its 16-pattern table).
+    Six children, one per route (_FRONT_CHAIN_ROUTES).  What must agree bit for bit:
+      * mask_embd's gates on ALL routes (the hidden unit depends on the mask row alone);
+      * within {seg_front, wave} -- x0's chunk sums go through the xor-butterfly order -- everything, as the test of
+        front_seg_fwd_kernel above asserts at the large shape: out, nograd, gx, g, and both gate exports;
+      * within {beyond, store_meh, block, stored_pq} -- x0's chunk sums go through row_sum's two-level order -- out, nograd, gx and
+        both gate exports; the flat parameter gradient g between store_meh and stored_pq as the P | Q test above does, and
+        between beyond and block (both take the recomputing backward front where it fits its scratch, see below);
+      * beyond against store_meh: g to RTOL (the recomputing backward front sums mask_embd's weight gradients in another order
+        than gemm_tn; at the large shape the test above also shows that they differ bitwise);
+      * a no_grad forward returns the bits of the training forward on every route.
+    The two groups differ from each other in x0's summation order for nchunk > 2: out is held to RTOL across them; at hidden_dim 6
+    both orders add the same two chunk sums (and exact zeros), so there out and gx agree bit for bit across the groups as well.
+    Finding, measured on the commit before the header existed: at H = 129 the input gradient differs ACROSS the groups
+    by 4.6e-4 of its largest entry (5.5e-7 against 1.2e-3) -- two summation orders take different ReLU decisions where a
+    pre-activation lies within rounding of zero (tests/util._assert_grads_on_hip_gates) -- so gx is compared within a group only.
+    Finding: at 354 rows front_bwd_wg_kernel runs for hidden_dim 6 only -- at H = 129 its per-workgroup partials
+    (51 x 1,192 floats) exceed the unused me_h buffer (354 x 132), so make_route keeps me_h stored and `beyond` equals `store_meh`
+    there; H = 129 through that kernel stays with the 35,400-row test above."""
+    res = _front_chain_children(tmp_path)
+    ref = res["seg_front"]
+    for case in _FRONT_CHAIN_CASES:
+        for key in _FRONT_CHAIN_KEYS:
+            a = ref[f"{case}.{key}"]
+            assert a.dtype == torch.bool or (torch.isfinite(a).all() and a.abs().max() > 0), f"{case}.{key}"
+        for tag, _ in _FRONT_CHAIN_ROUTES:
+            r = res[tag]
+            assert torch.equal(r[f"{case}.gates_me"], ref[f"{case}.gates_me"]), f"{case}: mask_embd gates of {tag}"
+            assert torch.equal(r[f"{case}.nograd"], r[f"{case}.out"]), f"{case}: no_grad forward of {tag} differs from its training forward"
+        for key in _FRONT_CHAIN_KEYS:
+            assert torch.equal(res["wave"][f"{case}.{key}"], ref[f"{case}.{key}"]), f"{case}.{key}: wave differs from seg_front"
+        base = res["store_meh"]
+        for tag in ("beyond", "block", "stored_pq"):
+            for key in ("out", "nograd", "gates0", "gx"):
+                assert torch.equal(res[tag][f"{case}.{key}"], base[f"{case}.{key}"]), f"{case}.{key}: {tag} differs from store_meh"
+            if case.startswith("h6"):     # across the two summation orders: the same two addends at nchunk = 2
+                for key in ("out", "gx"):
+                    assert torch.equal(res[tag][f"{case}.{key}"], ref[f"{case}.{key}"]), f"{case}.{key}: {tag} differs from seg_front"
+            else:
+                assert_close(res[tag][f"{case}.out"], ref[f"{case}.out"], RTOL, f"{case}.out: {tag} against seg_front")
+        assert torch.equal(res["stored_pq"][f"{case}.g"], base[f"{case}.g"]), f"{case}.g: stored_pq differs from store_meh"
+        assert torch.equal(res["block"][f"{case}.g"], res["beyond"][f"{case}.g"]), f"{case}.g: block differs from beyond"
+        assert_close(res["beyond"][f"{case}.g"], base[f"{case}.g"], RTOL, f"{case}: flat parameter gradient, recomputing backward front")
+        n_me = 4 * 129 + 129 + 4 * 129 + 4 if case.startswith("h129") else 4 * 6 + 6 + 4 * 6 + 4
+        assert_close(res["beyond"][f"{case}.g"][-n_me:], base[f"{case}.g"][-n_me:], RTOL, f"{case}: mask_embd gradients formed in the backward front")
+
+
 def test_backward_after_an_inference_forward_gives_nan_gradients_not_garbage():
     """C-ABI misuse the host cannot see: `pfn_mpn_forward` with need_backward = 0 on a TRAINING-sized workspace,
     then `pfn_mpn_backward` with need_backward = 1 on it -- the forward saved nothing the backward reads.  The forward stamps the
