@@ -137,7 +137,9 @@ size_t pfn_mpn_workspace_bytes(const pfn_mpn_config* cfg, int64_t n_nodes, int64
  * layout of datasets/PowerFlowData.py:193; 1: float32), edge_attr [e_stored, Fe] f32, out [N, output_dim] f32.  `ws` receives the activations backward needs.  `rng_state`: device
  * uint64[2] {seed, offset}; when training && dropout_rate > 0 the offset is advanced by one at the start of the call
  * and then read by the dropout epilogues.  `out` may be NULL where pfn_mpn_mse_tail_ok answers 1 and
- * pfn_mpn_backward_mse follows (which then writes the rows).                                        */
+ * pfn_mpn_backward_mse follows (which then writes the rows).  Non-finite entries of x or edge_attr
+ * propagate as in the reference (a ReLU unit is off iff its pre-activation compares <= 0: NaN is on);
+ * the rows they do not reach are unaffected, bit for bit.                                          */
 int pfn_mpn_forward(const pfn_mpn_config* cfg, const void* graph_ws, int64_t n_nodes, int64_t e_stored,
                     const float* const* params, const float* x, const void* pred_mask,
                     int mask_dtype, const float* edge_attr, float* out, void* ws, size_t ws_bytes,

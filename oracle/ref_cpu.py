@@ -52,12 +52,14 @@ def in_degree(edge_index: torch.Tensor, num_nodes: int, dtype=torch.float32) -> 
 
 # --------------------------------------------------------------------------- the two layers
 def gated_relu(z, gate=None, record=None):
-    """relu(z) -- or, test hook, z * gate with the {0,1} decisions supplied from outside (the HIP path exports the ones its
+    """relu(z) -- or, test hook, "z where gate else 0" with the {0,1} decisions supplied from outside (the HIP path exports the ones its
     forward took, pfn_mpn_export_gates): the same function on the branch those decisions select, so that a float64 run and an
-    fp32 run are differentiated on the SAME piecewise-linear piece.  `record`: list that receives this call's own z > 0."""
+    fp32 run are differentiated on the SAME piecewise-linear piece.  `record`: list that receives this call's own ~(z <= 0) -- a
+    NaN is ON, as in threshold_backward (for finite z this is z > 0)."""
     if record is not None:
-        record.append((z > 0).detach())
-    return F.relu(z) if gate is None else z * gate.to(z.dtype)
+        record.append((~(z <= 0)).detach())
+    # (a select, not z * gate: an off unit is an exact 0 with a zero gradient whatever z holds -- -Inf * 0 would be NaN)
+    return F.relu(z) if gate is None else torch.where(gate.to(torch.bool), z, torch.zeros((), dtype=z.dtype, device=z.device))
 
 
 def edge_aggregation(x, edge_index, edge_attr, w1, b1, w2, b2, gate=None, record=None):

@@ -22,7 +22,22 @@ __device__ __forceinline__ float4 mul4(float a, float4 x) { return make_float4(a
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 // (element-wise select: a ?: on the float4 struct goes through scratch)
 __device__ __forceinline__ float4 sel4(bool k, float4 a, float4 b) { return make_float4(k ? a.x : b.x, k ? a.y : b.y, k ? a.z : b.z, k ? a.w : b.w); }
-__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
+// ------------------------------------------------------------------------------ the ReLU and its gate
+// ONE rule, the reference's (torch.relu / threshold_backward), in both directions and on every route: a unit is OFF iff its
+// pre-activation compares <= 0.  A NaN compares false, so it is ON: the value stays NaN, the gate bit is 1 and the backward
+// passes the incoming gradient through.  +Inf stays +Inf, -Inf gives 0.  The sign of a zero is not part of the contract (-0
+// gives +0).  Never fmaxf(v, 0) or v > 0: both turn a NaN into "off, value 0" and bad data into plausible numbers.
+__device__ __forceinline__ bool relu_on(float v) { return !(v <= 0.f); }
+// (the value as ONE instruction, like the fmaxf it replaces: IEEE 754-2019 maximum propagates a NaN -- v_maximum3_f32 on gfx950;
+//  as a compare + select the generic edge walks lost occupancy and 5-11 % of their time)
+__device__ __forceinline__ float relu1(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(relu1(v.x), relu1(v.y), relu1(v.z), relu1(v.w)); }
+// the gate applied: g where the unit whose pre-activation (or ReLU output: the same test) is `pre` is on, else 0
+__device__ __forceinline__ float gate1(float pre, float g) { return pre <= 0.f ? 0.f : g; }
+__device__ __forceinline__ float4 gate4(float4 pre, float4 g) { return make_float4(gate1(pre.x, g.x), gate1(pre.y, g.y), gate1(pre.z, g.z), gate1(pre.w, g.w)); }
+// "ReLU or nothing" as one branch-free expression, x <= lo ? lo : x: lo = 0 is the ReLU, lo = -inf the identity for EVERY x (NaN
+// and -Inf included)
+__device__ __forceinline__ float clamp_lo(float x, float lo) { return __builtin_elementwise_maximum(x, lo); }
 // sum over the 64 lanes of a wave as a FIXED xor butterfly (DPP / permute shuffles, no LDS, no barrier): every lane ends with the
 // same, deterministic sum
 __device__ __forceinline__ float4 wave_sum4(float4 v) {

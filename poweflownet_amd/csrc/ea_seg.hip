@@ -233,7 +233,7 @@ constexpr int SG_W2A_CH = 34;        // float4 chunks per W2 row kept for the MS
 struct SegLds {
     float* P;
     float* Q;
-    float* D;      // backward only: dS
+    float* D;      // backward only: dS (its room also holds the W2 quarter first: seg_bwd_d_floats)
     float* we;     // [2][SG_TW]
     float* w2s;    // backward, last layer only: W2 slice [4][SG_TW]
     float4* w2a;   // backward, last layer with the MSELoss tail: all of W2 as [4][SG_W2A_CH] float4 chunks
@@ -242,12 +242,19 @@ struct SegLds {
     float4* part;  // backward only: dWe partials [8 waves][16 chunk lanes][2]
     SegCsr in, out;
 };
+// The backward's dS room: the tile, and before it exists the W2 quarter the tile is multiplied from (B0 aliases D) -- up to
+// SG_NCH * 256 floats, MORE than a 96-row tile (graphs of 43..48 and 65..96 nodes: rows_pb <= 96).  Sized by the tile alone, the
+// quarter's tail lay over `we` and what follows it, and we_commit wrote into the weights (hidden widths above 104).
+__host__ __device__ inline size_t seg_bwd_d_floats(int trows) {
+    const size_t tile = (size_t)trows * SG_TW, img = (size_t)SG_NCH * 256;
+    return tile > img ? tile : img;
+}
 __device__ __forceinline__ SegLds seg_lds(float* base, int trows, int rows_pb, int cap, bool bwd) {
     SegLds l;
     float* p = base;
     l.P = p; p += (size_t)trows * SG_TW;
     l.Q = p; p += (size_t)trows * SG_TW;
-    l.D = p; if (bwd) p += (size_t)trows * SG_TW;
+    l.D = p; if (bwd) p += seg_bwd_d_floats(trows);
     l.B0 = bwd ? l.D : p; if (!bwd) p += SG_NCH * 256;
     l.B1 = p; if (!bwd) p += SG_NCH * 256;
     l.we = p; p += 2 * SG_TW;
@@ -265,6 +272,7 @@ __device__ __forceinline__ SegLds seg_lds(float* base, int trows, int rows_pb, i
 }
 static size_t seg_lds_bytes(int trows, int rows_pb, int cap, bool bwd) {
     size_t f = (size_t)(bwd ? 3 : 2) * trows * SG_TW + (bwd ? 0 : 2 * SG_NCH * 256) + 2 * SG_TW + (bwd ? 4 * SG_TW + 4 * SG_W2A_CH * 4 + 8 * 16 * 2 * 4 : 0) + (size_t)(bwd ? 2 : 1) * 2 * cap;
+    if (bwd) f += seg_bwd_d_floats(trows) - (size_t)trows * SG_TW;
     size_t i = (size_t)(bwd ? 2 : 1) * (rows_pb + 1 + cap);
     return (f + i) * 4 + 16;
 }
@@ -634,20 +642,20 @@ __device__ __forceinline__ void seg_bwd_row(const SegLds& l, const SegCsr& cin, 
             v = fma4(ai[u].x, w0, v);
             v = fma4(ai[u].y, w1, v);
             float4 dh;
-            dh.x = (ki[u] && v.x > 0.f) ? g4.x : 0.f;
-            dh.y = (ki[u] && v.y > 0.f) ? g4.y : 0.f;
-            dh.z = (ki[u] && v.z > 0.f) ? g4.z : 0.f;
-            dh.w = (ki[u] && v.w > 0.f) ? g4.w : 0.f;
+            dh.x = (ki[u] && relu_on(v.x)) ? g4.x : 0.f;
+            dh.y = (ki[u] && relu_on(v.y)) ? g4.y : 0.f;
+            dh.z = (ki[u] && relu_on(v.z)) ? g4.z : 0.f;
+            dh.w = (ki[u] && relu_on(v.w)) ? g4.w : 0.f;
             accP = add4(accP, dh);
             dwe0 = fma4(ai[u].x, dh, dwe0);
             dwe1 = fma4(ai[u].y, dh, dwe1);
             float4 z = add4(pd[u], q4);
             z = fma4(ao[u].x, w0, z);
             z = fma4(ao[u].y, w1, z);
-            accQ.x += (ko[u] && z.x > 0.f) ? gd[u].x : 0.f;
-            accQ.y += (ko[u] && z.y > 0.f) ? gd[u].y : 0.f;
-            accQ.z += (ko[u] && z.z > 0.f) ? gd[u].z : 0.f;
-            accQ.w += (ko[u] && z.w > 0.f) ? gd[u].w : 0.f;
+            accQ.x += (ko[u] && relu_on(z.x)) ? gd[u].x : 0.f;
+            accQ.y += (ko[u] && relu_on(z.y)) ? gd[u].y : 0.f;
+            accQ.z += (ko[u] && relu_on(z.z)) ? gd[u].z : 0.f;
+            accQ.w += (ko[u] && relu_on(z.w)) ? gd[u].w : 0.f;
         }
     }
 }
@@ -676,10 +684,10 @@ __device__ __forceinline__ void seg_bwd_row_dst(const SegLds& l, const SegCsr& c
             v = fma4(ai[u].y, w1, v);
             const bool k = p + u < end;
             float4 dh;
-            dh.x = (k && v.x > 0.f) ? g4.x : 0.f;
-            dh.y = (k && v.y > 0.f) ? g4.y : 0.f;
-            dh.z = (k && v.z > 0.f) ? g4.z : 0.f;
-            dh.w = (k && v.w > 0.f) ? g4.w : 0.f;
+            dh.x = (k && relu_on(v.x)) ? g4.x : 0.f;
+            dh.y = (k && relu_on(v.y)) ? g4.y : 0.f;
+            dh.z = (k && relu_on(v.z)) ? g4.z : 0.f;
+            dh.w = (k && relu_on(v.w)) ? g4.w : 0.f;
             accP = add4(accP, dh);
             dwe0 = fma4(ai[u].x, dh, dwe0);
             dwe1 = fma4(ai[u].y, dh, dwe1);
@@ -712,10 +720,10 @@ __device__ __forceinline__ void seg_bwd_row_src(const SegLds& l, const SegCsr& c
             z = fma4(ao[u].x, w0, z);
             z = fma4(ao[u].y, w1, z);
             const bool k = p + u < end;
-            accQ.x += (k && z.x > 0.f) ? gd[u].x : 0.f;
-            accQ.y += (k && z.y > 0.f) ? gd[u].y : 0.f;
-            accQ.z += (k && z.z > 0.f) ? gd[u].z : 0.f;
-            accQ.w += (k && z.w > 0.f) ? gd[u].w : 0.f;
+            accQ.x += (k && relu_on(z.x)) ? gd[u].x : 0.f;
+            accQ.y += (k && relu_on(z.y)) ? gd[u].y : 0.f;
+            accQ.z += (k && relu_on(z.z)) ? gd[u].z : 0.f;
+            accQ.w += (k && relu_on(z.w)) ? gd[u].w : 0.f;
         }
     }
 }
@@ -736,10 +744,10 @@ __device__ __forceinline__ void seg_bwd_row_slow(const SegLds& l, const SegCsr& 
         v = fma4(a2.x, w0, v);
         v = fma4(a2.y, w1, v);
         float4 dh;
-        dh.x = v.x > 0.f ? g4.x : 0.f;
-        dh.y = v.y > 0.f ? g4.y : 0.f;
-        dh.z = v.z > 0.f ? g4.z : 0.f;
-        dh.w = v.w > 0.f ? g4.w : 0.f;
+        dh.x = relu_on(v.x) ? g4.x : 0.f;
+        dh.y = relu_on(v.y) ? g4.y : 0.f;
+        dh.z = relu_on(v.z) ? g4.z : 0.f;
+        dh.w = relu_on(v.w) ? g4.w : 0.f;
         accP = add4(accP, dh);
         dwe0 = fma4(a2.x, dh, dwe0);
         dwe1 = fma4(a2.y, dh, dwe1);
@@ -752,10 +760,10 @@ __device__ __forceinline__ void seg_bwd_row_slow(const SegLds& l, const SegCsr& 
         v = fma4(a2.x, w0, v);
         v = fma4(a2.y, w1, v);
         const float4 gd = ld4(l.D + (size_t)ld_ * SG_TW + tc);
-        accQ.x += v.x > 0.f ? gd.x : 0.f;
-        accQ.y += v.y > 0.f ? gd.y : 0.f;
-        accQ.z += v.z > 0.f ? gd.z : 0.f;
-        accQ.w += v.w > 0.f ? gd.w : 0.f;
+        accQ.x += relu_on(v.x) ? gd.x : 0.f;
+        accQ.y += relu_on(v.y) ? gd.y : 0.f;
+        accQ.z += relu_on(v.z) ? gd.z : 0.f;
+        accQ.w += relu_on(v.w) ? gd.w : 0.f;
     }
 }
 

@@ -57,10 +57,10 @@ __global__ __launch_bounds__(256) void hop_kernel(int n, int nchunk, const int* 
     if (add) acc = add4(acc, ld4(add + o));
     if (gate) {
         const float4 g = ld4(gate + o);
-        acc.x = g.x > 0.f ? acc.x * gate_scale : 0.f;
-        acc.y = g.y > 0.f ? acc.y * gate_scale : 0.f;
-        acc.z = g.z > 0.f ? acc.z * gate_scale : 0.f;
-        acc.w = g.w > 0.f ? acc.w * gate_scale : 0.f;
+        acc.x = relu_on(g.x) ? acc.x * gate_scale : 0.f;
+        acc.y = relu_on(g.y) ? acc.y * gate_scale : 0.f;
+        acc.z = relu_on(g.z) ? acc.z * gate_scale : 0.f;
+        acc.w = relu_on(g.w) ? acc.w * gate_scale : 0.f;
     }
     st4(y + o, acc);
 }
@@ -201,10 +201,10 @@ __global__ __launch_bounds__(FH_THREADS) void fused_hops_kernel(int n, int rows_
             if (addp) acc = add4(acc, ld4(addp + o));
             if (last && a.gate) {
                 const float4 g4 = ld4(a.gate + o);
-                acc.x = g4.x > 0.f ? acc.x * a.gate_scale : 0.f;
-                acc.y = g4.y > 0.f ? acc.y * a.gate_scale : 0.f;
-                acc.z = g4.z > 0.f ? acc.z * a.gate_scale : 0.f;
-                acc.w = g4.w > 0.f ? acc.w * a.gate_scale : 0.f;
+                acc.x = relu_on(g4.x) ? acc.x * a.gate_scale : 0.f;
+                acc.y = relu_on(g4.y) ? acc.y * a.gate_scale : 0.f;
+                acc.z = relu_on(g4.z) ? acc.z * a.gate_scale : 0.f;
+                acc.w = relu_on(g4.w) ? acc.w * a.gate_scale : 0.f;
             }
             if (!last) st4(nxt + (size_t)lr * tld + 4 * lc, acc);
             if (gout) st4(gout + o, acc);
@@ -1208,10 +1208,10 @@ __device__ __forceinline__ void edge_bwd_dst_body(int bid, int nblk, int n, int 
                         for (int f = 0; f < FE; ++f) v = fma4(a_[u][f], w4[f], v);
                         const bool k = p + u < end;
                         float4 dh;
-                        dh.x = (k && v.x > 0.f) ? g4.x : 0.f;
-                        dh.y = (k && v.y > 0.f) ? g4.y : 0.f;
-                        dh.z = (k && v.z > 0.f) ? g4.z : 0.f;
-                        dh.w = (k && v.w > 0.f) ? g4.w : 0.f;
+                        dh.x = (k && relu_on(v.x)) ? g4.x : 0.f;
+                        dh.y = (k && relu_on(v.y)) ? g4.y : 0.f;
+                        dh.z = (k && relu_on(v.z)) ? g4.z : 0.f;
+                        dh.w = (k && relu_on(v.w)) ? g4.w : 0.f;
                         acc = add4(acc, dh);
 #pragma unroll
                         for (int f = 0; f < FE; ++f) dwe[f] = fma4(a_[u][f], dh, dwe[f]);
@@ -1293,10 +1293,10 @@ __device__ __forceinline__ void edge_bwd_src_body(int bid, int n, int nchunk, in
 #pragma unroll
             for (int f = 0; f < FE; ++f) v = fma4(a_[u][f], w4[f], v);
             const bool k = p + u < end;
-            acc.x += (k && v.x > 0.f) ? g_[u].x : 0.f;
-            acc.y += (k && v.y > 0.f) ? g_[u].y : 0.f;
-            acc.z += (k && v.z > 0.f) ? g_[u].z : 0.f;
-            acc.w += (k && v.w > 0.f) ? g_[u].w : 0.f;
+            acc.x += (k && relu_on(v.x)) ? g_[u].x : 0.f;
+            acc.y += (k && relu_on(v.y)) ? g_[u].y : 0.f;
+            acc.z += (k && relu_on(v.z)) ? g_[u].z : 0.f;
+            acc.w += (k && relu_on(v.w)) ? g_[u].w : 0.f;
         }
     }
     st4(dQ + (size_t)row * ld + col, acc);
@@ -1573,7 +1573,7 @@ __global__ __launch_bounds__(256) void edge_attr_grad_kernel(int e_stored, const
     for (int k = lane; k < h; k += 64) {
         float v = P[(size_t)dst * ld + k] + Q[(size_t)src * ld + k];
         for (int f = 0; f < fe; ++f) v = fmaf(ea[(size_t)id * fe + f], w1[(size_t)k * ldw + 2 * fi + f], v);
-        const float dh = v > 0.f ? dS[(size_t)dst * ld + k] : 0.f;
+        const float dh = relu_on(v) ? dS[(size_t)dst * ld + k] : 0.f;
         for (int f = 0; f < fe; ++f) part[f] = fmaf(w1[(size_t)k * ldw + 2 * fi + f], dh, part[f]);
     }
     for (int f = 0; f < fe; ++f) {

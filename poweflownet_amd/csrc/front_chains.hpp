@@ -72,7 +72,7 @@ __device__ __forceinline__ float4 chain4_t(float4 x, float4 w0, float4 w1, float
     return fma4(x.w, w3, acc);
 }
 // mask_embd's hidden unit: relu(ba + Wa[u] . m)
-__device__ __forceinline__ float me_unit(float4 wa, float ba, float4 m) { return fmaxf(chain4(wa, m, ba), 0.f); }
+__device__ __forceinline__ float me_unit(float4 wa, float ba, float4 m) { return relu1(chain4(wa, m, ba)); }
 // ... and its step into the row's Wb me_h (wb = Wb[0..3][u]); a chunk of four units is a chain of these from zero
 __device__ __forceinline__ float4 wb_step(float4 acc, float4 wb, float v) { return fma4(v, wb, acc); }
 // the residual, in this association: s = the row's summed Wb me_h
@@ -86,11 +86,8 @@ __device__ __forceinline__ void pq_unit(float4 w1i, float4 w1j, float b1, float4
 }
 // backward: unit u's step into the chunk's share of g0 -- dP's four terms, then dQ's
 __device__ __forceinline__ float4 g0_step(float4 acc, float p, float q, float4 w1i, float4 w1j) { return fma4(q, w1j, fma4(p, w1i, acc)); }
-// ... and one element of dh: (g0 . Wb[0..3][u]) where the hidden unit y was positive
-__device__ __forceinline__ float dh_unit(float4 g, float4 wb, float y) {
-    const float v = chain4(g, wb, 0.f);
-    return y > 0.f ? v : 0.f;
-}
+// ... and one element of dh: (g0 . Wb[0..3][u]) where the hidden unit y was on
+__device__ __forceinline__ float dh_unit(float4 g, float4 wb, float y) { return gate1(y, chain4(g, wb, 0.f)); }
 
 // ------------------------------------------------------------------------------------------ the row sum
 // Sum of a row's nchunk float4 partials in a FIXED order, in two levels (a single thread walking all 33 was a chain of 33

@@ -456,9 +456,9 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
 #pragma unroll
             for (int q = 0; q < 16; ++q) il_acc[ct][q] = 0.f;
         }
-        // the activation as ONE max: against 0 (ReLU) or against a quiet NaN (none: max(x, NaN) = x, and a NaN x stays NaN -- the
-        // poison of an unvalidated topology must come through a GEMM without activation as it does through the plain flush)
-        il_lo = a.act == ACT_RELU ? 0.f : __builtin_nanf("");
+        // the activation as ONE branch-free lower bound (clamp_lo): 0 (ReLU) or -inf (none: the identity for every x, NaN and -Inf
+        // included -- the poison of an unvalidated topology and a non-finite input come through as they do through the plain flush)
+        il_lo = a.act == ACT_RELU ? 0.f : -__builtin_inff();
     }
     const int nr = rem_on ? (a.nrem > 1 ? 4 : 1) : 0;   // trailing columns this wave owns (the generic path always computes 4)
     const float* extra = a.gate ? a.gate : a.resid;     // at most one of rowscale / gate / resid per GEMM
@@ -574,13 +574,13 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                     const f32x4 cb = *reinterpret_cast<const f32x4*>(lds + a.bias_lds_off + 32 * q + (r32 & ~3));   // (LDS: 8 registers less)
                     const float sc = __shfl(il_sc, jrow + 8 * g);   // the scale of this lane's row of the group
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = fmaxf(fmaf(sc, cb[e], t[e]), il_lo);
+                    for (int e = 0; e < 4; ++e) t[e] = clamp_lo(fmaf(sc, cb[e], t[e]), il_lo);
                     const size_t ub = (size_t)(il_rbase + 8 * g) * il_rs_ + (size_t)q * il_qs_;
                     vstore_x4_sv_masked(reinterpret_cast<const char*>(il_C + ub), il_vc, f32x4{t[0], t[1], t[2], t[3]}, il_ok[g]);
                 };
                 auto il_rem = [&]() {
                     const float tot = il_racc + __shfl_xor(il_racc, 32);   // the two k halves
-                    const float x = fmaxf(fmaf(il_sc, lds[a.bias_lds_off + rem_col], tot), il_lo);
+                    const float x = clamp_lo(fmaf(il_sc, lds[a.bias_lds_off + rem_col], tot), il_lo);
                     const size_t ub = (size_t)il_rbase * il_rs_ + il_rq_;
                     vstore_x4_sv_masked(reinterpret_cast<const char*>(il_C + ub), il_vr, f32x4{x, 0.f, 0.f, 0.f}, il_okr);
                 };
@@ -732,7 +732,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
 #pragma unroll
                             for (int g = 0; g < 4; ++g)
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[g][e] = fmaxf(v[g][e], 0.f);
+                                for (int e = 0; e < 4; ++e) v[g][e] = relu1(v[g][e]);
                         } else if (ep.act == ACT_DROPOUT_RELU) {
                             // (opaque: the column group is loop-invariant per lane, and hipcc otherwise hoists the Philox
                             //  rounds' invariant parts out of the tile loop -- per-lane values alive through the whole
@@ -744,14 +744,14 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                                 float u[4];
                                 dropout_uniform4(ep.dk, (uint32_t)(row_of(g) + a.row0), cgv, u);
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[g][e] = (u[e] >= ep.p_drop && v[g][e] > 0.f) ? v[g][e] * ep.keep_scale : 0.f;
+                                for (int e = 0; e < 4; ++e) v[g][e] = (u[e] >= ep.p_drop && relu_on(v[g][e])) ? v[g][e] * ep.keep_scale : 0.f;
                             }
                         }
                         if (ep.has_gate) {
 #pragma unroll
                             for (int g = 0; g < 4; ++g)
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[g][e] = aux[ct][g][e] > 0.f ? v[g][e] * ep.gate_scale : 0.f;
+                                for (int e = 0; e < 4; ++e) v[g][e] = relu_on(aux[ct][g][e]) ? v[g][e] * ep.gate_scale : 0.f;
                         }
                     }
                     {   // uniform base + the lane's one offset (see the epilogue-operand loads); a full tile of a full quarter needs no mask
@@ -791,11 +791,11 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_kernel(const NtArgs a) 
                             if (ep.has_rowscale) x = fmaf(raux[e], rcb[e], x);
                             if (ep.has_resid) x += raux[e];
                             if (ep.act == ACT_RELU) {
-                                x = fmaxf(x, 0.f);
+                                x = relu1(x);
                             } else if (ep.act == ACT_DROPOUT_RELU) {
-                                x = (ud[e] >= ep.p_drop && x > 0.f) ? x * ep.keep_scale : 0.f;
+                                x = (ud[e] >= ep.p_drop && relu_on(x)) ? x * ep.keep_scale : 0.f;
                             }
-                            if (ep.has_gate) x = raux[e] > 0.f ? x * ep.gate_scale : 0.f;
+                            if (ep.has_gate) x = relu_on(raux[e]) ? x * ep.gate_scale : 0.f;
                             v[e] = rem_col + e < ep.ncols ? x : 0.f;
                         }
                     }
@@ -1081,7 +1081,7 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[g][e] = fmaxf(v[g][e], 0.f);
+                        for (int e = 0; e < 4; ++e) v[g][e] = relu1(v[g][e]);
                 } else if (ep.act == ACT_DROPOUT_RELU) {
                     uint32_t cgv = (uint32_t)(col0 >> 2);
                     PFN_OPAQUE(cgv);
@@ -1090,14 +1090,14 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
                         float u[4];
                         dropout_uniform4(ep.dk, (uint32_t)(row_of(g) + a.row0), cgv, u);
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[g][e] = (u[e] >= ep.p_drop && v[g][e] > 0.f) ? v[g][e] * ep.keep_scale : 0.f;
+                        for (int e = 0; e < 4; ++e) v[g][e] = (u[e] >= ep.p_drop && relu_on(v[g][e])) ? v[g][e] * ep.keep_scale : 0.f;
                     }
                 }
                 if (ep.has_gate) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[g][e] = aux[ct][g][e] > 0.f ? v[g][e] * ep.gate_scale : 0.f;
+                        for (int e = 0; e < 4; ++e) v[g][e] = relu_on(aux[ct][g][e]) ? v[g][e] * ep.gate_scale : 0.f;
                 }
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -1112,15 +1112,15 @@ __global__ __launch_bounds__(NT_THREADS, 1) void gemm_nt_ws_kernel(const NtArgs 
                     if (ep.has_rowscale) x = fmaf(raux[0], rcb[0], x);
                     if (ep.has_resid) x += raux[0];
                     if (ep.act == ACT_RELU) {
-                        x = fmaxf(x, 0.f);
+                        x = relu1(x);
                     } else if (ep.act == ACT_DROPOUT_RELU) {
                         float ud[4];
                         uint32_t cgv = (uint32_t)(rem_col >> 2);
                         PFN_OPAQUE(cgv);
                         dropout_uniform4(ep.dk, (uint32_t)(row + a.row0), cgv, ud);
-                        x = (ud[0] >= ep.p_drop && x > 0.f) ? x * ep.keep_scale : 0.f;
+                        x = (ud[0] >= ep.p_drop && relu_on(x)) ? x * ep.keep_scale : 0.f;
                     }
-                    if (ep.has_gate) x = raux[0] > 0.f ? x * ep.gate_scale : 0.f;
+                    if (ep.has_gate) x = relu_on(raux[0]) ? x * ep.gate_scale : 0.f;
                     vstore_x4(C + act_off(row, rem_col, a.ldc, a.c_cm_rows), f32x4{x, 0.f, 0.f, 0.f});
                 }
             }
@@ -1210,7 +1210,7 @@ __global__ __launch_bounds__(64 * TINY_MAX_PIECES) void gemm_nt_tiny_kernel(cons
             for (int e = 0; e < 4; ++e) {
                 const int col = col0 + e;
                 float x = t4[e] + ((cvec && col < a.ncols) ? rs * cvec[col] : 0.f);
-                if (a.act == ACT_RELU) x = fmaxf(x, 0.f);
+                if (a.act == ACT_RELU) x = relu1(x);
                 o[e] = col < a.ncols ? x : 0.f;
             }
             *reinterpret_cast<float4*>(C + act_off(row, col0, a.ldc, a.c_cm_rows)) = make_float4(o[0], o[1], o[2], o[3]);
@@ -1222,7 +1222,7 @@ __global__ __launch_bounds__(64 * TINY_MAX_PIECES) void gemm_nt_tiny_kernel(cons
         if (kh == 0 && row < a.M) {
             const float rs = a.rowscale ? a.rowscale[row] : 1.f;
             float x = tot + (cvec ? rs * cvec[128] : 0.f);
-            if (a.act == ACT_RELU) x = fmaxf(x, 0.f);
+            if (a.act == ACT_RELU) x = relu1(x);
             *reinterpret_cast<float4*>(C + act_off(row, 128, a.ldc, a.c_cm_rows)) = make_float4(x, 0.f, 0.f, 0.f);
         }
     }

@@ -314,15 +314,15 @@ bool big_hops_fit(int seg, int n, int64_t e_stored);
 int launch_big_graph_hops(const GraphView& g, const FusedHopsArgs& a, hipStream_t s);
 
 // S[i] = sum_{e -> i} relu(P[i] + Q[src(e)] + sum_f a_e[f] * W1[:, 2Fi + f])
-// ReLU masks of the edge stage: one byte per (incoming edge, float4 column chunk), bit i = pre-activation of column 4c + i > 0.
+// ReLU masks of the edge stage: one byte per (incoming edge, float4 column chunk), bit i = column 4c + i is on (relu_on).
 // Written by the forward walk when a backward pass will follow, read by the backward walks INSTEAD of recomputing
 // P[dst] + Q[src] + a_e We: they then gather dS rows only (a third of the gathers).  Layout: destination row i owns
 // nchunk * L4_i dwords at dword offset rp4[i] * nchunk, L4_i = ceil(deg_i / 4); chunk c's run of L4_i dwords holds the bytes of
 // the row's incoming edges in slot order, so the thread (i, c) of a walk writes / reads ONE whole dword per trip of four
 // slots (byte stores into slot-major records made the forward walk 23 % slower).  Size: mask_dwords(n, e, ld).
 __host__ __device__ inline size_t mask_dwords(size_t n, size_t e_stored, int ld) { return (n + e_stored / 2 + 2) * (size_t)(ld / 4); }
-__device__ __forceinline__ unsigned char relu_bits(float4 v) {   // bit i = component i > 0 (the edge stage's ReLU mask)
-    return (unsigned char)((v.x > 0.f ? 1 : 0) | (v.y > 0.f ? 2 : 0) | (v.z > 0.f ? 4 : 0) | (v.w > 0.f ? 8 : 0));
+__device__ __forceinline__ unsigned char relu_bits(float4 v) {   // bit i = component i is on (relu_on: the edge stage's ReLU mask)
+    return (unsigned char)((relu_on(v.x) ? 1 : 0) | (relu_on(v.y) ? 2 : 0) | (relu_on(v.z) ? 4 : 0) | (relu_on(v.w) ? 8 : 0));
 }
 __device__ __forceinline__ float4 mask4(unsigned m, float4 g) {   // g where the mask bit is set, else 0
     return make_float4((m & 1) ? g.x : 0.f, (m & 2) ? g.y : 0.f, (m & 4) ? g.z : 0.f, (m & 8) ? g.w : 0.f);

@@ -171,7 +171,7 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
     unsigned gbits = 0u;
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-        gbits |= ((gv[j].x > 0.f ? 1u : 0u) | (gv[j].y > 0.f ? 2u : 0u) | (gv[j].z > 0.f ? 4u : 0u) | (gv[j].w > 0.f ? 8u : 0u)) << (4 * j);
+        gbits |= ((relu_on(gv[j].x) ? 1u : 0u) | (relu_on(gv[j].y) ? 2u : 0u) | (relu_on(gv[j].z) ? 4u : 0u) | (relu_on(gv[j].w) ? 8u : 0u)) << (4 * j);
     // the operand fragment goes out NOW -- staging consumed, weight DMAs landed -- and stays in flight across the barrier: the
     // multiply runs while it arrives (protocol: seg_tile.hpp seg_load_a_async)
     seg_drain_visible();
@@ -228,12 +228,12 @@ void seg_lin_hops_kernel(int n, int rows_pb, int trows, int cap, const int* __re
             }
             if (a.act == ACT_RELU) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = relu1(v[e]);
             } else if (a.act == ACT_DROPOUT_RELU) {
                 float u[4];
                 dropout_uniform4(dk, (uint32_t)(r0 + lr), (uint32_t)(gc >> 2), u);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = (u[e] >= a.p_drop && v[e] > 0.f) ? v[e] * keep_scale : 0.f;
+                for (int e = 0; e < 4; ++e) v[e] = (u[e] >= a.p_drop && relu_on(v[e])) ? v[e] * keep_scale : 0.f;
             }
             if (a.gate) {
 #pragma unroll

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void export_edge_gates_kernel(int n, int e_sto
             const int id = eid[q], idm = id >= e_stored ? id - e_stored : id;
             float v = p + Q[(size_t)nbr[q] * ld + k];
             for (int f = 0; f < fe; ++f) v = fmaf(ea[(size_t)idm * fe + f], w1[(size_t)k * ldw + 2 * fi + f], v);
-            out[(size_t)id * h + k] = v > 0.f ? 1 : 0;
+            out[(size_t)id * h + k] = relu_on(v) ? 1 : 0;
         }
     }
 }
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void export_row_gates_kernel(int64_t n, int h,
     for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < n * h; it += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = it / h, col = it - row * h;
         const float v = cm ? y[((col >> 2) * n + row) * 4 + (col & 3)] : y[row * ld + col];   // (chunk-major: Act::out_cm)
-        out[it] = v > 0.f ? 1 : 0;
+        out[it] = relu_on(v) ? 1 : 0;
     }
 }
 

@@ -58,6 +58,8 @@ def k8_of(k):
 def seg_lds_bytes(trows, rows_pb, cap, bwd):
     f = ((3 if bwd else 2) * trows * SG_TW + (0 if bwd else 2 * SG_NCH * 256) + 2 * SG_TW
          + ((4 * SG_TW + 4 * SG_W2A_CH * 4 + 8 * 16 * 2 * 4) if bwd else 0) + (2 if bwd else 1) * 2 * cap)
+    if bwd:
+        f += max(trows * SG_TW, SG_NCH * 256) - trows * SG_TW     # seg_bwd_d_floats: the dS room also holds the W2 quarter
     i = (2 if bwd else 1) * (rows_pb + 1 + cap)
     return (f + i) * 4 + 16
 

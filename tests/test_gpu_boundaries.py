@@ -8,6 +8,7 @@ north_star's 1e-5 against oracle/ref_cpu.py (the float64 oracle on the HIP path'
 Where the profile classes cannot separate two kernels the restated predicate decides, and the test says so:
 `fused_hops_*` covers the two-tile, row and big-graph hop kernels; `gemm_nt` covers the tiny, stationary, streaming and wide ones.
 """
+import copy
 import os
 
 import numpy as np
@@ -19,7 +20,7 @@ from poweflownet_amd.data import Batch
 from poweflownet_amd.networks.MPN import GraphCSR, MaskEmbdMultiMPN, TAGConv
 from poweflownet_amd.synth import _MASK_TABLE, make_topology
 from tests import regimes as R
-from tests.util import RTOL, _assert_grads_on_hip_gates, _exported_masks, _fp64_truth, assert_close, record
+from tests.util import RTOL, _assert_grads_on_hip_gates, _cpu_gates, _exported_masks, _fp64_truth, _to64, assert_close, record
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -139,6 +140,44 @@ def test_graph_resident_kernels_at_every_graph_size_edge(seg, p):
     assert reg["ea_seg_fwd"] == (seg <= R.SG_MAX_ROWS)
     if seg <= R.SG_MAX_ROWS:
         assert launches.get("ea_seg_bwd", 0) + launches.get("front_seg_fwd+pack", 0) > 0
+
+
+@pytest.mark.parametrize("seg", [43, 48, 49, 65, 96, 97])
+def test_graph_resident_backward_at_the_96_row_tile(seg):
+    """ea_seg_bwd_kernel multiplies dS from a W2 quarter that first lies where the dS tile will be (seg_lds: B0 aliases D): up to
+    17 * 256 floats, more than a 96-row tile of 36-float rows.  rows_pb <= 96, i.e. graphs of 43..48 nodes (two per workgroup) and
+    of 65..96 (one), at H = 129 (K8 = 136): the room must be the larger of the two (seg_bwd_d_floats) -- sized by the tile alone
+    the quarter's tail lay over the We slice, whose commit then wrote into the weights, and every gradient behind the layer was
+    wrong by tens of per cent.  49 and 97 are the first sizes back on a 128-row tile."""
+    gpb = max(1, R.SG_MAX_ROWS // seg)
+    plan = R.seg_plan(seg, seg * (3 * gpb + 1), R.ld_of(129))
+    assert plan is not None and (plan["trows"] == 96) == (seg in (43, 48, 65, 96)), plan
+    what, B = f"seg {seg} at H 129", 3 * gpb + 1
+    ref, m = _models(129, 2, 3, 0.0, seg)
+    data = _batch(seg, B, seg)
+    dd = data.to(DEV)
+    dd.x.requires_grad_(True)
+
+    def step():
+        out = m(dd)
+        torch.nn.MSELoss()(out, dd.y).backward()
+        return out
+    out, launches = _profiled(step)
+    reg = R.model_regime(seg * B, seg, 129, 2, 3, 2, True, _cus())
+    _check_classes(launches, reg["must"], reg["must_not"], what)
+    assert reg["ea_seg_bwd"] and launches.get("ea_seg_bwd", 0) > 0, launches
+    with torch.no_grad():
+        assert_close(out, ref(data), RTOL, f"{what}: out")
+    # (gradients on the HIP forward's own ReLU decisions: in a net this small ONE gate that differs from the fp32 oracle's moves a
+    #  weight gradient by more than the tolerance, see _assert_grads_on_hip_gates)
+    gates = _cpu_gates(m)
+    _assert_grads_on_hip_gates(m, ref, data, what, out, gates)
+    ref64 = copy.deepcopy(ref).double()
+    ref64.gates = gates
+    d64 = _to64(data)
+    d64.x.requires_grad_(True)
+    torch.nn.MSELoss()(ref64(d64), d64.y).backward()
+    assert_close(dd.x.grad, d64.x.grad.float(), RTOL, f"{what}: grad x")
 
 
 # ------------------------------------------------------------------------------------------ batch count at the latency-regime bound

@@ -217,6 +217,8 @@ REGIME_PINS = {
                    "return p.ny >= 1 && ld <= 8 * SG_NCH &&", "(!bwd_limits || p.nblocks <= 1024) &&",
                    "size_t f = (size_t)(bwd ? 3 : 2) * trows * SG_TW + (bwd ? 0 : 2 * SG_NCH * 256) + 2 * SG_TW + (bwd ? 4 * SG_TW + 4 * "
                    "SG_W2A_CH * 4 + 8 * 16 * 2 * 4 : 0) + (size_t)(bwd ? 2 : 1) * 2 * cap;",
+                   "const size_t tile = (size_t)trows * SG_TW, img = (size_t)SG_NCH * 256;", "return tile > img ? tile : img;",
+                   "if (bwd) f += seg_bwd_d_floats(trows) - (size_t)trows * SG_TW;",
                    "size_t i = (size_t)(bwd ? 2 : 1) * (rows_pb + 1 + cap);", "return (f + i) * 4 + 16;",
                    "const long per_cu = 4L;",
                    "return !off && fe == 2 && seg_plan(seg, n, ld, p, bwd) && (long)p.nblocks * p.ny <= per_cu * device_cus();",
