@@ -6,12 +6,14 @@ a made-up per-unit base on the synthetic grid of the case's size) and are solved
 (csrc/powerflow.hip: Newton-Raphson, one workgroup per sample).  A sample whose status is negative is drawn again -- the
 reference's `continue` -- and counted.  A case with more unknowns than the dense solver takes (6470rte: 10782) goes through the
 sparse route (csrc/powerflow_sparse.hip): its plan is built once and serves every device batch and redraw; --route sparse forces
-that route at any size.  With -r / -a every sample has its own topology, which the sparse route does not take: at such a size the
-solver's refusal stands.
+that route at any size.  With -r / -a every sample has its own topology: the sparse route then solves the samples in chunks
+that share one plan each, built on the chunk's cover list -- the base lines and the lines any of its samples adds -- with a
+per-sample line mask (utils/powerflow.py cover_plan, CoverChunker); the chunk size follows the fill the added lines cost.
 
     python dataset_generator.py --case 118 --samples 2000 --root data
     python dataset_generator.py --case 118 --samples 2000 --root data -r 1 -a 1
     python dataset_generator.py --case 6470rte --samples 256 --root data
+    python dataset_generator.py --case 6470rte --samples 256 --root data -r 1 -a 1
 
     <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]
     <root>/raw/case<case>_edge_features.npy   (S, e, 4) float64 [from, to, r, x]
@@ -60,11 +62,13 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
     """(bus_type [n], edge_index, rx [S, e, 2], tables [S, n, 4], redrawn): `samples` converged samples, host arrays.  `edge_index`
     is the grid's [2, e]; with `remove` or `add` above 0 it is [S, 2, e - remove + add], one perturbed line list per sample, and
     rx holds the parameters of those lines.  `counts` (a dict, optional) receives "disconnected": the samples dropped because no
-    connected draw was found, "drawn": all samples drawn, and "route": the solver route that ran.  `route`: "auto" (the sparse
-    route where the case has more unknowns than the dense solver takes and one topology) or "sparse"."""
+    connected draw was found, "drawn": all samples drawn, and "route": the solver route that ran; with per-sample topologies on
+    the sparse route also "chunks": the sizes of the chunks that shared a cover plan, "growth": the largest multiply-add count of a
+    cover plan over the base plan's, and "extras": the most lines a cover added.  `route`: "auto" (the sparse route where the case
+    has more unknowns than the dense solver takes) or "sparse"."""
     import torch
     from poweflownet_amd.synth import CASES, make_physical_inputs
-    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
+    from poweflownet_amd.utils.powerflow import CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, sparse_plan
     from poweflownet_amd.utils.topology import perturb_topology
     if route not in ("auto", "sparse"):
         raise ValueError(f"dataset_generator: route must be 'auto' or 'sparse', not {route!r}")
@@ -74,16 +78,18 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         raise ValueError(f"dataset_generator: cannot remove {remove} and add {add} lines")
     n, e = CASES[str(case)]
     perturbed = remove > 0 or add > 0
-    if route == "sparse" and perturbed:
-        raise ValueError("dataset_generator: the sparse route takes one topology; it does not go with -r / -a")
-    plan = None
+    plan = chunker = None
     # the route is decided from the grid alone, before a sample is drawn: a draw of no samples gives the lines and the bus types
     ei0, bt0, _, _ = make_physical_inputs(n, e, 0, seed * 1_000_003, load)
-    if route == "auto" and not perturbed and (n - 1) + int((bt0 == 2).sum()) > max_unknowns():
+    if route == "auto" and (n - 1) + int((bt0 == 2).sum()) > max_unknowns():
         route = "sparse"
     if route == "sparse":
         batch = min(batch, SPARSE_BATCH)
-        plan = sparse_plan(bt0.to(device), ei0.to(device))       # one grid: built and uploaded once, it serves every batch and redraw
+        if perturbed:
+            chunker = CoverChunker(bt0.to(device), ei0.to(device))  # one plan per chunk of samples, on the chunk's cover list
+        else:
+            plan = sparse_plan(bt0.to(device), ei0.to(device))   # one grid: built and uploaded once, it serves every batch and redraw
+    growth, extras = 1.0, 0
     keep_ei, keep_rx, keep_t, have, redrawn, drawn, disconnected = [], [], [], 0, 0, 0, 0
     for rnd in range(max_rounds):
         if have >= samples:
@@ -104,7 +110,12 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         drawn += want
         if d_spec.shape[0] == 0:
             continue
-        res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter, route=route, plan=plan)
+        if chunker is not None:
+            res, covers = solve_power_flow_covered(chunker, d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
+            growth = max([growth] + [chunker.growth(c) for _, c in covers])
+            extras = max([extras] + [c.extras for _, c in covers])
+        else:
+            res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter, route=route, plan=plan)
         ok = res.status >= 0
         if int(res.flags.item()) != 0:
             raise RuntimeError("dataset_generator: the solver flagged its bus types")
@@ -117,6 +128,8 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         redrawn += int((~ok).sum())
     if counts is not None:
         counts.update(disconnected=disconnected, drawn=drawn, route=route)
+        if chunker is not None:
+            counts.update(chunks=list(chunker.sizes), growth=growth, extras=extras)
     if have < samples:
         raise RuntimeError(f"dataset_generator: only {have} of {samples} samples converged in {max_rounds} rounds (load {load})")
     lines = np.concatenate(keep_ei)[:samples] if perturbed else ei.numpy()
@@ -151,6 +164,10 @@ def main(argv=None):
     print(f"Failed to converge and drawn again: {redrawn}")
     if counts["route"] == "sparse":
         print("Solved on the sparse route")
+    if "chunks" in counts:
+        sizes = counts["chunks"]
+        print(f"Cover plans: {len(sizes)} chunk(s) of {min(sizes)}..{max(sizes)} samples, at most {counts['extras']} added lines and "
+              f"{counts['growth']:.3f} x the base plan's multiply-adds per factor")
     print(f"wrote {a.samples} samples of case{name} ({tables.shape[1]} buses, {ei.shape[-1]} lines): {paths[0]}, {paths[1]}")
     return 0
 

@@ -43,21 +43,20 @@ def solver_inputs(node, edge, device, rows=slice(None)):
 
 def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, device="cuda:0", split=(.5, .2, .3), route="auto"):
     """Per-sample losses (host float64 array) of the DC solve against the test split of `root`'s case; failed solves raise.  `route`:
-    "auto" -- the sparse route (one plan for the whole split) where the case has more buses than the dense solver takes and its
-    samples share one line list -- or "sparse"."""
+    "auto" -- the sparse route where the case has more buses than the dense solver takes -- or "sparse".  There a split whose samples
+    share one line list has one plan; a perturbed one (one list per sample) is solved in chunks that share a cover plan each
+    (utils/powerflow.py CoverChunker: the file's lists are its input, the first sample's list its base)."""
     import torch
     from poweflownet_amd.datasets import PowerFlowData
     from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
-    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
+    from poweflownet_amd.utils.powerflow import CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, sparse_plan
     if route not in ("auto", "sparse"):
         raise ValueError(f"dc_error: route must be 'auto' or 'sparse', not {route!r}")
     testset, node, edge = load_test_split(root, case, samples, split)
     one_topology = bool((edge[:, :, :2] == edge[:1, :, :2]).all())
-    if route == "auto" and one_topology and node.shape[1] - 1 > max_unknowns():
+    if route == "auto" and node.shape[1] - 1 > max_unknowns():
         route = "sparse"
-    if route == "sparse" and not one_topology:
-        raise RuntimeError("dc_error: the sparse route takes one line list for all samples; this set has one per sample")
-    plan = None
+    plan = chunker = None
     mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     mask = torch.tensor(PowerFlowData.bus_type_mask)[bus_type.cpu()].clone()
@@ -68,10 +67,14 @@ def dc_losses(root, case, samples=None, batch=4096, tol=1e-8, max_iter=10, devic
     out = []
     for s0 in range(0, len(node), batch):
         truth, ei, rx = solver_inputs(node, edge, device, slice(s0, s0 + batch))
-        if route == "sparse":
-            ei = ei[0].contiguous()
-            plan = plan or sparse_plan(bus_type, ei, "dc")
-        res = solve_power_flow(bus_type, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter, route=route, plan=plan)
+        if route == "sparse" and not one_topology:
+            chunker = chunker or CoverChunker(bus_type, ei[0].contiguous(), "dc")
+            res, _ = solve_power_flow_covered(chunker, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter)
+        else:
+            if route == "sparse":
+                ei = ei[0].contiguous()
+                plan = plan or sparse_plan(bus_type, ei, "dc")
+            res = solve_power_flow(bus_type, truth, ei, rx, mode="dc", tol=tol, max_iter=max_iter, route=route, plan=plan)
         if int((res.status < 0).sum()) or int(res.flags.item()):
             raise RuntimeError(f"dc_error: {int((res.status < 0).sum())} DC solves failed (statuses {sorted(set(res.status.tolist()))})")
         dc = res.table.clone()

@@ -623,10 +623,53 @@ size_t pfn_powerflow_sparse_fd_plan_bytes(const int64_t* edge_index, int64_t n_l
 int pfn_powerflow_sparse_fd_plan(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, void* plan,
                                  size_t plan_bytes);
 size_t pfn_powerflow_sparse_fd_workspace_bytes(int64_t n_samples, const void* plan_header);
+/* pfn_powerflow_sparse_plan_into (HOST arrays in, HOST blob out): the plan of mode 0, 1 or 2 (the fast-decoupled plan) built straight
+ *   into a buffer the caller sized by a guess, ONE elimination per matrix where pfn_powerflow_sparse_plan_bytes + _plan run two (the
+ *   fast-decoupled pair: six) -- for callers that plan often, as the per-sample-topology route does once per chunk.  *needed gets the
+ *   plan's size whenever the inputs are valid.  PFN_OK: the blob, byte for byte the two-call path's, stands in plan[0, *needed);
+ *   with plan_bytes < *needed (or plan null) it is PFN_ENOSPACE: come again with *needed bytes.  PFN_EINVAL: as the two-call path. */
+int pfn_powerflow_sparse_plan_into(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode, void* plan,
+                                   size_t plan_bytes, size_t* needed);
 int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
                                   const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
                                   const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
                                   double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------- sparse power-flow routes, per-sample topologies
+ * A factorisation under a static order without pivoting stays valid on any SUPERSET of a sample's pattern: a line the sample
+ * lacks is a structural zero.  So a chunk of samples with their own line lists shares ONE plan, built by pfn_powerflow_sparse_plan
+ * / _fd_plan on a COVER list that holds every line of every sample, and the kernels are told per sample which cover lines exist.
+ * A line's key is its unordered bus pair, min * n_bus + max.
+ * pfn_powerflow_cover_map (csrc/powerflow_cover.hip): ONE launch, one workgroup per sample, no host sync, no allocation
+ *   (capturable), no atomics.  edge_index int64 [n_samples, 2, n_lines], rx [n_samples, n_lines, 2]; cover_keys int64 [n_cover]: the
+ *   keys of the cover list sorted ascending, equal keys in cover order; cover_slot int32 [n_cover]: the cover line at each sorted
+ *   position.  THE SLOT RULE: sample s's k-th line with key q, in stored order, takes the k-th cover line with key q, in cover
+ *   order; its orientation does not matter (the line terms are symmetric in their ends).  line_mask uint8 [n_samples, n_cover]: 1
+ *   where the sample has the cover line; rx_cover [n_samples, n_cover, 2]: the line's (r, x) at its cover line, NOT WRITTEN where
+ *   the mask is 0; unplaced int32 [n_samples]: the sample's lines without a cover line -- a key the cover lacks or holds too few
+ *   times, a bus outside [0, n_bus), one bus twice.  Every id is tested before it indexes anything; the assignment is the rule's on every run (where two lines of a
+ *   sample meet at one cover line, the first in stored order keeps it).  rx and rx_cover 16-byte aligned.
+ * pfn_powerflow_solve_sparse_masked / pfn_powerflow_solve_sparse_fd_masked: pfn_powerflow_solve_sparse / _fd with edge_index the
+ *   COVER list [2, n_lines], rx = rx_cover, and line_mask uint8 [n_samples, n_lines] (or null: every line is there), unplaced int32
+ *   [n_samples] (or null).  A masked-off line end adds nothing to the line sums, the mismatch, the Jacobian, B' or B'', and its rx
+ *   is never read.  The plan is checked against the cover list as before; a sample with unplaced != 0 ends with -6 and NaN rows; a
+ *   mask that leaves a bus without a line ends with -2 (a zero pivot), as a bus without a line does on every route.  With both
+ *   pointers null these ARE the unmasked entries, bit for bit; with a mask a sample's result is a pure function of (its inputs,
+ *   its mask row, the plan), bit for bit, whatever the batch and the workgroup size.  Under another cover the factor's pattern and
+ *   order differ, so results agree to rounding, not bit for bit.                                                               */
+int pfn_powerflow_cover_map(const int64_t* edge_index, int64_t n_lines, const double* rx, int64_t n_samples, int64_t n_bus,
+                            const int64_t* cover_keys, const int32_t* cover_slot, int64_t n_cover, uint8_t* line_mask, double* rx_cover,
+                            int32_t* unplaced, void* stream);
+int pfn_powerflow_solve_sparse_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                      const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
+                                      int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
+                                      const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
+                                      int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                         const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
+                                         int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
+                                         const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
+                                         int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------- topology perturbation
  * The reference's perturb_topology (utils/data_utils.py:12-59, behind dataset_generator.py -r / -a) drawn per sample on the device:

@@ -34,6 +34,7 @@ SYMBOLS = (
     "pfn_powerflow_workspace_bytes_mode", "pfn_powerflow_solve_init",
     "pfn_powerflow_sparse_plan_bytes", "pfn_powerflow_sparse_plan", "pfn_powerflow_sparse_workspace_bytes", "pfn_powerflow_solve_sparse",
     "pfn_powerflow_sparse_fd_plan_bytes", "pfn_powerflow_sparse_fd_plan", "pfn_powerflow_sparse_fd_workspace_bytes", "pfn_powerflow_solve_sparse_fd",
+    "pfn_powerflow_sparse_plan_into", "pfn_powerflow_cover_map", "pfn_powerflow_solve_sparse_masked", "pfn_powerflow_solve_sparse_fd_masked",
     "pfn_topology_perturb", "pfn_topology_unsupplied",
 )
 
@@ -162,6 +163,12 @@ def load() -> C.CDLL:
         "pfn_powerflow_sparse_fd_workspace_bytes": (sz, [i64, p]),
         "pfn_powerflow_solve_sparse_fd": (C.c_int, [p, i64, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int, p, p, p, p, p,
                                                     sz, p]),
+        "pfn_powerflow_sparse_plan_into": (C.c_int, [p, i64, p, i64, C.c_int, p, sz, p]),
+        "pfn_powerflow_cover_map": (C.c_int, [p, i64, p, i64, i64, p, p, i64, p, p, p, p]),
+        "pfn_powerflow_solve_sparse_masked": (C.c_int, [p, i64, p, p, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int, p,
+                                                        p, p, p, p, sz, p]),
+        "pfn_powerflow_solve_sparse_fd_masked": (C.c_int, [p, i64, p, p, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int,
+                                                           p, p, p, p, p, sz, p]),
         "pfn_topology_perturb": (C.c_int, [p, i64, i64, i64, i64, i64, i64, C.c_uint64, i64, C.c_int, p, p, p, p]),
         "pfn_topology_unsupplied": (C.c_int, [p, C.c_int, i64, i64, i64, i64, p, p]),
     }

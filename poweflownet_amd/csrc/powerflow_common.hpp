@@ -35,6 +35,10 @@ struct PfProblem {
     void* ws;                                       // dense: the global route's fp32 slabs or null; sparse: the samples' vectors and slabs
     double tol;
     int n, e, max_iter;
+    // the cover route (powerflow_cover.hip) only, null elsewhere: which lines of the shared list sample s has, and whether one of
+    // its own lines found no place in that list
+    const uint8_t* line_mask;                       // [S, e] or null: every line is there
+    const int32_t* unplaced;                        // [S] or null
 };
 
 // sample s's rows of the per-sample arrays
@@ -49,6 +53,12 @@ __device__ __forceinline__ PfSample pf_sample(const PfProblem& p, int s) {
     return {p.init ? p.init + (int64_t)s * 2 * p.n : nullptr, p.rx + (int64_t)s * 2 * p.e, p.spec + (int64_t)s * 4 * p.n,
             p.table + (int64_t)s * 4 * p.n};
 }
+
+// sample s's row of the line mask, or null (uniform); and what it holds against the plan before anything is indexed (uniform)
+__device__ __forceinline__ const uint8_t* pf_line_mask(const PfProblem& p, int s) {
+    return p.line_mask ? p.line_mask + (int64_t)s * p.e : nullptr;
+}
+__device__ __forceinline__ int pf_unplaced(const PfProblem& p, int s) { return p.unplaced ? p.unplaced[s] != 0 : 0; }
 
 // ---- the start state: flat, or the caller's -- Va at the non-slack buses, Vm at the PQ buses (dc: Va only, its Vm is no unknown).
 // True, for all threads alike, when the caller's start holds a non-finite value.
@@ -203,7 +213,9 @@ __device__ __forceinline__ PfPlanView pf_plan_view(const unsigned char* pb) {
 // ---- the device arrays against the plan: the bus types decide the unknowns, the line list the line ends.  `stale` (uniform) is
 // what the caller already holds against the plan: nothing is indexed then.  contradicts(i, ty, stale) says whether bus i's type
 // disagrees with the kernel's unknowns and may raise `stale` itself.  A line number outside the list is stale, never followed.
-// Returns 0, PF_BAD_TYPES (flags bit 0 is set with it) or PF_STALE_PLAN, for all threads alike.
+// Returns 0, PF_BAD_TYPES (flags bit 0 is set with it) or PF_STALE_PLAN, for all threads alike.  A sample that comes in stale -- the
+// fast-decoupled plan's size test, an unplaced line of the cover route -- skips the bus-type scan with everything else: it reports
+// PF_STALE_PLAN, and flags bit 0 is set only by the samples that do scan (a batch of nothing but such samples leaves it clear).
 template <typename Contradicts>
 __device__ __forceinline__ int pf_check_plan(const PfProblem& p, const PfPlanView& v, int nt, int stale, Contradicts contradicts) {
     const int e = p.e;
@@ -259,10 +271,11 @@ static inline int pf_check_call(const char* who, const PfProblem& p, int64_t n_s
 // the launch of a sparse route's kernel, one workgroup per sample: one wave until the longest column of the plan exceeds 128 -- a
 // k-step then costs its load latency, not a barrier, and many samples share a compute unit --, four waves once the long columns
 // of the dense tail carry the multiply-adds (DESIGN 7k and 7l have the measurements behind the threshold); `threads` overrides.
-template <typename Args>
+// Pair tells kernel pairs with one argument struct apart: each needs its own dynamic-LDS attribute raised.
+template <int Pair = 0, typename Args>
 static int pf_launch_sparse(void (*k64)(Args), void (*k256)(Args), int threads, int max_col, int64_t n_samples, size_t lds, hipStream_t s,
                             const Args& a) {
-    static std::atomic<uint64_t> raised64{0}, raised256{0};      // (per Args: per kernel pair)
+    static std::atomic<uint64_t> raised64{0}, raised256{0};      // (per Pair and Args: per kernel pair)
     const int use = threads ? threads : (max_col > 128 ? 256 : 64);
     PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(use == 64 ? k64 : k256), kLdsCuBytes - kLdsReserve, use == 64 ? raised64 : raised256));
     (use == 64 ? k64 : k256)<<<(int)n_samples, use, lds, s>>>(a);

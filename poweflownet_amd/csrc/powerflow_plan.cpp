@@ -283,7 +283,7 @@ int build_plan(const char* who, const int64_t* ei, int64_t e, const int32_t* bt,
 extern "C" {
 
 // (the size is known only once the elimination has run: the sizing call and the build call each run it -- 0.35 s apiece at 6470
-//  buses, once per grid -- and neither keeps anything behind)
+//  buses, once per grid -- and neither keeps anything behind; pfn_powerflow_sparse_plan_into below runs it once)
 size_t pfn_powerflow_sparse_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode) {
     size_t bytes = 0;
     if (mode != 0 && mode != 1) mode = -1;          // (the internal kinds are not reachable from here)
@@ -300,31 +300,8 @@ int pfn_powerflow_sparse_plan(const int64_t* edge_index, int64_t n_lines, const 
     return build_plan("pfn_powerflow_sparse_plan", edge_index, n_lines, bus_type, n_bus, mode, plan, plan_bytes, nullptr);
 }
 
-// The fast-decoupled plan (layout: powerflow_plan.hpp): an outer header, then two complete sub-plans -- P, B' over the angle buses
-// (byte for byte the mode-1 plan), and Q, B'' over the PQ buses.  Each sizing call runs both eliminations.
-static int build_fd_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, void* plan, size_t plan_bytes, size_t* bytes_out) {
-    const char* who = "pfn_powerflow_sparse_fd_plan";
-    size_t bytes_p = 0, bytes_q = 0;
-    if (build_plan(who, ei, e, bt, n, 1, nullptr, 0, &bytes_p) != PFN_OK) return PFN_EINVAL;
-    if (build_plan(who, ei, e, bt, n, PLAN_PQ, nullptr, 0, &bytes_q) != PFN_OK) return PFN_EINVAL;
-    const int64_t off_p = (int64_t)PFP_HEADER_WORDS * 4, off_q = off_p + align16((int64_t)bytes_p), total = off_q + align16((int64_t)bytes_q);
-    if (total >= (1ll << 31)) {
-        set_error("%s: a plan of %lld bytes does not fit 32-bit offsets", who, (long long)total);
-        return PFN_EINVAL;
-    }
-    if (bytes_out) *bytes_out = (size_t)total;
-    if (!plan) return PFN_OK;
-    if (plan_bytes < (size_t)total) {
-        set_error("%s: the plan needs %lld bytes (got %zu)", who, (long long)total, plan_bytes);
-        return PFN_EINVAL;
-    }
-    unsigned char* base = static_cast<unsigned char*>(plan);
-    std::memset(base, 0, (size_t)total);
-    if (build_plan(who, ei, e, bt, n, 1, base + off_p, bytes_p, nullptr) != PFN_OK ||
-        build_plan(who, ei, e, bt, n, PLAN_PQ, base + off_q, bytes_q, nullptr) != PFN_OK) {
-        std::memset(base, 0, (size_t)total);
-        return PFN_EINVAL;
-    }
+// the outer header of a fast-decoupled plan whose two sub-plans stand at off_p and off_q of `base`
+static int finish_fd_plan(const char* who, unsigned char* base, int64_t off_p, int64_t off_q, int64_t total) {
     int32_t* H = reinterpret_cast<int32_t*>(base);
     const int32_t* P = reinterpret_cast<const int32_t*>(base + off_p);
     const int32_t* Q = reinterpret_cast<const int32_t*>(base + off_q);
@@ -356,6 +333,34 @@ static int build_fd_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_
     return PFN_OK;
 }
 
+// The fast-decoupled plan (layout: powerflow_plan.hpp): an outer header, then two complete sub-plans -- P, B' over the angle buses
+// (byte for byte the mode-1 plan), and Q, B'' over the PQ buses.  Each sizing call runs both eliminations.
+static int build_fd_plan(const int64_t* ei, int64_t e, const int32_t* bt, int64_t n, void* plan, size_t plan_bytes, size_t* bytes_out) {
+    const char* who = "pfn_powerflow_sparse_fd_plan";
+    size_t bytes_p = 0, bytes_q = 0;
+    if (build_plan(who, ei, e, bt, n, 1, nullptr, 0, &bytes_p) != PFN_OK) return PFN_EINVAL;
+    if (build_plan(who, ei, e, bt, n, PLAN_PQ, nullptr, 0, &bytes_q) != PFN_OK) return PFN_EINVAL;
+    const int64_t off_p = (int64_t)PFP_HEADER_WORDS * 4, off_q = off_p + align16((int64_t)bytes_p), total = off_q + align16((int64_t)bytes_q);
+    if (total >= (1ll << 31)) {
+        set_error("%s: a plan of %lld bytes does not fit 32-bit offsets", who, (long long)total);
+        return PFN_EINVAL;
+    }
+    if (bytes_out) *bytes_out = (size_t)total;
+    if (!plan) return PFN_OK;
+    if (plan_bytes < (size_t)total) {
+        set_error("%s: the plan needs %lld bytes (got %zu)", who, (long long)total, plan_bytes);
+        return PFN_EINVAL;
+    }
+    unsigned char* base = static_cast<unsigned char*>(plan);
+    std::memset(base, 0, (size_t)total);
+    if (build_plan(who, ei, e, bt, n, 1, base + off_p, bytes_p, nullptr) != PFN_OK ||
+        build_plan(who, ei, e, bt, n, PLAN_PQ, base + off_q, bytes_q, nullptr) != PFN_OK) {
+        std::memset(base, 0, (size_t)total);
+        return PFN_EINVAL;
+    }
+    return finish_fd_plan(who, base, off_p, off_q, total);
+}
+
 size_t pfn_powerflow_sparse_fd_plan_bytes(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus) {
     size_t bytes = 0;
     return build_fd_plan(edge_index, n_lines, bus_type, n_bus, nullptr, 0, &bytes) == PFN_OK ? bytes : 0;
@@ -368,6 +373,62 @@ int pfn_powerflow_sparse_fd_plan(const int64_t* edge_index, int64_t n_lines, con
         return PFN_EINVAL;
     }
     return build_fd_plan(edge_index, n_lines, bus_type, n_bus, plan, plan_bytes, nullptr);
+}
+
+// One elimination per matrix where the two calls above run two (the fast-decoupled pair: six): the plan is built straight into a
+// buffer the caller sized by a guess -- a plan of the same grid with a few lines more or fewer is a good one.  *needed gets the
+// plan's size whenever the inputs are valid; a buffer that is too small (or null) is PFN_ENOSPACE, nothing usable is written, and
+// the caller comes again with `needed` bytes.  mode 0, 1, or 2: the fast-decoupled plan.  The blob is the two-call path's, byte for byte.
+int pfn_powerflow_sparse_plan_into(const int64_t* edge_index, int64_t n_lines, const int32_t* bus_type, int64_t n_bus, int mode, void* plan,
+                                   size_t plan_bytes, size_t* needed) {
+    const char* who = "pfn_powerflow_sparse_plan_into";
+    if (!needed) {
+        set_error("%s: null needed", who);
+        return PFN_EINVAL;
+    }
+    *needed = 0;
+    if (!plan) plan_bytes = 0;
+    unsigned char* base = static_cast<unsigned char*>(plan);
+    if (mode == 0 || mode == 1) {
+        size_t bytes = 0;
+        const int rc = build_plan(who, edge_index, n_lines, bus_type, n_bus, mode, plan_bytes ? plan : nullptr, plan_bytes, &bytes);
+        *needed = bytes;
+        if (bytes == 0) return PFN_EINVAL;              // (the inputs were refused: the text is set)
+        if (bytes > plan_bytes) {
+            set_error("%s: the plan needs %zu bytes (got %zu)", who, bytes, plan_bytes);
+            return PFN_ENOSPACE;
+        }
+        return rc;
+    }
+    if (mode != PFD_MODE) {
+        set_error("%s: mode must be 0 (AC), 1 (DC) or 2 (the fast-decoupled plan)", who);
+        return PFN_EINVAL;
+    }
+    // each half goes where it belongs if the room behind it suffices; a half that does not fit is sized only
+    const int64_t off_p = (int64_t)PFP_HEADER_WORDS * 4;
+    size_t bytes_p = 0, bytes_q = 0;
+    const size_t room_p = plan_bytes > (size_t)off_p ? plan_bytes - (size_t)off_p : 0;
+    const int rc_p = build_plan(who, edge_index, n_lines, bus_type, n_bus, 1, room_p ? base + off_p : nullptr, room_p, &bytes_p);
+    if (bytes_p == 0) return PFN_EINVAL;
+    const int64_t off_q = off_p + align16((int64_t)bytes_p);
+    const size_t room_q = bytes_p <= room_p && plan_bytes > (size_t)off_q ? plan_bytes - (size_t)off_q : 0;
+    const int rc_q = build_plan(who, edge_index, n_lines, bus_type, n_bus, PLAN_PQ, room_q ? base + off_q : nullptr, room_q, &bytes_q);
+    if (bytes_q == 0) return PFN_EINVAL;
+    const int64_t total = off_q + align16((int64_t)bytes_q);
+    if (total >= (1ll << 31)) {
+        set_error("%s: a plan of %lld bytes does not fit 32-bit offsets", who, (long long)total);
+        return PFN_EINVAL;
+    }
+    *needed = (size_t)total;
+    if ((size_t)total > plan_bytes || bytes_p > room_p || bytes_q > room_q) {
+        set_error("%s: the plan needs %lld bytes (got %zu)", who, (long long)total, plan_bytes);
+        return PFN_ENOSPACE;
+    }
+    if (rc_p != PFN_OK || rc_q != PFN_OK) return PFN_EINVAL;
+    std::memset(base, 0, (size_t)off_p);
+    std::memset(base + off_p + bytes_p, 0, (size_t)(off_q - off_p) - bytes_p);
+    std::memset(base + off_q + bytes_q, 0, (size_t)(total - off_q) - bytes_q);
+    return finish_fd_plan(who, base, off_p, off_q, total);
 }
 
 }  // extern "C"

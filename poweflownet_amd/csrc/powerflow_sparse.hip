@@ -35,7 +35,10 @@ struct PfsArgs {
     int m, nnz, mode, f_in_lds;
 };
 
-template <int THREADS>
+// MASKED: the cover route's instantiation, which asks the sample's line mask about every line end.  The one-topology launch takes
+// the other one, whose assembly loop is the loop it always was (the test cost the Newton walk 1-1.6 % when it was made at run time;
+// DESIGN 7p).
+template <int THREADS, bool MASKED>
 __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pfs_smem[];
     __shared__ double s_red[THREADS / 64];
@@ -61,10 +64,12 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
     const PfSample sm = pf_sample(p, s);
     const double* rx = sm.rx;
     const double* spec = sm.spec;
+    const uint8_t* mask = MASKED ? pf_line_mask(p, s) : nullptr;
     double res = __builtin_nan("");
 
-    // ---- the device arrays against the plan, then the start state; code is uniform over the workgroup wherever it is tested
-    int code = pf_check_plan(p, v, nt, 0, [&](int i, int ty, int&) { return (ty != 0) != (ua[i] >= 0) || (ty == 2 && !dc) != (uv[i] >= 0); });
+    // ---- the device arrays against the plan, then the start state; code is uniform over the workgroup wherever it is tested.  A
+    // sample with a line the cover list has no place for is stale before anything is looked at
+    int code = pf_check_plan(p, v, nt, pf_unplaced(p, s), [&](int i, int ty, int&) { return (ty != 0) != (ua[i] >= 0) || (ty == 2 && !dc) != (uv[i] >= 0); });
     if (code == 0 && pf_start_state(p, sm, a.plan[PFP_H_SLACK], dc, nt, vm, th)) code = PF_NON_FINITE;
     int it = 0;
     if (code == 0) {
@@ -81,6 +86,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
                     const int2 lj = v.adj[q];
                     const int4 pos = v.adjpos[q];
                     const int k = lj.x >> 1, j = lj.y;
+                    if (MASKED && mask && !mask[k]) continue;   // a line this sample lacks: a structural zero, its rx is never read
                     const double r = rx[2 * k], x = rx[2 * k + 1];
                     if (dc) {
                         const double b = pf_dc_end(x, ti, th[j], sP);
@@ -158,30 +164,33 @@ size_t pfn_powerflow_sparse_workspace_bytes(int64_t n_samples, const void* plan_
     return (size_t)n_samples * pf_sample_bytes(h[PFP_H_N], h[PFP_H_M], h[PFP_H_NNZ]);
 }
 
-int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
-                               const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
-                               const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
-                               double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+int pfn_powerflow_solve_sparse_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                      const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
+                                      int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
+                                      const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
+                                      int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = line_mask || unplaced ? "pfn_powerflow_solve_sparse_masked" : "pfn_powerflow_solve_sparse";
     const int32_t* h = static_cast<const int32_t*>(plan_header);
-    PFN_TRY(pfs_check_header(h, "pfn_powerflow_solve_sparse"));
-    PFN_CHECK_ARG(mode == 0 || mode == 1, "pfn_powerflow_solve_sparse: mode must be 0 (AC) or 1 (DC); the fast-decoupled modes 2 and 3 are pfn_powerflow_solve_sparse_fd's");
+    PFN_TRY(pfs_check_header(h, who));
+    PFN_CHECK_ARG(mode == 0 || mode == 1, "%s: mode must be 0 (AC) or 1 (DC); the fast-decoupled modes 2 and 3 are pfn_powerflow_solve_sparse_fd's", who);
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines && h[PFP_H_MODE] == mode,
-                  "pfn_powerflow_solve_sparse: the plan is for %d buses, %d lines, mode %d; the call has %lld, %lld, mode %d", (int)h[PFP_H_N],
+                  "%s: the plan is for %d buses, %d lines, mode %d; the call has %lld, %lld, mode %d", who, (int)h[PFP_H_N],
                   (int)h[PFP_H_E], (int)h[PFP_H_MODE], (long long)n_bus, (long long)n_lines, mode);
-    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "pfn_powerflow_solve_sparse: threads must be 0 (the default), 64 or 256");
+    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
+    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
     const int n = h[PFP_H_N], m = h[PFP_H_M], nnz = h[PFP_H_NNZ];
     const size_t stride = pf_sample_bytes(n, m, nnz), need = (size_t)n_samples * stride;
-    const PfsArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter},
+    const PfsArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter, line_mask, unplaced},
                     static_cast<const int32_t*>(plan_dev), stride, m, nnz, mode, pf_f_in_lds(m)};
-    PFN_TRY(pf_check_call("pfn_powerflow_solve_sparse", a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
+    PFN_TRY(pf_check_call(who, a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
     if (n_samples == 0) return PFN_OK;
     // (a plan with 32-bit row ids has more than 65535 unknowns: its work vector would not fit LDS either; the kernel reads 16-bit ids only)
-    PFN_CHECK_ARG(h[PFP_H_IDX16] != 0, "pfn_powerflow_solve_sparse: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", m);
+    PFN_CHECK_ARG(h[PFP_H_IDX16] != 0, "%s: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", who, m);
     const size_t lds = pf_lds_bytes(m);
-    PFN_CHECK_ARG(lds <= (size_t)(kLdsCuBytes - kLdsReserve), "pfn_powerflow_solve_sparse: a work vector of %d unknowns needs %zu bytes of LDS, %d are there",
+    PFN_CHECK_ARG(lds <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns needs %zu bytes of LDS, %d are there", who,
                   m, lds, kLdsCuBytes - kLdsReserve);
     if (!ws || ws_bytes < need) {
-        set_error("pfn_powerflow_solve_sparse: the workspace must hold %zu bytes (got %zu)", need, ws ? ws_bytes : (size_t)0);
+        set_error("%s: the workspace must hold %zu bytes (got %zu)", who, need, ws ? ws_bytes : (size_t)0);
         return PFN_ENOSPACE;
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -189,7 +198,16 @@ int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const
     ProfScope ps(mode ? "powerflow_sparse_dc" : "powerflow_sparse_ac",
                  (double)n_samples * ((double)n_lines * 16.0 + (double)n * 64.0 + (init ? (double)n * 16.0 : 0.0)) + (double)h[PFP_H_BYTES],
                  (double)n_samples * 5.0 * 2.0 * (madds + 2.0 * (double)h[PFP_H_NNZ_L]), s);
-    return pf_launch_sparse(powerflow_sparse_kernel<64>, powerflow_sparse_kernel<256>, threads, h[PFP_H_MAX_COL], n_samples, lds, s, a);
+    if (line_mask) return pf_launch_sparse<1>(powerflow_sparse_kernel<64, true>, powerflow_sparse_kernel<256, true>, threads, h[PFP_H_MAX_COL], n_samples, lds, s, a);
+    return pf_launch_sparse(powerflow_sparse_kernel<64, false>, powerflow_sparse_kernel<256, false>, threads, h[PFP_H_MAX_COL], n_samples, lds, s, a);
+}
+
+int pfn_powerflow_solve_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                               const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
+                               const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
+                               double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+    return pfn_powerflow_solve_sparse_masked(edge_index, n_lines, rx, nullptr, nullptr, bus_type, spec, init, n_samples, n_bus, mode, tol,
+                                             max_iter, plan_header, plan_dev, threads, table, status, residual, flags, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -51,12 +51,14 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_fd_kernel(const PfdA
     const PfSample sm = pf_sample(p, s);
     const double* rx = sm.rx;
     const double* spec = sm.spec;
+    const uint8_t* mask = pf_line_mask(p, s);
     double res = __builtin_nan("");
 
     // ---- the device arrays against the plan, both halves: the bus types decide who has an unknown in B' and in B'' (a PV bus the
     // plan took for PQ is noticed here), the line list the line ends.  A plan whose sizes disagree with the outer header (it cannot
-    // come from the builder) is refused before anything is indexed with them.  code is uniform over the workgroup wherever it is tested.
-    int code = pf_check_plan(p, hp, nt, hp.A.m != a.m_p || hq.A.m != a.m_q || hp.nnz + hq.nnz != nnz, [&](int i, int ty, int& stale) {
+    // come from the builder) is refused before anything is indexed with them, and so is a sample with a line the cover list has no
+    // place for.  code is uniform over the workgroup wherever it is tested.
+    int code = pf_check_plan(p, hp, nt, hp.A.m != a.m_p || hq.A.m != a.m_q || hp.nnz + hq.nnz != nnz || pf_unplaced(p, s), [&](int i, int ty, int& stale) {
         stale |= hp.adjptr[i] != hq.adjptr[i] || hp.adjptr[i + 1] != hq.adjptr[i + 1];
         return (ty != 0) != (hp.ua[i] >= 0) || (ty == 2) != (hq.ua[i] >= 0);
     });
@@ -81,6 +83,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_fd_kernel(const PfdA
             const int q1 = hp.adjptr[i + 1];
             for (int q = hp.adjptr[i]; q < q1; ++q) {
                 const int k = hp.adj[q].x >> 1;
+                if (mask && !mask[k]) continue;                 // a line this sample lacks: a structural zero, its rx is never read
                 const int pp = hp.adjpos[q].x, pq = hq.adjpos[q].x;
                 const double r = rx[2 * k], x = rx[2 * k + 1];
                 const double w_x = 1.0 / x, w_b = x / (r * r + x * x);
@@ -113,6 +116,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_fd_kernel(const PfdA
                 for (int q = hp.adjptr[i]; q < q1; ++q) {
                     const int2 lj = hp.adj[q];
                     const int k = lj.x >> 1, j = lj.y;
+                    if (mask && !mask[k]) continue;
                     pf_ac_end(rx[2 * k], rx[2 * k + 1], vi, ti, vm[j], th[j], sP, sQ);
                 }
                 sp[i] = sP;
@@ -178,20 +182,22 @@ size_t pfn_powerflow_sparse_fd_workspace_bytes(int64_t n_samples, const void* pl
     return (size_t)n_samples * pf_sample_bytes(h[PFP_H_N], std::max(h[PFP_H_M], h[PFD_H_M_Q]), h[PFP_H_NNZ]);
 }
 
-int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
-                                  const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
-                                  const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
-                                  double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "pfn_powerflow_solve_sparse_fd";
+int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                         const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
+                                         int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
+                                         const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
+                                         int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = line_mask || unplaced ? "pfn_powerflow_solve_sparse_fd_masked" : "pfn_powerflow_solve_sparse_fd";
     const int32_t* h = static_cast<const int32_t*>(plan_header);
     PFN_TRY(pfd_check_header(h, who));
     PFN_CHECK_ARG(mode == 2 || mode == 3, "%s: mode must be 2 (fdxb) or 3 (fdbx); modes 0 and 1 are pfn_powerflow_solve_sparse's", who);
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines, "%s: the plan is for %d buses, %d lines; the call has %lld, %lld", who,
                   (int)h[PFP_H_N], (int)h[PFP_H_E], (long long)n_bus, (long long)n_lines);
     PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
+    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
     const int n = h[PFP_H_N], m_p = h[PFP_H_M], m_q = h[PFD_H_M_Q], nnz = h[PFP_H_NNZ], mmax = std::max(m_p, m_q);
     const size_t stride = pf_sample_bytes(n, mmax, nnz), need = (size_t)n_samples * stride;
-    const PfdArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter},
+    const PfdArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter, line_mask, unplaced},
                     static_cast<const int32_t*>(plan_dev), stride, m_p, m_q, nnz, mode == 3, pf_f_in_lds(mmax)};
     PFN_TRY(pf_check_call(who, a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
     if (n_samples == 0) return PFN_OK;
@@ -210,6 +216,14 @@ int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, co
                  (double)n_samples * ((double)n_lines * 16.0 + (double)n * 64.0 + (init ? (double)n * 16.0 : 0.0)) + (double)h[PFP_H_BYTES],
                  (double)n_samples * 2.0 * (madds + 20.0 * (double)h[PFP_H_NNZ]), s);
     return pf_launch_sparse(powerflow_sparse_fd_kernel<64>, powerflow_sparse_fd_kernel<256>, threads, h[PFP_H_MAX_COL], n_samples, lds, s, a);
+}
+
+int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                                  const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
+                                  const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status,
+                                  double* residual, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+    return pfn_powerflow_solve_sparse_fd_masked(edge_index, n_lines, rx, nullptr, nullptr, bus_type, spec, init, n_samples, n_bus, mode, tol,
+                                                max_iter, plan_header, plan_dev, threads, table, status, residual, flags, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -5,8 +5,9 @@ demand-positive per-unit, Va in degrees; no shunts, line charging, taps, Q-limit
 is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  No CPU path."""
 import ctypes as C
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
+import numpy as np
 import torch
 
 from .. import _lib as L
@@ -64,33 +65,49 @@ class SparsePlan:
     halves: tuple = ()
 
 
-def sparse_plan(bus_type, edge_index, mode="ac") -> SparsePlan:
+def sparse_plan(bus_type, edge_index, mode="ac", size_hint=None, device=None) -> SparsePlan:
     """Plan the sparse route for the grid (`bus_type` [n], `edge_index` int64 [2, e]; device or host tensors): one host read of the
     two, a minimum-degree order and the filled pattern built by the library on the host, one upload.  Reuse the plan for every solve
     on that grid and mode ("ac" or "dc").  mode "fd" (also spelled "fdxb" or "fdbx"; the plan's `mode` is "fd" either way): the
-    fast-decoupled plan, the symbolic factorisations of B' and B'' in one blob, for `solve_power_flow(mode="fdxb" | "fdbx")`."""
+    fast-decoupled plan, the symbolic factorisations of B' and B'' in one blob, for `solve_power_flow(mode="fdxb" | "fdbx")`.
+    `size_hint`: a guess of the plan's bytes (a plan of nearly the same grid is a good one); the plan is then built straight into a
+    buffer of that size, one elimination per matrix where the sizing call and the build call run two, and again only where the
+    guess was too small.  The plan is the same, byte for byte.  `device`: where the blob goes (default: where the inputs live)."""
     if mode not in ("ac", "dc") + _FD_PLAN_MODES:
         raise ValueError("sparse_plan: mode must be 'ac', 'dc' or 'fd' ('fdxb' and 'fdbx' are spellings of 'fd')")
     fd = mode in _FD_PLAN_MODES
     if edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.dtype != torch.int64 or bus_type.dim() != 1:
         raise RuntimeError(f"sparse_plan: edge_index must be int64 (2, e) and bus_type (n,); got {tuple(edge_index.shape)} and {tuple(bus_type.shape)}")
-    dev = edge_index.device if edge_index.is_cuda else bus_type.device
+    dev = torch.device(device) if device is not None else (edge_index.device if edge_index.is_cuda else bus_type.device)
     ei = edge_index.detach().cpu().contiguous()
     bt = bus_type.detach().to(torch.int32).cpu().contiguous()
     lib = L.load()
     e, n = int(ei.shape[1]), int(bt.shape[0])
     t0 = time.perf_counter()
-    if fd:
-        need = int(lib.pfn_powerflow_sparse_fd_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n))
+    if size_hint is not None:
+        needed, room = C.c_size_t(0), max(int(size_hint), 4 * _PLAN_HEADER_WORDS)
+        for _ in range(2):
+            host = torch.empty(room, dtype=torch.uint8)
+            rc = lib.pfn_powerflow_sparse_plan_into(ei.data_ptr(), e, bt.data_ptr(), n, 2 if fd else _MODES[mode], host.data_ptr(), room, C.byref(needed))
+            if rc != -2:                                           # (-2: PFN_ENOSPACE, the guess was too small; `needed` says by how much)
+                break
+            room = int(needed.value)
+        if rc != 0:
+            raise RuntimeError(f"sparse_plan failed: {lib.pfn_last_error().decode('utf-8', 'replace')}")
+        need = int(needed.value)
+        host = host[:need]
     else:
-        need = int(lib.pfn_powerflow_sparse_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode]))
-    if need == 0:
-        raise RuntimeError(f"sparse_plan failed: {lib.pfn_last_error().decode('utf-8', 'replace')}")
-    host = torch.empty(need, dtype=torch.uint8)
-    if fd:
-        L.check(lib.pfn_powerflow_sparse_fd_plan(ei.data_ptr(), e, bt.data_ptr(), n, host.data_ptr(), need), "pfn_powerflow_sparse_fd_plan")
-    else:
-        L.check(lib.pfn_powerflow_sparse_plan(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode], host.data_ptr(), need), "pfn_powerflow_sparse_plan")
+        if fd:
+            need = int(lib.pfn_powerflow_sparse_fd_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n))
+        else:
+            need = int(lib.pfn_powerflow_sparse_plan_bytes(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode]))
+        if need == 0:
+            raise RuntimeError(f"sparse_plan failed: {lib.pfn_last_error().decode('utf-8', 'replace')}")
+        host = torch.empty(need, dtype=torch.uint8)
+        if fd:
+            L.check(lib.pfn_powerflow_sparse_fd_plan(ei.data_ptr(), e, bt.data_ptr(), n, host.data_ptr(), need), "pfn_powerflow_sparse_fd_plan")
+        else:
+            L.check(lib.pfn_powerflow_sparse_plan(ei.data_ptr(), e, bt.data_ptr(), n, _MODES[mode], host.data_ptr(), need), "pfn_powerflow_sparse_plan")
     build_s = time.perf_counter() - t0
 
     def header(at):
@@ -102,6 +119,196 @@ def sparse_plan(bus_type, edge_index, mode="ac") -> SparsePlan:
     halves = tuple((int(w[4]), int(w[6]), int(w[7]), madds(w), int(w[11])) for w in (header(int(h[16])), header(int(h[17])))) if fd else ()
     return SparsePlan(blob=host.to(dev), header=h, n=n, e=e, m=int(h[4]), mode="fd" if fd else mode, nnz=int(h[6]), nnz_l=int(h[7]),
                       madds=madds(h), max_col=int(h[11]), bytes=need, build_s=build_s, m_q=int(h[15]) if fd else 0, halves=halves)
+
+
+@dataclass
+class CoverPlan:
+    """ONE sparse plan for a chunk of samples with their own line lists (`cover_plan`): `plan` the `SparsePlan` of the COVER list,
+    `cover` that list on the device (int64 [2, e_cover]: the base lines in base order, then the extra lines any sample needs),
+    `keys` / `slot` the table `pfn_powerflow_cover_map` searches (the cover's keys sorted ascending, equal keys in cover order, and
+    the cover line at each sorted position), `n`, `mode` as the plan's, `e_base` the base lines in front, `e_cover` all of them."""
+    plan: SparsePlan
+    cover: torch.Tensor
+    keys: torch.Tensor
+    slot: torch.Tensor
+    n: int
+    mode: str
+    e_base: int
+    e_cover: int
+
+    @property
+    def extras(self) -> int:
+        return self.e_cover - self.e_base
+
+    def to(self, device) -> "CoverPlan":
+        """The same plan with its blob, cover list and search table on `device`."""
+        plan = replace(self.plan, blob=self.plan.blob.to(device))
+        return replace(self, plan=plan, cover=self.cover.to(device), keys=self.keys.to(device), slot=self.slot.to(device))
+
+
+def _line_keys(ei, n):
+    """numpy int64 [..., 2, e] -> the lines' keys [..., e]: the unordered bus pair as min * n + max"""
+    return np.minimum(ei[..., 0, :], ei[..., 1, :]) * np.int64(n) + np.maximum(ei[..., 0, :], ei[..., 1, :])
+
+
+def _key_ranks(keys):
+    """numpy [S, e] -> the rank of every line among the lines of its row with its key, in stored order"""
+    S, e = keys.shape
+    order = np.argsort(keys, axis=1, kind="stable")
+    sk = np.take_along_axis(keys, order, 1)
+    idx = np.broadcast_to(np.arange(e, dtype=np.int64), (S, e))
+    first = np.ones((S, e), dtype=bool)
+    first[:, 1:] = sk[:, 1:] != sk[:, :-1]
+    rank = np.empty((S, e), dtype=np.int64)
+    np.put_along_axis(rank, order, idx - np.maximum.accumulate(np.where(first, idx, 0), axis=1), 1)
+    return rank
+
+
+def cover_list(edge_index, n, base=None):
+    """The COVER list of the samples' line lists (host numpy int64: `edge_index` [S, 2, e], `base` [2, e0] or None) on `n` buses:
+    `base` as it stands, then the missing copies ascending by key -- a line's key is its unordered bus pair, min * n + max --,
+    oriented (min, max).  A pair's multiplicity in the cover is the larger of its count in `base` and its count in any ONE sample;
+    base lines no sample uses stay.  Returns int64 [2, e_cover]."""
+    ei = np.asarray(edge_index, dtype=np.int64)
+    base = np.zeros((2, 0), dtype=np.int64) if base is None else np.asarray(base, dtype=np.int64)
+    if ei.ndim != 3 or ei.shape[1] != 2 or base.ndim != 2 or base.shape[0] != 2:
+        raise RuntimeError(f"cover_list: edge_index must be (S, 2, e) and base (2, e0); got {ei.shape} and {base.shape}")
+    span = max(ei.shape[2], base.shape[1]) + 1                      # (key, rank) as one word: rank < span
+    have = _line_keys(base, n) * span + _key_ranks(_line_keys(base, n)[None])[0]
+    keys = _line_keys(ei, n)
+    want = np.unique(keys * span + _key_ranks(keys))
+    extra = np.setdiff1d(want, have) // span                         # ascending by (key, rank): by key
+    return np.concatenate([base, np.stack([extra // n, extra % n])], axis=1)
+
+
+def cover_plan(bus_type, edge_index, mode="ac", base=None, size_hint=None, device=None) -> CoverPlan:
+    """Plan the sparse route for S samples with their own line lists (`edge_index` int64 [S, 2, e], `bus_type` [n]; device or host):
+    ONE `sparse_plan` (mode "ac", "dc" or "fd") on their cover list (`cover_list`; `base` [2, e0]: the grid the samples are
+    perturbations of, kept in front so that most lines keep their place).  A factorisation under a static order without pivoting
+    stays valid on a superset of a sample's pattern, so the one plan serves every sample of the chunk; `solve_power_flow(...,
+    route="sparse", plan=<CoverPlan>)` tells the kernels per sample which cover lines exist.  One host read of the lists, one host
+    elimination (`size_hint`: `sparse_plan`'s; without one the builder runs its sizing pass first), one upload -- on `device` where
+    given ("cpu": no upload yet; `CoverPlan.to` moves it), else where the inputs live.  A sample line that names a bus outside the
+    grid or one bus twice is refused HERE (RuntimeError "cover_plan failed"), before the builder runs: min * n + max would alias
+    another pair's key otherwise.  The builder's own PFN_EINVAL still answers a base line outside the grid."""
+    if edge_index.dim() != 3 or edge_index.shape[1] != 2 or edge_index.dtype != torch.int64 or bus_type.dim() != 1:
+        raise RuntimeError(f"cover_plan: edge_index must be int64 (S, 2, e) and bus_type (n,); got {tuple(edge_index.shape)} and {tuple(bus_type.shape)}")
+    if base is not None and (base.dim() != 2 or base.shape[0] != 2 or base.dtype != torch.int64):
+        raise RuntimeError(f"cover_plan: base must be int64 (2, e0); got {base.dtype} {tuple(base.shape)}")
+    dev = torch.device(device) if device is not None else (edge_index.device if edge_index.is_cuda else bus_type.device)
+    n = int(bus_type.shape[0])
+    ei = edge_index.detach().cpu().numpy()
+    b = None if base is None else base.detach().cpu().numpy()
+    lo, hi = np.minimum(ei[:, 0], ei[:, 1]), np.maximum(ei[:, 0], ei[:, 1])
+    wrong = (lo < 0) | (hi >= n) | (lo == hi)
+    if wrong.any():
+        s, k = (int(v[0]) for v in np.nonzero(wrong))
+        raise RuntimeError(f"cover_plan failed: line {k} of sample {s} joins buses {int(ei[s, 0, k])} and {int(ei[s, 1, k])}: "
+                           f"a line names two different buses inside [0, {n})")
+    cover = torch.from_numpy(cover_list(ei, n, b))
+    plan = sparse_plan(bus_type, cover, mode, size_hint, device=dev)   # (a base line outside the grid is the builder's refusal)
+    order = np.argsort(_line_keys(cover.numpy(), n), kind="stable")
+    return CoverPlan(plan=plan, cover=cover.to(dev), keys=torch.from_numpy(_line_keys(cover.numpy(), n)[order]).to(dev),
+                     slot=torch.from_numpy(order.astype(np.int32)).to(dev), n=n, mode=plan.mode,
+                     e_base=0 if b is None else int(b.shape[1]), e_cover=int(cover.shape[1]))
+
+
+def cover_map(plan: CoverPlan, edge_index, rx, fill=None):
+    """ONE `pfn_powerflow_cover_map` launch (csrc/powerflow_cover.hip): (`line_mask` uint8 [S, e_cover], `rx_cover` float64
+    [S, e_cover, 2], `unplaced` int32 [S]) of the samples' lists `edge_index` [S, 2, e] and parameters `rx` [S, e, 2] under the
+    plan's cover list, by the slot rule: a sample's k-th line with a key, in stored order, takes the k-th cover line with that key,
+    in cover order.  `rx_cover` is written where the mask is 1 only; `fill` (a float, e.g. NaN) is what the rest holds, None leaves
+    it unset.  Nothing is read back."""
+    dev = L.require_device(edge_index, rx, plan.cover, what="cover_map input")
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 3 or edge_index.shape[1] != 2:
+        raise RuntimeError(f"cover_map: edge_index must be int64 (S, 2, e); got {edge_index.dtype} {tuple(edge_index.shape)}")
+    S, e = int(edge_index.shape[0]), int(edge_index.shape[2])
+    if rx.dtype != torch.float64 or tuple(rx.shape) != (S, e, 2):
+        raise RuntimeError(f"cover_map: rx must be float64 ({S}, {e}, 2); got {rx.dtype} {tuple(rx.shape)}")
+    edge_index, rx = edge_index.contiguous(), rx.contiguous()
+    ec = plan.e_cover
+    mask = torch.empty(S, ec, dtype=torch.uint8, device=dev)
+    rx_cover = torch.empty(S, ec, 2, dtype=torch.float64, device=dev) if fill is None else torch.full((S, ec, 2), float(fill), dtype=torch.float64, device=dev)
+    unplaced = torch.empty(S, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.load().pfn_powerflow_cover_map(edge_index.data_ptr(), e, rx.data_ptr(), S, plan.n, plan.keys.data_ptr(), plan.slot.data_ptr(),
+                                                 ec, mask.data_ptr(), rx_cover.data_ptr(), unplaced.data_ptr(), L.stream_ptr()),
+                "pfn_powerflow_cover_map")
+    return mask, rx_cover, unplaced
+
+
+class CoverChunker:
+    """Splits batches of per-sample line lists into chunks that share one cover plan each.  Every extra line of a cover adds fill,
+    so a chunk is as large as keeps its plan's multiply-adds per factor within `max_growth` times those of the plan of `base` alone
+    (`base_plan`, built here once): more samples per chunk save host eliminations, fewer save factor work on the device.  The first
+    batch finds the size -- from `start`, doubled while the cover fits, halved while it does not, one plan build per trial -- and
+    the following chunks and batches reuse it, halving again only where a cover does not fit.  A chunk of one sample is taken as
+    it is.  `trials` counts the plans built, `sizes` the chunks handed out."""
+
+    def __init__(self, bus_type, base, mode="ac", max_growth=None, start=64):
+        self.bus_type, self.base, self.mode = bus_type, base, mode
+        self.max_growth = COVER_MAX_GROWTH if max_growth is None else float(max_growth)
+        if not self.max_growth >= 1.0 or start < 1:
+            raise ValueError(f"CoverChunker: max_growth must be at least 1 and start at least 1; got {max_growth!r}, {start!r}")
+        self.base_plan = sparse_plan(bus_type, base, mode)
+        self.device = self.base_plan.blob.device
+        self.size, self.settled, self.trials, self.sizes = int(start), False, 0, []
+        self.hint = self.base_plan.bytes + self.base_plan.bytes // 5
+
+    def growth(self, plan: CoverPlan) -> float:
+        return plan.plan.madds / max(self.base_plan.madds, 1)
+
+    def _try(self, edge_index, at, size):
+        self.trials += 1
+        # (the base plan's size and a fifth is the guess: a cover adds a few lines and their fill; a miss costs one more elimination)
+        # (a trial is judged by the header's multiply-adds alone: it stays on the host, and only an accepted plan is uploaded)
+        plan = cover_plan(self.bus_type, edge_index[at:at + size], self.mode, self.base, size_hint=self.hint, device="cpu")
+        self.hint = max(self.hint, plan.plan.bytes + plan.plan.bytes // 16)
+        return plan, size == 1 or self.growth(plan) <= self.max_growth
+
+    def plans(self, edge_index):
+        """Yields (rows, CoverPlan) over `edge_index` [S, 2, e]: `rows` a slice of consecutive samples, the plan their cover's."""
+        S, at = int(edge_index.shape[0]), 0
+        while at < S:
+            size = min(self.size, S - at)
+            plan, fits = self._try(edge_index, at, size)
+            while not fits:
+                size = max(1, size // 2)
+                self.size = size
+                self.settled = True
+                plan, fits = self._try(edge_index, at, size)
+            while not self.settled and size == self.size and at + 2 * size <= S:
+                wider, fits = self._try(edge_index, at, 2 * size)
+                if not fits:
+                    break
+                plan, size = wider, 2 * size
+                self.size = size
+            self.settled = True
+            self.sizes.append(size)
+            yield slice(at, at + size), plan.to(self.device)
+            at += size
+
+
+def solve_power_flow_covered(chunker: CoverChunker, spec, edge_index, rx, *, plans=None, **kw):
+    """`solve_power_flow(route="sparse")` for S samples with their own line lists `[S, 2, e]`, in chunks that share a cover plan
+    each: (`PowerFlowResult` over all samples, `plans`).  `plans`: the list of (rows, CoverPlan) of an earlier call on the same
+    lists, to solve them again (another start, a timing) without planning again; None asks `chunker` (its mode: "fd" serves
+    mode="fdxb" and "fdbx").  `kw` goes to `solve_power_flow`."""
+    plans = list(chunker.plans(edge_index)) if plans is None else plans
+    init = kw.pop("init", None)
+    parts = [solve_power_flow(chunker.bus_type, spec[rows], edge_index[rows], rx[rows], route="sparse", plan=plan,
+                              init=None if init is None else init[rows], **kw) for rows, plan in plans]
+    if not parts:
+        raise RuntimeError("solve_power_flow_covered: no samples")
+    whole = PowerFlowResult(*(torch.cat([getattr(r, f) for r in parts]) for f in ("table", "status", "iterations", "residual")),
+                            flags=torch.stack([r.flags for r in parts]).amax(0), route="sparse")
+    return whole, plans
+
+
+# what a cover may cost: its plan's multiply-adds per factor over the base plan's.  At (6470, 9005), one line removed and one added
+# per sample, chunks of 16 / 64 / 256 samples grew the factor work 0.99 / 1.03 / 1.28 times and took 133 / 37.9 / 15.1 ms per sample,
+# plan and solve together: the largest chunk won, so the bound admits it (DESIGN 7p has the rows; nothing larger was measured)
+COVER_MAX_GROWTH = 1.3
 
 
 def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max_iter=10, route="auto", init=None, plan=None) -> PowerFlowResult:
@@ -135,13 +342,40 @@ def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max
     per sample -- where the dense route keeps their inverses; same half-iterations, `init`, `tol` and `max_iter`.  They need
     `plan=sparse_plan(bus_type, edge_index, "fd")` (one plan serves both variants); without a plan they are dense only: ValueError.
 
+    Per-sample line lists `[S, 2, e]` on route "sparse": pass `plan=cover_plan(bus_type, edge_index, mode, base)` (mode "fd" for
+    fdxb / fdbx), ONE plan on a cover list that holds every line of every sample.  Two launches, no read-back: the map
+    (csrc/powerflow_cover.hip: which cover lines a sample has, its rx in cover order) and the masked solve, in which a line the
+    sample lacks is a structural zero.  A sample with a line the cover lacks gets status -6, one whose lists leave a bus without a
+    line -2.  `CoverChunker` splits a batch into chunks whose cover keeps the factor work within a growth bound.  A sample's bits
+    are a function of (sample, cover plan): independent of the other samples of the batch and of the workgroup size, but under
+    another cover the elimination order and fill differ, so the results agree to rounding only.  Without a plan, or with a
+    one-topology `SparsePlan`, per-sample lists raise as before.
+
     One host read (the counts of `bus_type`, which size the launch); no read-back of the results."""
     return _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, 0)
+
+
+def _check_plan_takes_the_lists(spec, edge_index, mode, route, plan):
+    """What the kind of plan decides about per-sample line lists on the sparse route, said before anything touches a device.  (So
+    CPU tensors with a per-sample list and no cover plan on route "sparse" now raise "one topology" where they used to raise "no CPU
+    fallback" first: that call was refused either way, only the order of its two refusals moved.)"""
+    if route != "sparse" or mode not in _MODES or not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 3:
+        return
+    fd = mode in ("fdxb", "fdbx")
+    if fd and plan is None:
+        return                                                     # (the fast-decoupled modes' own refusal follows)
+    if not isinstance(plan, CoverPlan):
+        raise RuntimeError("solve_power_flow: route 'sparse' takes one (2, e) line list for all samples: a plan belongs to one topology "
+                           "(per-sample lists: plan=cover_plan(bus_type, edge_index, mode))")
+    if isinstance(spec, torch.Tensor) and spec.dim() == 3 and (plan.n, plan.mode) != (int(spec.shape[1]), "fd" if fd else mode):
+        raise RuntimeError(f"solve_power_flow: the plan is for (n, mode) = {(plan.n, plan.mode)} and per-sample lists; "
+                           f"the call has {(int(spec.shape[1]), mode)}")
 
 
 def _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, threads) -> PowerFlowResult:
     """`solve_power_flow` with the sparse route's workgroup size exposed (`threads`: 0 the library's choice, 64 or 256): what
     tools/powerflow_bench.py and the tests measure the two sizes with."""
+    _check_plan_takes_the_lists(spec, edge_index, mode, route, plan)
     L.require_device(bus_type, spec, edge_index, rx, what="solve_power_flow input")
     if mode not in _MODES or route not in _ROUTES:
         raise ValueError(f"solve_power_flow: mode must be one of {sorted(_MODES)} and route one of {sorted(_ROUTES)}")
@@ -179,8 +413,15 @@ def _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, pla
         if fd and plan is None:
             raise ValueError(f"solve_power_flow: route 'sparse' with mode {mode!r}: pass plan=sparse_plan(bus_type, edge_index, 'fd'); "
                              "without a plan the fast-decoupled modes are dense only")
-        if edge_index.dim() == 3:
-            raise RuntimeError("solve_power_flow: route 'sparse' takes one (2, e) line list for all samples: a plan belongs to one topology")
+        line_mask = unplaced = None
+        if isinstance(plan, CoverPlan):
+            # per-sample lists under one cover plan: the map launch lays the samples out in cover order, then the masked solve
+            if edge_index.dim() != 3:
+                raise RuntimeError("solve_power_flow: a CoverPlan goes with per-sample (S, 2, e) line lists; one (2, e) list takes a sparse_plan")
+            if plan.cover.device != dev:
+                raise RuntimeError(f"solve_power_flow: the plan lives on {plan.cover.device}, the inputs on {dev}")
+            line_mask, rx, unplaced = cover_map(plan, edge_index, rx)
+            edge_index, e, plan = plan.cover, plan.e_cover, plan.plan
         if plan is None:
             plan = sparse_plan(bt, edge_index, mode)
         if not isinstance(plan, SparsePlan) or (plan.n, plan.e, plan.mode) != (n, e, "fd" if fd else mode):
@@ -188,15 +429,18 @@ def _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, pla
                                f"the call has {(n, e, mode)}")
         if plan.blob.device != dev:
             raise RuntimeError(f"solve_power_flow: the plan lives on {plan.blob.device}, the inputs on {dev}")
-        sizer, launch, what = ((lib.pfn_powerflow_sparse_fd_workspace_bytes, lib.pfn_powerflow_solve_sparse_fd, "pfn_powerflow_solve_sparse_fd") if fd
-                               else (lib.pfn_powerflow_sparse_workspace_bytes, lib.pfn_powerflow_solve_sparse, "pfn_powerflow_solve_sparse"))
+        sizer, what = ((lib.pfn_powerflow_sparse_fd_workspace_bytes, "pfn_powerflow_solve_sparse_fd") if fd
+                       else (lib.pfn_powerflow_sparse_workspace_bytes, "pfn_powerflow_solve_sparse"))
+        masked = () if line_mask is None else (line_mask.data_ptr(), L.ptr(unplaced))
+        if masked:
+            what += "_masked"
         need = int(sizer(S, C.addressof(plan.header))) if S else 0
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            L.check(launch(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), S, n,
-                           _MODES[mode], float(tol), int(max_iter), C.addressof(plan.header), plan.blob.data_ptr(),
-                           int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(), flags.data_ptr(),
-                           ws.data_ptr(), need, L.stream_ptr()),
+            L.check(getattr(lib, what)(edge_index.data_ptr(), e, rx.data_ptr(), *masked, bt.data_ptr(), spec.data_ptr(), L.ptr(init), S, n,
+                                       _MODES[mode], float(tol), int(max_iter), C.addressof(plan.header), plan.blob.data_ptr(),
+                                       int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(), flags.data_ptr(),
+                                       ws.data_ptr(), need, L.stream_ptr()),
                     what)
         return PowerFlowResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
                                residual=residual, flags=flags, route="sparse")

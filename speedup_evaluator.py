@@ -22,7 +22,9 @@ solver inputs are read as dc_error.py reads them.  No plots.
 A case with more unknowns than the dense solver takes (6470rte) runs every solver row on the sparse route (csrc/powerflow_sparse.hip
 for NR and DC, csrc/powerflow_sparse_fd.hip for the fast-decoupled rows, which keep the sparse factors of B' and B'' instead of
 their dense inverses); `--route sparse` forces that route at any size.  One plan per kind -- "ac", "dc" and one "fd" plan for the
-four fast-decoupled rows -- is built once, before the timing."""
+four fast-decoupled rows -- is built once, before the timing.  A perturbed set (one line list per sample) takes the same route in
+chunks of samples that share a cover plan each (utils/powerflow.py CoverChunker), planned before the timing too; a row's time then
+covers every chunk's map launch and masked solve."""
 import os
 import sys
 
@@ -67,7 +69,7 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     from poweflownet_amd.data import DataLoader
     from poweflownet_amd.utils.custom_loss_functions import Masked_L2_loss
     from poweflownet_amd.utils.error_analysis import bus_error_epoch
-    from poweflownet_amd.utils.powerflow import max_unknowns, solve_power_flow, sparse_plan
+    from poweflownet_amd.utils.powerflow import CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, sparse_plan
     testset, node, edge = dc_error.load_test_split(root, case, samples, tuple(split))
     if xy is not None:
         testset = type(testset)(root=root, case=case, split=list(split), task="test", xymean=xy[0], xystd=xy[1], edgemean=xy[2], edgestd=xy[3])
@@ -76,12 +78,16 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     mean, std = testset.xymean[0].double().to(device), testset.xystd[0].double().to(device)
     bus_type = torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device)
     spec, ei, rx = dc_error.solver_inputs(node, edge, device)
-    # beyond the dense solver: the sparse route, one line list for all samples and one plan per mode
+    # beyond the dense solver: the sparse route, one plan per mode -- for one line list shared by the samples, or, where every sample
+    # has its own (a perturbed set), per chunk of samples on the chunk's cover list (planned before the clock starts, as the one is)
     sparse = route == "sparse" or (node.shape[1] - 1) + int((node[0, :, 1] == 2).sum()) > max_unknowns()
-    plans = {}
-    if sparse:
-        if not bool((edge[:, :, :2] == edge[:1, :, :2]).all()):
-            raise RuntimeError("speedup_evaluator: the sparse route needs one line list for all samples")
+    plans, covers = {}, {}
+    if sparse and not bool((edge[:, :, :2] == edge[:1, :, :2]).all()):
+        for mode in ("ac", "dc", "fd"):
+            chunker = CoverChunker(bus_type, ei[0].contiguous(), mode)
+            covers[mode] = (chunker, list(chunker.plans(ei)))
+        covers["fdxb"] = covers["fdbx"] = covers["fd"]
+    elif sparse:
         ei = ei[0].contiguous()
         plans = {mode: sparse_plan(bus_type, ei, mode) for mode in ("ac", "dc", "fd")}
         plans["fdxb"] = plans["fdbx"] = plans["fd"]
@@ -103,8 +109,12 @@ def evaluate(root, case, model, samples=1000, device="cuda:0", batch_size=128, x
     for name, mode, start in (("nr", "ac", None), ("nr_result_init", "ac", init), ("fdxb", "fdxb", None), ("fdbx", "fdbx", None),
                               ("fdxb_result_init", "fdxb", init), ("fdbx_result_init", "fdbx", init), ("dc", "dc", None)):
         iters = FD_ITERS if mode.startswith("fd") else NR_ITERS
-        kw = {"route": "sparse", "plan": plans[mode]} if sparse else {}
-        sec, res = device_seconds(lambda: solve_power_flow(bus_type, spec, ei, rx, mode=mode, tol=TOL, max_iter=iters, init=start, **kw))
+        kw = {"route": "sparse", "plan": plans[mode]} if sparse and not covers else {}
+        if covers:
+            sec, res = device_seconds(lambda: solve_power_flow_covered(covers[mode][0], spec, ei, rx, plans=covers[mode][1], mode=mode, tol=TOL,
+                                                                       max_iter=iters, init=start)[0])
+        else:
+            sec, res = device_seconds(lambda: solve_power_flow(bus_type, spec, ei, rx, mode=mode, tol=TOL, max_iter=iters, init=start, **kw))
         status = res.status.cpu().numpy()
         ok = status[status >= 0]
         rows[name] = {"seconds_per_sample": sec / S, "solves_mean": float(ok.mean()) if len(ok) else float("nan"),

@@ -74,6 +74,26 @@ int main() {
             CHECK(pfn_powerflow_sparse_fd_plan(ei.data(), e, no_pq.data(), n, blob0.data(), need0) == PFN_OK);
             printf("n %d e %d fd: plan of %zu bytes (%zu without a PQ bus)\n", n, e, need, need0);
         }
+        for (int mode = 0; mode < 3; ++mode) {                                                    // the single-call entry: 2 is the fast-decoupled plan
+            const size_t need = mode == 2 ? pfn_powerflow_sparse_fd_plan_bytes(ei.data(), e, bt.data(), n)
+                                          : pfn_powerflow_sparse_plan_bytes(ei.data(), e, bt.data(), n, mode);
+            std::vector<unsigned char> want(need), blob(need);                                    // exact size: an overrun is an ASan report
+            CHECK((mode == 2 ? pfn_powerflow_sparse_fd_plan(ei.data(), e, bt.data(), n, want.data(), need)
+                             : pfn_powerflow_sparse_plan(ei.data(), e, bt.data(), n, mode, want.data(), need)) == PFN_OK);
+            size_t needed = 0;
+            CHECK(pfn_powerflow_sparse_plan_into(ei.data(), e, bt.data(), n, mode, blob.data(), need, &needed) == PFN_OK && needed == need);
+            CHECK(blob == want);
+            const size_t small[] = {0, 1, 127, 128, 129, need / 2, need - 16, need - 1};          // every way of being too small
+            for (size_t room : small) {
+                if (room >= need) continue;
+                std::vector<unsigned char> tight(room ? room : 1);
+                CHECK(pfn_powerflow_sparse_plan_into(ei.data(), e, bt.data(), n, mode, room ? tight.data() : nullptr, room, &needed) == PFN_ENOSPACE);
+                CHECK(needed == need);
+            }
+            std::vector<unsigned char> roomy(need + 64, 0xAB);
+            CHECK(pfn_powerflow_sparse_plan_into(ei.data(), e, bt.data(), n, mode, roomy.data(), roomy.size(), &needed) == PFN_OK && needed == need);
+            CHECK(std::vector<unsigned char>(roomy.begin(), roomy.begin() + (long)need) == want && roomy[need] == 0xAB && roomy[need + 63] == 0xAB);
+        }
         if (e > 0) {
             std::vector<unsigned char> blob(1 << 16);
             ei[e - 1] = n;

@@ -10,6 +10,7 @@ the start a good prediction would give).
     python tools/powerflow_bench.py [--samples 4096] [--repeats 5] [--cpu-samples 16]
     python tools/powerflow_bench.py --route sparse [--case 118 --case 130,200 --case 600,835 --case 6470rte] [--samples 4096]
     python tools/powerflow_bench.py --route sparse --mode fdxb [--mode fdbx] [--case ...]
+    python tools/powerflow_bench.py --route sparse --perturbed 1 1 [--case 6470rte] [--chunk 16 --chunk 64 --chunk 256]
 
 `--route sparse`: the sparse route (csrc/powerflow_sparse.hip) per `--case` column (a case name or "n,e"; default 118, 130,200,
 600,835 and 6470rte): the plan's fill, multiply-adds per factor, size and HOST build time, then ms and ms per sample of the solve
@@ -19,6 +20,12 @@ under the dense cap -- the dense global route beside it.  6470rte runs 64 sample
 one "fd" plan, reported per half (B' and B'': unknowns, fill, multiply-adds of the one-time factor, longest column), its host build
 time, then the same timing rows with max_iter 60 HALF-iterations (mean and maximum count), and `factor_only`: the same launch with
 max_iter 0, which assembles and factors both matrices and forms one mismatch -- the one-time share of the solve.
+
+`--perturbed R A`: per-sample topologies on that route (`perturb_topology`'s draw: R lines removed, A added per sample), one
+cover plan per chunk of `--chunk` samples (repeatable; default 16, 64 and 256), AC: per chunk size the lines the cover adds, its
+nnz(L) and multiply-adds per factor against the base grid's plan, the HOST seconds of the cover plan (the list read, the
+elimination, the upload), the seconds of the solve (the map launch and the masked solve: ONE timed call after one warm-up, not a
+median), both per sample, the solve counts, and `one_topology`: the same number of samples on the base grid with the base plan.
 
 Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
 max_iter 10 (the defaults).  One JSON line."""
@@ -92,6 +99,50 @@ def sparse_rows(a):
     print(json.dumps(res), flush=True)
 
 
+def perturbed_rows(a):
+    """The `--route sparse --perturbed R A` table: one row per chunk size."""
+    import torch
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.powerflow import cover_plan, solve_power_flow, sparse_plan
+    from poweflownet_amd.utils.topology import perturb_topology
+    dev = torch.device("cuda:0")
+    remove, add = a.perturbed
+    res = {"device": torch.cuda.get_device_name(0), "route": "sparse", "perturbed": [remove, add], "tol": 1e-8, "max_iter": 10, "cases": {}}
+    for case in a.case or ["6470rte"]:
+        n, e = CASES[case] if case in CASES else tuple(int(v) for v in case.split(","))
+        chunks = a.chunk or [16, 64, 256]
+        ei, bt, rx, spec = make_physical_inputs(n, e, max(chunks), seed=0)
+        bt, spec, ei, rx = (t.to(dev) for t in (bt, spec, ei, rx))
+        topo = perturb_topology(ei, n, num_samples=max(chunks), remove=remove, add=add, seed=0)
+        keep = topo.status >= 1
+        lists, prx, pspec = topo.edge_index[keep], torch.gather(rx, 1, topo.source.long().clamp(min=0)[:, :, None].expand(-1, -1, 2))[keep], spec[keep]
+        base = sparse_plan(bt, ei, "ac")
+        out = {"buses": n, "lines": e, "connected_draws": int(keep.sum()),
+               "base_plan": {"nnz_l": base.nnz_l, "multiply_adds_per_factor": base.madds, "longest_column": base.max_col, "host_build_s": round(base.build_s, 3)}}
+        for chunk in chunks:
+            S = min(chunk, int(lists.shape[0]))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cover = cover_plan(bt, lists[:S], "ac", ei)
+            torch.cuda.synchronize()
+            plan_s = time.perf_counter() - t0
+            per, last = _timed(lambda: solve_power_flow(bt, pspec[:S], lists[:S], prx[:S], route="sparse", plan=cover), 1)
+            one, _ = _timed(lambda: solve_power_flow(bt, spec[:S], ei, rx[:S], route="sparse", plan=base), 1)
+            status = last.status.cpu().numpy()
+            ok = status[status >= 0]
+            out[f"chunk_{chunk}"] = {"samples": S, "extras": cover.extras, "nnz_l": cover.plan.nnz_l, "nnz_l_growth": round(cover.plan.nnz_l / base.nnz_l, 4),
+                                     "multiply_adds_per_factor": cover.plan.madds, "madds_growth": round(cover.plan.madds / base.madds, 4),
+                                     "longest_column": cover.plan.max_col, "plan_s": round(plan_s, 3), "elimination_s": round(cover.plan.build_s, 3),
+                                     "solve_s": round(per[0], 4), "plan_ms_per_sample": round(1e3 * plan_s / S, 3),
+                                     "solve_ms_per_sample": round(1e3 * per[0] / S, 3), "total_ms_per_sample": round(1e3 * (plan_s + per[0]) / S, 3),
+                                     "failed": int((status < 0).sum()), "mean_iterations": round(float(ok.mean()), 3) if len(ok) else None,
+                                     "max_iterations": int(ok.max()) if len(ok) else None,
+                                     "one_topology": {"solve_s": round(one[0], 4), "solve_ms_per_sample": round(1e3 * one[0] / S, 3)}}
+            print(json.dumps({f"{case} chunk {chunk}": out[f"chunk_{chunk}"]}), flush=True)
+        res["cases"][case] = out
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -102,10 +153,15 @@ def main():
     ap.add_argument("--big-samples", type=int, default=512, help="with --route sparse: the large batch of a case beyond 2000 buses")
     ap.add_argument("--mode", action="append", default=None, choices=("ac", "dc", "fdxb", "fdbx"),
                     help="with --route sparse: the modes to run (repeatable; default ac and dc)")
+    ap.add_argument("--perturbed", type=int, nargs=2, default=None, metavar=("R", "A"),
+                    help="with --route sparse: per-sample topologies (R lines removed, A added) under one cover plan per chunk")
+    ap.add_argument("--chunk", type=int, action="append", default=None, help="with --perturbed: samples per cover plan (repeatable; default 16, 64, 256)")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("powerflow_bench.py needs a HIP device")
+    if a.route == "sparse" and a.perturbed:
+        return perturbed_rows(a)
     if a.route == "sparse":
         return sparse_rows(a)
     from poweflownet_amd.synth import CASES, make_physical_inputs
