@@ -9,13 +9,18 @@ sparse route (csrc/powerflow_sparse.hip): its plan is built once and serves ever
 that route at any size.  With -r / -a every sample has its own topology: the sparse route then solves the samples in chunks
 that share one plan each, built on the chunk's cover list -- the base lines and the lines any of its samples adds -- with a
 per-sample line mask (utils/powerflow.py cover_plan, CoverChunker); the chunk size follows the fill the added lines cost.
+--enforce-q-lims, the reference's ENFORCE_Q_LIMS (`pp.runpp(..., enforce_q_lims=True)`): a PV bus whose reactive output hits a limit
+becomes a load bus and the sample is solved again -- inside the one launch of `solve_power_flow_qlim` (csrc/powerflow_qlim.hip) --
+and is written as type 2 for THAT sample, as the reference writes it.  The synthetic cases carry no generator data, so --q-limit Q
+(per-unit, > 0) puts (-Q, +Q) on every PV bus.  Dense cases only, with and without -r / -a.
 
     python dataset_generator.py --case 118 --samples 2000 --root data
     python dataset_generator.py --case 118 --samples 2000 --root data -r 1 -a 1
+    python dataset_generator.py --case 118 --samples 2000 --root data --enforce-q-lims --q-limit 0.5
     python dataset_generator.py --case 6470rte --samples 256 --root data
     python dataset_generator.py --case 6470rte --samples 256 --root data -r 1 -a 1
 
-    <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]
+    <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]; the type is per sample
     <root>/raw/case<case>_edge_features.npy   (S, e, 4) float64 [from, to, r, x]
 
 -r / -a, the reference's topology perturbation (utils/data_utils.py:12-59): every sample loses r random lines -- drawn again, up to
@@ -24,7 +29,7 @@ existing line.  The draw is `perturb_topology` (csrc/topology.hip, one workgroup
 sample without a connected draw is dropped and counted.  The files are then named case<case>perturbed<r>r<a>a_*, the reference's
 naming, and hold e - r + a lines per sample: `PowerFlowData(case="118perturbed1r1a")` and train.py --case 118perturbed1r1a load them.
 
-Per-unit, demand-positive, the network model of `PowerImbalance` (no shunts, taps, line charging or Q-limits).  Needs a HIP device:
+Per-unit, demand-positive, the network model of `PowerImbalance` (no shunts, taps or line charging).  Needs a HIP device:
 there is no CPU solver in this package."""
 import argparse
 import os
@@ -38,11 +43,12 @@ SPARSE_BATCH = 1024              # samples per launch on the sparse route: a 647
 
 def write_raw(root, case, bus_type, edge_index, rx, tables):
     """Write solved tables [S, n, 4] with their line parameters [S, e, 2] and lines -- [2, e] for all samples or [S, 2, e] -- in the
-    reference's raw layout; returns the two paths."""
+    reference's raw layout; returns the two paths.  `bus_type` is [n] for all samples or [S, n], one row per sample (what
+    `generate(q_limit=...)` returns: a PV bus that hit its limit is a 2 in its sample's row)."""
     bus_type, edge_index = np.asarray(bus_type), np.asarray(edge_index)
     rx, tables = np.asarray(rx, dtype=np.float64), np.asarray(tables, dtype=np.float64)
     S, n, e = tables.shape[0], tables.shape[1], edge_index.shape[-1]
-    assert tables.shape == (S, n, 4) and rx.shape == (S, e, 2) and edge_index.shape in ((2, e), (S, 2, e)) and bus_type.shape == (n,)
+    assert tables.shape == (S, n, 4) and rx.shape == (S, e, 2) and edge_index.shape in ((2, e), (S, 2, e)) and bus_type.shape in ((n,), (S, n))
     node = np.empty((S, n, 6), dtype=np.float64)
     node[:, :, 0] = np.arange(n)
     node[:, :, 1] = bus_type
@@ -58,17 +64,21 @@ def write_raw(root, case, bus_type, edge_index, rx, tables):
 
 
 def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10, device="cuda:0", max_rounds=64, remove=0, add=0,
-             counts=None, route="auto"):
+             counts=None, route="auto", q_limit=None):
     """(bus_type [n], edge_index, rx [S, e, 2], tables [S, n, 4], redrawn): `samples` converged samples, host arrays.  `edge_index`
     is the grid's [2, e]; with `remove` or `add` above 0 it is [S, 2, e - remove + add], one perturbed line list per sample, and
     rx holds the parameters of those lines.  `counts` (a dict, optional) receives "disconnected": the samples dropped because no
     connected draw was found, "drawn": all samples drawn, and "route": the solver route that ran; with per-sample topologies on
     the sparse route also "chunks": the sizes of the chunks that shared a cover plan, "growth": the largest multiply-add count of a
     cover plan over the base plan's, and "extras": the most lines a cover added.  `route`: "auto" (the sparse route where the case
-    has more unknowns than the dense solver takes) or "sparse"."""
+    has more unknowns than the dense solver takes) or "sparse".  `q_limit` (per-unit, > 0; None: no limits): every PV bus's Q is held
+    within (-q_limit, +q_limit) by `solve_power_flow_qlim`; `bus_type` is then [S, n], the types each sample ended with, and `counts`
+    receives "switched": the kept samples in which a bus switched, and "q_rounds": the most re-solves a kept sample took.  Dense
+    cases only: on a case that needs the sparse route it raises."""
     import torch
     from poweflownet_amd.synth import CASES, make_physical_inputs
-    from poweflownet_amd.utils.powerflow import CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, sparse_plan
+    from poweflownet_amd.utils.powerflow import (CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, solve_power_flow_qlim,
+                                                 sparse_plan)
     from poweflownet_amd.utils.topology import perturb_topology
     if route not in ("auto", "sparse"):
         raise ValueError(f"dataset_generator: route must be 'auto' or 'sparse', not {route!r}")
@@ -76,6 +86,8 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         raise ValueError("dataset_generator: --samples must be at least 1")
     if remove < 0 or add < 0:
         raise ValueError(f"dataset_generator: cannot remove {remove} and add {add} lines")
+    if q_limit is not None and not q_limit > 0:
+        raise ValueError(f"dataset_generator: --q-limit must be above 0, not {q_limit!r}")
     n, e = CASES[str(case)]
     perturbed = remove > 0 or add > 0
     plan = chunker = None
@@ -83,6 +95,9 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
     ei0, bt0, _, _ = make_physical_inputs(n, e, 0, seed * 1_000_003, load)
     if route == "auto" and (n - 1) + int((bt0 == 2).sum()) > max_unknowns():
         route = "sparse"
+    if route == "sparse" and q_limit is not None:
+        raise RuntimeError(f"dataset_generator: --enforce-q-lims needs the dense solver, and case {case} takes the sparse route: "
+                           "Q-limits are not built there (a sparse plan is for one set of unknowns)")
     if route == "sparse":
         batch = min(batch, SPARSE_BATCH)
         if perturbed:
@@ -90,7 +105,7 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         else:
             plan = sparse_plan(bt0.to(device), ei0.to(device))   # one grid: built and uploaded once, it serves every batch and redraw
     growth, extras = 1.0, 0
-    keep_ei, keep_rx, keep_t, have, redrawn, drawn, disconnected = [], [], [], 0, 0, 0, 0
+    keep_ei, keep_rx, keep_t, keep_bt, keep_rounds, have, redrawn, drawn, disconnected = [], [], [], [], [], 0, 0, 0, 0
     for rnd in range(max_rounds):
         if have >= samples:
             break
@@ -114,6 +129,9 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
             res, covers = solve_power_flow_covered(chunker, d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
             growth = max([growth] + [chunker.growth(c) for _, c in covers])
             extras = max([extras] + [c.extras for _, c in covers])
+        elif q_limit is not None:
+            limits = torch.tensor([-q_limit, q_limit], dtype=torch.float64, device=device).expand(n, 2)
+            res = solve_power_flow_qlim(bt.to(device), d_spec, d_ei, d_rx, limits, tol=tol, max_iter=max_iter)
         else:
             res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter, route=route, plan=plan)
         ok = res.status >= 0
@@ -124,6 +142,9 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         ok = ok.cpu().numpy()
         keep_rx.append(d_rx.cpu().numpy()[ok])
         keep_t.append(res.table.cpu().numpy()[ok])
+        if q_limit is not None:
+            keep_bt.append(res.bus_type.cpu().numpy()[ok])
+            keep_rounds.append(res.rounds.cpu().numpy()[ok])
         have += int(ok.sum())
         redrawn += int((~ok).sum())
     if counts is not None:
@@ -133,7 +154,12 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
     if have < samples:
         raise RuntimeError(f"dataset_generator: only {have} of {samples} samples converged in {max_rounds} rounds (load {load})")
     lines = np.concatenate(keep_ei)[:samples] if perturbed else ei.numpy()
-    return bt.numpy(), lines, np.concatenate(keep_rx)[:samples], np.concatenate(keep_t)[:samples], redrawn
+    types = bt.numpy()
+    if q_limit is not None:
+        types, q_rounds = np.concatenate(keep_bt)[:samples].astype(np.int64), np.concatenate(keep_rounds)[:samples]
+        if counts is not None:
+            counts.update(switched=int((types != bt.numpy()).any(axis=1).sum()), q_rounds=int(q_rounds.max()))
+    return types, lines, np.concatenate(keep_rx)[:samples], np.concatenate(keep_t)[:samples], redrawn
 
 
 def main(argv=None):
@@ -148,20 +174,29 @@ def main(argv=None):
     ap.add_argument("-a", "--num_lines_to_add", type=int, default=0, help="lines every sample gains, each a copy of a random line")
     ap.add_argument("--route", default="auto", choices=("auto", "sparse"),
                     help="solver route: auto takes the sparse one where the case exceeds the dense solver; sparse forces it")
+    ap.add_argument("--enforce-q-lims", action="store_true",
+                    help="a PV bus whose Q hits its limit becomes a load bus for that sample (needs --q-limit; dense cases only)")
+    ap.add_argument("--q-limit", type=float, default=None, metavar="Q", help="with --enforce-q-lims: every PV bus's Q stays within (-Q, +Q), per-unit")
     a = ap.parse_args(argv)
     r, add = a.num_lines_to_remove, a.num_lines_to_add
     if r < 0 or add < 0:
         ap.error("-r and -a must be at least 0")
+    if a.enforce_q_lims != (a.q_limit is not None) or (a.q_limit is not None and not a.q_limit > 0):
+        ap.error("--enforce-q-lims and --q-limit Q (per-unit, above 0) go together")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("dataset_generator.py needs a HIP device: poweflownet_amd has no CPU solver")
     counts = {}
-    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load, remove=r, add=add, counts=counts, route=a.route)
+    bt, ei, rx, tables, redrawn = generate(a.case, a.samples, a.seed, a.batch, a.load, remove=r, add=add, counts=counts, route=a.route,
+                                            q_limit=a.q_limit)
     name = f"{a.case}perturbed{r}r{add}a" if r > 0 or add > 0 else a.case
     paths = write_raw(a.root, name, bt, ei, rx, tables)
     if r > 0 or add > 0:
         print(f"Left a bus unsupplied in every draw and dropped: {counts['disconnected']}")
     print(f"Failed to converge and drawn again: {redrawn}")
+    if a.q_limit is not None:
+        print(f"Q-limits (-{a.q_limit:g}, +{a.q_limit:g}) at every PV bus: {counts['switched']} sample(s) had a bus switched to a load bus, "
+              f"at most {counts['q_rounds']} re-solve(s)")
     if counts["route"] == "sparse":
         print("Solved on the sparse route")
     if "chunks" in counts:

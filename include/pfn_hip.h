@@ -573,6 +573,37 @@ int pfn_powerflow_solve(const int64_t* edge_index, int lines_per_sample, int64_t
                         int max_iter, int route, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------- generator Q-limits, per-sample bus types
+ * pfn_powerflow_solve_qlim (csrc/powerflow_qlim.hip): mode 0 of pfn_powerflow_solve_init on the dense route with the bus types the
+ * SAMPLE's and the reference's enforce_q_lims loop inside the kernel.  ONE launch, one workgroup per sample, no host sync, no
+ * allocation (capturable).  edge_index, lines_per_sample, rx, spec, init, tol, max_iter, table, status, residual, flags as there.
+ *   bus_type     int32 [n_bus] (types_per_sample = 0) or [n_samples, n_bus] (1).  The workgroup copies its row into LDS and owns it:
+ *                the host passes no counts.  A row that does not hold exactly one slack and only types 0, 1, 2 gives THAT sample
+ *                status -5 (and sets bit 0 of flags[0]).
+ *   q_limits     f64 [n_bus, 2] (limits_per_sample = 0) or [n_samples, n_bus, 2] (1) = (lo, hi) on the TABLE's Q column, i.e.
+ *                demand-positive per-unit: a generator's [Qmin, Qmax] arrives as [-Qmax, -Qmin].  Read at PV buses only; NaN or
+ *                +-inf: no limit on that side.  NULL: no limits at all (the plain solve with per-sample types).
+ *   rounds       After an inner Newton loop converges, the line sum sq of every PV bus is tested: sq > hi + q_tol makes the bus PQ
+ *                with Q = hi, sq < lo - q_tol with Q = lo.  All violators of a round switch together, none switches back, the slack
+ *                is never limited.  No violator: done.  Otherwise the unknowns are numbered again and Newton goes on from the
+ *                current state (a switched bus's Vm starts at the value it held).  max_iter bounds the solves of EACH inner loop,
+ *                max_rounds the re-solves.
+ *   table        as mode 0's; a switched bus holds its solved Vm and, bit for bit, the limit as Q; a bus still PV its line sum.
+ *   bus_type_out int32 [n_samples, n_bus]: the final types;  rounds int32 [n_samples]: the re-solves (0: no limit was hit).
+ *   status       >= 0: the Jacobian solves over all rounds; -1 ... -5 as above; -7: limits still violated after max_rounds
+ *                re-solves.  A failed sample has NaN rows, its INPUT types in bus_type_out and the rounds it completed.
+ *   route        0 auto, 1 LDS, 2 global.  Storage is sized for the worst case, every non-slack bus PQ: m_max = 2 (n_bus - 1)
+ *                unknowns, whatever the types are.  LDS when the vectors (52 n_bus + 8 m_max bytes) and m_max rows of m_max | 1
+ *                floats fit 160 KiB - 1 KiB -- 70 buses do, 118 do not --, else a per-sample slab of `ws`;
+ *                pfn_powerflow_qlim_workspace_bytes(n_samples, n_bus, route) is what the route needs, 0 exactly on the LDS route.
+ *                m_max > pfn_powerflow_max_unknowns() is PFN_EINVAL.                                                              */
+size_t pfn_powerflow_qlim_workspace_bytes(int64_t n_samples, int64_t n_bus, int route);
+int pfn_powerflow_solve_qlim(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, const double* rx, const int32_t* bus_type,
+                             int types_per_sample, const double* spec, const double* init, const double* q_limits, int limits_per_sample,
+                             int64_t n_samples, int64_t n_bus, double tol, double q_tol, int max_iter, int max_rounds, int route,
+                             double* table, int32_t* status, double* residual, int32_t* flags, int32_t* bus_type_out, int32_t* rounds,
+                             void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- sparse power-flow route
  * The same Newton / DC loop beyond pfn_powerflow_max_unknowns() (csrc/powerflow_sparse.hip), for ONE line list [2, n_lines] shared by
  * the samples: a static minimum-degree order and the filled pattern under it are planned once per grid on the host, the fp32

@@ -32,6 +32,7 @@ SYMBOLS = (
     "pfn_branch_flows_lds_max_bus", "pfn_branch_flows_workspace_bytes", "pfn_branch_flows",
     "pfn_powerflow_max_unknowns", "pfn_powerflow_workspace_bytes", "pfn_powerflow_solve",
     "pfn_powerflow_workspace_bytes_mode", "pfn_powerflow_solve_init",
+    "pfn_powerflow_qlim_workspace_bytes", "pfn_powerflow_solve_qlim",
     "pfn_powerflow_sparse_plan_bytes", "pfn_powerflow_sparse_plan", "pfn_powerflow_sparse_workspace_bytes", "pfn_powerflow_solve_sparse",
     "pfn_powerflow_sparse_fd_plan_bytes", "pfn_powerflow_sparse_fd_plan", "pfn_powerflow_sparse_fd_workspace_bytes", "pfn_powerflow_solve_sparse_fd",
     "pfn_powerflow_sparse_plan_into", "pfn_powerflow_cover_map", "pfn_powerflow_solve_sparse_masked", "pfn_powerflow_solve_sparse_fd_masked",
@@ -153,6 +154,9 @@ def load() -> C.CDLL:
         "pfn_powerflow_workspace_bytes_mode": (sz, [i64, i64, i64, i64, C.c_int, C.c_int]),
         "pfn_powerflow_solve_init": (C.c_int, [p, C.c_int, i64, p, p, p, p, i64, i64, i64, i64, C.c_int, C.c_double, C.c_int, C.c_int, p, p,
                                                p, p, p, sz, p]),
+        "pfn_powerflow_qlim_workspace_bytes": (sz, [i64, i64, C.c_int]),
+        "pfn_powerflow_solve_qlim": (C.c_int, [p, C.c_int, i64, p, p, C.c_int, p, p, p, C.c_int, i64, i64, C.c_double, C.c_double, C.c_int,
+                                               C.c_int, C.c_int, p, p, p, p, p, p, p, sz, p]),
         "pfn_powerflow_sparse_plan_bytes": (sz, [p, i64, p, i64, C.c_int]),
         "pfn_powerflow_sparse_plan": (C.c_int, [p, i64, p, i64, C.c_int, p, sz]),
         "pfn_powerflow_sparse_workspace_bytes": (sz, [i64, p]),

@@ -16,7 +16,8 @@
 namespace pfn {
 
 // status[s] < 0; >= 0 it is the count of solves.  (utils/powerflow.py STATUS has the texts; topology.hip's TP_BAD_LINE is PF_BAD_LINE)
-enum { PF_NOT_CONVERGED = -1, PF_SINGULAR = -2, PF_NON_FINITE = -3, PF_BAD_LINE = -4, PF_BAD_TYPES = -5, PF_STALE_PLAN = -6 };
+enum { PF_NOT_CONVERGED = -1, PF_SINGULAR = -2, PF_NON_FINITE = -3, PF_BAD_LINE = -4, PF_BAD_TYPES = -5, PF_STALE_PLAN = -6,
+       PF_QLIM_ROUNDS = -7 };                      // (powerflow_qlim.hip only: limits still violated after max_rounds re-solves)
 constexpr double PF_RAD = 3.14159265358979323846 / 180.0;
 constexpr float PF_TINY_PIVOT = 1e-30f;            // |pivot| <= this (or NaN): singular
 constexpr int PF_F_LDS_BYTES = 80 * 1024;          // sparse routes: w + the right-hand side in LDS up to here (two workgroups per compute unit at least)

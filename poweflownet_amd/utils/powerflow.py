@@ -1,8 +1,10 @@
 """Batched AC / DC / fast-decoupled power flow on the device: `solve_power_flow` is ONE `pfn_powerflow_solve_init` launch
 (csrc/powerflow.hip), one workgroup per sample, from a flat start or from a table the caller gives (a model's prediction).  It stands where the reference calls pandapower -- `pp.runpp` in dataset_generator.py, `pp.rundcpp` in
 dc_error.py -- for this project's network model: series admittance only, every stored line in both directions, P and Q
-demand-positive per-unit, Va in degrees; no shunts, line charging, taps, Q-limits or unit conversion.  The mismatch it drives to zero
-is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  No CPU path."""
+demand-positive per-unit, Va in degrees; no shunts, line charging, taps or unit conversion.  The mismatch it drives to zero
+is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  `solve_power_flow_qlim`
+(csrc/powerflow_qlim.hip) is the dense AC solve with per-sample bus types and generator Q-limits, the reference's
+`enforce_q_lims=True`.  No CPU path."""
 import ctypes as C
 import time
 from dataclasses import dataclass, replace
@@ -12,10 +14,11 @@ import torch
 
 from .. import _lib as L
 
-# the texts of csrc/powerflow_common.hpp's status enum (PF_NOT_CONVERGED ... PF_STALE_PLAN), which every route's kernel writes
+# the texts of csrc/powerflow_common.hpp's status enum (PF_NOT_CONVERGED ... PF_QLIM_ROUNDS), which every route's kernel writes
 STATUS = {-1: "not converged in max_iter", -2: "singular Jacobian", -3: "non-finite mismatch", -4: "a line names a bus outside the grid",
           -5: "bus_type disagrees with the counts the launch was sized for",
-          -6: "the sparse plan was built from another line list or other bus types"}
+          -6: "the sparse plan was built from another line list or other bus types",
+          -7: "Q-limits still violated after max_rounds re-solves"}
 _MODES = {"ac": 0, "dc": 1, "fdxb": 2, "fdbx": 3}
 _ROUTES = {"auto": 0, "lds": 1, "global": 2, "sparse": 3}
 _PLAN_HEADER_WORDS = 32          # csrc/powerflow_plan.hpp: n, e, m, mode at words 2..5, slab positions 6, nnz(L) 7, multiply-adds 8 / 9
@@ -353,6 +356,88 @@ def solve_power_flow(bus_type, spec, edge_index, rx, *, mode="ac", tol=1e-8, max
 
     One host read (the counts of `bus_type`, which size the launch); no read-back of the results."""
     return _solve(bus_type, spec, edge_index, rx, mode, tol, max_iter, route, init, plan, 0)
+
+
+@dataclass
+class QLimResult(PowerFlowResult):
+    """`PowerFlowResult` of `solve_power_flow_qlim` with `bus_type` [S, n] int32, the types the samples ended with (a PV bus that hit
+    a limit is 2; a failed sample's are the ones it came with), and `rounds` [S] int32, the re-solves (0: no limit was hit).
+    `status` >= 0 counts the Jacobian solves of all rounds."""
+    bus_type: torch.Tensor = None
+    rounds: torch.Tensor = None
+
+
+def solve_power_flow_qlim(bus_type, spec, edge_index, rx, q_limits=None, *, tol=1e-8, max_iter=10, max_rounds=8, q_tol=None,
+                          route="auto", init=None) -> QLimResult:
+    """`solve_power_flow(mode="ac")` with the bus types the SAMPLE's and generator Q-limits enforced, as the reference's
+    `pp.runpp(..., enforce_q_lims=True)` does: ONE `pfn_powerflow_solve_qlim` launch (csrc/powerflow_qlim.hip), one workgroup per
+    sample, the rounds inside the kernel.  `bus_type` [n] or [S, n] integer (0 slack, 1 PV, 2 PQ; a row without exactly one slack or
+    with another type fails that sample alone, status -5), `spec`, `edge_index` ([2, e] or [S, 2, e]), `rx`, `init` as in
+    `solve_power_flow`.  `q_limits` float64 [n, 2] or [S, n, 2] = (lo, hi) on the TABLE's Q column -- demand-positive per-unit, so a
+    generator's [Qmin, Qmax] arrives as [-Qmax, -Qmin] --, read at PV buses only, NaN or +-inf meaning no limit on that side; None:
+    no limits, the plain Newton solve with per-sample types.
+
+    After an inner Newton loop converges, every PV bus whose Q line sum exceeds `hi + q_tol` becomes a PQ bus with Q fixed at `hi`,
+    one below `lo - q_tol` a PQ bus at `lo`; all violators of a round switch together, none switches back, the slack is never
+    limited; Newton then continues from the current state.  `max_iter` bounds the solves of each inner loop, `max_rounds` the
+    re-solves (status -7 where limits are still violated after them).  `q_tol` None means `tol`: Q is only known to the mismatch
+    tolerance, so a violation smaller than that is not one.
+
+    Routes "auto", "lds" and "global"; storage is sized for every non-slack bus ending PQ, m_max = 2 (n - 1) unknowns, so 118 buses
+    take the global route.  There is no sparse route here (ValueError).  No host read at all: nothing is sized by the type counts."""
+    if route == "sparse":
+        raise ValueError("solve_power_flow_qlim: there is no sparse route with Q-limits or per-sample bus types: the sparse plan is "
+                         "built for one set of unknowns, and a plan over the all-PQ superset pattern is not built")
+    if route not in ("auto", "lds", "global"):
+        raise ValueError("solve_power_flow_qlim: route must be one of 'auto', 'lds', 'global'")
+    if spec.dtype != torch.float64 or spec.dim() != 3 or spec.shape[2] != 4:
+        raise RuntimeError(f"solve_power_flow_qlim: spec must be float64 (S, n, 4); got {spec.dtype} {tuple(spec.shape)}")
+    S, n = int(spec.shape[0]), int(spec.shape[1])
+    if bus_type.dtype not in (torch.int32, torch.int64) or tuple(bus_type.shape) not in ((n,), (S, n)):
+        raise RuntimeError(f"solve_power_flow_qlim: bus_type must be an integer tensor ({n},) or ({S}, {n}); got {bus_type.dtype} {tuple(bus_type.shape)}")
+    if edge_index.dtype != torch.int64 or edge_index.dim() not in (2, 3) or edge_index.shape[-2] != 2:
+        raise RuntimeError(f"solve_power_flow_qlim: edge_index must be int64 (2, e) or (S, 2, e); got {edge_index.dtype} {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[-1])
+    if edge_index.dim() == 3 and edge_index.shape[0] != S:
+        raise RuntimeError(f"solve_power_flow_qlim: per-sample edge_index of {edge_index.shape[0]} samples against {S}")
+    if rx.dtype != torch.float64 or tuple(rx.shape) != (S, e, 2):
+        raise RuntimeError(f"solve_power_flow_qlim: rx must be float64 ({S}, {e}, 2); got {rx.dtype} {tuple(rx.shape)}")
+    if q_limits is not None and (q_limits.dtype != torch.float64 or tuple(q_limits.shape) not in ((n, 2), (S, n, 2))):
+        raise RuntimeError(f"solve_power_flow_qlim: q_limits must be float64 ({n}, 2) or ({S}, {n}, 2); got {q_limits.dtype} {tuple(q_limits.shape)}")
+    if init is not None and (not init.is_floating_point() or init.dim() != 3 or tuple(init.shape[:2]) != (S, n) or init.shape[2] < 2):
+        raise RuntimeError(f"solve_power_flow_qlim: init must be a float table ({S}, {n}, >= 2); got {init.dtype} {tuple(init.shape)}")
+    q_tol = tol if q_tol is None else q_tol
+    if max_rounds < 0 or not 0.0 <= q_tol < float("inf"):
+        raise ValueError(f"solve_power_flow_qlim: max_rounds must be at least 0 and q_tol finite and at least 0; got {max_rounds!r}, {q_tol!r}")
+    if 2 * (n - 1) > max_unknowns():
+        raise RuntimeError(f"solve_power_flow_qlim: {2 * (n - 1)} unknowns per sample (every non-slack bus of {n} may end PQ) exceed the "
+                           f"dense solver's {max_unknowns()}; a sparse factorisation is needed, and Q-limits have no sparse route")
+    dev = L.require_device(bus_type, spec, edge_index, rx, q_limits, init, what="solve_power_flow_qlim input")
+    if init is not None:
+        init = init[:, :, :2].to(torch.float64).contiguous()
+    bt = bus_type.to(torch.int32).contiguous()
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    q_limits = None if q_limits is None else q_limits.contiguous()
+    lib = L.load()
+    table = torch.empty(S, n, 4, dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    residual = torch.empty(S, dtype=torch.float64, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    types = torch.empty(S, n, dtype=torch.int32, device=dev)
+    rounds = torch.empty(S, dtype=torch.int32, device=dev)
+    code = {"auto": 0, "lds": 1, "global": 2}[route]
+    need = int(lib.pfn_powerflow_qlim_workspace_bytes(S, n, code))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with torch.cuda.device(dev):
+        L.check(lib.pfn_powerflow_solve_qlim(edge_index.data_ptr(), int(edge_index.dim() == 3), e, rx.data_ptr(), bt.data_ptr(),
+                                             int(bt.dim() == 2), spec.data_ptr(), L.ptr(init), L.ptr(q_limits),
+                                             int(q_limits is not None and q_limits.dim() == 3), S, n, float(tol), float(q_tol),
+                                             int(max_iter), int(max_rounds), code, table.data_ptr(), status.data_ptr(),
+                                             residual.data_ptr(), flags.data_ptr(), types.data_ptr(), rounds.data_ptr(), L.ptr(ws), need,
+                                             L.stream_ptr()),
+                "pfn_powerflow_solve_qlim")
+    return QLimResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
+                      residual=residual, flags=flags, route="global" if need else "lds", bus_type=types, rounds=rounds)
 
 
 def _check_plan_takes_the_lists(spec, edge_index, mode, route, plan):

@@ -11,6 +11,7 @@ the start a good prediction would give).
     python tools/powerflow_bench.py --route sparse [--case 118 --case 130,200 --case 600,835 --case 6470rte] [--samples 4096]
     python tools/powerflow_bench.py --route sparse --mode fdxb [--mode fdbx] [--case ...]
     python tools/powerflow_bench.py --route sparse --perturbed 1 1 [--case 6470rte] [--chunk 16 --chunk 64 --chunk 256]
+    python tools/powerflow_bench.py --q-limit 0.4 --samples 1024 [--case 118 --case 70,100]
 
 `--route sparse`: the sparse route (csrc/powerflow_sparse.hip) per `--case` column (a case name or "n,e"; default 118, 130,200,
 600,835 and 6470rte): the plan's fill, multiply-adds per factor, size and HOST build time, then ms and ms per sample of the solve
@@ -26,6 +27,12 @@ cover plan per chunk of `--chunk` samples (repeatable; default 16, 64 and 256), 
 nnz(L) and multiply-adds per factor against the base grid's plan, the HOST seconds of the cover plan (the list read, the
 elimination, the upload), the seconds of the solve (the map launch and the masked solve: ONE timed call after one warm-up, not a
 median), both per sample, the solve counts, and `one_topology`: the same number of samples on the base grid with the base plan.
+
+`--q-limit Q`: the Q-limited solve (`solve_power_flow_qlim`, csrc/powerflow_qlim.hip) with (-Q, +Q) at every PV bus, per `--case`
+column (default 118 and 70,100): the re-solves and the total of Jacobian solves (mean and maximum), the buses switched and the
+unknowns a sample ends with, ms and ms per sample -- beside the unconstrained `solve_power_flow(mode="ac")` of the SAME batch in
+the same process, and `no_limits`: the Q-limited entry with q_limits=None, i.e. what sizing the launch for m_max = 2 (n - 1) costs
+by itself.
 
 Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
 max_iter 10 (the defaults).  One JSON line."""
@@ -143,6 +150,41 @@ def perturbed_rows(a):
     print(json.dumps(res), flush=True)
 
 
+def qlim_rows(a):
+    """The `--q-limit` table: one column per case."""
+    import torch
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.powerflow import solve_power_flow, solve_power_flow_qlim
+    dev = torch.device("cuda:0")
+    S = a.samples
+    res = {"device": torch.cuda.get_device_name(0), "samples": S, "tol": 1e-8, "max_iter": 10, "max_rounds": 8, "q_limit": a.q_limit, "cases": {}}
+    for case in a.case or ["118", "70,100"]:
+        n, e = CASES[case] if case in CASES else tuple(int(v) for v in case.split(","))
+        ei, bt, rx, spec = make_physical_inputs(n, e, S, seed=0)
+        d = [t.to(dev) for t in (bt, spec, ei, rx)]
+        limits = torch.tensor([-a.q_limit, a.q_limit], dtype=torch.float64, device=dev).expand(n, 2).contiguous()
+        m0 = (n - 1) + int((bt == 2).sum())
+        out = {"buses": n, "lines": e, "pv_buses": int((bt == 1).sum()), "unknowns": m0, "unknowns_sized_for": 2 * (n - 1)}
+
+        def row(per, last):
+            status = last.status.cpu().numpy()
+            ms = 1e3 * float(np.median(per))
+            return {"route": last.route, "ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3),
+                    "ms_per_sample": round(ms / S, 5), "failed": int((status < 0).sum()), "mean_solves": round(float(status[status >= 0].mean()), 3),
+                    "max_solves": int(status.max())}
+        out["unconstrained_solve_power_flow"] = row(*_timed(lambda: solve_power_flow(*d, mode="ac"), a.repeats))
+        out["no_limits"] = row(*_timed(lambda: solve_power_flow_qlim(*d, None), a.repeats))
+        per, last = _timed(lambda: solve_power_flow_qlim(*d, limits), a.repeats)
+        ok = (last.status >= 0).cpu().numpy()
+        rounds, types = last.rounds.cpu().numpy()[ok], last.bus_type.cpu().numpy()[ok]
+        switched = (types != bt.numpy()).sum(axis=1)
+        out["q_limited"] = dict(row(per, last), mean_rounds=round(float(rounds.mean()), 3), max_rounds=int(rounds.max()),
+                                samples_switched=int((switched > 0).sum()), mean_switched=round(float(switched.mean()), 3),
+                                max_switched=int(switched.max()), mean_final_unknowns=round(m0 + float(switched.mean()), 2))
+        res["cases"][case] = out
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -156,10 +198,16 @@ def main():
     ap.add_argument("--perturbed", type=int, nargs=2, default=None, metavar=("R", "A"),
                     help="with --route sparse: per-sample topologies (R lines removed, A added) under one cover plan per chunk")
     ap.add_argument("--chunk", type=int, action="append", default=None, help="with --perturbed: samples per cover plan (repeatable; default 16, 64, 256)")
+    ap.add_argument("--q-limit", type=float, default=None, metavar="Q",
+                    help="the Q-limited solve with (-Q, +Q) at every PV bus beside the unconstrained one (--case: default 118 and 70,100)")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("powerflow_bench.py needs a HIP device")
+    if a.q_limit is not None:
+        if a.route or not a.q_limit > 0:
+            ap.error("--q-limit Q (above 0) is a dense-route table: it does not go with --route sparse")
+        return qlim_rows(a)
     if a.route == "sparse" and a.perturbed:
         return perturbed_rows(a)
     if a.route == "sparse":
