@@ -12,13 +12,16 @@ per-sample line mask (utils/powerflow.py cover_plan, CoverChunker); the chunk si
 --enforce-q-lims, the reference's ENFORCE_Q_LIMS (`pp.runpp(..., enforce_q_lims=True)`): a PV bus whose reactive output hits a limit
 becomes a load bus and the sample is solved again -- inside the one launch of `solve_power_flow_qlim` (csrc/powerflow_qlim.hip) --
 and is written as type 2 for THAT sample, as the reference writes it.  The synthetic cases carry no generator data, so --q-limit Q
-(per-unit, > 0) puts (-Q, +Q) on every PV bus.  Dense cases only, with and without -r / -a.
+(per-unit, > 0) puts (-Q, +Q) on every PV bus.  With and without -r / -a; a case beyond the dense solver (6470rte) takes the
+sparse route's Q-limited solve (csrc/powerflow_sparse_qlim.hip) on the plan of the grid with every non-slack bus PQ
+(utils/powerflow.py qlim_plan), with -r / -a in chunks that share one cover plan each, as above.
 
     python dataset_generator.py --case 118 --samples 2000 --root data
     python dataset_generator.py --case 118 --samples 2000 --root data -r 1 -a 1
     python dataset_generator.py --case 118 --samples 2000 --root data --enforce-q-lims --q-limit 0.5
     python dataset_generator.py --case 6470rte --samples 256 --root data
     python dataset_generator.py --case 6470rte --samples 256 --root data -r 1 -a 1
+    python dataset_generator.py --case 6470rte --samples 256 --root data --enforce-q-lims --q-limit 0.5
 
     <root>/raw/case<case>_node_features.npy   (S, n, 6) float64 [index, type, Vm, Va (degrees), P, Q]; the type is per sample
     <root>/raw/case<case>_edge_features.npy   (S, e, 4) float64 [from, to, r, x]
@@ -73,12 +76,13 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
     cover plan over the base plan's, and "extras": the most lines a cover added.  `route`: "auto" (the sparse route where the case
     has more unknowns than the dense solver takes) or "sparse".  `q_limit` (per-unit, > 0; None: no limits): every PV bus's Q is held
     within (-q_limit, +q_limit) by `solve_power_flow_qlim`; `bus_type` is then [S, n], the types each sample ended with, and `counts`
-    receives "switched": the kept samples in which a bus switched, and "q_rounds": the most re-solves a kept sample took.  Dense
-    cases only: on a case that needs the sparse route it raises."""
+    receives "switched": the kept samples in which a bus switched, and "q_rounds": the most re-solves a kept sample took.  On the
+    sparse route the plan is `qlim_plan`'s, the grid with every non-slack bus PQ (2 (n - 1) unknowns, which also decide "auto"
+    then); with per-sample topologies the chunker plans that type row, one cover plan and one Q-limited solve per chunk."""
     import torch
     from poweflownet_amd.synth import CASES, make_physical_inputs
-    from poweflownet_amd.utils.powerflow import (CoverChunker, max_unknowns, solve_power_flow, solve_power_flow_covered, solve_power_flow_qlim,
-                                                 sparse_plan)
+    from poweflownet_amd.utils.powerflow import (CoverChunker, QLimResult, max_unknowns, qlim_plan, solve_power_flow, solve_power_flow_covered,
+                                                 solve_power_flow_qlim, sparse_plan)
     from poweflownet_amd.utils.topology import perturb_topology
     if route not in ("auto", "sparse"):
         raise ValueError(f"dataset_generator: route must be 'auto' or 'sparse', not {route!r}")
@@ -93,15 +97,17 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
     plan = chunker = None
     # the route is decided from the grid alone, before a sample is drawn: a draw of no samples gives the lines and the bus types
     ei0, bt0, _, _ = make_physical_inputs(n, e, 0, seed * 1_000_003, load)
-    if route == "auto" and (n - 1) + int((bt0 == 2).sum()) > max_unknowns():
+    # (with Q-limits every non-slack bus may end PQ: the dense solver is sized for 2 (n - 1) unknowns then)
+    if route == "auto" and (2 * (n - 1) if q_limit is not None else (n - 1) + int((bt0 == 2).sum())) > max_unknowns():
         route = "sparse"
-    if route == "sparse" and q_limit is not None:
-        raise RuntimeError(f"dataset_generator: --enforce-q-lims needs the dense solver, and case {case} takes the sparse route: "
-                           "Q-limits are not built there (a sparse plan is for one set of unknowns)")
     if route == "sparse":
         batch = min(batch, SPARSE_BATCH)
+        # with Q-limits the plan is the grid's with every non-slack bus PQ: it serves whichever PV buses a sample switches
+        plan_bt = torch.where(bt0 == 0, 0, 2) if q_limit is not None else bt0
         if perturbed:
-            chunker = CoverChunker(bt0.to(device), ei0.to(device))  # one plan per chunk of samples, on the chunk's cover list
+            chunker = CoverChunker(plan_bt.to(device), ei0.to(device))  # one plan per chunk of samples, on the chunk's cover list
+        elif q_limit is not None:
+            plan = qlim_plan(bt0.to(device), ei0.to(device))
         else:
             plan = sparse_plan(bt0.to(device), ei0.to(device))   # one grid: built and uploaded once, it serves every batch and redraw
     growth, extras = 1.0, 0
@@ -125,15 +131,27 @@ def generate(case, samples, seed=0, batch=4096, load=0.2, tol=1e-8, max_iter=10,
         drawn += want
         if d_spec.shape[0] == 0:
             continue
-        if chunker is not None:
-            res, covers = solve_power_flow_covered(chunker, d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
-            growth = max([growth] + [chunker.growth(c) for _, c in covers])
-            extras = max([extras] + [c.extras for _, c in covers])
-        elif q_limit is not None:
+        if q_limit is not None:
             limits = torch.tensor([-q_limit, q_limit], dtype=torch.float64, device=device).expand(n, 2)
+        if chunker is not None and q_limit is not None:
+            # per chunk: one cover plan of the all-PQ row and one Q-limited solve (its map launch and its masked solve)
+            covers = list(chunker.plans(d_ei))
+            parts = [solve_power_flow_qlim(bt.to(device), d_spec[rows], d_ei[rows], d_rx[rows], limits, tol=tol, max_iter=max_iter,
+                                           route="sparse", plan=cover) for rows, cover in covers]
+            res = QLimResult(*(torch.cat([getattr(r, f) for r in parts]) for f in ("table", "status", "iterations", "residual")),
+                             flags=torch.stack([r.flags for r in parts]).amax(0), route="sparse",
+                             bus_type=torch.cat([r.bus_type for r in parts]), rounds=torch.cat([r.rounds for r in parts]))
+        elif chunker is not None:
+            res, covers = solve_power_flow_covered(chunker, d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter)
+        elif q_limit is not None and route == "sparse":
+            res = solve_power_flow_qlim(bt.to(device), d_spec, d_ei, d_rx, limits, tol=tol, max_iter=max_iter, route="sparse", plan=plan)
+        elif q_limit is not None:
             res = solve_power_flow_qlim(bt.to(device), d_spec, d_ei, d_rx, limits, tol=tol, max_iter=max_iter)
         else:
             res = solve_power_flow(bt.to(device), d_spec, d_ei, d_rx, tol=tol, max_iter=max_iter, route=route, plan=plan)
+        if chunker is not None:
+            growth = max([growth] + [chunker.growth(c) for _, c in covers])
+            extras = max([extras] + [c.extras for _, c in covers])
         ok = res.status >= 0
         if int(res.flags.item()) != 0:
             raise RuntimeError("dataset_generator: the solver flagged its bus types")
@@ -175,7 +193,7 @@ def main(argv=None):
     ap.add_argument("--route", default="auto", choices=("auto", "sparse"),
                     help="solver route: auto takes the sparse one where the case exceeds the dense solver; sparse forces it")
     ap.add_argument("--enforce-q-lims", action="store_true",
-                    help="a PV bus whose Q hits its limit becomes a load bus for that sample (needs --q-limit; dense cases only)")
+                    help="a PV bus whose Q hits its limit becomes a load bus for that sample (needs --q-limit)")
     ap.add_argument("--q-limit", type=float, default=None, metavar="Q", help="with --enforce-q-lims: every PV bus's Q stays within (-Q, +Q), per-unit")
     a = ap.parse_args(argv)
     r, add = a.num_lines_to_remove, a.num_lines_to_add

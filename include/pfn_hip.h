@@ -702,6 +702,33 @@ int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_li
                                          const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
                                          int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------- sparse power-flow route, generator Q-limits and per-sample bus types
+ * pfn_powerflow_solve_sparse_qlim (csrc/powerflow_sparse_qlim.hip): pfn_powerflow_solve_qlim beyond pfn_powerflow_max_unknowns().
+ * ONE launch, one workgroup per sample, the rounds inside the kernel, no host sync, no allocation (capturable).  The plan is
+ * pfn_powerflow_sparse_plan's, mode 0, for the type row in which EVERY non-slack bus is PQ: m = 2 (n_bus - 1) unknowns, a theta and
+ * a Vm at every non-slack bus.  A sample's live types say which Vm unknowns are dead (the bus is PV now); a dead unknown is an
+ * identity row and column (diagonal 1, right-hand side 0, its row and column structural zeros), so nothing is renumbered when a
+ * bus switches, and a PV bus's Vm is never updated.
+ *   edge_index, rx, line_mask, unplaced, spec, init, tol, max_iter, plan_header, plan_dev, threads, table, status, residual, flags:
+ *   as pfn_powerflow_solve_sparse_masked with mode 0 (line_mask and unplaced null: one topology for all samples).
+ *   bus_type, types_per_sample, q_limits, limits_per_sample, q_tol, max_rounds, bus_type_out, rounds, the round rule and the table:
+ *   as pfn_powerflow_solve_qlim.
+ *   status  as there: -5 (flag bit 0) for a row without exactly one slack or with a type outside 0, 1, 2, that sample alone; -6 for
+ *           a slack at another bus than the plan's, a plan without theta and Vm at every non-slack bus, another line list, an
+ *           unplaced line; -7 after max_rounds re-solves; -2 a tiny or NaN pivot.  A failed sample has NaN rows, its input types in
+ *           bus_type_out and the rounds it completed.
+ *   ws      pfn_powerflow_sparse_qlim_workspace_bytes(n_samples, plan_header) bytes: the sparse route's sample and its effective Q
+ *           specification (8 n_bus bytes more per sample); too little is PFN_ENOSPACE.  The live types are n_bus bytes of LDS.
+ *   refused with PFN_EINVAL: a plan with m != 2 (n_bus - 1) or another mode, for another n_bus / n_lines, with 32-bit row ids, or
+ *   whose work vector and type bytes do not fit LDS.  A sample's bits are a function of (sample, plan), whatever the batch.    */
+size_t pfn_powerflow_sparse_qlim_workspace_bytes(int64_t n_samples, const void* plan_header);
+int pfn_powerflow_solve_sparse_qlim(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                    const int32_t* unplaced, const int32_t* bus_type, int types_per_sample, const double* spec,
+                                    const double* init, const double* q_limits, int limits_per_sample, int64_t n_samples, int64_t n_bus,
+                                    double tol, double q_tol, int max_iter, int max_rounds, const void* plan_header, const void* plan_dev,
+                                    int threads, double* table, int32_t* status, double* residual, int32_t* flags, int32_t* bus_type_out,
+                                    int32_t* rounds, void* ws, size_t ws_bytes, void* stream);
+
 /* --------------------------------------------------------------------------- topology perturbation
  * The reference's perturb_topology (utils/data_utils.py:12-59, behind dataset_generator.py -r / -a) drawn per sample on the device:
  * remove n_remove random lines, start over while a bus is left unsupplied, then add n_add lines between random bus pairs, each a copy

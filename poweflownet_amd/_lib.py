@@ -36,6 +36,7 @@ SYMBOLS = (
     "pfn_powerflow_sparse_plan_bytes", "pfn_powerflow_sparse_plan", "pfn_powerflow_sparse_workspace_bytes", "pfn_powerflow_solve_sparse",
     "pfn_powerflow_sparse_fd_plan_bytes", "pfn_powerflow_sparse_fd_plan", "pfn_powerflow_sparse_fd_workspace_bytes", "pfn_powerflow_solve_sparse_fd",
     "pfn_powerflow_sparse_plan_into", "pfn_powerflow_cover_map", "pfn_powerflow_solve_sparse_masked", "pfn_powerflow_solve_sparse_fd_masked",
+    "pfn_powerflow_sparse_qlim_workspace_bytes", "pfn_powerflow_solve_sparse_qlim",
     "pfn_topology_perturb", "pfn_topology_unsupplied",
 )
 
@@ -173,6 +174,9 @@ def load() -> C.CDLL:
                                                         p, p, p, p, sz, p]),
         "pfn_powerflow_solve_sparse_fd_masked": (C.c_int, [p, i64, p, p, p, p, p, p, i64, i64, C.c_int, C.c_double, C.c_int, p, p, C.c_int,
                                                            p, p, p, p, p, sz, p]),
+        "pfn_powerflow_sparse_qlim_workspace_bytes": (sz, [i64, p]),
+        "pfn_powerflow_solve_sparse_qlim": (C.c_int, [p, i64, p, p, p, p, C.c_int, p, p, p, C.c_int, i64, i64, C.c_double, C.c_double,
+                                                      C.c_int, C.c_int, p, p, C.c_int, p, p, p, p, p, p, p, sz, p]),
         "pfn_topology_perturb": (C.c_int, [p, i64, i64, i64, i64, i64, i64, C.c_uint64, i64, C.c_int, p, p, p, p]),
         "pfn_topology_unsupplied": (C.c_int, [p, C.c_int, i64, i64, i64, i64, p, p]),
     }

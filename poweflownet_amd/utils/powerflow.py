@@ -4,7 +4,8 @@ dc_error.py -- for this project's network model: series admittance only, every s
 demand-positive per-unit, Va in degrees; no shunts, line charging, taps or unit conversion.  The mismatch it drives to zero
 is exactly `PowerImbalance`'s dP_i, dQ_i, so a solved table is what that loss calls balanced.  `solve_power_flow_qlim`
 (csrc/powerflow_qlim.hip) is the dense AC solve with per-sample bus types and generator Q-limits, the reference's
-`enforce_q_lims=True`.  No CPU path."""
+`enforce_q_lims=True`; with `route="sparse", plan=qlim_plan(...)` (csrc/powerflow_sparse_qlim.hip) it is the same solve beyond the
+dense cap, on the plan of the grid with every non-slack bus PQ.  No CPU path."""
 import ctypes as C
 import time
 from dataclasses import dataclass, replace
@@ -367,8 +368,32 @@ class QLimResult(PowerFlowResult):
     rounds: torch.Tensor = None
 
 
+def qlim_plan(bus_type, edge_index, base=None, size_hint=None, device=None):
+    """The plan `solve_power_flow_qlim(route="sparse", plan=...)` takes: the AC plan of the grid for the type row in which EVERY
+    non-slack bus is PQ, m = 2 (n - 1) unknowns, so that one plan serves whatever PV set a sample has and whichever of its PV buses
+    switch (csrc/powerflow_sparse_qlim.hip: the Vm of a bus that is PV is a dead unknown, an identity row and column).  `bus_type`
+    [n] or [S, n] integer: only the slack's place is read, and all rows must have their one slack at the same bus (RuntimeError
+    otherwise; the plan is built on the host anyway, so the read costs nothing more).  `edge_index` int64 [2, e]: `sparse_plan(all_pq,
+    edge_index, "ac", size_hint, device)`, a `SparsePlan`; [S, 2, e]: `cover_plan(all_pq, edge_index, "ac", base, size_hint, device)`,
+    a `CoverPlan` on the samples' cover list.  No new blob format.  To chunk a batch of per-sample lists, `CoverChunker(all_pq_row,
+    base, "ac")` works as it stands: its plans are these plans."""
+    if bus_type.dim() not in (1, 2) or bus_type.dtype not in (torch.int32, torch.int64) or bus_type.shape[-1] < 1:
+        raise RuntimeError(f"qlim_plan: bus_type must be an integer tensor (n,) or (S, n); got {bus_type.dtype} {tuple(bus_type.shape)}")
+    if edge_index.dtype != torch.int64 or edge_index.dim() not in (2, 3) or edge_index.shape[-2] != 2:
+        raise RuntimeError(f"qlim_plan: edge_index must be int64 (2, e) or (S, 2, e); got {edge_index.dtype} {tuple(edge_index.shape)}")
+    dev = torch.device(device) if device is not None else (edge_index.device if edge_index.is_cuda else bus_type.device)
+    rows = bus_type.detach().cpu().reshape(-1, bus_type.shape[-1])
+    slack = rows == 0
+    if rows.shape[0] == 0 or bool((slack.sum(1) != 1).any()) or bool((slack != slack[0]).any()):
+        raise RuntimeError("qlim_plan: every row of bus_type needs exactly one slack (0), all at the same bus: the plan is built around it")
+    all_pq = torch.where(slack[0], 0, 2).to(torch.int32)
+    if edge_index.dim() == 2:
+        return sparse_plan(all_pq, edge_index, "ac", size_hint, device=dev)
+    return cover_plan(all_pq, edge_index, "ac", base, size_hint, device=dev)
+
+
 def solve_power_flow_qlim(bus_type, spec, edge_index, rx, q_limits=None, *, tol=1e-8, max_iter=10, max_rounds=8, q_tol=None,
-                          route="auto", init=None) -> QLimResult:
+                          route="auto", init=None, plan=None) -> QLimResult:
     """`solve_power_flow(mode="ac")` with the bus types the SAMPLE's and generator Q-limits enforced, as the reference's
     `pp.runpp(..., enforce_q_lims=True)` does: ONE `pfn_powerflow_solve_qlim` launch (csrc/powerflow_qlim.hip), one workgroup per
     sample, the rounds inside the kernel.  `bus_type` [n] or [S, n] integer (0 slack, 1 PV, 2 PQ; a row without exactly one slack or
@@ -384,12 +409,27 @@ def solve_power_flow_qlim(bus_type, spec, edge_index, rx, q_limits=None, *, tol=
     tolerance, so a violation smaller than that is not one.
 
     Routes "auto", "lds" and "global"; storage is sized for every non-slack bus ending PQ, m_max = 2 (n - 1) unknowns, so 118 buses
-    take the global route.  There is no sparse route here (ValueError).  No host read at all: nothing is sized by the type counts."""
-    if route == "sparse":
-        raise ValueError("solve_power_flow_qlim: there is no sparse route with Q-limits or per-sample bus types: the sparse plan is "
-                         "built for one set of unknowns, and a plan over the all-PQ superset pattern is not built")
-    if route not in ("auto", "lds", "global"):
-        raise ValueError("solve_power_flow_qlim: route must be one of 'auto', 'lds', 'global'")
+    take the global route.  No host read at all: nothing is sized by the type counts.
+
+    route "sparse", beyond `max_unknowns()` (csrc/powerflow_sparse_qlim.hip, ONE `pfn_powerflow_solve_sparse_qlim` launch): the same
+    rounds on the sparse route's fp32 factor, static order, no pivoting.  It needs `plan=qlim_plan(bus_type, edge_index)`, the
+    grid's plan with every non-slack bus PQ, built once per grid (without one: ValueError); "auto" never takes this route.  Per-sample
+    line lists `[S, 2, e]` take the `CoverPlan` `qlim_plan(bus_type, edge_index, base)` gives: the map launch of `cover_map` first,
+    then the masked solve -- two launches, no read-back.  A plan with m != 2 (n - 1), for another n, e or mode, on another device,
+    a `CoverPlan` with one `[2, e]` list or a `SparsePlan` with per-sample lists raise before a device is touched.  A sample whose
+    slack is not the plan's, or with a line the cover lacks, gets status -6; a sample's bits are a function of (sample, plan)."""
+    return _solve_qlim(bus_type, spec, edge_index, rx, q_limits, tol, max_iter, max_rounds, q_tol, route, init, plan, 0)
+
+
+def _solve_qlim(bus_type, spec, edge_index, rx, q_limits, tol, max_iter, max_rounds, q_tol, route, init, plan, threads) -> QLimResult:
+    """`solve_power_flow_qlim` with the sparse route's workgroup size exposed (`threads`: 0 the library's choice, 64 or 256)."""
+    if route == "sparse" and plan is None:
+        raise ValueError("solve_power_flow_qlim: the sparse route with Q-limits or per-sample bus types needs the grid's plan with every "
+                         "non-slack bus PQ: pass plan=qlim_plan(bus_type, edge_index)")
+    if route not in ("auto", "lds", "global", "sparse"):
+        raise ValueError("solve_power_flow_qlim: route must be one of 'auto', 'lds', 'global', 'sparse'")
+    if plan is not None and route != "sparse":
+        raise ValueError("solve_power_flow_qlim: a plan goes with route='sparse' only")
     if spec.dtype != torch.float64 or spec.dim() != 3 or spec.shape[2] != 4:
         raise RuntimeError(f"solve_power_flow_qlim: spec must be float64 (S, n, 4); got {spec.dtype} {tuple(spec.shape)}")
     S, n = int(spec.shape[0]), int(spec.shape[1])
@@ -409,9 +449,26 @@ def solve_power_flow_qlim(bus_type, spec, edge_index, rx, q_limits=None, *, tol=
     q_tol = tol if q_tol is None else q_tol
     if max_rounds < 0 or not 0.0 <= q_tol < float("inf"):
         raise ValueError(f"solve_power_flow_qlim: max_rounds must be at least 0 and q_tol finite and at least 0; got {max_rounds!r}, {q_tol!r}")
-    if 2 * (n - 1) > max_unknowns():
+    if route != "sparse" and 2 * (n - 1) > max_unknowns():
         raise RuntimeError(f"solve_power_flow_qlim: {2 * (n - 1)} unknowns per sample (every non-slack bus of {n} may end PQ) exceed the "
-                           f"dense solver's {max_unknowns()}; a sparse factorisation is needed, and Q-limits have no sparse route")
+                           f"dense solver's {max_unknowns()}; a sparse factorisation is needed: route='sparse' with "
+                           "plan=qlim_plan(bus_type, edge_index)")
+    if route == "sparse":
+        # what the kind of plan decides, said before anything touches a device
+        covered = isinstance(plan, CoverPlan)
+        if covered != (edge_index.dim() == 3):
+            raise RuntimeError("solve_power_flow_qlim: a CoverPlan goes with per-sample (S, 2, e) line lists and a SparsePlan with one (2, e) "
+                               f"list; got {type(plan).__name__} and edge_index {tuple(edge_index.shape)}")
+        inner = plan.plan if covered else plan
+        if not isinstance(inner, SparsePlan):
+            raise RuntimeError(f"solve_power_flow_qlim: plan must be what qlim_plan returns, a SparsePlan or a CoverPlan; got {plan!r}")
+        if (inner.n, inner.mode, inner.m) != (n, "ac", 2 * (n - 1)) or (not covered and inner.e != e):
+            raise RuntimeError(f"solve_power_flow_qlim: the plan is for (n, e, mode) = {(inner.n, inner.e, inner.mode)} with {inner.m} unknowns; "
+                               f"the call has {(n, e, 'ac')} and needs the plan with every non-slack bus PQ, {2 * (n - 1)} unknowns "
+                               "(qlim_plan(bus_type, edge_index))")
+        where = {t.device for t in (bus_type, spec, edge_index, rx)}
+        if where != {inner.blob.device} or (covered and plan.cover.device != inner.blob.device):
+            raise RuntimeError(f"solve_power_flow_qlim: the plan lives on {inner.blob.device}, the inputs on {sorted(map(str, where))}")
     dev = L.require_device(bus_type, spec, edge_index, rx, q_limits, init, what="solve_power_flow_qlim input")
     if init is not None:
         init = init[:, :, :2].to(torch.float64).contiguous()
@@ -425,6 +482,25 @@ def solve_power_flow_qlim(bus_type, spec, edge_index, rx, q_limits=None, *, tol=
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     types = torch.empty(S, n, dtype=torch.int32, device=dev)
     rounds = torch.empty(S, dtype=torch.int32, device=dev)
+    if route == "sparse":
+        line_mask = unplaced = None
+        if isinstance(plan, CoverPlan):
+            # per-sample lists under one cover plan: the map launch lays the samples out in cover order, then the masked solve
+            line_mask, rx, unplaced = cover_map(plan, edge_index, rx)
+            edge_index, e, plan = plan.cover, plan.e_cover, plan.plan
+        need = int(lib.pfn_powerflow_sparse_qlim_workspace_bytes(S, C.addressof(plan.header))) if S else 0
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            L.check(lib.pfn_powerflow_solve_sparse_qlim(edge_index.data_ptr(), e, rx.data_ptr(), L.ptr(line_mask), L.ptr(unplaced), bt.data_ptr(),
+                                                        int(bt.dim() == 2), spec.data_ptr(), L.ptr(init), L.ptr(q_limits),
+                                                        int(q_limits is not None and q_limits.dim() == 3), S, n, float(tol), float(q_tol),
+                                                        int(max_iter), int(max_rounds), C.addressof(plan.header), plan.blob.data_ptr(),
+                                                        int(threads), table.data_ptr(), status.data_ptr(), residual.data_ptr(),
+                                                        flags.data_ptr(), types.data_ptr(), rounds.data_ptr(), ws.data_ptr(), need,
+                                                        L.stream_ptr()),
+                    "pfn_powerflow_solve_sparse_qlim")
+        return QLimResult(table=table, status=status, iterations=torch.where(status >= 0, status, torch.full_like(status, -1)),
+                          residual=residual, flags=flags, route="sparse", bus_type=types, rounds=rounds)
     code = {"auto": 0, "lds": 1, "global": 2}[route]
     need = int(lib.pfn_powerflow_qlim_workspace_bytes(S, n, code))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None

@@ -12,6 +12,7 @@ the start a good prediction would give).
     python tools/powerflow_bench.py --route sparse --mode fdxb [--mode fdbx] [--case ...]
     python tools/powerflow_bench.py --route sparse --perturbed 1 1 [--case 6470rte] [--chunk 16 --chunk 64 --chunk 256]
     python tools/powerflow_bench.py --q-limit 0.4 --samples 1024 [--case 118 --case 70,100]
+    python tools/powerflow_bench.py --route sparse --q-limit 0.4 --samples 256 --big-samples 64 [--case 1100,1530 --case 6470rte]
 
 `--route sparse`: the sparse route (csrc/powerflow_sparse.hip) per `--case` column (a case name or "n,e"; default 118, 130,200,
 600,835 and 6470rte): the plan's fill, multiply-adds per factor, size and HOST build time, then ms and ms per sample of the solve
@@ -32,7 +33,11 @@ median), both per sample, the solve counts, and `one_topology`: the same number 
 column (default 118 and 70,100): the re-solves and the total of Jacobian solves (mean and maximum), the buses switched and the
 unknowns a sample ends with, ms and ms per sample -- beside the unconstrained `solve_power_flow(mode="ac")` of the SAME batch in
 the same process, and `no_limits`: the Q-limited entry with q_limits=None, i.e. what sizing the launch for m_max = 2 (n - 1) costs
-by itself.
+by itself.  With `--route sparse` (csrc/powerflow_sparse_qlim.hip; `--case` default 1100,1530 and 6470rte, the latter with
+`--big-samples` samples and one timed call): the plan of the grid with every non-slack bus PQ (`qlim_plan`) beside the own-types
+plan -- unknowns, fill, multiply-adds per factor, host build time --, then `solve_power_flow(route="sparse")` of the SAME batch in
+the same process, `no_limits` and `q_limited` on the all-PQ plan with solves, rounds and switched buses (mean and maximum), the
+quantiles of |Q| at the PV buses of the unconstrained solution (what a Q means on this grid), and the ratios DESIGN 7r quotes.
 
 Host wall time around the call with a device synchronise at either end, median of `--repeats` after one warm-up; tol 1e-8,
 max_iter 10 (the defaults).  One JSON line."""
@@ -185,6 +190,59 @@ def qlim_rows(a):
     print(json.dumps(res), flush=True)
 
 
+def qlim_sparse_rows(a):
+    """The `--route sparse --q-limit Q` table: one column per case."""
+    import torch
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.powerflow import qlim_plan, solve_power_flow, solve_power_flow_qlim, sparse_plan
+    dev = torch.device("cuda:0")
+    res = {"device": torch.cuda.get_device_name(0), "route": "sparse", "tol": 1e-8, "max_iter": 10, "max_rounds": 8, "q_limit": a.q_limit, "cases": {}}
+    for case in a.case or ["1100,1530", "6470rte"]:
+        n, e = CASES[case] if case in CASES else tuple(int(v) for v in case.split(","))
+        big = n > 2000
+        S = a.big_samples if big else a.samples
+        repeats = 1 if big else a.repeats
+        ei, bt, rx, spec = make_physical_inputs(n, e, S, seed=0)
+        d = [t.to(dev) for t in (bt, spec, ei, rx)]
+        limits = torch.tensor([-a.q_limit, a.q_limit], dtype=torch.float64, device=dev).expand(n, 2).contiguous()
+        own, plan = sparse_plan(d[0], d[2], "ac"), qlim_plan(d[0], d[2])
+        out = {"buses": n, "lines": e, "samples": S, "pv_buses": int((bt == 1).sum())}
+        for name, p in (("own_types_plan", own), ("all_pq_plan", plan)):
+            out[name] = {"unknowns": p.m, "slab_positions": p.nnz, "nnz_l": p.nnz_l, "multiply_adds_per_factor": p.madds, "longest_column": p.max_col,
+                         "plan_bytes": p.bytes, "factor_bytes_per_sample": 4 * p.nnz, "host_build_ms": round(1e3 * p.build_s, 2)}
+        out["slab_growth"], out["madds_growth"] = round(plan.nnz / own.nnz, 4), round(plan.madds / max(own.madds, 1), 4)
+
+        def row(per, last):
+            status = last.status.cpu().numpy()
+            ms = 1e3 * float(np.median(per))
+            ok = status[status >= 0]
+            return {"ms": round(ms, 3), "min_ms": round(1e3 * min(per), 3), "max_ms": round(1e3 * max(per), 3), "ms_per_sample": round(ms / S, 5),
+                    "failed": int((status < 0).sum()), "mean_solves": round(float(ok.mean()), 3) if len(ok) else None,
+                    "max_solves": int(ok.max()) if len(ok) else None}
+        per, free = _timed(lambda: solve_power_flow(*d, mode="ac", route="sparse", plan=own), repeats)
+        out["unconstrained_solve_power_flow"] = row(per, free)
+        q = free.table[:, bt.to(dev) == 1, 3].abs()
+        q = q[torch.isfinite(q)]
+        out["unconstrained_pv_abs_q_quantiles"] = {k: round(float(torch.quantile(q, v)), 5) for k, v in (("p50", .5), ("p90", .9), ("p99", .99), ("max", 1.))} if q.numel() else None
+        out["no_limits"] = row(*_timed(lambda: solve_power_flow_qlim(*d, None, route="sparse", plan=plan), repeats))
+        per, last = _timed(lambda: solve_power_flow_qlim(*d, limits, route="sparse", plan=plan), repeats)
+        ok = (last.status >= 0).cpu().numpy()
+        rounds, types = last.rounds.cpu().numpy()[ok], last.bus_type.cpu().numpy()[ok]
+        switched = (types != bt.numpy()).sum(axis=1)
+        out["q_limited"] = row(per, last)
+        if ok.any():
+            out["q_limited"].update(mean_rounds=round(float(rounds.mean()), 3), max_rounds=int(rounds.max()), samples_switched=int((switched > 0).sum()),
+                                    mean_switched=round(float(switched.mean()), 3), max_switched=int(switched.max()))
+        base = out["unconstrained_solve_power_flow"]
+        out["no_limits_over_unconstrained"] = round(out["no_limits"]["ms"] / base["ms"], 4)
+        if out["q_limited"]["mean_solves"] and base["mean_solves"]:
+            out["q_limited_over_unconstrained"] = round(out["q_limited"]["ms"] / base["ms"], 4)
+            out["solves_ratio_times_no_limits_factor"] = round(out["q_limited"]["mean_solves"] / base["mean_solves"] * out["no_limits_over_unconstrained"], 4)
+        res["cases"][f"{case}x{S}"] = out
+        print(json.dumps({f"{case}x{S}": out}), flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=4096)
@@ -205,9 +263,9 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("powerflow_bench.py needs a HIP device")
     if a.q_limit is not None:
-        if a.route or not a.q_limit > 0:
-            ap.error("--q-limit Q (above 0) is a dense-route table: it does not go with --route sparse")
-        return qlim_rows(a)
+        if not a.q_limit > 0 or a.perturbed or a.mode:
+            ap.error("--q-limit Q must be above 0 and goes with neither --perturbed nor --mode")
+        return qlim_sparse_rows(a) if a.route == "sparse" else qlim_rows(a)
     if a.route == "sparse" and a.perturbed:
         return perturbed_rows(a)
     if a.route == "sparse":
