@@ -15,6 +15,9 @@ results/<case>_error_hist.npy [n, 4, nbins] with results/<case>_error_hist_edges
 results/<case>_predictions.npy.  `--graphed-eval` replays the per-batch body from a hipGraph.  No plots: the .npy files are what
 the reference's plotting half reads.
 
+`--model GCN` / `--model MLP` (with `--with-mask` for a baseline trained so) runs the same analysis on a baseline, as the reference's
+script does on its GCN (:109-131): the checkpoint is models/testing/{gcn,mlp}_<case>.pt (train_baselines.py), the pass is the eager one.
+
 `--branch-errors` adds the per-line analysis the reference left commented out (:186-223; utils/branch_analysis.py): the errors of the
 line currents, flows and losses the predicted voltages imply, from one more device pass over the finished tables.  It prints their
 report after the lines above and writes results/<case>_i_error_table.npy [S, e] (the reference's file name), _branch_errors.npy
@@ -28,6 +31,8 @@ import torch
 
 from poweflownet_amd.data import DataLoader
 from poweflownet_amd.datasets import PowerFlowData
+from poweflownet_amd.networks.GCN import GCN
+from poweflownet_amd.networks.MLP import MLP
 from poweflownet_amd.networks.MPN import MaskEmbdMultiMPN, MPN_simplenet
 from poweflownet_amd.synth import make_dataset
 from poweflownet_amd.utils.argument_parser import argument_parser
@@ -53,6 +58,7 @@ def main(argv=None):
     save_flows = _take(argv, "--save-flows", has_value=False, default=False)
     nbins = int(_take(argv, "--nbins", default=300))
     out_dir = _take(argv, "--results-dir", default="results")
+    with_mask = bool(_take(argv, "--with-mask", has_value=False, default=False))
     args = argument_parser(argv)
     if not torch.cuda.is_available():
         raise SystemExit("error_per_feature.py needs a HIP device: poweflownet_amd has no CPU fallback")
@@ -73,15 +79,30 @@ def main(argv=None):
         nin, nout, ne = 4, 4, 2
     loader = DataLoader(testset, batch_size=args.batch_size, shuffle=False)
     models = {"MaskEmbdMultiMPN": MaskEmbdMultiMPN, "MPN_simplenet": MPN_simplenet}
-    model = models[args.model](nfeature_dim=nin, efeature_dim=ne, output_dim=nout, hidden_dim=args.hidden_dim,
-                               n_gnn_layers=args.n_gnn_layers, K=args.K, dropout_rate=args.dropout_rate).to(device)
+    baseline = args.model in ("GCN", "MLP")
+    if baseline:
+        # the reference runs this analysis on its GCN baseline (error_per_feature.py:109-131); checkpoints are what
+        # train_baselines.py saves, models/testing/{gcn,mlp}_<case>.pt
+        n_bus, f_in = int(testset[0].x.shape[0]), 8 if with_mask else 4
+        model = (GCN(nfeature_dim=f_in, output_dim=nout, hidden_dim=129, with_mask=with_mask) if args.model == "GCN"
+                 else MLP(n_bus * f_in, n_bus * nout, 128, 3, 0.2, with_mask=with_mask)).to(device)
+    else:
+        model = models[args.model](nfeature_dim=nin, efeature_dim=ne, output_dim=nout, hidden_dim=args.hidden_dim,
+                                   n_gnn_layers=args.n_gnn_layers, K=args.K, dropout_rate=args.dropout_rate).to(device)
     model.eval()
-    if os.path.exists(os.path.join("models", f"model_{run_id}.pt")):
+    saved = os.path.join("models", "testing", f"{args.model.lower()}_{args.case}.pt")
+    if baseline and os.path.exists(saved):
+        model.load_state_dict(torch.load(saved, map_location=device)["model_state_dict"])
+    elif baseline:
+        print(f"no checkpoint {saved}: the model keeps its random initialisation")
+    elif os.path.exists(os.path.join("models", f"model_{run_id}.pt")):
         model, _ = load_model(model, run_id, device)
     else:
         print(f"no checkpoint models/model_{run_id}.pt: the model keeps its random initialisation")
     print(f"Model: {args.model}\nCase: {args.case}\nNumber of samples: {len(testset)}")
     graphed = getattr(args, "graphed_eval", None) is True           # (off unless asked for: one pass cannot repay the captures)
+    if baseline and graphed:
+        raise SystemExit("--graphed-eval: the baselines run the eager pass only")
     res = bus_error_epoch(model, loader, device, xymean=xymean, xystd=xystd, graph=GraphedEvalStep(model) if graphed else None,
                           keep_errors=True, keep_predictions=bool(save_predictions or branch_errors))
     if res.flags & 1:

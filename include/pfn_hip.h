@@ -225,6 +225,31 @@ int pfn_tag_conv_backward(const void* graph_ws, int64_t n_nodes, int64_t e_store
                           int64_t ldgo, float* grad_x, int64_t ldgx, float* const* grad_weights,
                           float* grad_bias, void* ws, size_t ws_bytes, int64_t seg_nodes, void* stream);
 
+/* GCNConv(in, out).forward (PyG, defaults add_self_loops / normalize / bias, flow source -> target; the layer of the reference's
+ * GCN baseline, networks/GCN.py:8-19), over the adjacency pfn_graph_build made with MODE 0: the list is used as stored and is not
+ * undirected (the reference's GCN.forward hands data.edge_index to the layer as it is).
+ *   - a stored edge whose two ends are equal is dropped (add_remaining_self_loops), then every node gets ONE unit self loop;
+ *     parallel lines count once each;
+ *   - d_i = 1 + #{stored e : dst(e) = i, src(e) != i},  dis_i = d_i^-1/2  (never 0 or inf);
+ *   - H = X W^T,  out_i = dis_i * ( sum_{e: dst = i, src != i} dis_src * H_src  +  dis_i * H_i ) + b.
+ * weight (cout, cin) row-major, bias [cout] or NULL.  x [N, ldx], out [N, ldo], ld = pfn_padded_ld(F), pad columns zero.
+ * relu = 1 fuses the caller's ReLU: a unit is off iff its pre-activation compares <= 0 (a NaN stays on and stays NaN).  The
+ * decisions are kept in `ws` for the backward call -- as the FIRST n_nodes * pfn_padded_ld(cout) bytes of it, one byte per
+ * (row, padded column), 1 = on (valid after a relu = 1 forward; callers may read them) -- together with dis, the packed weight
+ * images and the forward's intermediate: the backward call takes the SAME ws, sizes, weight and relu.  Rows are summed in edge-id
+ * order by one lane, without float atomics: the same call gives the same bits.  The layer multiplies on the narrower side:
+ * pfn_padded_ld(cin) <= pfn_padded_ld(cout): (A X) W^T, else A (X W^T).  `graph_ws` is only read.  No host sync, no allocation.
+ * Backward = exact autograd of the above; grad_x [N, ldgx = ldx] (or NULL: not formed), grad_weight (cout, cin) and grad_bias
+ * [cout] (or NULL) are OVERWRITTEN, not accumulated.  Argument errors: PFN_EINVAL with pfn_last_error.                       */
+size_t pfn_gcn_conv_workspace_bytes(int64_t n_nodes, int64_t e_stored, int cin, int cout);
+int pfn_gcn_conv_forward(const void* graph_ws, int64_t n_nodes, int64_t e_stored, int cin, int cout, const float* x,
+                         int64_t ldx, const float* weight, const float* bias, int relu, float* out, int64_t ldo,
+                         void* ws, size_t ws_bytes, void* stream);
+int pfn_gcn_conv_backward(const void* graph_ws, int64_t n_nodes, int64_t e_stored, int cin, int cout, const float* x,
+                          int64_t ldx, const float* weight, const float* grad_out, int64_t ldgo, int relu,
+                          float* grad_x, int64_t ldgx, float* grad_weight, float* grad_bias, void* ws,
+                          size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------------------------- utilities
  * The segmented scatter-add in isolation (PyG SumAggregation / scatter_add_ under propagate):
  * out[i] = sum_{e -> i} x[src(e)], F columns, ld = pfn_padded_ld(F).  Used for the roofline run.  */

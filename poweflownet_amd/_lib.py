@@ -22,6 +22,7 @@ SYMBOLS = (
     "pfn_mpn_num_params", "pfn_mpn_workspace_bytes", "pfn_mpn_forward", "pfn_mpn_backward", "pfn_mpn_mse_tail_ok", "pfn_mpn_backward_mse", "pfn_mpn_backward_masked_l2", "pfn_mpn_export_gates",
     "pfn_edge_aggr_workspace_bytes", "pfn_edge_aggr_forward", "pfn_edge_aggr_backward",
     "pfn_tag_conv_workspace_bytes", "pfn_tag_conv_forward", "pfn_tag_conv_backward",
+    "pfn_gcn_conv_workspace_bytes", "pfn_gcn_conv_forward", "pfn_gcn_conv_backward",
     "pfn_scatter_add", "pfn_pad_rows", "pfn_mse_loss", "pfn_masked_l2_loss", "pfn_power_imbalance", "pfn_dropout_mask", "pfn_adamw_step", "pfn_adamw_step_dev", "pfn_adamw_step_guarded",
     "pfn_profile_enable", "pfn_profile_report",
     "pfn_khop_distances", "pfn_khop_histograms", "pfn_khop_pack",
@@ -119,6 +120,9 @@ def load() -> C.CDLL:
         "pfn_tag_conv_workspace_bytes": (sz, [i64, i64, i32, i32, i32]),
         "pfn_tag_conv_forward": (C.c_int, [p, i64, i64, i32, i32, i32, p, i64, p, p, p, i64, p, sz, i64, p]),
         "pfn_tag_conv_backward": (C.c_int, [p, i64, i64, i32, i32, i32, p, i64, p, p, i64, p, i64, p, p, p, sz, i64, p]),
+        "pfn_gcn_conv_workspace_bytes": (sz, [i64, i64, i32, i32]),
+        "pfn_gcn_conv_forward": (C.c_int, [p, i64, i64, i32, i32, p, i64, p, p, i32, p, i64, p, sz, p]),
+        "pfn_gcn_conv_backward": (C.c_int, [p, i64, i64, i32, i32, p, i64, p, p, i64, i32, p, i64, p, p, p, sz, p]),
         "pfn_scatter_add": (C.c_int, [p, i64, i64, p, p, i64, p]),
         "pfn_pad_rows": (C.c_int, [p, i64, p, i64, i64, i64, p]),
         "pfn_mse_loss": (C.c_int, [p, p, i64, p, p, p, sz, p]),
