@@ -1,0 +1,82 @@
+#!/usr/bin/env python3
+"""N-1 line-outage screening of a case: which single line outages overload the rest of the grid?  Every scenario of the test split
+of a dataset on disk -- its bus specification and its lines' r and x, read the way dc_error.py reads them -- is screened under the DC
+model with line outage distribution factors (`contingency_screen`: two launches for all scenarios and all outages), the worst
+outages of every scenario are solved again with the AC solver on the grid without the line (`verify_contingencies`), and the two
+are set side by side.  Ratings are `--rating-margin` times the largest base-case flow of a line over the scenarios; a line that
+never carries flow is unmonitored.  Without --data-dir the scenarios are `make_physical_inputs`' synthetic ones.
+
+    python contingency.py --case 118 --data-dir data [--samples 1000] [--rating-margin 1.5] [--verify-top 5]
+
+Writes results/<case>_contingency_{severity,worst_line,overloads,islands,base_flow}.npy.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+
+def scenarios(case, data_dir, samples, device, split=(.5, .2, .3)):
+    """(bus_type [n], spec [S, n, 4], edge_index [2, e], rx [S, e, 2]) on `device`: the test split of `data_dir`'s case, or synthetic."""
+    import torch
+    if data_dir is None:
+        from poweflownet_amd.synth import CASES, make_physical_inputs
+        n, e = CASES[str(case)]
+        ei, bt, rx, spec = make_physical_inputs(n, e, samples or 64, seed=0)
+        return bt.to(device), spec.to(device), ei.to(device), rx.to(device)
+    from dc_error import load_test_split, solver_inputs
+    _, node, edge = load_test_split(data_dir, case, samples, split)
+    if (edge[:, :, :2] != edge[:1, :, :2]).any():
+        raise RuntimeError("contingency: the scenarios have different line lists; the screen takes one list for all")
+    spec, ei, rx = solver_inputs(node, edge, device)
+    return torch.from_numpy(node[0, :, 1].astype(np.int64)).to(device), spec, ei[0].contiguous(), rx
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--case", default="118")
+    ap.add_argument("--data-dir", default=None, help="dataset root; without it: synthetic scenarios of the case's size")
+    ap.add_argument("--samples", type=int, default=None, help="only the first N scenarios of the test split (synthetic: 64)")
+    ap.add_argument("--rating-margin", type=float, default=1.5, help="rating = margin x the line's largest base-case flow")
+    ap.add_argument("--verify-top", type=int, default=5, help="AC-verify the worst N non-islanding outages of every scenario")
+    ap.add_argument("--route", default="auto", choices=("auto", "lds", "global"))
+    ap.add_argument("--split", type=float, nargs=3, default=[.5, .2, .3], help="train / val / test fractions of the dataset")
+    ap.add_argument("--out-dir", default="results")
+    a = ap.parse_args(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("contingency.py needs a HIP device: poweflownet_amd has no CPU solver")
+    from poweflownet_amd.utils.contingency import contingency_screen, verify_contingencies
+    bt, spec, ei, rx = scenarios(a.case, a.data_dir, a.samples, "cuda:0", tuple(a.split))
+    S, e = int(spec.shape[0]), int(ei.shape[1])
+    base = contingency_screen(bt, spec, ei, rx, route=a.route)              # the base flows decide the ratings
+    if int((base.status < 0).sum()):
+        raise RuntimeError(f"contingency: {int((base.status < 0).sum())} base cases failed (statuses {sorted(set(base.status.tolist()))})")
+    ratings = a.rating_margin * base.base_flow.abs().max(dim=0).values     # [e]; 0 where a line never carries flow: unmonitored
+    res = contingency_screen(bt, spec, ei, rx, ratings, route=a.route)
+    islands = res.islands.cpu().numpy()
+    print(f"Case {a.case}: {S} scenarios x {e} outages on the {res.route} route; {int((ratings > 0).sum())} of {e} lines monitored")
+    print(f"{int((islands > 0).sum())} islanding outages, {int(islands[islands > 0].sum())} buses lost over them")
+    top = min(a.verify_top, int((islands == 0).sum()))
+    ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top)
+    pairs, dc, ac = ver.pairs.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy()
+    dc_worst, ac_worst = res.worst_line[ver.pairs[:, 0], ver.pairs[:, 1]].cpu().numpy(), ver.worst_line.cpu().numpy()
+    status = ver.status.cpu().numpy()
+    for s in range(S):
+        rows = [f"line {pairs[t, 1]}: DC {dc[t]:.3f} AC {'failed' if status[t] < 0 else format(ac[t], '.3f')} "
+                f"worst line {dc_worst[t]}{'=' if dc_worst[t] == ac_worst[t] else '!='}{ac_worst[t]}" for t in np.flatnonzero(pairs[:, 0] == s)]
+        print(f"scenario {s}: " + "; ".join(rows))
+    solved = status >= 0
+    missed = int((solved & (dc < 1) & (ac > 1)).sum())
+    agree = int((solved & (dc_worst == ac_worst)).sum())
+    print(f"{len(pairs)} pairs verified, {int((~solved).sum())} AC solves failed; worst line agrees in {agree}; "
+          f"{missed} of {int((solved & (dc < 1)).sum())} the DC screen called secure are overloaded under AC")
+    os.makedirs(a.out_dir, exist_ok=True)
+    for name in ("severity", "worst_line", "overloads", "islands", "base_flow"):
+        np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_{name}.npy"), getattr(res, name).cpu().numpy())
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -791,6 +791,53 @@ int pfn_topology_perturb(const int64_t* edge_index, int64_t n_lines, int64_t n_b
 int pfn_topology_unsupplied(const int64_t* edge_index, int lines_per_sample, int64_t n_lines, int64_t n_samples, int64_t n_bus,
                             int64_t root, int32_t* count, void* stream);
 
+/* ------------------------------------------------------------------------------ N-1 line-outage screening
+ * Which single line outages overload the rest of the grid (csrc/contingency.hip)?  Two launches over ONE line list [2, n_lines] for
+ * all scenarios; no host sync, no allocation (capturable), no float atomics.  Dense route only: n_bus - 1 <= pfn_powerflow_max_unknowns().
+ *
+ * pfn_contingency_islands: islands[k] = the number of buses NOT reachable from `root` (the slack) when line k is removed -- one
+ * workgroup per outage, pfn_topology_unsupplied's reach routine over the base list with line k skipped, nothing materialised.  > 0 is
+ * a bridge: decided combinatorially, from the line list alone.  -4 for EVERY k where a line names a bus outside [0, n_bus) (never
+ * followed).  PFN_EINVAL: root outside [0, n_bus), a shape beyond the LDS budget (5 n_lines + n_bus bytes with 16-bit ids).
+ *
+ * pfn_contingency_dc: one workgroup per scenario.  THE MODEL is mode 1's (pfn_powerflow_solve): B' the Laplacian of 1 / x over the
+ * non-slack buses, B' theta = -P, theta refined under the fp64 residual to tol / max_iter from ONE fp32 inverse X = B'^-1 (Gauss-Jordan
+ * in place, the fast-decoupled modes'); base flow of the stored line l = (a -> b): f_l = (theta_a - theta_b) / x_l, fp64.  The
+ * outage of line k = (i -> j), with X extended by zeros at the slack:
+ *     w_k = X[:, i] - X[:, j]    phi_{l,k} = (w_k[a] - w_k[b]) / x_l    den_k = 1 - phi_{k,k}
+ *     f_l^(k) = f_l + phi_{l,k} / den_k * f_k  (l != k),   f_k^(k) = 0              -- fp32, every operation rounded on its own.
+ *   rx, spec     DEVICE fp64 [n_samples, n_lines, 2] (r, x) and [n_samples, n_bus, 4] (Vm, Va, P, Q demand-positive), as the solver's.
+ *   bus_type     DEVICE int32 [n_bus], exactly one slack (0); n_pv / n_pq are the host's counts of types 1 and 2.
+ *   ratings      DEVICE fp64 per-unit current, [n_lines] (ratings_per_sample == 0) or [n_samples, n_lines]; null: 1.0 everywhere.  A
+ *                rating whose fp32 value is not > 0 (zero, negative, NaN) leaves its line unmonitored: it enters no max and no count.
+ *                Loading of line l is |f_l^(k)| / (float)rating_l (V = 1 under the DC model: |f| is the current).
+ *   islands      DEVICE int32 [n_lines]: pfn_contingency_islands' output for this line list and slack.
+ *   severity     fp32 [n_samples, n_lines]: per (scenario, outage) the largest loading over the monitored lines l != k; 0 where no
+ *                line is monitored; NaN where a monitored loading is not finite.
+ *   worst_line   int32 [n_samples, n_lines]: the line of that maximum, ties to the lowest l (a non-finite loading counts as the
+ *                largest); -1 where no line is monitored.
+ *   overloads    int32 [n_samples, n_lines]: the monitored lines with loading > 1.
+ *                Where islands[k] != 0: severity +inf (islanding outages rank first), worst_line -1, overloads -1, a NaN table row.
+ *   base_flow    fp64 [n_samples, n_lines].
+ *   status       int32 [n_samples]: >= 0 the refinement solves used; -1 not converged in max_iter; -2 singular (a bus without a line
+ *                in the base grid); -3 a non-finite residual (a NaN in P, x = 0); -4 a line names a bus outside [0, n_bus); -5 (and bit
+ *                0 of flags[0]) bus_type disagrees with n_pv / n_pq.  A failed scenario's float outputs are NaN and its integer
+ *                outputs -1; it touches nothing of another scenario.
+ *   post_flow    fp32 [n_samples, n_lines, n_lines] (row = outage, column = line) or null: the full table.
+ *   route        0 auto, 1 LDS, 2 global.  LDS: X sits behind the scenario's vectors (20 n_bus + 28 n_lines + 4 n_bus per wave
+ *                bytes) in LDS while both fit the 159 KiB a workgroup may take (case118: yes); else X lives in a per-scenario slab of
+ *                `ws`, same code, same bits.  pfn_contingency_workspace_bytes(n_samples, n_bus, n_lines, route) is what the call
+ *                needs: 0 exactly for the LDS route.  256 threads up to 90 unknowns, 1024 beyond, as the solver.
+ * A scenario's bits are a function of its own inputs, whatever the batch, the workgroup size or the route.  PFN_EINVAL: bad sizes or
+ * counts, n_bus < 2, more unknowns than the dense cap, vectors beyond LDS, route 1 where it does not fit; PFN_ENOSPACE: too little ws. */
+int pfn_contingency_islands(const int64_t* edge_index, int64_t n_lines, int64_t n_bus, int64_t root, int32_t* islands, void* stream);
+size_t pfn_contingency_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int route);
+int pfn_contingency_dc(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                       const double* ratings, int ratings_per_sample, const int32_t* islands, int64_t n_samples, int64_t n_bus,
+                       int64_t n_pv, int64_t n_pq, double tol, int max_iter, int route, float* severity, int32_t* worst_line,
+                       int32_t* overloads, double* base_flow, int32_t* status, float* post_flow, int32_t* flags, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

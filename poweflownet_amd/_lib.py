@@ -39,6 +39,7 @@ SYMBOLS = (
     "pfn_powerflow_sparse_plan_into", "pfn_powerflow_cover_map", "pfn_powerflow_solve_sparse_masked", "pfn_powerflow_solve_sparse_fd_masked",
     "pfn_powerflow_sparse_qlim_workspace_bytes", "pfn_powerflow_solve_sparse_qlim",
     "pfn_topology_perturb", "pfn_topology_unsupplied",
+    "pfn_contingency_islands", "pfn_contingency_workspace_bytes", "pfn_contingency_dc",
 )
 
 # enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
@@ -183,6 +184,10 @@ def load() -> C.CDLL:
                                                       C.c_int, C.c_int, p, p, C.c_int, p, p, p, p, p, p, p, sz, p]),
         "pfn_topology_perturb": (C.c_int, [p, i64, i64, i64, i64, i64, i64, C.c_uint64, i64, C.c_int, p, p, p, p]),
         "pfn_topology_unsupplied": (C.c_int, [p, C.c_int, i64, i64, i64, i64, p, p]),
+        "pfn_contingency_islands": (C.c_int, [p, i64, i64, i64, p, p]),
+        "pfn_contingency_workspace_bytes": (sz, [i64, i64, i64, C.c_int]),
+        "pfn_contingency_dc": (C.c_int, [p, i64, p, p, p, p, C.c_int, p, i64, i64, i64, i64, C.c_double, C.c_int, C.c_int, p, p, p, p, p,
+                                         p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -21,7 +21,7 @@
 // (6470rte: 9 lines per thread and round).  The kernel is a chain of short phases between barriers, so a sample wants one item per
 // thread where it can have it, and many samples per compute unit hide each other's barriers: at 256 threads and 1.8 KB (case118) the
 // 32-wave limit of a compute unit admits 8 samples at once, at 64 threads and 200 bytes (case14) 32.
-#include "pfn_internal.hpp"
+#include "topology_reach.hpp"
 
 namespace pfn {
 
@@ -38,61 +38,12 @@ struct TpArgs {
     int n, e, r, a, root, max_attempts, lines_per_sample;
 };
 
-__host__ __device__ inline size_t tp_align4(size_t v) { return (v + 3) & ~(size_t)3; }
 // dynamic LDS of one sample; `draw`: the keys, the removed list and the keep flags of pfn_topology_perturb on top of the reach state
 __host__ __device__ inline size_t tp_lds_bytes(int n, int e, int r, bool draw) {
     const size_t id = n <= 65536 ? 2 : 4;
     return (draw ? (size_t)4 * e + (size_t)4 * r : 0) + tp_align4(2 * id * (size_t)e) + (draw ? tp_align4((size_t)e) : 0) + tp_align4((size_t)n);
 }
-static inline int tp_threads(int n, int e) {
-    const int items = n > e ? n : e;
-    return items <= 64 ? 64 : items <= 2048 ? 256 : 1024;
-}
-
-// The lines name buses of the grid?  Checked on the 64-bit ids before any is narrowed or followed; every thread calls it.
-__device__ __forceinline__ int tp_bad_lines(const int64_t* __restrict__ ei, int e, int n) {
-    int bad = 0;
-    for (int j = threadIdx.x; j < e; j += blockDim.x) bad |= (uint64_t)ei[j] >= (uint64_t)n || (uint64_t)ei[e + j] >= (uint64_t)n;
-    return __syncthreads_or(bad);
-}
-
-// Buses NOT reachable from `root` over the lines (keep == null: all of them; else those with keep[j] != 0).  Level-synchronous
-// relaxation like khop.hip's BFS without a queue: a round lets every line whose ends differ mark both reached; the writers of a
-// flag all store 1, a round may see flags of its own round (it then gets further, never elsewhere: the flags only rise and the
-// fixed point is the component of the root), and `changed` is combined by the barrier itself.  At most n - 1 rounds can change
-// anything, so the loop is bounded by n whatever the input.  A thread reads the ids and keep flags of its OWN lines only (t,
-// t + nt, ...: the ones it staged and flagged itself), so the first barrier it needs is the one behind the clearing of the flags.
-// Every thread calls it; the count is uniform.
-template <typename ID>
-__device__ __forceinline__ int tp_unreached(const ID* __restrict__ from, const ID* __restrict__ to, const uint8_t* __restrict__ keep,
-                                            int e, int n, int root, uint8_t* __restrict__ reached, int* __restrict__ s_count) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    for (int i = t; i < n; i += nt) reached[i] = i == root;
-    if (t == 0) *s_count = 0;
-    __syncthreads();
-    for (int round = 0; round < n; ++round) {
-        int changed = 0;
-        for (int j = t; j < e; j += nt) {
-            if (keep && !keep[j]) continue;
-            const int f = from[j], g = to[j];
-            if (reached[f] != reached[g]) {
-                reached[f] = 1;
-                reached[g] = 1;
-                changed = 1;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;
-    }
-    int c = 0;
-    for (int i = t; i < n; i += nt) c += !reached[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if ((t & 63) == 0 && c) atomicAdd(s_count, c);   // (an LDS word; integer sums have no order)
-    __syncthreads();
-    const int total = *s_count;
-    __syncthreads();                                 // (the next call clears the word)
-    return total;
-}
+// (tp_align4, tp_threads, tp_bad_lines and the reach routine tp_unreached: topology_reach.hpp, with contingency.hip)
 
 // min over the workgroup of one 64-bit word per thread (exact, order-free).  `red`: two rows of 16 words, used in turn, so that one
 // barrier per call is enough: a row is rewritten two calls later, behind the barrier of the call in between.  Every thread calls it.

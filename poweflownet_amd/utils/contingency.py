@@ -1,0 +1,206 @@
+"""N-1 line-outage screening on the device: `contingency_screen` asks, for every scenario and every single line outage, how hard the
+remaining lines are loaded -- two launches (csrc/contingency.hip): `pfn_contingency_islands`, one workgroup per outage, finds the
+outages that cut buses off the slack; `pfn_contingency_dc`, one workgroup per scenario, solves the DC model of
+`solve_power_flow(mode="dc")` once, keeps B'^-1 resident and reads every outage's flows off line outage distribution factors.
+`verify_contingencies` re-solves chosen (scenario, outage) pairs with the unchanged AC solver on the reduced line lists and reports
+the AC current loadings beside the DC screen's.  Dense grids only (n - 1 <= `max_unknowns()`).  No CPU path."""
+from dataclasses import dataclass
+
+import torch
+
+from .. import _lib as L
+from .powerflow import STATUS, solve_power_flow  # noqa: F401  (STATUS: the texts of `ContingencyResult.status`)
+
+_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+_COUNTS_ATTR = "_pfn_bus_counts"  # on a bus_type tensor: (version, (n_pv, n_pq, slack)) -- one host read per tensor
+
+
+@dataclass
+class ContingencyResult:
+    """Per (scenario s, outage k): `severity` [S, e] float32 (the largest loading |f_l| / rating_l over the monitored lines l != k;
+    +inf where the outage islands buses, NaN where the scenario failed or a loading is not finite), `worst_line` [S, e] int32 (its
+    line, ties to the lowest; -1 where none), `overloads` [S, e] int32 (monitored lines with loading > 1; -1 where islanding or
+    failed).  `islands` [e] int32: buses cut off the slack by outage k (the line list decides, not the scenario; -4: a line names a
+    bus outside the grid).  Per scenario: `base_flow` [S, e] float64 and `status` [S] int32 (>= 0: refinement solves; < 0:
+    `utils.powerflow.STATUS`).  `post_flow` [S, e, e] float32 (row = outage, column = line) with `keep_table`, else None.  `flags`
+    [1] int32 (bit 0: `bus_type` changed under the launch).  All on the device, nothing read back; `route`: "lds" or "global"."""
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    islands: torch.Tensor
+    base_flow: torch.Tensor
+    status: torch.Tensor
+    post_flow: object
+    route: str
+    flags: object = None
+
+    def ranking(self, top):
+        """(int64 [S, top] outage ids, [S, top] their severities): per scenario the `top` outages by severity, descending -- NaN
+        first (a failure must not hide), then +inf (the islanding outages), ties to the lowest outage id.  Plain torch on the
+        tensors' device: it is not hot."""
+        e = int(self.severity.shape[1])
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= e:
+            raise ValueError(f"ranking: top must be an int in [0, {e}]; got {top!r}")
+        sev = self.severity
+        # NaN, +inf and the finite values as three classes, then the value: a stable sort keeps the lowest id among equals
+        cls = torch.where(torch.isnan(sev), 2, torch.where(torch.isposinf(sev), 1, 0))
+        val = torch.where(cls == 0, sev, torch.zeros_like(sev))
+        order = torch.sort(val, dim=1, descending=True, stable=True).indices
+        order = order.gather(1, torch.sort(cls.gather(1, order), dim=1, descending=True, stable=True).indices)[:, :top]
+        return order, sev.gather(1, order)
+
+
+@dataclass
+class ContingencyVerification:
+    """`pairs` [T, 2] int64 (scenario, outage), the AC `table` [T, n, 4] float64 and `status` [T] int32 of `solve_power_flow` on the
+    grid without the line, `loading` [T, e] float32 = I_l / rating_l in the ORIGINAL line numbering (NaN at the outaged line),
+    `severity` [T] float32 / `worst_line` [T] int32 / `overloads` [T] int32 by the screen's rules, and `dc_severity` [T] float32, the
+    screen's figure for the pair."""
+    pairs: torch.Tensor
+    table: torch.Tensor
+    status: torch.Tensor
+    loading: torch.Tensor
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    dc_severity: torch.Tensor
+
+
+def _bus_counts(bus_type):
+    """(n_pv, n_pq, slack) of a device bus_type tensor: ONE host read, kept ON the tensor object with the version it was read at, so
+    that a second call with the same, unmodified tensor -- a graph capture after its eager warm-up -- reads nothing.  (Not keyed by
+    address: another tensor may come to live where a freed one was.)"""
+    kept = getattr(bus_type, _COUNTS_ATTR, None)
+    got = kept[1] if kept is not None and kept[0] == bus_type._version else None
+    if got is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("contingency_screen: the bus_type counts are read on the host once per tensor; call it eagerly once before capturing")
+        bt = bus_type.long()
+        info = torch.cat([torch.bincount(bt.clamp(0, 3), minlength=4), (bt < 0).sum().view(1), (bt == 0).long().argmax().view(1)]).tolist()
+        if info[0] != 1 or info[3] != 0 or info[4] != 0:
+            raise RuntimeError(f"contingency_screen: bus_type needs exactly one slack (0) and only types 0, 1, 2; got counts {info[:4]}")
+        got = (info[1], info[2], info[5])
+        setattr(bus_type, _COUNTS_ATTR, (bus_type._version, got))
+    return got
+
+
+def _ratings(ratings, S, e, who):
+    if ratings is None:
+        return None
+    L.require_device(ratings, what=f"{who} ratings")
+    if ratings.dtype != torch.float64 or tuple(ratings.shape) not in ((e,), (S, e)):
+        raise RuntimeError(f"{who}: ratings must be float64 ({e},) or ({S}, {e}); got {ratings.dtype} {tuple(ratings.shape)}")
+    return ratings.contiguous()
+
+
+def _check(bus_type, spec, edge_index, rx, who):
+    L.require_device(bus_type, spec, edge_index, rx, what=f"{who} input")
+    if spec.dtype != torch.float64 or spec.dim() != 3 or spec.shape[2] != 4:
+        raise RuntimeError(f"{who}: spec must be float64 (S, n, 4); got {spec.dtype} {tuple(spec.shape)}")
+    S, n = int(spec.shape[0]), int(spec.shape[1])
+    if bus_type.dim() != 1 or bus_type.shape[0] != n or bus_type.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"{who}: bus_type must be an integer tensor of {n} entries; got {bus_type.dtype} {tuple(bus_type.shape)}")
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise RuntimeError(f"{who}: edge_index must be int64 (2, e), one line list for all scenarios; got {edge_index.dtype} {tuple(edge_index.shape)}")
+    e = int(edge_index.shape[1])
+    if rx.dtype != torch.float64 or tuple(rx.shape) != (S, e, 2):
+        raise RuntimeError(f"{who}: rx must be float64 ({S}, {e}, 2); got {rx.dtype} {tuple(rx.shape)}")
+    if n < 2 or e < 1:
+        raise ValueError(f"{who}: a grid of {n} buses and {e} lines has no outage to screen")
+    return S, n, e
+
+
+def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8, max_iter=10, route="auto", keep_table=False) -> ContingencyResult:
+    """Screen every single line outage of every scenario under the DC model: `bus_type` [n] (exactly one slack), `spec` [S, n, 4] and
+    `rx` [S, e, 2] float64 as `solve_power_flow` takes them, ONE line list `edge_index` int64 [2, e].  `ratings`: float64 per-unit
+    current, [e] or [S, e]; None: 1.0 everywhere; a rating that is not > 0 (zero, negative, NaN) leaves its line unmonitored.
+    `route`: "auto", "lds" (raises where B'^-1 does not fit LDS) or "global" (forces the workspace slab).  `keep_table`: also return
+    the full post-outage flow table [S, e, e].  Two launches; one host read (the bus_type counts, once per tensor); nothing is read
+    back."""
+    who = "contingency_screen"
+    if route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    ratings = _ratings(ratings, S, e, who)
+    n_pv, n_pq, slack = _bus_counts(bus_type)
+    dev = spec.device
+    bt = bus_type.to(torch.int32).contiguous()
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    lib = L.load()
+    islands = torch.empty(e, dtype=torch.int32, device=dev)
+    severity = torch.empty(S, e, dtype=torch.float32, device=dev)
+    worst = torch.empty(S, e, dtype=torch.int32, device=dev)
+    overloads = torch.empty(S, e, dtype=torch.int32, device=dev)
+    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = torch.empty(S, e, e, dtype=torch.float32, device=dev) if keep_table else None
+    need = int(lib.pfn_contingency_workspace_bytes(S, n, e, _ROUTES[route]))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with torch.cuda.device(dev):
+        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+        L.check(lib.pfn_contingency_dc(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
+                                       int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
+                                       int(max_iter), _ROUTES[route], severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(),
+                                       base_flow.data_ptr(), status.data_ptr(), L.ptr(table), flags.data_ptr(), L.ptr(ws), need,
+                                       L.stream_ptr()),
+                "pfn_contingency_dc")
+    return ContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, base_flow=base_flow, status=status,
+                             post_flow=table, route="global" if need else "lds", flags=flags)
+
+
+def summarise_loadings(loading, monitored):
+    """(severity float32 [T], worst_line int32 [T], overloads int32 [T]) of loadings [T, e] over the `monitored` lines by the
+    screen's rules: the maximum with ties to the lowest line, a non-finite loading counts as the largest and makes the severity NaN,
+    no monitored line gives (0, -1, 0)."""
+    e = loading.shape[1]
+    ar = torch.arange(e, device=loading.device)
+    wild = monitored & ~torch.isfinite(loading)
+    key = torch.where(monitored, torch.where(wild, torch.full_like(loading, float("inf")), loading), torch.full_like(loading, -1.0))
+    best = key.max(dim=1).values
+    worst = torch.where(key == best[:, None], ar, e).min(dim=1).values
+    none = ~monitored.any(dim=1)
+    severity = torch.where(none, torch.zeros_like(best), torch.where(wild.any(dim=1), torch.full_like(best, float("nan")), best))
+    return severity, torch.where(none, -1, worst).to(torch.int32), (monitored & (loading > 1)).sum(dim=1).to(torch.int32)
+
+
+def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *, top=5, pairs=None, **solver_kw) -> ContingencyVerification:
+    """AC check of chosen outages of a `contingency_screen` result (same inputs): for every pair (scenario s, outage k) -- `pairs`
+    [T, 2], or per scenario the `top` outages of `result.ranking` -- that does not island a bus, the line list without line k and its
+    rx are built on the device, `solve_power_flow(mode="ac", **solver_kw)` solves them, `loss.branch_flows` gives the line currents,
+    and the loadings I_l / rating_l go back to the original line numbering.  The pairs are chosen on the host (T is small)."""
+    from ..loss import branch_flows
+    who = "verify_contingencies"
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    ratings = _ratings(ratings, S, e, who)
+    dev = spec.device
+    islands = result.islands.cpu()
+    if pairs is None:
+        if isinstance(top, bool) or not isinstance(top, int) or top < 0:
+            raise ValueError(f"{who}: top must be an int >= 0; got {top!r}")
+        order = result.ranking(e)[0].cpu()
+        chosen = [(s, k) for s in range(S) for k in [k for k in order[s].tolist() if int(islands[k]) == 0][:top]]
+    else:
+        chosen = [(int(s), int(k)) for s, k in (pairs.tolist() if torch.is_tensor(pairs) else pairs)]
+        for s, k in chosen:
+            if not (0 <= s < S and 0 <= k < e):
+                raise ValueError(f"{who}: pair ({s}, {k}) is outside ({S} scenarios, {e} lines)")
+        chosen = [(s, k) for s, k in chosen if int(islands[k]) == 0]
+    pairs_t = torch.tensor(chosen, dtype=torch.int64, device=dev).reshape(-1, 2)
+    T = int(pairs_t.shape[0])
+    sc, out = pairs_t[:, 0], pairs_t[:, 1]
+    ar = torch.arange(e - 1, device=dev)
+    idx = ar[None, :] + (ar[None, :] >= out[:, None])                          # [T, e - 1]: the lines that stay, in stored order
+    lists = edge_index[:, idx].permute(1, 0, 2).contiguous()                   # [T, 2, e - 1]
+    rx_post = rx[sc[:, None], idx].contiguous()                                # [T, e - 1, 2]
+    solved = solve_power_flow(bus_type, spec[sc].contiguous(), lists, rx_post, mode="ac", **solver_kw)
+    rate = torch.ones(S, e, dtype=torch.float32, device=dev) if ratings is None else ratings.float().expand(S, e)
+    rate = rate[sc]                                                            # [T, e]
+    loading = torch.full((T, e), float("nan"), dtype=torch.float32, device=dev)
+    if T and e > 1:
+        flows = branch_flows(solved.table.float(), lists, rx_post.float())[0]  # [T, e - 1, 4]: column 0 is the current
+        loading.scatter_(1, idx, flows[:, :, 0] / rate.gather(1, idx))
+    monitored = (rate > 0) & (torch.arange(e, device=dev)[None, :] != out[:, None])
+    severity, worst, overloads = summarise_loadings(loading, monitored)
+    return ContingencyVerification(pairs=pairs_t, table=solved.table, status=solved.status, loading=loading, severity=severity,
+                                   worst_line=worst, overloads=overloads, dc_severity=result.severity[sc, out])
