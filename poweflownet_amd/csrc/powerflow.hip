@@ -28,7 +28,8 @@
 // code; the Newton / DC instantiation does not pay registers for it.
 //
 // What this kernel shares with the sparse routes -- the status codes, the start state, the line-end terms, the stopping rule, the
-// table write-back, the argument checks -- is powerflow_common.hpp's.
+// table write-back, the argument checks -- is powerflow_common.hpp's; the Newton pass itself (rows, LU, update), shared with the
+// Q-limit kernel, and the route decision are powerflow_dense.hpp's.
 #include <algorithm>
 
 #include "powerflow_dense.hpp"
@@ -49,9 +50,8 @@ template <bool LDS, bool FD>
 __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
     __shared__ double s_red[16];
-    __shared__ float s_pval;
-    __shared__ int s_piv, s_ok, s_slack;
-    const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
+    __shared__ int s_ok, s_slack;
+    const int t = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
     const int s = blockIdx.x;
     const PfProblem& p = a.p;
     const int n = p.n, e = p.e, m = a.m, ld = pf_ld(m);
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     const PfSample sm = pf_sample(p, s);
     const int64_t* ei = p.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
     const double* rx = sm.rx;
-    const double* spec = sm.spec;
+    const PfDense d{ei, rx, sm.spec, sm.spec + 3, 4, n, e, aidx, vidx, vm, th, sp, sq, F};
     int code = 0;                                   // (uniform over the workgroup wherever it is tested)
     double res = __builtin_nan("");
 
@@ -104,76 +104,12 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
     }
 
     int it = 0;
-    if (code == 0 && pf_start_state(p, sm, s_slack, dc, nt, vm, th)) code = PF_NON_FINITE;
+    if (code == 0 && pf_start_state(p, sm, p.bus_type, s_slack, dc, nt, vm, th)) code = PF_NON_FINITE;
     if (code == 0) {
         int half = 0;                               // FD: 0 the P half comes next, 1 the Q half
         for (;; ++it) {
-            if constexpr (!FD) {
-                for (int k = t; k < m * ld; k += nt) A[k] = 0.f;
-                __syncthreads();
-            }
-            // ---- line sums, mismatch and matrix rows of bus i, its lines in stored order
-            for (int i = t; i < n; i += nt) {
-                const int ra = aidx[i], rv = vidx[i];
-                const double vi = vm[i], ti = th[i];
-                double sP = 0.0, sQ = 0.0, dPt = 0.0, dPv = 0.0, dQt = 0.0, dQv = 0.0;
-                for (int k = 0; k < e; ++k) {
-                    const int la = (int)ei[k], lb = (int)ei[e + k];
-                    if (la != i && lb != i) continue;
-                    const double r = rx[2 * k], x = rx[2 * k + 1];
-#pragma unroll 1
-                    for (int side = 0; side < 2; ++side) {       // the stored direction, then the reverse (a self-loop: both)
-                        if ((side ? lb : la) != i) continue;
-                        const int j = side ? la : lb;
-                        const int ca = aidx[j], cv = vidx[j];
-                        if (dc) {
-                            const double b = pf_dc_end(x, ti, th[j], sP);
-                            dPt += b;
-                            if (ra >= 0 && ca >= 0) A[ra * ld + ca] += (float)(-b);
-                            continue;
-                        }
-                        const PfEnd end = pf_ac_end(r, x, vi, ti, vm[j], th[j], sP, sQ);
-                        if constexpr (FD) continue;
-                        const PfEndJac J = pf_ac_end_jac(end, vi);
-                        dPt += J.pti;
-                        dPv += J.pvi;
-                        dQt += J.qti;
-                        dQv += J.qvi;
-                        if (ra >= 0) {
-                            if (ca >= 0) A[ra * ld + ca] += (float)(-J.pti);
-                            if (cv >= 0) A[ra * ld + cv] += (float)J.pvj;
-                        }
-                        if (rv >= 0) {
-                            if (ca >= 0) A[rv * ld + ca] += (float)(-J.qti);
-                            if (cv >= 0) A[rv * ld + cv] += (float)J.qvj;
-                        }
-                    }
-                }
-                sp[i] = sP;
-                sq[i] = sQ;
-                if constexpr (FD) {
-                    if (ra >= 0) {
-                        F[ra] = spec[4 * i + 2] - sP;
-                        G[ra] = F[ra] / vi;
-                    }
-                    if (rv >= 0) {
-                        F[rv] = spec[4 * i + 3] - sQ;
-                        G[rv] = F[rv] / vi;
-                    }
-                    continue;
-                }
-                if (ra >= 0) {
-                    F[ra] = spec[4 * i + 2] - sP;
-                    A[ra * ld + ra] += (float)dPt;
-                    if (rv >= 0) A[ra * ld + rv] += (float)dPv;
-                }
-                if (rv >= 0) {
-                    F[rv] = spec[4 * i + 3] - sQ;
-                    A[rv * ld + ra] += (float)dQt;
-                    A[rv * ld + rv] += (float)dQv;
-                }
-            }
-            __syncthreads();
+            // ---- line sums, mismatch and matrix rows (powerflow_dense.hpp)
+            pf_dense_rows<FD>(d, dc, A, m, ld, G);
             // ---- max |F| in fp64; a non-finite entry counts as +inf
             double mx = 0.0;
             for (int k = t; k < m; k += nt) mx = fmax(mx, pf_abs_clamped(F[k]));
@@ -230,60 +166,9 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs 
                 half = mq ? !half : 0;
                 continue;
             }
-            // ---- LU with partial pivoting, the right-hand side F eliminated along (fp64); L is not kept
-            for (int k = 0; k < m; ++k) {
-                if (wave == 0) {
-                    float best = -1.f;
-                    int bi = m;
-                    for (int i = k + lane; i < m; i += 64) {
-                        const float v = fabsf(A[i * ld + k]);
-                        if (v > best) { best = v; bi = i; }
-                    }
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) {
-                        const float ob = __shfl_xor(best, off);
-                        const int oi = __shfl_xor(bi, off);
-                        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-                    }
-                    if (lane == 0) { s_piv = bi; s_pval = best; }
-                }
-                __syncthreads();
-                const int p = s_piv;
-                if (!(s_pval > PF_TINY_PIVOT)) { code = PF_SINGULAR; break; }
-                if (p != k) {
-                    for (int j = k + t; j < m; j += nt) {
-                        const float u = A[k * ld + j];
-                        A[k * ld + j] = A[p * ld + j];
-                        A[p * ld + j] = u;
-                    }
-                    if (t == 0) {
-                        const double f = F[k];
-                        F[k] = F[p];
-                        F[p] = f;
-                    }
-                }
-                __syncthreads();
-                const float piv = A[k * ld + k];
-                for (int i = k + 1 + wave; i < m; i += nw) {
-                    const float l = A[i * ld + k] / piv;
-                    for (int j = k + 1 + lane; j < m; j += 64) A[i * ld + j] = fmaf(-l, A[k * ld + j], A[i * ld + j]);
-                    if (lane == 0) F[i] -= (double)l * F[k];
-                }
-                __syncthreads();
-            }
-            if (code) break;
-            // ---- back substitution by columns: after step k, F[k] / U[k][k] is x_k
-            for (int k = m - 1; k > 0; --k) {
-                const double xk = F[k] / (double)A[k * ld + k];
-                for (int i = t; i < k; i += nt) F[i] -= (double)A[i * ld + k] * xk;
-                __syncthreads();
-            }
-            for (int i = t; i < n; i += nt) {
-                const int ia = aidx[i], iv = vidx[i];
-                if (ia >= 0) th[i] += F[ia] / (double)A[ia * ld + ia];
-                if (iv >= 0) vm[i] += F[iv] / (double)A[iv * ld + iv];
-            }
-            __syncthreads();
+            // ---- A dx = F by LU with partial pivoting, then x += dx (powerflow_dense.hpp)
+            if (!pf_lu_solve(A, ld, m, F)) { code = PF_SINGULAR; break; }
+            pf_dense_update(d, A, ld);
         }
     }
 
@@ -347,18 +232,9 @@ int pfn_powerflow_solve_init(const int64_t* edge_index, int lines_per_sample, in
     PFN_TRY(pf_check_call("pfn_powerflow_solve", a.p, n_samples, nullptr, "the workspace 16-byte"));
     if (n_samples == 0) return PFN_OK;
     const size_t lds_need = fd ? pf_fd_lds_bytes(n, (int)n_pq) : pf_vec_bytes(n, m) + pf_mat_floats(m) * 4;
-    const bool fits = fd ? pf_fd_fits_lds(n, (int)n_pq) : pf_fits_lds(n, m);
-    PFN_CHECK_ARG(route != 1 || fits, "pfn_powerflow_solve: route 1 (LDS): %d unknowns of %d buses need %zu bytes of LDS, %d are there", m, n,
-                  lds_need, kLdsCuBytes - kLdsReserve);
-    const bool lds = route == 1 || (route == 0 && fits);
     const size_t mat_floats = fd ? pf_fd_mat_floats(n, (int)n_pq) : pf_mat_floats(m);
-    if (!lds) {
-        const size_t need = (size_t)n_samples * mat_floats * sizeof(float);
-        if (need && (!ws || ws_bytes < need)) {
-            set_error("pfn_powerflow_solve: the global route needs a workspace of %zu bytes (got %zu)", need, ws ? ws_bytes : (size_t)0);
-            return PFN_ENOSPACE;
-        }
-    }
+    bool lds;
+    PFN_TRY(pf_dense_route("pfn_powerflow_solve", route, m, n, lds_need, n_samples, mat_floats, ws, ws_bytes, &lds));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int big = fd ? std::max(n - 1, (int)n_pq) : m;            // the rule of the one matrix, applied to the larger of the two
     const int threads = big > PF_BIG_M ? PF_BIG_THREADS : PF_SMALL_THREADS;

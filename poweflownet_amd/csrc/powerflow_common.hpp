@@ -2,7 +2,9 @@
 // the status codes and constants, the problem as the launch passes it, the start state, the AC and DC line-end terms with the
 // Jacobian derivatives of an end, the max |F| and the stopping rule, the table write-back, the view of a sparse (sub-)plan with its
 // check against the device arrays, and -- host side -- the sizes of the sparse routes' sample, the argument checks every entry
-// makes and the launch of a sparse kernel.  The kernels keep what differs between them: their matrix and how it is solved.
+// makes, those the sparse entries make (plan header, launch arguments, workspace) and the launch of a sparse kernel.  The kernels
+// keep what differs between them: their matrix and how it is solved (the dense one: powerflow_dense.hpp; what the Q-limit kernels
+// add: powerflow_qlim.hpp).
 //
 // Every device function here is called by ALL threads of the workgroup with the same arguments (`nt` is the workgroup size: a
 // compile-time constant on the sparse routes, blockDim.x on the dense one).  The expressions of the line-end terms keep the shape
@@ -62,12 +64,15 @@ __device__ __forceinline__ const uint8_t* pf_line_mask(const PfProblem& p, int s
 __device__ __forceinline__ int pf_unplaced(const PfProblem& p, int s) { return p.unplaced ? p.unplaced[s] != 0 : 0; }
 
 // ---- the start state: flat, or the caller's -- Va at the non-slack buses, Vm at the PQ buses (dc: Va only, its Vm is no unknown).
-// True, for all threads alike, when the caller's start holds a non-finite value.
-__device__ __forceinline__ bool pf_start_state(const PfProblem& p, const PfSample& sm, int slack, bool dc, int nt, double* vm, double* th) {
+// True, for all threads alike, when the caller's start holds a non-finite value.  `types` is the row that decides: p.bus_type, or
+// the Q-limit kernels' live copy of the sample's own row in LDS (int or byte; they pass dc = false).
+template <typename Ty>
+__device__ __forceinline__ bool pf_start_state(const PfProblem& p, const PfSample& sm, const Ty* types, int slack, bool dc, int nt, double* vm,
+                                               double* th) {
     const double th0 = sm.spec[4 * slack + 1] * PF_RAD;
     int wild = 0;
     for (int i = threadIdx.x; i < p.n; i += nt) {
-        const int ty = p.bus_type[i];
+        const int ty = types[i];
         double v = ty == 2 ? 1.0 : sm.spec[4 * i], ang = th0;
         if (sm.init) {
             if (ty == 2 && !dc) v = sm.init[2 * i];
@@ -266,6 +271,32 @@ static inline int pf_check_call(const char* who, const PfProblem& p, int64_t n_s
                         reinterpret_cast<uintptr_t>(p.residual) | reinterpret_cast<uintptr_t>(p.init)) & 7) == 0 &&
                       ((reinterpret_cast<uintptr_t>(p.bus_type) | reinterpret_cast<uintptr_t>(p.status) | reinterpret_cast<uintptr_t>(p.flags)) & 3) == 0,
                   "%s: table must be 32-byte aligned, %s, fp64 and int64 inputs 8-byte, int32 arrays 4-byte", who, sixteen);
+    return PFN_OK;
+}
+
+// what the sparse entries ask of their plan header before they read sizes from it (the entry adds its own mode and size conditions)
+// and of their launch arguments; the row ids are looked at only when there are samples
+static inline int pf_check_plan_header(const char* who, const int32_t* h) {
+    PFN_CHECK_ARG(h, "%s: null plan header", who);
+    PFN_CHECK_ARG(h[PFP_H_MAGIC] == PFP_MAGIC && h[PFP_H_VERSION] == PFP_VERSION, "%s: not a sparse power-flow plan (magic %08x, version %d)",
+                  who, (unsigned)h[PFP_H_MAGIC], (int)h[PFP_H_VERSION]);
+    PFN_CHECK_ARG(h[PFP_H_N] >= 1 && h[PFP_H_E] >= 0 && h[PFP_H_M] >= 0 && h[PFP_H_NNZ] >= h[PFP_H_M], "%s: the plan header is inconsistent", who);
+    return PFN_OK;
+}
+
+static inline int pf_check_sparse_launch(const char* who, int threads, const int32_t* unplaced, int64_t n_samples, const int32_t* h, int m) {
+    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
+    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
+    // (a plan with 32-bit row ids has more than 65535 unknowns: its work vector would not fit LDS either; the kernels read 16-bit ids only)
+    PFN_CHECK_ARG(n_samples <= 0 || h[PFP_H_IDX16] != 0, "%s: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", who, m);
+    return PFN_OK;
+}
+
+static inline int pf_check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need) {
+        set_error("%s: the workspace must hold %zu bytes (got %zu)", who, need, ws ? ws_bytes : (size_t)0);
+        return PFN_ENOSPACE;
+    }
     return PFN_OK;
 }
 

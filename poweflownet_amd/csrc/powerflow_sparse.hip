@@ -70,7 +70,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
     // ---- the device arrays against the plan, then the start state; code is uniform over the workgroup wherever it is tested.  A
     // sample with a line the cover list has no place for is stale before anything is looked at
     int code = pf_check_plan(p, v, nt, pf_unplaced(p, s), [&](int i, int ty, int&) { return (ty != 0) != (ua[i] >= 0) || (ty == 2 && !dc) != (uv[i] >= 0); });
-    if (code == 0 && pf_start_state(p, sm, a.plan[PFP_H_SLACK], dc, nt, vm, th)) code = PF_NON_FINITE;
+    if (code == 0 && pf_start_state(p, sm, p.bus_type, a.plan[PFP_H_SLACK], dc, nt, vm, th)) code = PF_NON_FINITE;
     int it = 0;
     if (code == 0) {
         for (;; ++it) {
@@ -144,11 +144,8 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_kernel(const PfsArgs
 }
 
 static int pfs_check_header(const int32_t* h, const char* who) {
-    PFN_CHECK_ARG(h, "%s: null plan header", who);
-    PFN_CHECK_ARG(h[PFP_H_MAGIC] == PFP_MAGIC && h[PFP_H_VERSION] == PFP_VERSION, "%s: not a sparse power-flow plan (magic %08x, version %d)",
-                  who, (unsigned)h[PFP_H_MAGIC], (int)h[PFP_H_VERSION]);
-    PFN_CHECK_ARG(h[PFP_H_N] >= 1 && h[PFP_H_E] >= 0 && h[PFP_H_M] >= 0 && h[PFP_H_NNZ] >= h[PFP_H_M] && (h[PFP_H_MODE] == 0 || h[PFP_H_MODE] == 1),
-                  "%s: the plan header is inconsistent", who);
+    PFN_TRY(pf_check_plan_header(who, h));
+    PFN_CHECK_ARG(h[PFP_H_MODE] == 0 || h[PFP_H_MODE] == 1, "%s: the plan header is inconsistent", who);
     return PFN_OK;
 }
 
@@ -176,23 +173,17 @@ int pfn_powerflow_solve_sparse_masked(const int64_t* edge_index, int64_t n_lines
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines && h[PFP_H_MODE] == mode,
                   "%s: the plan is for %d buses, %d lines, mode %d; the call has %lld, %lld, mode %d", who, (int)h[PFP_H_N],
                   (int)h[PFP_H_E], (int)h[PFP_H_MODE], (long long)n_bus, (long long)n_lines, mode);
-    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
-    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
     const int n = h[PFP_H_N], m = h[PFP_H_M], nnz = h[PFP_H_NNZ];
+    PFN_TRY(pf_check_sparse_launch(who, threads, unplaced, n_samples, h, m));
     const size_t stride = pf_sample_bytes(n, m, nnz), need = (size_t)n_samples * stride;
     const PfsArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter, line_mask, unplaced},
                     static_cast<const int32_t*>(plan_dev), stride, m, nnz, mode, pf_f_in_lds(m)};
     PFN_TRY(pf_check_call(who, a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
     if (n_samples == 0) return PFN_OK;
-    // (a plan with 32-bit row ids has more than 65535 unknowns: its work vector would not fit LDS either; the kernel reads 16-bit ids only)
-    PFN_CHECK_ARG(h[PFP_H_IDX16] != 0, "%s: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", who, m);
     const size_t lds = pf_lds_bytes(m);
     PFN_CHECK_ARG(lds <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns needs %zu bytes of LDS, %d are there", who,
                   m, lds, kLdsCuBytes - kLdsReserve);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: the workspace must hold %zu bytes (got %zu)", who, need, ws ? ws_bytes : (size_t)0);
-        return PFN_ENOSPACE;
-    }
+    PFN_TRY(pf_check_workspace(who, ws, ws_bytes, need));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double madds = (double)(((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]);
     ProfScope ps(mode ? "powerflow_sparse_dc" : "powerflow_sparse_ac",

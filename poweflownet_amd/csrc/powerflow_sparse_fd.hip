@@ -71,7 +71,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_fd_kernel(const PfdA
         }
         if (__syncthreads_or(differ)) code = PF_STALE_PLAN;
     }
-    if (code == 0 && pf_start_state(p, sm, H[PFP_H_SLACK], false, nt, vm, th)) code = PF_NON_FINITE;
+    if (code == 0 && pf_start_state(p, sm, p.bus_type, H[PFP_H_SLACK], false, nt, vm, th)) code = PF_NON_FINITE;
     int it = 0;
     if (code == 0) {
         // ---- B' and B'': bus i's owner adds the off-diagonals of its row at their planned positions, line ends in stored order
@@ -193,22 +193,17 @@ int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_li
     PFN_CHECK_ARG(mode == 2 || mode == 3, "%s: mode must be 2 (fdxb) or 3 (fdbx); modes 0 and 1 are pfn_powerflow_solve_sparse's", who);
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines, "%s: the plan is for %d buses, %d lines; the call has %lld, %lld", who,
                   (int)h[PFP_H_N], (int)h[PFP_H_E], (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
-    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
     const int n = h[PFP_H_N], m_p = h[PFP_H_M], m_q = h[PFD_H_M_Q], nnz = h[PFP_H_NNZ], mmax = std::max(m_p, m_q);
+    PFN_TRY(pf_check_sparse_launch(who, threads, unplaced, n_samples, h, mmax));
     const size_t stride = pf_sample_bytes(n, mmax, nnz), need = (size_t)n_samples * stride;
     const PfdArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter, line_mask, unplaced},
                     static_cast<const int32_t*>(plan_dev), stride, m_p, m_q, nnz, mode == 3, pf_f_in_lds(mmax)};
     PFN_TRY(pf_check_call(who, a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
     if (n_samples == 0) return PFN_OK;
-    PFN_CHECK_ARG(h[PFP_H_IDX16] != 0, "%s: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", who, mmax);
     const size_t lds = pf_lds_bytes(mmax);
     PFN_CHECK_ARG(lds <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns needs %zu bytes of LDS, %d are there", who, mmax, lds,
                   kLdsCuBytes - kLdsReserve);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: the workspace must hold %zu bytes (got %zu)", who, need, ws ? ws_bytes : (size_t)0);
-        return PFN_ENOSPACE;
-    }
+    PFN_TRY(pf_check_workspace(who, ws, ws_bytes, need));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double madds = (double)(((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]);
     // (the model: one factor of each half, and some twenty half-iterations of one pair of substitutions and one mismatch walk)

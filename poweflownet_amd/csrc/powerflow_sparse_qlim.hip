@@ -17,16 +17,16 @@
 // read once per bus and pass and stands in the workspace behind the sample's slab.  pf_sample_bytes is unchanged; the sizer here
 // adds qs.
 //
-// Rounds, statuses and the table are powerflow_qlim.hip's exactly: after a converged inner loop the owner of each live PV bus tests
-// its sq against (lo, hi), NaN or +-inf meaning no limit on that side; sq > hi + q_tol fixes Q at hi, sq < lo - q_tol at lo; all
-// violators of a round switch together, none switches back; max_iter bounds the solves of each inner loop, max_rounds the re-solves
-// (-7 after them); status >= 0 is the total of solves.  With a line mask (the cover route's, powerflow_cover.hip) every sample has
-// its own line list as well.
+// Rounds, statuses and the table are powerflow_qlim.hip's exactly, by the same text (powerflow_qlim.hpp: pfq_switch tests the live PV
+// buses against their limits, pfq_write_back writes the table and the final types); max_iter bounds the solves of each inner loop,
+// max_rounds the re-solves (-7 after them); status >= 0 is the total of solves.  With a line mask (the cover route's,
+// powerflow_cover.hip) every sample has its own line list as well.
 //
 // Every loop bound comes from the plan or is uniform over the workgroup, and every exit is taken by all threads after a barrier.
-// powerflow_common.hpp's device functions and powerflow_sparse_core.hpp are called as they stand; the start state and the
-// write-back are the variants of powerflow_qlim.hip, which read ty and qs.  A sample's bits are a function of (sample, plan) alone.
-#include "powerflow_common.hpp"
+// powerflow_common.hpp's device functions (the start state reads ty) and powerflow_sparse_core.hpp are called as they stand; the
+// round's limit test and the write-back, which read ty and qs, are powerflow_qlim.hpp's, shared with powerflow_qlim.hip.  A sample's
+// bits are a function of (sample, plan) alone.
+#include "powerflow_qlim.hpp"
 #include "powerflow_sparse_core.hpp"
 
 namespace pfn {
@@ -107,23 +107,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
     }
 
     int it = 0, rounds = 0;                          // solves over all rounds; re-solves begun
-    if (code == 0) {
-        // ---- the start state: flat, or the caller's -- Va at the non-slack buses, Vm at the buses that are PQ on entry
-        const double th0 = spec[4 * slack + 1] * PF_RAD;
-        int wild = 0;
-        for (int i = t; i < n; i += nt) {
-            const int y = ty[i];
-            double vv = y == 2 ? 1.0 : spec[4 * i], ang = th0;
-            if (sm.init) {
-                if (y == 2) vv = sm.init[2 * i];
-                if (y != 0) ang = sm.init[2 * i + 1] * PF_RAD;
-                wild |= !(fabs(vv) < __builtin_inf()) || !(fabs(ang) < __builtin_inf());
-            }
-            vm[i] = vv;
-            th[i] = ang;
-        }
-        if (__syncthreads_or(wild)) code = PF_NON_FINITE;
-    }
+    if (code == 0 && pf_start_state(p, sm, ty, slack, false, nt, vm, th)) code = PF_NON_FINITE;
     while (code == 0) {
         for (int inner = 0;; ++inner, ++it) {
             for (int k = t; k < nnz; k += nt) slab[k] = 0.f;
@@ -192,55 +176,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
             __syncthreads();
         }
         if (code) break;
-        // ---- the round's limits: a thread tests the PV buses it owns; all violators switch together and stay switched
-        int viol = 0;
-        if (ql) {
-            for (int i = t; i < n; i += nt) {
-                if (ty[i] != 1) continue;
-                const double lo = ql[2 * i], hi = ql[2 * i + 1], q = sq[i];
-                double fix;
-                if (fabs(hi) < __builtin_inf() && q > hi + a.q_tol) fix = hi;
-                else if (fabs(lo) < __builtin_inf() && q < lo - a.q_tol) fix = lo;
-                else continue;
-                ty[i] = 2;
-                qs[i] = fix;
-                viol = 1;
-            }
-        }
-        if (!__syncthreads_or(viol)) break;
+        // ---- the round's limits (powerflow_qlim.hpp): no violator, done
+        if (!pfq_switch(ty, qs, sq, ql, a.q_tol, n, nt)) break;
         if (rounds >= a.max_rounds) { code = PF_QLIM_ROUNDS; break; }
         ++rounds;
     }
 
-    // ---- the table, the final types and the sample's status / residual / rounds: slack P, Q and the Q of a bus still PV are the
-    // line sums of the last pass, a switched bus holds its solved Vm and its limit; a failed sample's rows are NaN and its types
-    // the ones it came with
-    const double nanv = __builtin_nan("");
-    for (int i = t; i < n; i += nt) {
-        double4 row = make_double4(nanv, nanv, nanv, nanv);
-        int y = ty_in[i];
-        if (code == 0) {
-            y = ty[i];
-            row.x = vm[i];
-            row.y = y == 0 ? spec[4 * i + 1] : th[i] * (1.0 / PF_RAD);
-            row.z = y == 0 ? sp[i] : spec[4 * i + 2];
-            row.w = y == 2 ? qs[i] : sq[i];
-        }
-        *reinterpret_cast<double4*>(sm.out + 4 * i) = row;
-        a.bus_type_out[(int64_t)s * n + i] = y;
-    }
-    if (t == 0) {
-        p.status[s] = code ? code : it;
-        p.residual[s] = res;
-        a.rounds[s] = rounds;
-    }
+    pfq_write_back(p, sm, s, nt, code, it, res, rounds, ty_in, ty, vm, th, sp, sq, qs, a.bus_type_out, a.rounds);
 }
 
 static int pfsq_check_header(const int32_t* h, const char* who) {
-    PFN_CHECK_ARG(h, "%s: null plan header", who);
-    PFN_CHECK_ARG(h[PFP_H_MAGIC] == PFP_MAGIC && h[PFP_H_VERSION] == PFP_VERSION, "%s: not a sparse power-flow plan (magic %08x, version %d)",
-                  who, (unsigned)h[PFP_H_MAGIC], (int)h[PFP_H_VERSION]);
-    PFN_CHECK_ARG(h[PFP_H_N] >= 1 && h[PFP_H_E] >= 0 && h[PFP_H_M] >= 0 && h[PFP_H_NNZ] >= h[PFP_H_M], "%s: the plan header is inconsistent", who);
+    PFN_TRY(pf_check_plan_header(who, h));
     PFN_CHECK_ARG(h[PFP_H_MODE] == 0 && h[PFP_H_M] == 2 * (h[PFP_H_N] - 1),
                   "%s: the plan has %d unknowns of %d buses in mode %d; Q-limits take the AC plan of the grid with every non-slack bus PQ, %d unknowns",
                   who, (int)h[PFP_H_M], (int)h[PFP_H_N], (int)h[PFP_H_MODE], 2 * ((int)h[PFP_H_N] - 1));
@@ -270,31 +216,19 @@ int pfn_powerflow_solve_sparse_qlim(const int64_t* edge_index, int64_t n_lines, 
     PFN_TRY(pfsq_check_header(h, who));
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines, "%s: the plan is for %d buses, %d lines; the call has %lld, %lld", who,
                   (int)h[PFP_H_N], (int)h[PFP_H_E], (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(threads == 0 || threads == 64 || threads == 256, "%s: threads must be 0 (the default), 64 or 256", who);
-    PFN_CHECK_ARG(max_rounds >= 0 && q_tol >= 0.0 && q_tol < __builtin_inf(), "%s: max_rounds must be >= 0 and q_tol finite and >= 0", who);
-    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(unplaced) & 3) == 0, "%s: unplaced must be 4-byte aligned", who);
     const int n = h[PFP_H_N], m = h[PFP_H_M], nnz = h[PFP_H_NNZ];
+    PFN_TRY(pf_check_sparse_launch(who, threads, unplaced, n_samples, h, m));
+    PFN_TRY(pfq_check_call(who, n_samples, bus_type, q_limits, limits_per_sample, q_tol, max_rounds, bus_type_out, rounds));
     const size_t stride = pfsq_sample_bytes(n, m, nnz), need = (size_t)n_samples * stride;
     const PfsqArgs a{{edge_index, rx, bus_type, spec, init, table, status, residual, flags, ws, tol, n, h[PFP_H_E], max_iter, line_mask, unplaced},
                      static_cast<const int32_t*>(plan_dev), q_limits, bus_type_out, rounds, stride, q_tol, m, nnz, pf_f_in_lds(m), max_rounds,
                      types_per_sample != 0, limits_per_sample != 0};
     PFN_TRY(pf_check_call(who, a.p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
     if (n_samples == 0) return PFN_OK;
-    PFN_CHECK_ARG(bus_type_out && rounds, "%s: null bus_type_out or rounds", who);
-    PFN_CHECK_ARG(((reinterpret_cast<uintptr_t>(bus_type_out) | reinterpret_cast<uintptr_t>(rounds)) & 3) == 0 &&
-                      (reinterpret_cast<uintptr_t>(q_limits) & 7) == 0,
-                  "%s: q_limits must be 8-byte aligned, bus_type_out and rounds 4-byte", who);
-    PFN_CHECK_ARG(q_limits || !limits_per_sample, "%s: limits_per_sample without q_limits", who);
-    PFN_CHECK_ARG(bus_type_out != bus_type, "%s: bus_type_out must not be bus_type (a failed sample reads its input row back)", who);
-    // (a plan with 32-bit row ids has more than 65535 unknowns: its work vector would not fit LDS either; the kernel reads 16-bit ids only)
-    PFN_CHECK_ARG(h[PFP_H_IDX16] != 0, "%s: %d unknowns: the kernel takes plans with 16-bit row ids (m <= 65535) only", who, m);
     const size_t lds = pfsq_lds_bytes(n, m);
     PFN_CHECK_ARG(lds <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns and %d type bytes need %zu bytes of LDS, %d are there",
                   who, m, n, lds, kLdsCuBytes - kLdsReserve);
-    if (!ws || ws_bytes < need) {
-        set_error("%s: the workspace must hold %zu bytes (got %zu)", who, need, ws ? ws_bytes : (size_t)0);
-        return PFN_ENOSPACE;
-    }
+    PFN_TRY(pf_check_workspace(who, ws, ws_bytes, need));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double madds = (double)(((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]);
     // (the figures of eight solves, a sample that switches in two rounds: an estimate, as the dense entry's)
