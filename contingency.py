@@ -4,9 +4,11 @@ of a dataset on disk -- its bus specification and its lines' r and x, read the w
 model with line outage distribution factors (`contingency_screen`: two launches for all scenarios and all outages), the worst
 outages of every scenario are solved again with the AC solver on the grid without the line (`verify_contingencies`), and the two
 are set side by side.  Ratings are `--rating-margin` times the largest base-case flow of a line over the scenarios; a line that
-never carries flow is unmonitored.  Without --data-dir the scenarios are `make_physical_inputs`' synthetic ones.
+never carries flow is unmonitored.  Without --data-dir the scenarios are `make_physical_inputs`' synthetic ones.  Beyond the dense cap
+of the screen (6470rte) the sparse route is taken by itself: one `sparse_plan(mode="dc")` for both screens, three launches each, and
+the AC verification on the sparse solver under one cover plan; `--route sparse` asks for it on any case.
 
-    python contingency.py --case 118 --data-dir data [--samples 1000] [--rating-margin 1.5] [--verify-top 5]
+    python contingency.py --case 118 --data-dir data [--samples 1000] [--rating-margin 1.5] [--verify-top 5] [--route sparse]
 
 Writes results/<case>_contingency_{severity,worst_line,overloads,islands,base_flow}.npy.
 """
@@ -40,7 +42,8 @@ def main(argv=None):
     ap.add_argument("--samples", type=int, default=None, help="only the first N scenarios of the test split (synthetic: 64)")
     ap.add_argument("--rating-margin", type=float, default=1.5, help="rating = margin x the line's largest base-case flow")
     ap.add_argument("--verify-top", type=int, default=5, help="AC-verify the worst N non-islanding outages of every scenario")
-    ap.add_argument("--route", default="auto", choices=("auto", "lds", "global"))
+    ap.add_argument("--route", default="auto", choices=("auto", "lds", "global", "sparse"),
+                    help="auto: the dense screen up to its cap, the sparse route beyond")
     ap.add_argument("--split", type=float, nargs=3, default=[.5, .2, .3], help="train / val / test fractions of the dataset")
     ap.add_argument("--out-dir", default="results")
     a = ap.parse_args(argv)
@@ -48,18 +51,24 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("contingency.py needs a HIP device: poweflownet_amd has no CPU solver")
     from poweflownet_amd.utils.contingency import contingency_screen, verify_contingencies
+    from poweflownet_amd.utils.powerflow import max_unknowns, sparse_plan
     bt, spec, ei, rx = scenarios(a.case, a.data_dir, a.samples, "cuda:0", tuple(a.split))
     S, e = int(spec.shape[0]), int(ei.shape[1])
-    base = contingency_screen(bt, spec, ei, rx, route=a.route)              # the base flows decide the ratings
+    kw, solver_kw = {"route": a.route}, {}
+    if a.route == "sparse" or (a.route == "auto" and int(bt.shape[0]) - 1 > max_unknowns()):
+        plan = sparse_plan(bt, ei, mode="dc")                              # once: both screens share it
+        print(f"sparse route: {plan.m} unknowns, nnz(L) {plan.nnz_l}, plan built in {plan.build_s:.2f} s")
+        kw, solver_kw = {"route": "sparse", "plan": plan}, {"route": "sparse"}
+    base = contingency_screen(bt, spec, ei, rx, **kw)                       # the base flows decide the ratings
     if int((base.status < 0).sum()):
         raise RuntimeError(f"contingency: {int((base.status < 0).sum())} base cases failed (statuses {sorted(set(base.status.tolist()))})")
     ratings = a.rating_margin * base.base_flow.abs().max(dim=0).values     # [e]; 0 where a line never carries flow: unmonitored
-    res = contingency_screen(bt, spec, ei, rx, ratings, route=a.route)
+    res = contingency_screen(bt, spec, ei, rx, ratings, **kw)
     islands = res.islands.cpu().numpy()
     print(f"Case {a.case}: {S} scenarios x {e} outages on the {res.route} route; {int((ratings > 0).sum())} of {e} lines monitored")
     print(f"{int((islands > 0).sum())} islanding outages, {int(islands[islands > 0].sum())} buses lost over them")
     top = min(a.verify_top, int((islands == 0).sum()))
-    ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top)
+    ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top, **solver_kw)
     pairs, dc, ac = ver.pairs.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy()
     dc_worst, ac_worst = res.worst_line[ver.pairs[:, 0], ver.pairs[:, 1]].cpu().numpy(), ver.worst_line.cpu().numpy()
     status = ver.status.cpu().numpy()

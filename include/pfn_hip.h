@@ -793,7 +793,7 @@ int pfn_topology_unsupplied(const int64_t* edge_index, int lines_per_sample, int
 
 /* ------------------------------------------------------------------------------ N-1 line-outage screening
  * Which single line outages overload the rest of the grid (csrc/contingency.hip)?  Two launches over ONE line list [2, n_lines] for
- * all scenarios; no host sync, no allocation (capturable), no float atomics.  Dense route only: n_bus - 1 <= pfn_powerflow_max_unknowns().
+ * all scenarios; no host sync, no allocation (capturable), no float atomics.  pfn_contingency_dc: n_bus - 1 <= pfn_powerflow_max_unknowns(); beyond it pfn_contingency_sparse, below.
  *
  * pfn_contingency_islands: islands[k] = the number of buses NOT reachable from `root` (the slack) when line k is removed -- one
  * workgroup per outage, pfn_topology_unsupplied's reach routine over the base list with line k skipped, nothing materialised.  > 0 is
@@ -837,6 +837,36 @@ int pfn_contingency_dc(const int64_t* edge_index, int64_t n_lines, const double*
                        int64_t n_pv, int64_t n_pq, double tol, int max_iter, int route, float* severity, int32_t* worst_line,
                        int32_t* overloads, double* base_flow, int32_t* status, float* post_flow, int32_t* flags, void* ws,
                        size_t ws_bytes, void* stream);
+
+/* The same screen beyond the dense cap (csrc/contingency_sparse.hip): B' is kept as a sparse fp32 FACTOR under the mode-1 plan of the
+ * sparse power-flow route (pfn_powerflow_sparse_plan(..., mode 1, ...): plan_header its first 32 words on the host, plan_dev the blob
+ * on the device) where pfn_contingency_dc keeps its inverse.  Model, definitions, outputs and statuses are pfn_contingency_dc's, and
+ * status -6 is added where the device line list is not the plan's.  Two launches behind pfn_contingency_islands, no host sync, no
+ * allocation (capturable), no float atomics:
+ *   base     one workgroup per scenario (64 threads, 256 where the plan's longest L column exceeds 128; `threads` 64 / 256 forces
+ *            either, 0 the default): the fp64 residual first, B' at the planned positions factored ONCE in fp32, theta refined to
+ *            tol / max_iter by column substitutions, the fp64 base flows; the factor stays in the scenario's workspace slab.
+ *   outages  a lane per outage, a one-wave workgroup per tile of 64 consecutive outages: the tile's 64 right-hand sides e_i - e_j sit
+ *            in one block [n_bus][64] fp32 (row = unknown in plan order, the last row the slack's zeros) and go through the forward
+ *            and backward column substitutions together -- column bounds, row ids and factor values are read once per wave, a lane
+ *            touches its own column only: no barrier, no shuffle, no atomic --, then den_k and one loop over the lines in ascending
+ *            order with pfn_contingency_dc's per-line expression.  Workgroup g of G takes the items (scenario, tile) g, g + G, ...;
+ *            groups = 0: G = min(n_samples * tiles, 16 * compute units), else G = min(n_samples * tiles, groups).  An item's bits do
+ *            not depend on G.
+ *   block_route  0 auto, 1 LDS, 2 global: the block sits in LDS where 256 n_bus bytes fit the 159 KiB a workgroup may take
+ *            (n_bus <= 636), else in a per-workgroup block of `ws`; same code, same bits.
+ * pfn_contingency_sparse_workspace_bytes(n_samples, n_lines, plan_header, block_route, groups): per scenario 8 (2 n_bus + m) +
+ * 4 nnz + 20 n_lines bytes rounded up to 16, plus G blocks of 256 n_bus bytes on the global placement; 0 for arguments the call
+ * would refuse.  A scenario's bits are a function of its own inputs and the plan, whatever the batch, `threads`, G or the placement.
+ * PFN_EINVAL: bad sizes or counts, a plan that is no mode-1 plan or is for another n_bus / n_lines, 32-bit row ids, block_route 1
+ * where the block does not fit, bad threads / groups, null or misaligned pointers; PFN_ENOSPACE: too little ws.                     */
+size_t pfn_contingency_sparse_workspace_bytes(int64_t n_samples, int64_t n_lines, const void* plan_header, int block_route, int groups);
+int pfn_contingency_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                           const double* ratings, int ratings_per_sample, const int32_t* islands, int64_t n_samples, int64_t n_bus,
+                           int64_t n_pv, int64_t n_pq, double tol, int max_iter, float* severity, int32_t* worst_line,
+                           int32_t* overloads, double* base_flow, int32_t* status, float* post_flow, int32_t* flags, void* ws,
+                           size_t ws_bytes, const void* plan_header, const void* plan_dev, int threads, int block_route, int groups,
+                           void* stream);
 
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select

@@ -21,6 +21,7 @@
 // integer sum, one owner per output: a scenario's bits are a pure function of its own inputs, whatever the batch, the workgroup
 // size or the route.  LDS route: X sits behind the scenario's vectors in LDS; global route: in a per-scenario slab of the caller's
 // workspace, same code.  No host sync, no allocation (capturable), no float atomics.
+#include "contingency_line.hpp"
 #include "powerflow_dense.hpp"
 #include "topology_reach.hpp"
 
@@ -85,20 +86,7 @@ static inline int ct_threads(int m) { return m > PF_BIG_M ? PF_BIG_THREADS : PF_
 static inline size_t ct_lds_bytes(int n, int e) { return ct_vec_bytes(n, e, ct_threads(n - 1) >> 6) + pf_mat_floats(n - 1) * 4; }
 static inline bool ct_fits_lds(int n, int e) { return ct_lds_bytes(n, e) <= (size_t)(kLdsCuBytes - kLdsReserve); }
 
-// den_k and the post-outage flow of line l, every operation rounded on its own: what hipcc fuses must not depend on the
-// instantiation or on whether the table row is written
-__device__ __forceinline__ float ct_den(float wi, float wj, float x) {
-#pragma clang fp contract(off)
-    const float phi = (wi - wj) / x;
-    return 1.f - phi;
-}
-__device__ __forceinline__ float ct_post(float wa, float wb, float x, float den, float fl, float fk) {
-#pragma clang fp contract(off)
-    const float phi = (wa - wb) / x;
-    const float q = phi / den;
-    const float d = q * fk;
-    return fl + d;
-}
+// (den_k and the post-outage flow of line l, ct_den and ct_post: contingency_line.hpp, shared with the sparse route)
 
 template <bool LDS>
 __global__ __launch_bounds__(PF_BIG_THREADS) void contingency_dc_kernel(const CtArgs a) {

@@ -3,15 +3,19 @@ remaining lines are loaded -- two launches (csrc/contingency.hip): `pfn_continge
 outages that cut buses off the slack; `pfn_contingency_dc`, one workgroup per scenario, solves the DC model of
 `solve_power_flow(mode="dc")` once, keeps B'^-1 resident and reads every outage's flows off line outage distribution factors.
 `verify_contingencies` re-solves chosen (scenario, outage) pairs with the unchanged AC solver on the reduced line lists and reports
-the AC current loadings beside the DC screen's.  Dense grids only (n - 1 <= `max_unknowns()`).  No CPU path."""
+the AC current loadings beside the DC screen's.  Beyond the dense cap (n - 1 > `max_unknowns()`) `route="sparse"` keeps the sparse
+fp32 FACTOR of B' under a `sparse_plan(..., mode="dc")` and substitutes 64 outages at a time (csrc/contingency_sparse.hip:
+`pfn_contingency_sparse`, two launches behind the islands).  No CPU path."""
+import ctypes as C
 from dataclasses import dataclass
 
 import torch
 
 from .. import _lib as L
-from .powerflow import STATUS, solve_power_flow  # noqa: F401  (STATUS: the texts of `ContingencyResult.status`)
+from .powerflow import STATUS, SparsePlan, cover_plan, solve_power_flow  # noqa: F401  (STATUS: the texts of `ContingencyResult.status`)
 
 _ROUTES = {"auto": 0, "lds": 1, "global": 2}
+_BLOCKS = {"auto": 0, "lds": 1, "global": 2}
 _COUNTS_ATTR = "_pfn_bus_counts"  # on a bus_type tensor: (version, (n_pv, n_pq, slack)) -- one host read per tensor
 
 
@@ -23,7 +27,8 @@ class ContingencyResult:
     failed).  `islands` [e] int32: buses cut off the slack by outage k (the line list decides, not the scenario; -4: a line names a
     bus outside the grid).  Per scenario: `base_flow` [S, e] float64 and `status` [S] int32 (>= 0: refinement solves; < 0:
     `utils.powerflow.STATUS`).  `post_flow` [S, e, e] float32 (row = outage, column = line) with `keep_table`, else None.  `flags`
-    [1] int32 (bit 0: `bus_type` changed under the launch).  All on the device, nothing read back; `route`: "lds" or "global"."""
+    [1] int32 (bit 0: `bus_type` changed under the launch).  All on the device, nothing read back; `route`: "lds", "global" or
+    "sparse" (there `block` says where the outage blocks sat: "lds" or "global")."""
     severity: torch.Tensor
     worst_line: torch.Tensor
     overloads: torch.Tensor
@@ -33,6 +38,7 @@ class ContingencyResult:
     post_flow: object
     route: str
     flags: object = None
+    block: object = None
 
     def ranking(self, top):
         """(int64 [S, top] outage ids, [S, top] their severities): per scenario the `top` outages by severity, descending -- NaN
@@ -110,16 +116,30 @@ def _check(bus_type, spec, edge_index, rx, who):
     return S, n, e
 
 
-def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8, max_iter=10, route="auto", keep_table=False) -> ContingencyResult:
+def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8, max_iter=10, route="auto", keep_table=False, plan=None,
+                       block="auto", groups=None, threads=None) -> ContingencyResult:
     """Screen every single line outage of every scenario under the DC model: `bus_type` [n] (exactly one slack), `spec` [S, n, 4] and
     `rx` [S, e, 2] float64 as `solve_power_flow` takes them, ONE line list `edge_index` int64 [2, e].  `ratings`: float64 per-unit
     current, [e] or [S, e]; None: 1.0 everywhere; a rating that is not > 0 (zero, negative, NaN) leaves its line unmonitored.
     `route`: "auto", "lds" (raises where B'^-1 does not fit LDS) or "global" (forces the workspace slab).  `keep_table`: also return
     the full post-outage flow table [S, e, e].  Two launches; one host read (the bus_type counts, once per tensor); nothing is read
-    back."""
+    back.
+
+    `route="sparse"` with `plan=sparse_plan(bus_type, edge_index, mode="dc")`: the same screen beyond `max_unknowns()` -- the same
+    fields, definitions and statuses, plus status -6 where the device line list is not the plan's.  Three launches (islands, base,
+    outages).  "auto" never takes it; without a plan, with a plan of another mode or of another n / e it raises ValueError.  There
+    `block`: where a tile's 64 right-hand sides sit -- "auto" (LDS where 256 n bytes fit, about 600 buses), "lds" (raises where they
+    do not) or "global" (a block of the workspace per workgroup); the same bits.  `groups`: the number of one-wave workgroups the
+    (scenario, tile) items are dealt to, None: min(S * tiles, 16 * compute units), each with a block of 256 n bytes
+    on the global placement; no bit depends on it.  `threads`: the base solve's
+    workgroup, None (64, or 256 where the plan's longest L column exceeds 128), 64 or 256."""
     who = "contingency_screen"
+    if route == "sparse":
+        return _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_table, plan, block, groups, threads)
     if route not in _ROUTES:
-        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES) + ['sparse']}")
+    if plan is not None or block != "auto" or groups is not None or threads is not None:
+        raise ValueError(f"{who}: plan, block, groups and threads go with route='sparse' only")
     S, n, e = _check(bus_type, spec, edge_index, rx, who)
     ratings = _ratings(ratings, S, e, who)
     n_pv, n_pq, slack = _bus_counts(bus_type)
@@ -149,6 +169,55 @@ def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8
                              post_flow=table, route="global" if need else "lds", flags=flags)
 
 
+def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_table, plan, block, groups, threads) -> ContingencyResult:
+    """`contingency_screen(route="sparse")`: islands, base, outages -- three launches, the one host read of `_bus_counts`."""
+    who = "contingency_screen"
+    if block not in _BLOCKS:
+        raise ValueError(f"{who}: block must be one of {sorted(_BLOCKS)}")
+    if groups is not None and (isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups < 2 ** 31):
+        raise ValueError(f"{who}: groups must be None or a positive int; got {groups!r}")
+    if threads not in (None, 64, 256):
+        raise ValueError(f"{who}: threads must be None, 64 or 256; got {threads!r}")
+    if not isinstance(plan, SparsePlan):
+        raise ValueError(f"{who}: route 'sparse' needs plan=sparse_plan(bus_type, edge_index, mode='dc'); got {plan!r}")
+    if plan.mode != "dc":
+        raise ValueError(f"{who}: route 'sparse' takes a plan of mode 'dc'; this one has mode {plan.mode!r}")
+    if torch.is_tensor(spec) and spec.dim() == 3 and torch.is_tensor(edge_index) and edge_index.dim() == 2:
+        if (plan.n, plan.e) != (int(spec.shape[1]), int(edge_index.shape[1])):
+            raise ValueError(f"{who}: the plan is for (n, e) = {(plan.n, plan.e)}; the call has {(int(spec.shape[1]), int(edge_index.shape[1]))}")
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    ratings = _ratings(ratings, S, e, who)
+    dev = spec.device
+    if plan.blob.device != dev:
+        raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
+    n_pv, n_pq, slack = _bus_counts(bus_type)
+    bt = bus_type.to(torch.int32).contiguous()
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    lib = L.load()
+    islands = torch.empty(e, dtype=torch.int32, device=dev)
+    severity = torch.empty(S, e, dtype=torch.float32, device=dev)
+    worst = torch.empty(S, e, dtype=torch.int32, device=dev)
+    overloads = torch.empty(S, e, dtype=torch.int32, device=dev)
+    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = torch.empty(S, e, e, dtype=torch.float32, device=dev) if keep_table else None
+    header, g = C.addressof(plan.header), 0 if groups is None else groups
+    with torch.cuda.device(dev):
+        need = int(lib.pfn_contingency_sparse_workspace_bytes(S, e, header, _BLOCKS[block], g)) if S else 0
+        in_lds = block != "global" and (not S or need == int(lib.pfn_contingency_sparse_workspace_bytes(S, e, header, 1, g)))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+        L.check(lib.pfn_contingency_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
+                                           int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
+                                           int(max_iter), severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(),
+                                           status.data_ptr(), L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, header, plan.blob.data_ptr(),
+                                           0 if threads is None else threads, _BLOCKS[block], g, L.stream_ptr()),
+                "pfn_contingency_sparse")
+    return ContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, base_flow=base_flow, status=status,
+                             post_flow=table, route="sparse", flags=flags, block="lds" if in_lds else "global")
+
+
 def summarise_loadings(loading, monitored):
     """(severity float32 [T], worst_line int32 [T], overloads int32 [T]) of loadings [T, e] over the `monitored` lines by the
     screen's rules: the maximum with ties to the lowest line, a non-finite loading counts as the largest and makes the severity NaN,
@@ -168,7 +237,9 @@ def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *
     """AC check of chosen outages of a `contingency_screen` result (same inputs): for every pair (scenario s, outage k) -- `pairs`
     [T, 2], or per scenario the `top` outages of `result.ranking` -- that does not island a bus, the line list without line k and its
     rx are built on the device, `solve_power_flow(mode="ac", **solver_kw)` solves them, `loss.branch_flows` gives the line currents,
-    and the loadings I_l / rating_l go back to the original line numbering.  The pairs are chosen on the host (T is small)."""
+    and the loadings I_l / rating_l go back to the original line numbering.  The pairs are chosen on the host (T is small).
+    `route="sparse"` without `plan=`: ONE `cover_plan` whose cover is the base list is built here (every reduced list is a subset of
+    it); a `plan=` that is given is reused."""
     from ..loss import branch_flows
     who = "verify_contingencies"
     S, n, e = _check(bus_type, spec, edge_index, rx, who)
@@ -193,6 +264,9 @@ def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *
     idx = ar[None, :] + (ar[None, :] >= out[:, None])                          # [T, e - 1]: the lines that stay, in stored order
     lists = edge_index[:, idx].permute(1, 0, 2).contiguous()                   # [T, 2, e - 1]
     rx_post = rx[sc[:, None], idx].contiguous()                                # [T, e - 1, 2]
+    if solver_kw.get("route") == "sparse" and solver_kw.get("plan") is None and T:
+        # every reduced list is a subset of the base list: ONE cover plan whose cover IS the base list serves all pairs
+        solver_kw = {**solver_kw, "plan": cover_plan(bus_type, edge_index[None], mode="ac", base=edge_index)}
     solved = solve_power_flow(bus_type, spec[sc].contiguous(), lists, rx_post, mode="ac", **solver_kw)
     rate = torch.ones(S, e, dtype=torch.float32, device=dev) if ratings is None else ratings.float().expand(S, e)
     rate = rate[sc]                                                            # [T, e]

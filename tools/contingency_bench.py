@@ -9,7 +9,18 @@ scenario count small enough to hold.  Not part of bench.py; no threshold.
 Protocol: every case is measured in `--processes` FRESH child processes; in each, after one warm-up of both paths, the two are timed
 alternately `--repeats` times (host wall clock around the call, a device synchronise at either end) and the child reports its
 medians; the parent reports the median over the children and their spread (min .. max).  `keep_table` is off: the screen writes
-three numbers per (scenario, outage), the brute force a bus table per solve.  tol 1e-8, max_iter 10.  One JSON line."""
+three numbers per (scenario, outage), the brute force a bus table per solve.  tol 1e-8, max_iter 10.  One JSON line.
+
+    python tools/contingency_bench.py --route sparse [--shape 118x186 --shape 600x835 --shape 6470x9005] [--samples 64]
+                                      [--groups-sweep 1 4 16] [--brute-pairs 64]
+
+The sparse route (`contingency_screen(route="sparse")`), same protocol.  Per shape (buses x lines, synthetic scenarios) a
+row per block placement that the shape allows and per `groups` = the given multiples of the compute units (the default placement
+only): the plan's build time, the wall time of the three launches, the base and the outage launch apart (the library's event
+brackets, a pass of their own), pairs per second.  Beside it, alternating in the same child: the dense screen where the shape is
+within its cap, else the brute force the parent commit has there -- `solve_power_flow(mode="dc", route="sparse", plan=<cover plan of
+the base list>)` over explicit per-outage lists of `--brute-pairs` non-islanding outages spread evenly over the list, scaled per
+pair."""
 import argparse
 import json
 import os
@@ -61,6 +72,90 @@ def child(case, samples, brute_solves, repeats):
                       "ratio": brute_us / screen_us}))
 
 
+def child_sparse(shape, samples, block, groups_x, brute_pairs, repeats):
+    import torch
+    from poweflownet_amd import _lib as L
+    from poweflownet_amd.synth import make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen
+    from poweflownet_amd.utils.powerflow import cover_plan, max_unknowns, solve_power_flow, sparse_plan
+    dev = torch.device("cuda:0")
+    n, e = (int(v) for v in shape.split("x"))
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    plan = sparse_plan(bt, ei, mode="dc")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    kw = {"route": "sparse", "plan": plan, "block": block, "groups": groups_x * cus if groups_x else None}
+    res = contingency_screen(bt, spec, ei, rx, **kw)                       # (warm-up)
+    assert bool((res.status >= 0).all())
+    dense = n - 1 <= max_unknowns()
+    if dense:
+        def other():
+            return contingency_screen(bt, spec, ei, rx)
+        other_pairs = samples * e
+    else:
+        ok = torch.nonzero(res.islands == 0).flatten()
+        outages = ok[torch.linspace(0, ok.numel() - 1, min(brute_pairs, ok.numel())).long()]
+        T = int(outages.numel())
+        ar = torch.arange(e - 1, device=dev)
+        idx = ar[None, :] + (ar[None, :] >= outages[:, None])              # [T, e - 1]
+        lists = ei[:, idx].permute(1, 0, 2).contiguous()
+        sc = torch.arange(T, device=dev) % samples
+        rx_b, spec_b = rx[sc[:, None], idx].contiguous(), spec[sc].contiguous()
+        cover = cover_plan(bt, ei[None], mode="dc", base=ei)
+
+        def other():
+            return solve_power_flow(bt, spec_b, lists, rx_b, mode="dc", route="sparse", plan=cover)
+        other_pairs = T
+    assert bool((other().status >= 0).all())                               # (warm-up)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    t_screen, t_other = [], []
+    for _ in range(repeats):
+        t_screen.append(timed(lambda: contingency_screen(bt, spec, ei, rx, **kw)))
+        t_other.append(timed(other))
+    L.profile_enable(True)                                                  # the two launches apart: event brackets, a pass of their own
+    for _ in range(repeats):
+        contingency_screen(bt, spec, ei, rx, **kw)
+    prof = L.profile_report()
+    L.profile_enable(False)
+    screen_s, other_s = statistics.median(t_screen), statistics.median(t_other)
+    print(json.dumps({"buses": n, "lines": e, "scenarios": samples, "block": res.block, "groups_x_cus": groups_x, "cus": cus, "unknowns": plan.m,
+                      "nnz_l": plan.nnz_l, "plan_build_s": plan.build_s, "screen_ms": 1e3 * screen_s,
+                      "base_ms": prof["contingency_sparse_base"]["ms"] / repeats, "outages_ms": prof["contingency_sparse_outages"]["ms"] / repeats,
+                      "pairs_per_s": samples * e / screen_s, "screen_us_per_pair": 1e6 * screen_s / (samples * e),
+                      "other": "dense screen" if dense else "brute force", "other_pairs": other_pairs, "other_ms": 1e3 * other_s,
+                      "other_us_per_pair": 1e6 * other_s / other_pairs, "ratio": (other_s / other_pairs) / (screen_s / (samples * e))}))
+
+
+def main_sparse(a):
+    out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "rows": []}
+    for shape in a.shape or ["118x186", "600x835", "6470x9005"]:
+        n = int(shape.split("x")[0])
+        configs = [(b, 0) for b in (("lds", "global") if 256 * n <= 159 * 1024 else ("global",))] + [("auto", g) for g in a.groups_sweep]
+        for block, gx in configs:
+            rows = []
+            for _ in range(a.processes):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-sparse", shape, "--samples", str(a.samples), "--block", block,
+                                    "--groups-x", str(gx), "--brute-pairs", str(a.brute_pairs), "--repeats", str(a.repeats)],
+                                   capture_output=True, text=True, timeout=900)
+                if r.returncode != 0:
+                    raise SystemExit(f"contingency_bench: the child for {shape} {block} x{gx} failed:\n{r.stdout}\n{r.stderr}")
+                rows.append(json.loads(r.stdout.strip().splitlines()[-1]))
+            row = dict(rows[0])
+            for key in ("screen_ms", "base_ms", "outages_ms", "pairs_per_s", "screen_us_per_pair", "other_ms", "other_us_per_pair", "ratio", "plan_build_s"):
+                vals = [x[key] for x in rows]
+                row[key] = round(statistics.median(vals), 4)
+                row[key + "_spread"] = [round(min(vals), 4), round(max(vals), 4)]
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--case", action="append", default=None)
@@ -69,7 +164,19 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--processes", type=int, default=3)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--route", default="dense", choices=("dense", "sparse"), help="sparse: contingency_screen(route='sparse'), DESIGN 7v")
+    ap.add_argument("--shape", action="append", default=None, help="sparse: BUSESxLINES (repeatable)")
+    ap.add_argument("--groups-sweep", type=int, nargs="*", default=[1, 4, 16], help="sparse: groups as multiples of the compute units")
+    ap.add_argument("--brute-pairs", type=int, default=64, help="sparse, beyond the dense cap: the brute force solves this many outages")
+    ap.add_argument("--child-sparse", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--block", default="auto", help=argparse.SUPPRESS)
+    ap.add_argument("--groups-x", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_sparse:
+        child_sparse(a.child_sparse, a.samples, a.block, a.groups_x, a.brute_pairs, a.repeats)
+        return 0
+    if a.route == "sparse":
+        return main_sparse(a)
     if a.child:
         child(a.child, a.samples, a.brute_solves, a.repeats)
         return 0
