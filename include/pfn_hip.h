@@ -838,6 +838,44 @@ int pfn_contingency_dc(const int64_t* edge_index, int64_t n_lines, const double*
                        int32_t* overloads, double* base_flow, int32_t* status, float* post_flow, int32_t* flags, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* N-2: which PAIRS of line outages overload the rest of the grid (csrc/contingency_pairs.hip)?  The dense DC route only
+ * (n_bus - 1 <= pfn_powerflow_max_unknowns()).  `lines`: DEVICE int32 [n_candidates], strictly increasing ids in [0, n_lines); pair
+ * p = (lines[i], lines[j]), i < j, row-major in (i, j), P = n_candidates (n_candidates - 1) / 2; all n_lines lines stay monitored.
+ * Three launches, no host sync, no allocation (capturable), no float atomics.
+ *
+ * pfn_contingency_pair_islands: islands[p] = the number of buses NOT reachable from `root` with BOTH lines of pair p removed -- one
+ * workgroup per first candidate loops over the second, pfn_contingency_islands' reach routine with two keep flags cleared, nothing
+ * materialised.  > 0 also where neither line is a bridge; decided combinatorially, never from a small determinant.  -4 for EVERY p
+ * where a line names a bus outside [0, n_bus), and for a pair with a candidate outside [0, n_lines).  Fewer than 2 candidates: nothing
+ * is launched.  PFN_EINVAL: root outside [0, n_bus), more candidates than lines, a shape beyond the LDS budget.
+ *
+ * pfn_contingency_pairs: the model, X, w_k and phi_{l,k} are pfn_contingency_dc's.  The outage of lines a and b:
+ *     M = [[1 - phi_aa, -phi_ab], [-phi_ba, 1 - phi_bb]]      t = M^-1 (f_a, f_b)   (Cramer's rule)
+ *     f_l^(a,b) = f_l + phi_la t_a + phi_lb t_b  (l != a, b),   f_a^(a,b) = f_b^(a,b) = 0     -- fp32, every operation rounded on its own.
+ *   base   one workgroup per scenario: pfn_contingency_dc's base solve (the same code: base_flow and status carry its bits for the same
+ *          inputs).  It leaves in the scenario's slab of `ws` X TRANSPOSED (the walk that forms w_k reads consecutive words; the element
+ *          read is X[r][c] as in pfn_contingency_dc -- the fp32 inverse is not bitwise symmetric) and the staged per-line vectors.
+ *   pairs  one workgroup per (scenario, first candidate): w_a once, its waves take the second candidates.
+ *   severity, worst_line, overloads  [n_samples, P], pfn_contingency_dc's definitions with BOTH outaged lines unmonitored; where
+ *          islands[p] != 0: +inf, -1, -1 and a NaN table row; a failed scenario: NaN, -1, -1.
+ *   post_flow  fp32 [n_samples, P, n_lines] or null.
+ *   route  0 auto, 1 LDS, 2 global: the pair launch copies X from the slab into LDS where it fits beside its vectors (16 n_lines +
+ *          8 n_bus + 4 n_bus per wave bytes) in the 159 KiB a workgroup may take, else reads the slab; same code, same bits.
+ * pfn_contingency_pairs_workspace_bytes(n_samples, n_bus, n_lines, n_candidates, route): what the call needs -- per scenario
+ * 4 m (m | 1) rounded up to 16 (m = n_bus - 1) + 16 n_lines + 4 n_bus bytes, rounded up to 16 -- on EITHER route; 0 for arguments the
+ * call would refuse, route 1 where X does not fit LDS among them (which is how a caller finds the threshold).
+ * The bits of (scenario, a, b) are a function of the scenario's inputs and the two lines, whatever the batch, the candidate list, the
+ * workgroup size or the route.  PFN_EINVAL: bad sizes or counts, more unknowns than the dense cap, vectors beyond LDS, route 1 where it
+ * does not fit, null or misaligned pointers; PFN_ENOSPACE: too little ws.                                                          */
+int pfn_contingency_pair_islands(const int64_t* edge_index, int64_t n_lines, int64_t n_bus, int64_t root, const int32_t* lines,
+                                 int64_t n_candidates, int32_t* islands, void* stream);
+size_t pfn_contingency_pairs_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_candidates, int route);
+int pfn_contingency_pairs(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                          const double* ratings, int ratings_per_sample, const int32_t* lines, int64_t n_candidates,
+                          const int32_t* islands, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, double tol, int max_iter,
+                          int route, float* severity, int32_t* worst_line, int32_t* overloads, double* base_flow, int32_t* status,
+                          float* post_flow, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* The same screen beyond the dense cap (csrc/contingency_sparse.hip): B' is kept as a sparse fp32 FACTOR under the mode-1 plan of the
  * sparse power-flow route (pfn_powerflow_sparse_plan(..., mode 1, ...): plan_header its first 32 words on the host, plan_dev the blob
  * on the device) where pfn_contingency_dc keeps its inverse.  Model, definitions, outputs and statuses are pfn_contingency_dc's, and

@@ -9,10 +9,11 @@
 //     w_k = X[:, i] - X[:, j]      phi_{l,k} = (w_k[a] - w_k[b]) / x_l  for line l = (a -> b)      den_k = 1 - phi_{k,k}
 //     f_l^(k) = f_l + phi_{l,k} / den_k * f_k   (l != k),   f_k^(k) = 0
 // -- one inverse per scenario and e^2 multiply-adds where the brute-force path factorises e matrices.
-//   PHASE A, the whole workgroup, once: the lines are staged in LDS, B' is built in fp32 (row-major, ld = m | 1, m = n - 1) by the
-//   row owners in stored order exactly as the fast-decoupled modes build theirs and inverted in place by THEIR Gauss-Jordan
-//   (powerflow_dense.hpp); theta is refined, theta -= X F, under the fp64 residual F = B' theta + P of mode 1 to tol / max_iter
-//   (status = the refinement solves used); the base flows f_l = (theta_a - theta_b) / x_l are fp64.
+//   PHASE A, the whole workgroup, once (contingency_base.hpp ct_base_solve, shared with the N-2 screen's base launch): the lines are
+//   staged in LDS, B' is built in fp32 (row-major, ld = m | 1, m = n - 1) by the row owners in stored order exactly as the
+//   fast-decoupled modes build theirs and inverted in place by THEIR Gauss-Jordan (powerflow_dense.hpp); theta is refined,
+//   theta -= X F, under the fp64 residual F = B' theta + P of mode 1 to tol / max_iter (status = the refinement solves used); the base
+//   flows f_l = (theta_a - theta_b) / x_l are fp64.
 //   PHASE B, no workgroup barrier: wave w takes the outages w, w + nw, ...  Its lanes form w_k into the wave's own fp32 vector [n]
 //   (two column walks of X: stride ld, odd, so conflict-free), then stride over the lines: phi, post-outage flow, loading
 //   |f| / rating.  The wave reduces by max (ties to the lowest line) and by an integer sum; lane 0 writes severity, worst line and
@@ -21,8 +22,8 @@
 // integer sum, one owner per output: a scenario's bits are a pure function of its own inputs, whatever the batch, the workgroup
 // size or the route.  LDS route: X sits behind the scenario's vectors in LDS; global route: in a per-scenario slab of the caller's
 // workspace, same code.  No host sync, no allocation (capturable), no float atomics.
+#include "contingency_base.hpp"
 #include "contingency_line.hpp"
-#include "powerflow_dense.hpp"
 #include "topology_reach.hpp"
 
 namespace pfn {
@@ -77,158 +78,33 @@ struct CtArgs {
     int n, e, max_iter, n_pv, n_pq, ratings_per_sample;
 };
 
-// the scenario's vectors: double th [n], F [m], flow [e], bl [e]; float x32 [e], rat [e], wk [nw][n]; int aidx [n];
-// uint16 la [e], lb [e] (n <= PF_MAX_UNKNOWNS + 1); rounded to 16 bytes
-__host__ __device__ inline size_t ct_vec_bytes(int n, int e, int nw) {
-    return ((size_t)8 * ((size_t)n + (n - 1) + 2 * (size_t)e) + (size_t)4 * (2 * (size_t)e + (size_t)nw * n + n) + (size_t)4 * e + 15) & ~(size_t)15;
-}
-static inline int ct_threads(int m) { return m > PF_BIG_M ? PF_BIG_THREADS : PF_SMALL_THREADS; }
-static inline size_t ct_lds_bytes(int n, int e) { return ct_vec_bytes(n, e, ct_threads(n - 1) >> 6) + pf_mat_floats(n - 1) * 4; }
-static inline bool ct_fits_lds(int n, int e) { return ct_lds_bytes(n, e) <= (size_t)(kLdsCuBytes - kLdsReserve); }
+// (the scenario's vectors, ct_vec_bytes / ct_vecs, the workgroup-size and LDS-fit rules and PHASE A itself: contingency_base.hpp)
 
 // (den_k and the post-outage flow of line l, ct_den and ct_post: contingency_line.hpp, shared with the sparse route)
 
 template <bool LDS>
 __global__ __launch_bounds__(PF_BIG_THREADS) void contingency_dc_kernel(const CtArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ct_smem[];
-    __shared__ double s_red[16];
-    __shared__ int s_ok, s_slack;
     const int t = threadIdx.x, nt = blockDim.x, lane = t & 63, wave = t >> 6, nw = nt >> 6;
     const int s = blockIdx.x;
     const int n = a.n, e = a.e, m = n - 1, ld = pf_ld(m);
-    double* th = reinterpret_cast<double*>(ct_smem);
-    double* F = th + n;
-    double* flow = F + m;
-    double* bl = flow + e;                          // -1 / x_l, the DC end's b
-    float* x32 = reinterpret_cast<float*>(bl + e);
-    float* rat = x32 + e;
-    float* wk = rat + e;
-    int* aidx = reinterpret_cast<int*>(wk + (size_t)nw * n);
-    uint16_t* la = reinterpret_cast<uint16_t*>(aidx + n);
-    uint16_t* lb = la + e;
+    const CtVecs v = ct_vecs(ct_smem, n, e, nw);
+    const double* flow = v.flow;
+    const float* x32 = v.x32;
+    const float* rat = v.rat;
+    float* wk = v.wk;
+    const int* aidx = v.aidx;
+    const uint16_t* la = v.la;
+    const uint16_t* lb = v.lb;
     float* X;
     if constexpr (LDS) X = reinterpret_cast<float*>(ct_smem + ct_vec_bytes(n, e, nw));
     else X = static_cast<float*>(a.ws) + (size_t)s * pf_mat_floats(m);
-    const int64_t* ei = a.edge_index;
-    const double* rx = a.rx + (int64_t)s * 2 * e;
-    const double* spec = a.spec + (int64_t)s * 4 * n;
-    const double* rat_in = a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * e : 0) : nullptr;
-    int code = 0;                                   // (uniform over the workgroup wherever it is tested)
-
-    // ---- the lines name buses of the grid?  (an id outside [0, n) is never followed)
-    int bad = 0;
-    for (int k = t; k < e; k += nt) bad |= (uint64_t)ei[k] >= (uint64_t)n || (uint64_t)ei[e + k] >= (uint64_t)n;
-    // ---- unknown numbering; the host's n_pv / n_pq against the device bus types, as the solver does
-    if (t == 0) {
-        int na = 0, ns = 0, npv = 0, npq = 0, odd = 0, slack = 0;
-        for (int i = 0; i < n; ++i) {
-            const int ty = a.bus_type[i];
-            int ia = -1;
-            if (ty == 0) { ++ns; slack = i; }
-            else if (ty == 1) { ++npv; ia = na++; }
-            else if (ty == 2) { ++npq; ia = na++; }
-            else odd = 1;
-            aidx[i] = ia;
-        }
-        s_slack = slack;
-        s_ok = !odd && ns == 1 && npv == a.n_pv && npq == a.n_pq;
-    }
-    bad = __syncthreads_or(bad);
-    if (!s_ok) {
-        code = PF_BAD_TYPES;
-        if (t == 0) a.flags[0] = a.flags[0] | 1;    // (every writer stores the same bit over the same word)
-    } else if (bad) {
-        code = PF_BAD_LINE;
-    }
 
     // ================================================================================================ PHASE A
-    int it = 0;
-    if (code == 0) {
-        const double th0 = spec[4 * s_slack + 1] * PF_RAD;
-        for (int k = t; k < e; k += nt) {
-            const double x = rx[2 * k + 1];
-            la[k] = (uint16_t)ei[k];
-            lb[k] = (uint16_t)ei[e + k];
-            bl[k] = -1.0 / x;
-            x32[k] = (float)x;
-            rat[k] = rat_in ? (float)rat_in[k] : 1.f;
-        }
-        for (int i = t; i < n; i += nt) th[i] = th0;
-        __syncthreads();
-        for (;; ++it) {
-            // ---- F = B' theta + P at the non-slack buses: bus i's lines in stored order, the stored direction, then the reverse
-            for (int i = t; i < n; i += nt) {
-                const int ra = aidx[i];
-                if (ra < 0) continue;
-                const double ti = th[i];
-                double sP = 0.0;
-                for (int k = 0; k < e; ++k) {
-                    const int ka = la[k], kb = lb[k];
-                    if (ka != i && kb != i) continue;
-                    const double b = bl[k];
-                    if (ka == i) sP += b * (ti - th[kb]);
-                    if (kb == i) sP += b * (ti - th[ka]);
-                }
-                F[ra] = spec[4 * i + 2] - sP;
-            }
-            __syncthreads();
-            double mx = 0.0;
-            for (int k = t; k < m; k += nt) mx = fmax(mx, pf_abs_clamped(F[k]));
-            const double res = pf_block_max(mx, s_red, nw);
-            const int stop = pf_stop(res, a.tol, it, a.max_iter);
-            if (stop < 0) { code = stop; break; }
-            if (it == 0) {
-                // ---- B', once: the Laplacian of 1 / x over the stored lines (parallel lines add, a self-loop cancels), bus i's row
-                //      by bus i in stored order, the diagonal summed in fp64 and added last; then inverted in place.  A scenario
-                //      that starts converged still needs X: the outages do.
-                for (int k = t; k < (int)pf_mat_floats(m); k += nt) X[k] = 0.f;
-                __syncthreads();
-                for (int i = t; i < n; i += nt) {
-                    const int ra = aidx[i];
-                    if (ra < 0) continue;
-                    double dp = 0.0;
-                    for (int k = 0; k < e; ++k) {
-                        const int ka = la[k], kb = lb[k];
-                        if (ka != i && kb != i) continue;
-                        const double w = -bl[k];
-#pragma unroll 1
-                        for (int side = 0; side < 2; ++side) {
-                            if ((side ? kb : ka) != i) continue;
-                            const int ca = aidx[side ? ka : kb];
-                            dp += w;
-                            if (ca >= 0) X[ra * ld + ca] += (float)(-w);
-                        }
-                    }
-                    X[ra * ld + ra] += (float)dp;
-                }
-                __syncthreads();
-                if (!pf_invert_in_place(X, m, ld)) { code = PF_SINGULAR; break; }
-            }
-            if (stop) break;
-            // ---- theta -= X F: a row by its owner, fp64 sum in column order
-            for (int i = t; i < n; i += nt) {
-                const int r = aidx[i];
-                if (r < 0) continue;
-                const float* row = X + r * ld;
-                double acc = 0.0;
-                for (int c = 0; c < m; ++c) acc += (double)row[c] * F[c];
-                th[i] -= acc;
-            }
-            __syncthreads();
-        }
-    }
-    // ---- the base flows (fp64) and the scenario's status
-    double* bf = a.base_flow + (int64_t)s * e;
-    for (int k = t; k < e; k += nt) {
-        double f = __builtin_nan("");
-        if (code == 0) {
-            f = (th[la[k]] - th[lb[k]]) / rx[2 * k + 1];
-            flow[k] = f;
-        }
-        bf[k] = f;
-    }
-    if (t == 0) a.status[s] = code ? code : it;
-    __syncthreads();
+    const CtBaseIn in{a.edge_index, a.rx + (int64_t)s * 2 * e, a.bus_type, a.spec + (int64_t)s * 4 * n,
+                      a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * e : 0) : nullptr, a.base_flow + (int64_t)s * e, a.status + s,
+                      a.flags, a.tol, n, e, a.max_iter, a.n_pv, a.n_pq};
+    const int code = ct_base_solve(in, v, X);
 
     // ================================================================================================ PHASE B
     const float nanv = __builtin_nanf(""), infv = __builtin_inff();

@@ -1,5 +1,6 @@
-// The per-line arithmetic of the N-1 screen, spelled once for the dense kernel (contingency.hip) and the sparse route
-// (contingency_sparse.hip): den_k and the post-outage flow of line l from the outage's sensitivity vector, in fp32.
+// The per-line arithmetic of the contingency screens, spelled once: for the dense N-1 kernel (contingency.hip) and the sparse route
+// (contingency_sparse.hip) den_k and the post-outage flow of line l from the outage's sensitivity vector; for the N-2 pair screen
+// (contingency_pairs.hip) the ct_pair_* functions below.  All fp32.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,34 @@ __device__ __forceinline__ float ct_post(float wa, float wb, float x, float den,
     const float q = phi / den;
     const float d = q * fk;
     return fl + d;
+}
+
+// ---- the N-2 screen (contingency_pairs.hip): the simultaneous outage of lines a and b is a rank-2 update of the same inverse.
+//     M = [[1 - phi_aa, -phi_ab], [-phi_ba, 1 - phi_bb]]      t = M^-1 (f_a, f_b)      f_l^(a,b) = f_l + phi_la t_a + phi_lb t_b
+// phi_{l,k}, the sensitivity of line l = (a -> b) to the outage of line k, from w_k
+__device__ __forceinline__ float ct_pair_phi(float wa, float wb, float x) {
+#pragma clang fp contract(off)
+    return (wa - wb) / x;
+}
+// t = M^-1 (f_a, f_b) by Cramer's rule; a singular M (an islanding pair, which the line list decides and nobody reads) divides by 0
+__device__ __forceinline__ void ct_pair_solve(float paa, float pab, float pba, float pbb, float fa, float fb, float* ta, float* tb) {
+#pragma clang fp contract(off)
+    const float da = 1.f - paa, db = 1.f - pbb;
+    const float dd = da * db;
+    const float oo = pab * pba;
+    const float det = dd - oo;
+    const float na1 = db * fa, na2 = pab * fb;
+    const float nb1 = pba * fa, nb2 = da * fb;
+    const float na = na1 + na2, nb = nb1 + nb2;
+    *ta = na / det;
+    *tb = nb / det;
+}
+__device__ __forceinline__ float ct_pair_post(float pla, float plb, float fl, float ta, float tb) {
+#pragma clang fp contract(off)
+    const float d1 = pla * ta;
+    const float d2 = plb * tb;
+    const float s1 = fl + d1;
+    return s1 + d2;
 }
 
 }  // namespace pfn

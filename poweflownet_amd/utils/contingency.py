@@ -5,8 +5,11 @@ outages that cut buses off the slack; `pfn_contingency_dc`, one workgroup per sc
 `verify_contingencies` re-solves chosen (scenario, outage) pairs with the unchanged AC solver on the reduced line lists and reports
 the AC current loadings beside the DC screen's.  Beyond the dense cap (n - 1 > `max_unknowns()`) `route="sparse"` keeps the sparse
 fp32 FACTOR of B' under a `sparse_plan(..., mode="dc")` and substitutes 64 outages at a time (csrc/contingency_sparse.hip:
-`pfn_contingency_sparse`, two launches behind the islands).  No CPU path."""
+`pfn_contingency_sparse`, two launches behind the islands).  `contingency_screen_pairs` is the N-2 screen of the dense route: every
+pair of candidate lines out together, a rank-2 update of the same inverse (csrc/contingency_pairs.hip: `pfn_contingency_pair_islands`,
+`pfn_contingency_pairs`), and `verify_pair_contingencies` its AC check.  No CPU path."""
 import ctypes as C
+import operator
 from dataclasses import dataclass
 
 import torch
@@ -44,16 +47,7 @@ class ContingencyResult:
         """(int64 [S, top] outage ids, [S, top] their severities): per scenario the `top` outages by severity, descending -- NaN
         first (a failure must not hide), then +inf (the islanding outages), ties to the lowest outage id.  Plain torch on the
         tensors' device: it is not hot."""
-        e = int(self.severity.shape[1])
-        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= e:
-            raise ValueError(f"ranking: top must be an int in [0, {e}]; got {top!r}")
-        sev = self.severity
-        # NaN, +inf and the finite values as three classes, then the value: a stable sort keeps the lowest id among equals
-        cls = torch.where(torch.isnan(sev), 2, torch.where(torch.isposinf(sev), 1, 0))
-        val = torch.where(cls == 0, sev, torch.zeros_like(sev))
-        order = torch.sort(val, dim=1, descending=True, stable=True).indices
-        order = order.gather(1, torch.sort(cls.gather(1, order), dim=1, descending=True, stable=True).indices)[:, :top]
-        return order, sev.gather(1, order)
+        return _rank(self.severity, top, "ranking")
 
 
 @dataclass
@@ -70,6 +64,88 @@ class ContingencyVerification:
     worst_line: torch.Tensor
     overloads: torch.Tensor
     dc_severity: torch.Tensor
+
+
+def _rank(sev, top, who):
+    """`ContingencyResult.ranking`'s order over the columns of `sev`"""
+    width = int(sev.shape[1])
+    if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= width:
+        raise ValueError(f"{who}: top must be an int in [0, {width}]; got {top!r}")
+    # NaN, +inf and the finite values as three classes, then the value: a stable sort keeps the lowest id among equals
+    cls = torch.where(torch.isnan(sev), 2, torch.where(torch.isposinf(sev), 1, 0))
+    val = torch.where(cls == 0, sev, torch.zeros_like(sev))
+    order = torch.sort(val, dim=1, descending=True, stable=True).indices
+    order = order.gather(1, torch.sort(cls.gather(1, order), dim=1, descending=True, stable=True).indices)[:, :top]
+    return order, sev.gather(1, order)
+
+
+@dataclass
+class PairContingencyResult:
+    """Per (scenario s, pair p): `severity` [S, P] float32, `worst_line` [S, P] int32 and `overloads` [S, P] int32 by
+    `ContingencyResult`'s rules with BOTH outaged lines unmonitored (+inf, -1, -1 where the pair islands buses; NaN, -1, -1 where the
+    scenario failed).  `pairs` [P, 2] int64: the two lines of pair p, in `pair_lines`' order.  `islands` [P] int32: buses cut off
+    the slack with both lines removed (-4: a line names a bus outside the grid).  `base_flow` [S, e] float64 and `status` [S] int32
+    carry `contingency_screen`'s bits for the same inputs.  `post_flow` [S, P, e] float32 with `keep_table`, else None.  `flags` [1]
+    int32 (bit 0: `bus_type` changed under the launch).  All on the device; `route`: "lds" or "global"."""
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    islands: torch.Tensor
+    pairs: torch.Tensor
+    base_flow: torch.Tensor
+    status: torch.Tensor
+    post_flow: object
+    route: str
+    flags: object = None
+
+    def ranking(self, top):
+        """(int64 [S, top] pair indices, [S, top] their severities): `ContingencyResult.ranking`'s order -- NaN first, then +inf,
+        then descending, ties to the lowest pair index."""
+        return _rank(self.severity, top, "ranking")
+
+
+def _candidates(lines_or_e, who):
+    """the candidate lines as a list of ints: an int e means range(e); else a host sequence or a CPU int64 tensor"""
+    if isinstance(lines_or_e, int) and not isinstance(lines_or_e, bool):
+        if lines_or_e < 0:
+            raise ValueError(f"{who}: a line count must be >= 0; got {lines_or_e}")
+        return list(range(lines_or_e))
+    if torch.is_tensor(lines_or_e):
+        if lines_or_e.device.type != "cpu" or lines_or_e.dtype != torch.int64 or lines_or_e.dim() != 1:
+            raise ValueError(f"{who}: lines as a tensor must be a CPU int64 vector; got {lines_or_e.dtype} {tuple(lines_or_e.shape)} on {lines_or_e.device}")
+        return lines_or_e.tolist()
+    got = list(lines_or_e)
+    try:
+        if any(isinstance(k, bool) for k in got):
+            raise TypeError
+        return [operator.index(k) for k in got]                               # (numpy integers too)
+    except TypeError:
+        raise ValueError(f"{who}: lines must be ints; got {got!r}") from None
+
+
+def pair_lines(lines_or_e):
+    """int64 [P, 2] (CPU): the pairs of the candidate lines (an int e: all of range(e)) in the screen's order -- pair p is
+    (lines[i], lines[j]), i < j, row-major in (i, j); P = c (c - 1) / 2."""
+    lines = _candidates(lines_or_e, "pair_lines")
+    c = len(lines)
+    ij = torch.triu_indices(c, c, 1)
+    return torch.tensor(lines, dtype=torch.int64)[ij].t().contiguous().reshape(-1, 2)
+
+
+def pair_index(i, j, c):
+    """`pair_lines`' inverse: the index p of the pair of candidate POSITIONS i < j among c candidates (ints or integer tensors)."""
+    return i * (2 * c - i - 1) // 2 + (j - i - 1)
+
+
+def pair_positions(p, c):
+    """(i, j), the candidate positions of pair index p among c candidates (a Python int)."""
+    if isinstance(p, bool) or not isinstance(p, int) or not 0 <= p < c * (c - 1) // 2:
+        raise ValueError(f"pair_positions: pair {p!r} is outside [0, {c * (c - 1) // 2})")
+    i = 0
+    while p >= c - 1 - i:                                                      # (row i of the upper triangle holds c - 1 - i pairs)
+        p -= c - 1 - i
+        i += 1
+    return i, i + 1 + p
 
 
 def _bus_counts(bus_type):
@@ -218,6 +294,87 @@ def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_
                              post_flow=table, route="sparse", flags=flags, block="lds" if in_lds else "global")
 
 
+_LINES_KEPT = {}  # (device, candidate tuple) -> (int32 [c] lines, int64 [P, 2] pairs) on the device: a capture after its eager call uploads nothing
+
+
+def _device_lines(lines, dev):
+    key = (str(dev), tuple(lines))
+    got = _LINES_KEPT.get(key)
+    if got is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("contingency_screen_pairs: the candidate lines are uploaded once per list; call it eagerly once before capturing")
+        if len(_LINES_KEPT) >= 16:
+            _LINES_KEPT.pop(next(iter(_LINES_KEPT)))
+        got = (torch.tensor(lines, dtype=torch.int32).to(dev), pair_lines(lines).to(dev))
+        _LINES_KEPT[key] = got
+    return got
+
+
+def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, lines=None, tol=1e-8, max_iter=10, route="auto",
+                             keep_table=False) -> PairContingencyResult:
+    """Screen every PAIR of line outages among the candidate `lines` of every scenario under the DC model (N-2): inputs and their
+    checks are `contingency_screen`'s.  `lines`: a host sequence or a CPU int64 tensor of line ids, strictly increasing and within
+    [0, e), at least two (checked on the host, no device read; ValueError otherwise); None: all lines.  All e lines stay monitored
+    whatever the candidates are -- N-1 first, then the pairs among its top outages, is how larger grids are screened.  With c
+    candidates there are P = c (c - 1) / 2 pairs in `pair_lines`' order.  `route`: "auto", "lds" (raises where B'^-1 does not fit
+    LDS beside the pair launch's vectors) or "global" (the pair launch reads the workspace slab); the same bits.  Dense only: beyond
+    `max_unknowns()` it raises.  Three launches; one host read (the bus_type counts, once per tensor); nothing is read back."""
+    who = "contingency_screen_pairs"
+    if route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    e_given = int(edge_index.shape[1]) if torch.is_tensor(edge_index) and edge_index.dim() == 2 else None
+    if lines is not None:                                                     # on the host, before anything touches the library
+        lines = _candidates(lines, who)
+        if isinstance(lines, list) and len(lines) < 2:
+            raise ValueError(f"{who}: a pair needs at least two candidate lines; got {len(lines)}")
+        if any(b <= a for a, b in zip(lines, lines[1:])):
+            raise ValueError(f"{who}: lines must be strictly increasing (sorted, no duplicates)")
+        if lines[0] < 0 or (e_given is not None and lines[-1] >= e_given):
+            raise ValueError(f"{who}: lines must lie within [0, {e_given}); got {lines[0]} .. {lines[-1]}")
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    if e < 2:
+        raise ValueError(f"{who}: a grid of {e} line has no pair to screen")
+    lib = L.load()
+    cap = int(lib.pfn_powerflow_max_unknowns())
+    if n - 1 > cap:
+        raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); a sparse pair screen is not built")
+    ratings = _ratings(ratings, S, e, who)
+    n_pv, n_pq, slack = _bus_counts(bus_type)
+    dev = spec.device
+    bt = bus_type.to(torch.int32).contiguous()
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    if lines is None:                                                         # all lines: built on the device, nothing uploaded
+        c = e
+        ij = torch.triu_indices(c, c, 1, device=dev)
+        lines_d, pairs = torch.arange(c, dtype=torch.int32, device=dev), ij.t().contiguous()
+    else:
+        c = len(lines)
+        lines_d, pairs = _device_lines(lines, dev)
+    P = c * (c - 1) // 2
+    islands = torch.empty(P, dtype=torch.int32, device=dev)
+    severity = torch.empty(S, P, dtype=torch.float32, device=dev)
+    worst = torch.empty(S, P, dtype=torch.int32, device=dev)
+    overloads = torch.empty(S, P, dtype=torch.int32, device=dev)
+    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
+    status = torch.empty(S, dtype=torch.int32, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    table = torch.empty(S, P, e, dtype=torch.float32, device=dev) if keep_table else None
+    need = int(lib.pfn_contingency_pairs_workspace_bytes(S, n, e, c, 2)) if S else 0
+    in_lds = route != "global" and int(lib.pfn_contingency_pairs_workspace_bytes(1, n, e, c, 1)) != 0
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.pfn_contingency_pair_islands(edge_index.data_ptr(), e, n, slack, lines_d.data_ptr(), c, islands.data_ptr(), L.stream_ptr()),
+                "pfn_contingency_pair_islands")
+        L.check(lib.pfn_contingency_pairs(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
+                                          int(ratings is not None and ratings.dim() == 2), lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv,
+                                          n_pq, float(tol), int(max_iter), _ROUTES[route], severity.data_ptr(), worst.data_ptr(),
+                                          overloads.data_ptr(), base_flow.data_ptr(), status.data_ptr(), L.ptr(table), flags.data_ptr(),
+                                          ws.data_ptr(), need, L.stream_ptr()),
+                "pfn_contingency_pairs")
+    return PairContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, pairs=pairs, base_flow=base_flow,
+                                 status=status, post_flow=table, route="lds" if in_lds else "global", flags=flags)
+
+
 def summarise_loadings(loading, monitored):
     """(severity float32 [T], worst_line int32 [T], overloads int32 [T]) of loadings [T, e] over the `monitored` lines by the
     screen's rules: the maximum with ties to the lowest line, a non-finite loading counts as the largest and makes the severity NaN,
@@ -233,6 +390,34 @@ def summarise_loadings(loading, monitored):
     return severity, torch.where(none, -1, worst).to(torch.int32), (monitored & (loading > 1)).sum(dim=1).to(torch.int32)
 
 
+def _verify_removed(bus_type, spec, edge_index, rx, ratings, S, e, chosen, removed, solver_kw):
+    """The AC re-solve both verifications share: row t is scenario chosen[t] with the K = `removed.shape[1]` (1 or 2) lines
+    removed[t] (ascending) left out.  The reduced lists and their rx are built on the device, `solve_power_flow(mode="ac")` solves
+    them, `loss.branch_flows` gives the line currents and the loadings go back to the original numbering (NaN at the removed lines).
+    Returns (solved, loading [T, e] float32, severity, worst_line, overloads)."""
+    from ..loss import branch_flows
+    dev = spec.device
+    T, K = int(removed.shape[0]), int(removed.shape[1])
+    ar = torch.arange(e - K, device=dev)
+    idx = ar[None, :].expand(T, e - K)
+    for k in range(K):                                                         # the lines that stay, in stored order
+        idx = idx + (idx >= removed[:, k:k + 1])
+    lists = edge_index[:, idx].permute(1, 0, 2).contiguous()                   # [T, 2, e - K]
+    rx_post = rx[chosen[:, None], idx].contiguous()                            # [T, e - K, 2]
+    if solver_kw.get("route") == "sparse" and solver_kw.get("plan") is None and T:
+        # every reduced list is a subset of the base list: ONE cover plan whose cover IS the base list serves all rows
+        solver_kw = {**solver_kw, "plan": cover_plan(bus_type, edge_index[None], mode="ac", base=edge_index)}
+    solved = solve_power_flow(bus_type, spec[chosen].contiguous(), lists, rx_post, mode="ac", **solver_kw)
+    rate = torch.ones(S, e, dtype=torch.float32, device=dev) if ratings is None else ratings.float().expand(S, e)
+    rate = rate[chosen]                                                        # [T, e]
+    loading = torch.full((T, e), float("nan"), dtype=torch.float32, device=dev)
+    if T and e > K:
+        flows = branch_flows(solved.table.float(), lists, rx_post.float())[0]  # [T, e - K, 4]: column 0 is the current
+        loading.scatter_(1, idx, flows[:, :, 0] / rate.gather(1, idx))
+    monitored = (rate > 0) & (torch.arange(e, device=dev)[None, :, None] != removed[:, None, :]).all(dim=2)
+    return (solved, loading) + tuple(summarise_loadings(loading, monitored))
+
+
 def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *, top=5, pairs=None, **solver_kw) -> ContingencyVerification:
     """AC check of chosen outages of a `contingency_screen` result (same inputs): for every pair (scenario s, outage k) -- `pairs`
     [T, 2], or per scenario the `top` outages of `result.ranking` -- that does not island a bus, the line list without line k and its
@@ -240,7 +425,6 @@ def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *
     and the loadings I_l / rating_l go back to the original line numbering.  The pairs are chosen on the host (T is small).
     `route="sparse"` without `plan=`: ONE `cover_plan` whose cover is the base list is built here (every reduced list is a subset of
     it); a `plan=` that is given is reused."""
-    from ..loss import branch_flows
     who = "verify_contingencies"
     S, n, e = _check(bus_type, spec, edge_index, rx, who)
     ratings = _ratings(ratings, S, e, who)
@@ -258,23 +442,58 @@ def verify_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *
                 raise ValueError(f"{who}: pair ({s}, {k}) is outside ({S} scenarios, {e} lines)")
         chosen = [(s, k) for s, k in chosen if int(islands[k]) == 0]
     pairs_t = torch.tensor(chosen, dtype=torch.int64, device=dev).reshape(-1, 2)
-    T = int(pairs_t.shape[0])
     sc, out = pairs_t[:, 0], pairs_t[:, 1]
-    ar = torch.arange(e - 1, device=dev)
-    idx = ar[None, :] + (ar[None, :] >= out[:, None])                          # [T, e - 1]: the lines that stay, in stored order
-    lists = edge_index[:, idx].permute(1, 0, 2).contiguous()                   # [T, 2, e - 1]
-    rx_post = rx[sc[:, None], idx].contiguous()                                # [T, e - 1, 2]
-    if solver_kw.get("route") == "sparse" and solver_kw.get("plan") is None and T:
-        # every reduced list is a subset of the base list: ONE cover plan whose cover IS the base list serves all pairs
-        solver_kw = {**solver_kw, "plan": cover_plan(bus_type, edge_index[None], mode="ac", base=edge_index)}
-    solved = solve_power_flow(bus_type, spec[sc].contiguous(), lists, rx_post, mode="ac", **solver_kw)
-    rate = torch.ones(S, e, dtype=torch.float32, device=dev) if ratings is None else ratings.float().expand(S, e)
-    rate = rate[sc]                                                            # [T, e]
-    loading = torch.full((T, e), float("nan"), dtype=torch.float32, device=dev)
-    if T and e > 1:
-        flows = branch_flows(solved.table.float(), lists, rx_post.float())[0]  # [T, e - 1, 4]: column 0 is the current
-        loading.scatter_(1, idx, flows[:, :, 0] / rate.gather(1, idx))
-    monitored = (rate > 0) & (torch.arange(e, device=dev)[None, :] != out[:, None])
-    severity, worst, overloads = summarise_loadings(loading, monitored)
+    solved, loading, severity, worst, overloads = _verify_removed(bus_type, spec, edge_index, rx, ratings, S, e, sc, out[:, None], solver_kw)
     return ContingencyVerification(pairs=pairs_t, table=solved.table, status=solved.status, loading=loading, severity=severity,
                                    worst_line=worst, overloads=overloads, dc_severity=result.severity[sc, out])
+
+
+@dataclass
+class PairContingencyVerification:
+    """`triples` [T, 3] int64 (scenario, line a, line b; a < b), `pair_index` [T] int64 (the pair's column in the screen's result),
+    the AC `table` [T, n, 4] float64 and `status` [T] int32 of `solve_power_flow` on the grid without both lines, `loading` [T, e]
+    float32 = I_l / rating_l in the ORIGINAL line numbering (NaN at both outaged lines), `severity` / `worst_line` / `overloads` by
+    the screen's rules, and `dc_severity` [T] float32, the screen's figure for the pair."""
+    triples: torch.Tensor
+    pair_index: torch.Tensor
+    table: torch.Tensor
+    status: torch.Tensor
+    loading: torch.Tensor
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    dc_severity: torch.Tensor
+
+
+def verify_pair_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *, top=5, triples=None,
+                              **solver_kw) -> PairContingencyVerification:
+    """`verify_contingencies` with two lines removed: AC check of chosen pairs of a `contingency_screen_pairs` result (same inputs).
+    `triples` [T, 3] (scenario, line a, line b) name pairs the screen holds (ValueError otherwise), or per scenario the `top` pairs
+    of `result.ranking`; pairs that island buses are skipped.  The rows are chosen on the host (T is small)."""
+    who = "verify_pair_contingencies"
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    ratings = _ratings(ratings, S, e, who)
+    dev = spec.device
+    islands, held = result.islands.cpu().tolist(), result.pairs.cpu().tolist()
+    P = len(held)
+    if triples is None:
+        if isinstance(top, bool) or not isinstance(top, int) or top < 0:
+            raise ValueError(f"{who}: top must be an int >= 0; got {top!r}")
+        order = result.ranking(P)[0].cpu()
+        chosen = [(s, p) for s in range(S) for p in [p for p in order[s].tolist() if islands[p] == 0][:top]]
+    else:
+        where = {(a, b): p for p, (a, b) in enumerate(held)}
+        chosen = []
+        for s, a, b in ([tuple(int(v) for v in row) for row in (triples.tolist() if torch.is_tensor(triples) else triples)]):
+            a, b = min(a, b), max(a, b)
+            if not 0 <= s < S or (a, b) not in where:
+                raise ValueError(f"{who}: ({s}, {a}, {b}) is no (scenario, pair) of this screen ({S} scenarios, {P} pairs)")
+            chosen.append((s, where[(a, b)]))
+        chosen = [(s, p) for s, p in chosen if islands[p] == 0]
+    rows = torch.tensor(chosen, dtype=torch.int64, device=dev).reshape(-1, 2)
+    sc, pi = rows[:, 0], rows[:, 1]
+    removed = result.pairs[pi]                                                 # [T, 2], ascending
+    solved, loading, severity, worst, overloads = _verify_removed(bus_type, spec, edge_index, rx, ratings, S, e, sc, removed, solver_kw)
+    return PairContingencyVerification(triples=torch.cat([sc[:, None], removed], dim=1), pair_index=pi, table=solved.table, status=solved.status,
+                                       loading=loading, severity=severity, worst_line=worst, overloads=overloads,
+                                       dc_severity=result.severity[sc, pi])

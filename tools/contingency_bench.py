@@ -20,7 +20,15 @@ only): the plan's build time, the wall time of the three launches, the base and 
 brackets, a pass of their own), pairs per second.  Beside it, alternating in the same child: the dense screen where the shape is
 within its cap, else the brute force the parent commit has there -- `solve_power_flow(mode="dc", route="sparse", plan=<cover plan of
 the base list>)` over explicit per-outage lists of `--brute-pairs` non-islanding outages spread evenly over the list, scaled per
-pair."""
+pair.
+
+    python tools/contingency_bench.py --pairs [--candidates 16] [--samples 4096] [--brute-solves 4096] [--case 118 --case 14]
+
+The N-2 pair screen (`contingency_screen_pairs`), same protocol: the candidates are the `--candidates` non-islanding single
+outages with the largest severity over the scenarios (the N-1 screen's, unrated), every pair of them is screened -- three launches:
+pair islands, one B' inverse per scenario, the rank-2 updates -- on the route "auto" picks and, where that is "lds", on the forced
+"global" route too; time per (scenario, pair), the base and the pair launch apart (the library's event brackets, a pass of their
+own), beside the brute force: `solve_power_flow(mode="dc")` over explicit [2, e - 2] lists, one per (scenario, non-islanding pair)."""
 import argparse
 import json
 import os
@@ -70,6 +78,90 @@ def child(case, samples, brute_solves, repeats):
                       "brute_scenarios": Sb, "brute_solves": Sb * K, "screen_ms": 1e3 * statistics.median(t_screen),
                       "brute_ms": 1e3 * statistics.median(t_brute), "screen_us_per_pair": screen_us, "brute_us_per_pair": brute_us,
                       "ratio": brute_us / screen_us}))
+
+
+def child_pairs(case, samples, candidates, brute_solves, repeats):
+    import torch
+    from poweflownet_amd import _lib as L
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen, contingency_screen_pairs
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    dev = torch.device("cuda:0")
+    n, e = CASES[case]
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    single = contingency_screen(bt, spec, ei, rx)
+    sev = torch.where(single.islands[None, :] == 0, single.severity, torch.full_like(single.severity, -1.0)).max(dim=0).values
+    lines = sorted(torch.topk(sev, min(candidates, int((single.islands == 0).sum()))).indices.tolist())
+    res = contingency_screen_pairs(bt, spec, ei, rx, lines=lines)           # (warm-up; its islands choose the brute force's pairs)
+    routes = [res.route] + (["global"] if res.route == "lds" else [])
+    for r in routes[1:]:
+        contingency_screen_pairs(bt, spec, ei, rx, lines=lines, route=r)    # (warm-up)
+    P = int(res.pairs.shape[0])
+    out = res.pairs[res.islands == 0]                                       # [K, 2], a < b
+    K = int(out.shape[0])
+    Sb = max(1, min(samples, brute_solves // K))
+    # the brute force's inputs, built once and not timed: scenario s, pair k -> sample s * K + k of [Sb K, 2, e - 2] lists
+    idx = torch.arange(e - 2, device=dev)[None, :].expand(K, e - 2)
+    for k in range(2):
+        idx = idx + (idx >= out[:, k:k + 1])
+    lists = ei[:, idx].permute(1, 0, 2).repeat(Sb, 1, 1).contiguous()
+    rx_b = rx[:Sb][:, idx].reshape(Sb * K, e - 2, 2).contiguous()
+    spec_b = spec[:Sb].repeat_interleave(K, dim=0).contiguous()
+    brute = solve_power_flow(bt, spec_b, lists, rx_b, mode="dc")            # (warm-up)
+    assert bool((res.status >= 0).all()) and bool((brute.status >= 0).all())
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    t_screen, t_brute = {r: [] for r in routes}, []
+    for _ in range(repeats):
+        for r in routes:
+            t_screen[r].append(timed(lambda: contingency_screen_pairs(bt, spec, ei, rx, lines=lines, route=r)))
+        t_brute.append(timed(lambda: solve_power_flow(bt, spec_b, lists, rx_b, mode="dc")))
+    row = {"case": case, "buses": n, "lines": e, "scenarios": samples, "candidates": len(lines), "pairs": P, "non_islanding": K,
+           "brute_scenarios": Sb, "brute_solves": Sb * K, "brute_ms": 1e3 * statistics.median(t_brute),
+           "brute_us_per_pair": 1e6 * statistics.median(t_brute) / (Sb * K)}
+    for r in routes:
+        L.profile_report(reset=True)
+        L.profile_enable(True)                                              # the launches apart: event brackets, a pass of their own
+        for _ in range(repeats):
+            contingency_screen_pairs(bt, spec, ei, rx, lines=lines, route=r)
+        prof = L.profile_report()
+        L.profile_enable(False)
+        sec = statistics.median(t_screen[r])
+        row[r] = {"screen_ms": 1e3 * sec, "screen_us_per_pair": 1e6 * sec / (samples * P), "ratio": row["brute_us_per_pair"] / (1e6 * sec / (samples * P)),
+                  "islands_ms": prof["contingency_pair_islands"]["ms"] / repeats, "base_ms": prof["contingency_pairs_base"]["ms"] / repeats,
+                  "pairs_ms": prof["contingency_pairs"]["ms"] / repeats}
+    row["route"] = routes[0]
+    print(json.dumps(row))
+
+
+def main_pairs(a):
+    out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "cases": {}}
+    for case in a.case or ["118", "14"]:
+        rows = []
+        for _ in range(a.processes):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-pairs", case, "--samples", str(a.samples), "--brute-solves",
+                                str(a.brute_solves), "--repeats", str(a.repeats), "--candidates", str(a.candidates)], capture_output=True, text=True,
+                               timeout=600)
+            if r.returncode != 0:
+                raise SystemExit(f"contingency_bench: the pairs child for case {case} failed:\n{r.stdout}\n{r.stderr}")
+            rows.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        row = dict(rows[0])
+        for key in ("brute_ms", "brute_us_per_pair"):
+            vals = [x[key] for x in rows]
+            row[key], row[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+        for route in [k for k in ("lds", "global") if k in row]:
+            row[route] = dict(row[route])
+            for key in list(rows[0][route]):
+                vals = [x[route][key] for x in rows]
+                row[route][key], row[route][key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+        out["cases"][case] = row
+    print(json.dumps(out))
+    return 0
 
 
 def child_sparse(shape, samples, block, groups_x, brute_pairs, repeats):
@@ -171,7 +263,15 @@ def main(argv=None):
     ap.add_argument("--child-sparse", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--block", default="auto", help=argparse.SUPPRESS)
     ap.add_argument("--groups-x", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--pairs", action="store_true", help="the N-2 pair screen, contingency_screen_pairs, DESIGN 7w")
+    ap.add_argument("--candidates", type=int, default=16, help="pairs: the K worst non-islanding single outages are the candidates")
+    ap.add_argument("--child-pairs", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_pairs:
+        child_pairs(a.child_pairs, a.samples, a.candidates, a.brute_solves, a.repeats)
+        return 0
+    if a.pairs:
+        return main_pairs(a)
     if a.child_sparse:
         child_sparse(a.child_sparse, a.samples, a.block, a.groups_x, a.brute_pairs, a.repeats)
         return 0
