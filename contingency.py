@@ -12,9 +12,10 @@ the AC verification on the sparse solver under one cover plan; `--route sparse` 
 
 Writes results/<case>_contingency_{severity,worst_line,overloads,islands,base_flow}.npy.
 
---pairs [--candidates K] goes on to N-2 on the dense route (`contingency_screen_pairs`): the candidates are the union over the scenarios
-of each scenario's top-K non-islanding single outages (K defaults to 10), every pair of them is screened with all lines monitored,
-the worst pairs of every scenario are AC-verified (`verify_pair_contingencies`), and
+--pairs [--candidates K] goes on to N-2 (`contingency_screen_pairs`) on the route of the N-1 screen -- the sparse route reuses its one
+DC plan --: the candidates are the union over the scenarios of each scenario's top-K non-islanding single outages (K defaults to
+10), every pair of them is screened with all lines monitored, the worst pairs of every scenario are AC-verified
+(`verify_pair_contingencies`, on the sparse solver where the screen took the sparse route), and
 results/<case>_contingency_pairs_{severity,worst_line,overloads,islands,pairs}.npy are written too.
 """
 import argparse
@@ -49,7 +50,7 @@ def main(argv=None):
     ap.add_argument("--verify-top", type=int, default=5, help="AC-verify the worst N non-islanding outages of every scenario")
     ap.add_argument("--route", default="auto", choices=("auto", "lds", "global", "sparse"),
                     help="auto: the dense screen up to its cap, the sparse route beyond")
-    ap.add_argument("--pairs", action="store_true", help="also screen the pairs of the worst single outages (N-2, dense route)")
+    ap.add_argument("--pairs", action="store_true", help="also screen the pairs of the worst single outages (N-2) on the same route")
     ap.add_argument("--candidates", type=int, default=10, help="--pairs: every scenario's top K non-islanding outages are candidates")
     ap.add_argument("--split", type=float, nargs=3, default=[.5, .2, .3], help="train / val / test fractions of the dataset")
     ap.add_argument("--out-dir", default="results")
@@ -92,15 +93,14 @@ def main(argv=None):
     for name in ("severity", "worst_line", "overloads", "islands", "base_flow"):
         np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_{name}.npy"), getattr(res, name).cpu().numpy())
     if a.pairs:
-        screen_pairs(a, res, islands, bt, spec, ei, rx, ratings)
+        screen_pairs(a, res, islands, bt, spec, ei, rx, ratings, kw, solver_kw)
     return 0
 
 
-def screen_pairs(a, res, islands, bt, spec, ei, rx, ratings):
-    """--pairs: N-2 among the worst single outages, DC beside AC, and the five result files"""
+def screen_pairs(a, res, islands, bt, spec, ei, rx, ratings, kw, solver_kw):
+    """--pairs: N-2 among the worst single outages on the N-1 screen's route (`kw`: its route and plan), DC beside AC (`solver_kw`:
+    the AC solver's route), and the five result files"""
     from poweflownet_amd.utils.contingency import contingency_screen_pairs, verify_pair_contingencies
-    if a.route == "sparse" or res.route == "sparse":
-        raise SystemExit("contingency.py --pairs: the pair screen runs on the dense route only")
     if a.candidates < 2:
         raise SystemExit("contingency.py --pairs: --candidates must be at least 2")
     S, e = int(spec.shape[0]), int(ei.shape[1])
@@ -108,13 +108,13 @@ def screen_pairs(a, res, islands, bt, spec, ei, rx, ratings):
     lines = sorted({int(k) for s in range(S) for k in [k for k in order[s] if islands[k] == 0][:a.candidates]})
     if len(lines) < 2:
         raise SystemExit(f"contingency.py --pairs: {len(lines)} non-islanding outage(s) leave no pair to screen")
-    two = contingency_screen_pairs(bt, spec, ei, rx, ratings, lines=lines, route=a.route)
+    two = contingency_screen_pairs(bt, spec, ei, rx, ratings, lines=lines, **kw)
     pair_islands = two.islands.cpu().numpy()
     held = two.pairs.cpu().numpy()
     print(f"N-2: {len(lines)} candidate lines (top {a.candidates} of every scenario), {len(held)} pairs x {S} scenarios on the {two.route} route")
     print(f"{int((pair_islands > 0).sum())} islanding pairs of non-islanding outages, {int(pair_islands[pair_islands > 0].sum())} buses lost over them")
     top = min(a.verify_top, int((pair_islands == 0).sum()))
-    ver = verify_pair_contingencies(two, bt, spec, ei, rx, ratings, top=top)
+    ver = verify_pair_contingencies(two, bt, spec, ei, rx, ratings, top=top, **solver_kw)
     triples, dc, ac, status = ver.triples.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy(), ver.status.cpu().numpy()
     dc_worst, ac_worst = two.worst_line[ver.triples[:, 0], ver.pair_index].cpu().numpy(), ver.worst_line.cpu().numpy()
     for s in range(S):

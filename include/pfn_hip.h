@@ -839,7 +839,7 @@ int pfn_contingency_dc(const int64_t* edge_index, int64_t n_lines, const double*
                        size_t ws_bytes, void* stream);
 
 /* N-2: which PAIRS of line outages overload the rest of the grid (csrc/contingency_pairs.hip)?  The dense DC route only
- * (n_bus - 1 <= pfn_powerflow_max_unknowns()).  `lines`: DEVICE int32 [n_candidates], strictly increasing ids in [0, n_lines); pair
+ * (n_bus - 1 <= pfn_powerflow_max_unknowns(); beyond it pfn_contingency_pairs_sparse, below).  `lines`: DEVICE int32 [n_candidates], strictly increasing ids in [0, n_lines); pair
  * p = (lines[i], lines[j]), i < j, row-major in (i, j), P = n_candidates (n_candidates - 1) / 2; all n_lines lines stay monitored.
  * Three launches, no host sync, no allocation (capturable), no float atomics.
  *
@@ -905,6 +905,42 @@ int pfn_contingency_sparse(const int64_t* edge_index, int64_t n_lines, const dou
                            int32_t* overloads, double* base_flow, int32_t* status, float* post_flow, int32_t* flags, void* ws,
                            size_t ws_bytes, const void* plan_header, const void* plan_dev, int threads, int block_route, int groups,
                            void* stream);
+
+/* N-2 beyond the dense cap (csrc/contingency_pairs_sparse.hip): pfn_contingency_pairs' screen -- the same pairs of `lines` in the same
+ * order, the same formulas, definitions and outputs -- from the sparse fp32 factor of pfn_contingency_sparse under the same mode-1
+ * plan; statuses are pfn_contingency_sparse's (-6 where the device line list is not the plan's).  `islands`: DEVICE int32 [P],
+ * pfn_contingency_pair_islands' output for this line list, slack and candidates.  Three launches behind it, no host sync, no
+ * allocation (capturable after one eager call), no float atomics:
+ *   base     pfn_contingency_sparse's base launch, the same kernel: base_flow and status carry its bits for the same inputs; `threads`
+ *            as there.
+ *   columns  a lane per candidate, a one-wave workgroup per tile of 64 consecutive candidates: pfn_contingency_sparse's tile
+ *            substitution (the same function: column k has the bits its outage launch holds for outage lines[k]), then the tile is
+ *            written into the scenario's column table [n_candidates][n_bus] fp32 (candidate-major, plan order, the last row the
+ *            slack's zero).  block_route / groups as in pfn_contingency_sparse, the items being (scenario, tile of candidates):
+ *            G = min(n_samples * ceil(n_candidates / 64), groups or 16 * compute units).
+ *   pairs    one workgroup of `waves` waves (0: the default, 4; else 1, 2, 4, 8, 16) per (scenario, first candidate); a wave takes
+ *            second candidates: M, t, then its lanes stride over the lines (the per-line vectors are read from the slab) and reduce
+ *            as pfn_contingency_pairs does.
+ *   column_route  0 auto, 1 LDS, 2 global: the pair launch copies w_a and one w_b per wave into LDS where 4 n_bus (1 + waves) bytes,
+ *            rounded up to 16, fit the 159 KiB a workgroup may take, else gathers from the column table; same code, same bits.
+ *   severity, worst_line, overloads  [n_samples, P]; post_flow fp32 [n_samples, P, n_lines] or null.
+ * pfn_contingency_pairs_sparse_workspace_bytes(n_samples, n_lines, n_candidates, plan_header, block_route, groups, column_route,
+ * waves): per scenario pfn_contingency_sparse's slab (8 (2 n_bus + m) + 4 nnz + 20 n_lines bytes rounded up to 16) plus the column
+ * table, 4 n_candidates n_bus bytes rounded up to 16; plus G blocks of 256 n_bus bytes where the block sits in the workspace.  0 for
+ * arguments the call would refuse -- block_route 1 where the block does not fit, column_route 1 where the columns do not fit (which is
+ * how a caller finds the thresholds), waves that is none of the six, more candidates than lines, a plan of another mode or size.
+ * The bits of (scenario, a, b) are a function of the scenario's inputs, the plan and the two lines, whatever the batch, the candidate
+ * list, G, `threads`, `waves` or either placement.  PFN_EINVAL: what pfn_contingency_sparse refuses, bad candidate counts,
+ * column_route 1 where it does not fit, bad waves, null or misaligned pointers; PFN_ENOSPACE: too little ws.                        */
+size_t pfn_contingency_pairs_sparse_workspace_bytes(int64_t n_samples, int64_t n_lines, int64_t n_candidates, const void* plan_header,
+                                                    int block_route, int groups, int column_route, int waves);
+int pfn_contingency_pairs_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                                 const double* ratings, int ratings_per_sample, const int32_t* lines, int64_t n_candidates,
+                                 const int32_t* islands, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq, double tol,
+                                 int max_iter, float* severity, int32_t* worst_line, int32_t* overloads, double* base_flow,
+                                 int32_t* status, float* post_flow, int32_t* flags, void* ws, size_t ws_bytes, const void* plan_header,
+                                 const void* plan_dev, int threads, int block_route, int groups, int column_route, int waves,
+                                 void* stream);
 
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select

@@ -1,6 +1,6 @@
 // The per-line arithmetic of the contingency screens, spelled once: for the dense N-1 kernel (contingency.hip) and the sparse route
 // (contingency_sparse.hip) den_k and the post-outage flow of line l from the outage's sensitivity vector; for the N-2 pair screen
-// (contingency_pairs.hip) the ct_pair_* functions below.  All fp32.
+// (contingency_pairs.hip, contingency_pairs_sparse.hip) the ct_pair_* functions below.  All fp32.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,8 @@ __device__ __forceinline__ float ct_post(float wa, float wb, float x, float den,
 
 // ---- the N-2 screen (contingency_pairs.hip): the simultaneous outage of lines a and b is a rank-2 update of the same inverse.
 //     M = [[1 - phi_aa, -phi_ab], [-phi_ba, 1 - phi_bb]]      t = M^-1 (f_a, f_b)      f_l^(a,b) = f_l + phi_la t_a + phi_lb t_b
+// pair p = (lines[i], lines[j]), i < j, row-major in (i, j) among c candidates (also contingency_pairs_sparse.hip): the index of pair (i, i + 1)
+__host__ __device__ inline int64_t cp_first_pair(int64_t i, int64_t c) { return i * (2 * c - i - 1) / 2; }
 // phi_{l,k}, the sensitivity of line l = (a -> b) to the outage of line k, from w_k
 __device__ __forceinline__ float ct_pair_phi(float wa, float wb, float x) {
 #pragma clang fp contract(off)

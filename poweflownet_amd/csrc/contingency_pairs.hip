@@ -33,8 +33,6 @@
 
 namespace pfn {
 
-__host__ __device__ inline int64_t cp_first_pair(int64_t i, int64_t c) { return i * (2 * c - i - 1) / 2; }   // the index of pair (i, i + 1)
-
 // ------------------------------------------------------------------------------------------------------ islands
 // dynamic LDS: ID from[e] | ID to[e] | uint8 keep[e] | uint8 reached[n] (contingency.hip's)
 __host__ __device__ inline size_t cp_islands_lds_bytes(int n, int e) {
@@ -336,7 +334,7 @@ int pfn_contingency_pairs(const int64_t* edge_index, int64_t n_lines, const doub
                   who, (long long)n_pv, (long long)n_pq, (long long)n_bus);
     PFN_CHECK_ARG(route >= 0 && route <= 2, "%s: route must be 0 (auto), 1 (LDS) or 2 (global)", who);
     PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "%s: max_iter must be >= 0 and tol > 0", who);
-    PFN_CHECK_ARG(n_bus - 1 <= PF_MAX_UNKNOWNS, "%s: %lld unknowns per scenario exceed the dense screen's %d; a sparse pair screen is not built", who,
+    PFN_CHECK_ARG(n_bus - 1 <= PF_MAX_UNKNOWNS, "%s: %lld unknowns per scenario exceed the dense screen's %d; pfn_contingency_pairs_sparse goes beyond it", who,
                   (long long)(n_bus - 1), PF_MAX_UNKNOWNS);
     const int n = (int)n_bus, e = (int)n_lines, c = (int)n_candidates, m = n - 1;
     const int threads = ct_threads(m), nw = threads >> 6;

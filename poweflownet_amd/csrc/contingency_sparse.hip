@@ -19,66 +19,9 @@
 // Workgroup g of G takes the items (scenario, tile) g, g + G, ...; an item's arithmetic does not know G.  W sits in LDS where
 // 256 (m + 1) bytes fit, else in the workgroup's block of the workspace: the same code, the same bits.
 #include "contingency_line.hpp"
-#include "powerflow_common.hpp"
-#include "powerflow_sparse_core.hpp"
+#include "contingency_sparse_core.hpp"
 
 namespace pfn {
-
-constexpr int CS_GROUPS_PER_CU = 16;                // groups = 0: min(items, this many one-wave workgroups per compute unit): the sweep of DESIGN 7v
-
-// a scenario's slab: double vm, th [n], F [m]; float factor [nnz], f32, x32, rat [e]; int pa, pb [e]; rounded to 16 bytes
-__host__ __device__ inline size_t cs_sample_bytes(int n, int m, int nnz, int e) {
-    return ((size_t)8 * (2 * (size_t)n + m) + (size_t)4 * nnz + (size_t)20 * e + 15) & ~(size_t)15;
-}
-// an outage block: m + 1 rows of 64 floats
-__host__ __device__ inline size_t cs_block_bytes(int m) { return (size_t)256 * ((size_t)m + 1); }
-static inline bool cs_block_fits_lds(int m) { return cs_block_bytes(m) <= (size_t)(kLdsCuBytes - kLdsReserve); }
-static inline int64_t cs_tiles(int64_t e) { return (e + 63) / 64; }
-static inline int64_t cs_groups(int64_t n_samples, int64_t e, int groups) {
-    const int64_t items = n_samples * cs_tiles(e);
-    const int64_t want = groups > 0 ? (int64_t)groups : (int64_t)CS_GROUPS_PER_CU * device_cus();
-    return items < want ? items : want;
-}
-
-struct CsSlab {
-    double* vm;
-    double* th;
-    double* F;
-    float* factor;
-    float* f32;
-    float* x32;
-    float* rat;
-    int32_t* pa;
-    int32_t* pb;
-};
-__device__ __forceinline__ CsSlab cs_slab(void* ws, size_t stride, int s, int n, int m, int nnz, int e) {
-    CsSlab b;
-    b.vm = reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + (size_t)s * stride);
-    b.th = b.vm + n;
-    b.F = b.th + n;
-    b.factor = reinterpret_cast<float*>(b.F + m);
-    b.f32 = b.factor + nnz;
-    b.x32 = b.f32 + e;
-    b.rat = b.x32 + e;
-    b.pa = reinterpret_cast<int32_t*>(b.rat + e);
-    b.pb = b.pa + e;
-    return b;
-}
-
-struct CsArgs {
-    PfProblem p;                                    // (table, residual, init, line_mask, unplaced: null; ws: the scenarios' slabs)
-    const int32_t* plan;
-    const double* ratings;                          // [e], [S, e] or null (1.0 everywhere)
-    const int32_t* islands;                         // [e]
-    float* severity;                                // [S, e]
-    int32_t* worst_line;                            // [S, e]
-    int32_t* overloads;                             // [S, e]
-    double* base_flow;                              // [S, e]
-    float* post_flow;                               // [S, e, e] or null
-    float* blocks;                                  // the global placement's outage blocks, one per workgroup, or null
-    size_t ws_stride;
-    int m, nnz, n_pv, ratings_per_sample, f_in_lds;
-};
 
 // ------------------------------------------------------------------------------------------------------ launch 1
 template <int THREADS>
@@ -190,39 +133,7 @@ __global__ __launch_bounds__(THREADS) void contingency_sparse_base_kernel(const 
 }
 
 // ------------------------------------------------------------------------------------------------------ launch 2
-// What the launch reads but never writes comes in through its own const __restrict__ arguments: hipcc may then take the wave-uniform
-// loads (column bounds, row ids, factor values, the per-line vectors) for what they are, whatever the lanes store into W meanwhile.
-// A row id is read as half of an aligned 32-bit word (the plan's sections are 16-byte aligned).
-__device__ __forceinline__ size_t cs_row(const uint32_t* __restrict__ row32, int i) {
-    const uint32_t wd = row32[i >> 1];
-    return (size_t)((i & 1) ? wd >> 16 : wd & 0xffffu) * 64;
-}
-// W[r] = fma(-v, y, W[r]) for the B entries at i of one column: the rows of a column are distinct, so the B loads go out together
-template <int B>
-__device__ __forceinline__ void cs_update(float* __restrict__ W, const uint32_t* __restrict__ row32, const float* __restrict__ fac, int i, float y) {
-    size_t r[B];
-    float f[B], w[B];
-#pragma unroll
-    for (int u = 0; u < B; ++u) {
-        r[u] = cs_row(row32, i + u);
-        f[u] = fac[i + u];
-    }
-#pragma unroll
-    for (int u = 0; u < B; ++u) w[u] = W[r[u]];
-#pragma unroll
-    for (int u = 0; u < B; ++u) W[r[u]] = fmaf(-f[u], y, w[u]);
-}
-__device__ __forceinline__ void cs_column(float* __restrict__ W, const uint32_t* __restrict__ row32, const float* __restrict__ fac, int cb, int ce,
-                                          float y) {
-    int i = cb;
-    for (; i + 8 <= ce; i += 8) cs_update<8>(W, row32, fac, i, y);
-    if (i + 4 <= ce) {
-        cs_update<4>(W, row32, fac, i, y);
-        i += 4;
-    }
-    for (; i < ce; ++i) cs_update<1>(W, row32, fac, i, y);
-}
-
+// (what the launch reads but never writes comes in through its own const __restrict__ arguments: contingency_sparse_core.hpp)
 template <bool LDS>
 __global__ __launch_bounds__(64) void contingency_sparse_outages_kernel(const unsigned char* __restrict__ plan, const unsigned char* __restrict__ slabs,
                                                                         float* __restrict__ blocks, const int32_t* __restrict__ status,
@@ -272,35 +183,7 @@ __global__ __launch_bounds__(64) void contingency_sparse_outages_kernel(const un
         // an islanding outage keeps a zero right-hand side: +inf, -1, -1 and a NaN row in the end
         const bool run = live && islands[kc] == 0;
         const int pi = pa[kc], pj = pb[kc];
-        // ---- the right-hand side e_i - e_j in plan order; a slack end adds nothing
-        for (int r = 0; r < m; ++r) W[(size_t)r * 64] = 0.f;
-        if (run) {
-            if (pi < m) W[(size_t)pi * 64] += 1.f;
-            if (pj < m) W[(size_t)pj * 64] -= 1.f;
-        }
-        // ---- L y = rhs, columns ascending: the bounds of the next column are requested while this one runs
-        int lb = diag[0] + 1, le = colptr[1];
-        for (int j = 0; j < m; ++j) {
-            const int cb = lb, ce = le;
-            if (j + 1 < m) {
-                lb = diag[j + 1] + 1;
-                le = colptr[j + 2];
-            }
-            if (cb >= ce) continue;
-            cs_column(W, row32, fac, cb, ce, W[(size_t)j * 64]);
-        }
-        // ---- U x = y, columns descending
-        int ub = colptr[m - 1], ue = diag[m - 1];
-        for (int j = m - 1; j >= 0; --j) {
-            const int cb = ub, ce = ue;
-            if (j > 0) {
-                ub = colptr[j - 1];
-                ue = diag[j - 1];
-            }
-            const float x = W[(size_t)j * 64] / fac[ce];
-            W[(size_t)j * 64] = x;
-            cs_column(W, row32, fac, cb, ce, x);
-        }
+        cs_substitute(W, colptr, diag, row32, fac, m, run, pi, pj);
         // ---- den_k from two gathers, then the lines in ascending order: post-outage flow, loading, the running maximum
         const float den = ct_den(W[(size_t)pi * 64], W[(size_t)pj * 64], x32[kc]);
         const float fk = f32[kc];
@@ -328,11 +211,48 @@ __global__ __launch_bounds__(64) void contingency_sparse_outages_kernel(const un
     }
 }
 
-static int cs_check_header(const int32_t* h, const char* who) {
+int cs_check_header(const int32_t* h, const char* who) {
     PFN_TRY(pf_check_plan_header(who, h));
     PFN_CHECK_ARG(h[PFP_H_MODE] == 1, "%s: the screen takes a mode-1 (\"dc\") plan; this one has mode %d", who, (int)h[PFP_H_MODE]);
     PFN_CHECK_ARG(h[PFP_H_N] >= 2 && h[PFP_H_M] == h[PFP_H_N] - 1, "%s: the plan header is inconsistent", who);
     return PFN_OK;
+}
+
+int cs_check_call(const char* who, const CsCall& c, PfProblem* p, size_t* base_lds) {
+    const int32_t* h = static_cast<const int32_t*>(c.plan_header);
+    PFN_TRY(cs_check_header(h, who));
+    PFN_CHECK_ARG(c.n_bus >= 2 && c.n_lines >= 0 && c.n_lines < (1ll << 24) && c.n_bus < (1ll << 24),
+                  "%s: bad sizes (%lld scenarios of %lld buses and %lld lines)", who, (long long)c.n_samples, (long long)c.n_bus, (long long)c.n_lines);
+    PFN_CHECK_ARG(c.n_pv >= 0 && c.n_pq >= 0 && c.n_pv + c.n_pq == c.n_bus - 1,
+                  "%s: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses", who, (long long)c.n_pv, (long long)c.n_pq,
+                  (long long)c.n_bus);
+    PFN_CHECK_ARG(h[PFP_H_N] == c.n_bus && h[PFP_H_E] == c.n_lines, "%s: the plan is for %d buses and %d lines; the call has %lld and %lld", who,
+                  (int)h[PFP_H_N], (int)h[PFP_H_E], (long long)c.n_bus, (long long)c.n_lines);
+    PFN_CHECK_ARG(c.block_route >= 0 && c.block_route <= 2, "%s: block_route must be 0 (auto), 1 (LDS) or 2 (global)", who);
+    PFN_CHECK_ARG(c.groups >= 0, "%s: groups must be 0 (the default) or the number of one-wave workgroups", who);
+    const int n = h[PFP_H_N], m = h[PFP_H_M], e = (int)c.n_lines;
+    PFN_TRY(pf_check_sparse_launch(who, c.threads, nullptr, c.n_samples, h, m));
+    // (the screen writes no table and no residual: pf_check_call looks at a stand-in and at base_flow in their places)
+    static double table_stand_in[4] __attribute__((aligned(32)));
+    *p = PfProblem{c.edge_index, c.rx, c.bus_type, c.spec, nullptr, table_stand_in, c.status, c.base_flow, c.flags, c.ws, c.tol, n, e, c.max_iter,
+                   nullptr, nullptr};
+    PFN_TRY(pf_check_call(who, *p, c.n_samples, &c.plan_dev, "the workspace and the plan 16-byte"));
+    p->table = nullptr;
+    p->residual = nullptr;
+    PFN_CHECK_ARG(c.block_route != 1 || cs_block_fits_lds(m), "%s: block_route 1 (LDS): an outage block of %d unknowns needs %zu bytes of LDS, %d are there",
+                  who, m, cs_block_bytes(m), kLdsCuBytes - kLdsReserve);
+    *base_lds = pf_lds_bytes(m);
+    PFN_CHECK_ARG(*base_lds <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns needs %zu bytes of LDS, %d are there", who, m,
+                  *base_lds, kLdsCuBytes - kLdsReserve);
+    return PFN_OK;
+}
+
+int cs_launch_base(const CsArgs& a, const int32_t* h, int threads, int64_t n_samples, size_t base_lds, hipStream_t s) {
+    const double madds = (double)(((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]);
+    const double ss = (double)n_samples, ee = (double)a.p.e, nz = (double)a.nnz;
+    ProfScope ps("contingency_sparse_base", ss * (ee * 44.0 + (double)a.p.n * 32.0 + nz * 4.0) + (double)h[PFP_H_BYTES], ss * 2.0 * (madds + 4.0 * nz), s);
+    return pf_launch_sparse<2>(contingency_sparse_base_kernel<64>, contingency_sparse_base_kernel<256>, threads, h[PFP_H_MAX_COL], n_samples, base_lds,
+                               s, a);
 }
 
 }  // namespace pfn
@@ -359,36 +279,18 @@ int pfn_contingency_sparse(const int64_t* edge_index, int64_t n_lines, const dou
                            void* stream) {
     const char* who = "pfn_contingency_sparse";
     const int32_t* h = static_cast<const int32_t*>(plan_header);
-    PFN_TRY(cs_check_header(h, who));
-    PFN_CHECK_ARG(n_bus >= 2 && n_lines >= 0 && n_lines < (1ll << 24) && n_bus < (1ll << 24),
-                  "%s: bad sizes (%lld scenarios of %lld buses and %lld lines)", who, (long long)n_samples, (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(n_pv >= 0 && n_pq >= 0 && n_pv + n_pq == n_bus - 1, "%s: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses",
-                  who, (long long)n_pv, (long long)n_pq, (long long)n_bus);
-    PFN_CHECK_ARG(h[PFP_H_N] == n_bus && h[PFP_H_E] == n_lines, "%s: the plan is for %d buses and %d lines; the call has %lld and %lld", who,
-                  (int)h[PFP_H_N], (int)h[PFP_H_E], (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(block_route >= 0 && block_route <= 2, "%s: block_route must be 0 (auto), 1 (LDS) or 2 (global)", who);
-    PFN_CHECK_ARG(groups >= 0, "%s: groups must be 0 (the default) or the number of one-wave workgroups", who);
-    const int n = h[PFP_H_N], m = h[PFP_H_M], nnz = h[PFP_H_NNZ], e = (int)n_lines;
-    PFN_TRY(pf_check_sparse_launch(who, threads, nullptr, n_samples, h, m));
-    // (the screen writes no table and no residual: pf_check_call looks at a stand-in and at base_flow in their places)
-    static double table_stand_in[4] __attribute__((aligned(32)));
-    PfProblem p{edge_index, rx, bus_type, spec, nullptr, table_stand_in, status, base_flow, flags, ws, tol, n, e, max_iter, nullptr, nullptr};
-    PFN_TRY(pf_check_call(who, p, n_samples, &plan_dev, "the workspace and the plan 16-byte"));
-    p.table = nullptr;
-    p.residual = nullptr;
-    const bool fits = cs_block_fits_lds(m);
-    PFN_CHECK_ARG(block_route != 1 || fits, "%s: block_route 1 (LDS): an outage block of %d unknowns needs %zu bytes of LDS, %d are there", who, m,
-                  cs_block_bytes(m), kLdsCuBytes - kLdsReserve);
-    const size_t lds1 = pf_lds_bytes(m);
-    PFN_CHECK_ARG(lds1 <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: a work vector of %d unknowns needs %zu bytes of LDS, %d are there", who, m, lds1,
-                  kLdsCuBytes - kLdsReserve);
+    PfProblem p;
+    size_t lds1;
+    PFN_TRY(cs_check_call(who, CsCall{edge_index, n_lines, rx, bus_type, spec, n_samples, n_bus, n_pv, n_pq, tol, max_iter, base_flow, status, flags, ws,
+                                      plan_header, plan_dev, threads, block_route, groups}, &p, &lds1));
     if (n_samples == 0 || n_lines == 0) return PFN_OK;
+    const int n = h[PFP_H_N], m = h[PFP_H_M], nnz = h[PFP_H_NNZ], e = (int)n_lines;
     PFN_CHECK_ARG(islands && severity && worst_line && overloads && base_flow, "%s: null pointer", who);
     PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(ratings) & 7) == 0 &&
                       ((reinterpret_cast<uintptr_t>(islands) | reinterpret_cast<uintptr_t>(severity) | reinterpret_cast<uintptr_t>(worst_line) |
                         reinterpret_cast<uintptr_t>(overloads) | reinterpret_cast<uintptr_t>(post_flow)) & 3) == 0,
                   "%s: ratings must be 8-byte aligned, fp32 and int32 arrays 4-byte", who);
-    const bool lds = block_route == 1 || (block_route == 0 && fits);
+    const bool lds = block_route == 1 || (block_route == 0 && cs_block_fits_lds(m));
     const size_t stride = cs_sample_bytes(n, m, nnz, e), slabs = (size_t)n_samples * stride;
     const int64_t G = cs_groups(n_samples, e, groups);
     PFN_TRY(pf_check_workspace(who, ws, ws_bytes, slabs + (lds ? 0 : (size_t)G * cs_block_bytes(m))));
@@ -396,14 +298,9 @@ int pfn_contingency_sparse(const int64_t* edge_index, int64_t n_lines, const dou
                    lds ? nullptr : reinterpret_cast<float*>(static_cast<unsigned char*>(ws) + slabs), stride, m, nnz, (int)n_pv,
                    ratings_per_sample != 0, pf_f_in_lds(m)};
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const double madds = (double)(((int64_t)h[PFP_H_MADDS_HI] << 32) | (uint32_t)h[PFP_H_MADDS_LO]);
-    const double ss = (double)n_samples, ee = (double)e, nz = (double)nnz;
+    PFN_TRY(cs_launch_base(a, h, threads, n_samples, lds1, s));
     {
-        ProfScope ps("contingency_sparse_base", ss * (ee * 44.0 + (double)n * 32.0 + nz * 4.0) + (double)h[PFP_H_BYTES], ss * 2.0 * (madds + 4.0 * nz), s);
-        PFN_TRY(pf_launch_sparse<2>(contingency_sparse_base_kernel<64>, contingency_sparse_base_kernel<256>, threads, h[PFP_H_MAX_COL], n_samples,
-                                    lds1, s, a));
-    }
-    {
+        const double ss = (double)n_samples, ee = (double)e, nz = (double)nnz;
         const double tl = (double)cs_tiles(e);
         ProfScope ps("contingency_sparse_outages", ss * (tl * (nz * 6.0 + ee * 20.0) + ee * (12.0 + (post_flow ? 4.0 * ee : 0.0))),
                      ss * tl * 64.0 * (2.0 * nz + 8.0 * ee), s);

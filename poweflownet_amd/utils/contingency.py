@@ -5,9 +5,10 @@ outages that cut buses off the slack; `pfn_contingency_dc`, one workgroup per sc
 `verify_contingencies` re-solves chosen (scenario, outage) pairs with the unchanged AC solver on the reduced line lists and reports
 the AC current loadings beside the DC screen's.  Beyond the dense cap (n - 1 > `max_unknowns()`) `route="sparse"` keeps the sparse
 fp32 FACTOR of B' under a `sparse_plan(..., mode="dc")` and substitutes 64 outages at a time (csrc/contingency_sparse.hip:
-`pfn_contingency_sparse`, two launches behind the islands).  `contingency_screen_pairs` is the N-2 screen of the dense route: every
-pair of candidate lines out together, a rank-2 update of the same inverse (csrc/contingency_pairs.hip: `pfn_contingency_pair_islands`,
-`pfn_contingency_pairs`), and `verify_pair_contingencies` its AC check.  No CPU path."""
+`pfn_contingency_sparse`, two launches behind the islands).  `contingency_screen_pairs` is the N-2 screen: every pair of candidate
+lines out together, a rank-2 update of the same inverse (csrc/contingency_pairs.hip: `pfn_contingency_pair_islands`,
+`pfn_contingency_pairs`) or, with `route="sparse"`, of one substituted column per candidate under the same plan
+(csrc/contingency_pairs_sparse.hip: `pfn_contingency_pairs_sparse`); `verify_pair_contingencies` is its AC check.  No CPU path."""
 import ctypes as C
 import operator
 from dataclasses import dataclass
@@ -19,6 +20,7 @@ from .powerflow import STATUS, SparsePlan, cover_plan, solve_power_flow  # noqa:
 
 _ROUTES = {"auto": 0, "lds": 1, "global": 2}
 _BLOCKS = {"auto": 0, "lds": 1, "global": 2}
+_COLUMNS = {"auto": 0, "lds": 1, "global": 2}
 _COUNTS_ATTR = "_pfn_bus_counts"  # on a bus_type tensor: (version, (n_pv, n_pq, slack)) -- one host read per tensor
 
 
@@ -86,7 +88,8 @@ class PairContingencyResult:
     scenario failed).  `pairs` [P, 2] int64: the two lines of pair p, in `pair_lines`' order.  `islands` [P] int32: buses cut off
     the slack with both lines removed (-4: a line names a bus outside the grid).  `base_flow` [S, e] float64 and `status` [S] int32
     carry `contingency_screen`'s bits for the same inputs.  `post_flow` [S, P, e] float32 with `keep_table`, else None.  `flags` [1]
-    int32 (bit 0: `bus_type` changed under the launch).  All on the device; `route`: "lds" or "global"."""
+    int32 (bit 0: `bus_type` changed under the launch).  All on the device; `route`: "lds", "global" or "sparse" (there `block` says
+    where the column launch's blocks sat and `columns` where the pair launch's columns: "lds" or "global")."""
     severity: torch.Tensor
     worst_line: torch.Tensor
     overloads: torch.Tensor
@@ -97,6 +100,8 @@ class PairContingencyResult:
     post_flow: object
     route: str
     flags: object = None
+    block: object = None
+    columns: object = None
 
     def ranking(self, top):
         """(int64 [S, top] pair indices, [S, top] their severities): `ContingencyResult.ranking`'s order -- NaN first, then +inf,
@@ -245,9 +250,8 @@ def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8
                              post_flow=table, route="global" if need else "lds", flags=flags)
 
 
-def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_table, plan, block, groups, threads) -> ContingencyResult:
-    """`contingency_screen(route="sparse")`: islands, base, outages -- three launches, the one host read of `_bus_counts`."""
-    who = "contingency_screen"
+def _sparse_options(who, spec, edge_index, plan, block, groups, threads):
+    """what `route="sparse"` asks of its own options, on the host, before anything touches the library: both screens"""
     if block not in _BLOCKS:
         raise ValueError(f"{who}: block must be one of {sorted(_BLOCKS)}")
     if groups is not None and (isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups < 2 ** 31):
@@ -261,11 +265,21 @@ def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_
     if torch.is_tensor(spec) and spec.dim() == 3 and torch.is_tensor(edge_index) and edge_index.dim() == 2:
         if (plan.n, plan.e) != (int(spec.shape[1]), int(edge_index.shape[1])):
             raise ValueError(f"{who}: the plan is for (n, e) = {(plan.n, plan.e)}; the call has {(int(spec.shape[1]), int(edge_index.shape[1]))}")
+
+
+def _plan_device(who, plan, dev):
+    if plan.blob.device != dev:
+        raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
+
+
+def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_table, plan, block, groups, threads) -> ContingencyResult:
+    """`contingency_screen(route="sparse")`: islands, base, outages -- three launches, the one host read of `_bus_counts`."""
+    who = "contingency_screen"
+    _sparse_options(who, spec, edge_index, plan, block, groups, threads)
     S, n, e = _check(bus_type, spec, edge_index, rx, who)
     ratings = _ratings(ratings, S, e, who)
     dev = spec.device
-    if plan.blob.device != dev:
-        raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
+    _plan_device(who, plan, dev)
     n_pv, n_pq, slack = _bus_counts(bus_type)
     bt = bus_type.to(torch.int32).contiguous()
     spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
@@ -311,17 +325,36 @@ def _device_lines(lines, dev):
 
 
 def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, lines=None, tol=1e-8, max_iter=10, route="auto",
-                             keep_table=False) -> PairContingencyResult:
+                             keep_table=False, plan=None, block="auto", groups=None, threads=None, columns="auto",
+                             waves=None) -> PairContingencyResult:
     """Screen every PAIR of line outages among the candidate `lines` of every scenario under the DC model (N-2): inputs and their
     checks are `contingency_screen`'s.  `lines`: a host sequence or a CPU int64 tensor of line ids, strictly increasing and within
     [0, e), at least two (checked on the host, no device read; ValueError otherwise); None: all lines.  All e lines stay monitored
     whatever the candidates are -- N-1 first, then the pairs among its top outages, is how larger grids are screened.  With c
     candidates there are P = c (c - 1) / 2 pairs in `pair_lines`' order.  `route`: "auto", "lds" (raises where B'^-1 does not fit
-    LDS beside the pair launch's vectors) or "global" (the pair launch reads the workspace slab); the same bits.  Dense only: beyond
-    `max_unknowns()` it raises.  Three launches; one host read (the bus_type counts, once per tensor); nothing is read back."""
+    LDS beside the pair launch's vectors) or "global" (the pair launch reads the workspace slab); the same bits.  These are the dense
+    routes: beyond `max_unknowns()` they raise.  Three launches; one host read (the bus_type counts, once per tensor); nothing is
+    read back.
+
+    `route="sparse"` with `plan=sparse_plan(bus_type, edge_index, mode="dc")`: the same screen beyond `max_unknowns()` from the
+    sparse factor of `contingency_screen(route="sparse")` -- the same fields, pair order, definitions and statuses, plus status -6
+    where the device line list is not the plan's; `base_flow` and `status` carry that screen's bits.  Four launches (pair islands,
+    base, columns, pairs).  "auto" never takes it.  `block`, `groups`, `threads`: as in `contingency_screen`, for the launch that
+    substitutes one column per candidate, 64 candidates to a workgroup.  `columns`: where the pair launch keeps the two columns of
+    a pair -- "auto" (LDS where 4 n (1 + waves) bytes fit), "lds" (raises where they do not) or "global" (gathered from the
+    workspace); `waves`: the pair launch's waves per (scenario, first candidate), None (4), 1, 2, 4, 8 or 16.  No bit depends on
+    any of them."""
     who = "contingency_screen_pairs"
-    if route not in _ROUTES:
-        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    if route == "sparse":
+        _sparse_options(who, spec, edge_index, plan, block, groups, threads)
+        if columns not in _COLUMNS:
+            raise ValueError(f"{who}: columns must be one of {sorted(_COLUMNS)}")
+        if isinstance(waves, bool) or waves not in (None, 1, 2, 4, 8, 16):
+            raise ValueError(f"{who}: waves must be None, 1, 2, 4, 8 or 16; got {waves!r}")
+    elif route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES) + ['sparse']}")
+    elif plan is not None or block != "auto" or groups is not None or threads is not None or columns != "auto" or waves is not None:
+        raise ValueError(f"{who}: plan, block, groups, threads, columns and waves go with route='sparse' only")
     e_given = int(edge_index.shape[1]) if torch.is_tensor(edge_index) and edge_index.dim() == 2 else None
     if lines is not None:                                                     # on the host, before anything touches the library
         lines = _candidates(lines, who)
@@ -336,11 +369,14 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
         raise ValueError(f"{who}: a grid of {e} line has no pair to screen")
     lib = L.load()
     cap = int(lib.pfn_powerflow_max_unknowns())
-    if n - 1 > cap:
-        raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); a sparse pair screen is not built")
+    if route != "sparse" and n - 1 > cap:
+        raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); beyond it: "
+                         f"route='sparse' with plan=sparse_plan(bus_type, edge_index, mode='dc')")
     ratings = _ratings(ratings, S, e, who)
-    n_pv, n_pq, slack = _bus_counts(bus_type)
     dev = spec.device
+    if route == "sparse":
+        _plan_device(who, plan, dev)
+    n_pv, n_pq, slack = _bus_counts(bus_type)
     bt = bus_type.to(torch.int32).contiguous()
     spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
     if lines is None:                                                         # all lines: built on the device, nothing uploaded
@@ -359,20 +395,37 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
     status = torch.empty(S, dtype=torch.int32, device=dev)
     flags = torch.zeros(1, dtype=torch.int32, device=dev)
     table = torch.empty(S, P, e, dtype=torch.float32, device=dev) if keep_table else None
-    need = int(lib.pfn_contingency_pairs_workspace_bytes(S, n, e, c, 2)) if S else 0
-    in_lds = route != "global" and int(lib.pfn_contingency_pairs_workspace_bytes(1, n, e, c, 1)) != 0
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    out = dict(severity=severity, worst_line=worst, overloads=overloads, islands=islands, pairs=pairs, base_flow=base_flow, status=status,
+               post_flow=table, flags=flags)
+    per_sample = int(ratings is not None and ratings.dim() == 2)
     with torch.cuda.device(dev):
         L.check(lib.pfn_contingency_pair_islands(edge_index.data_ptr(), e, n, slack, lines_d.data_ptr(), c, islands.data_ptr(), L.stream_ptr()),
                 "pfn_contingency_pair_islands")
-        L.check(lib.pfn_contingency_pairs(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
-                                          int(ratings is not None and ratings.dim() == 2), lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv,
-                                          n_pq, float(tol), int(max_iter), _ROUTES[route], severity.data_ptr(), worst.data_ptr(),
-                                          overloads.data_ptr(), base_flow.data_ptr(), status.data_ptr(), L.ptr(table), flags.data_ptr(),
-                                          ws.data_ptr(), need, L.stream_ptr()),
+        if route == "sparse":
+            header, g, w = C.addressof(plan.header), 0 if groups is None else groups, 0 if waves is None else waves
+            size = lib.pfn_contingency_pairs_sparse_workspace_bytes
+            need = int(size(S, e, c, header, _BLOCKS[block], g, _COLUMNS[columns], w)) if S else 0
+            # what "auto" took, by what the forced placements would be given: 0 where the call refuses them
+            block_lds = block != "global" and int(size(1, e, c, header, 1, g, 2, w)) != 0
+            columns_lds = columns != "global" and int(size(1, e, c, header, 2, g, 1, w)) != 0
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            L.check(lib.pfn_contingency_pairs_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings), per_sample,
+                                                     lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv, n_pq, float(tol), int(max_iter),
+                                                     severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(),
+                                                     status.data_ptr(), L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, header,
+                                                     plan.blob.data_ptr(), 0 if threads is None else threads, _BLOCKS[block], g, _COLUMNS[columns], w,
+                                                     L.stream_ptr()),
+                    "pfn_contingency_pairs_sparse")
+            return PairContingencyResult(route="sparse", block="lds" if block_lds else "global", columns="lds" if columns_lds else "global", **out)
+        need = int(lib.pfn_contingency_pairs_workspace_bytes(S, n, e, c, 2)) if S else 0
+        in_lds = route != "global" and int(lib.pfn_contingency_pairs_workspace_bytes(1, n, e, c, 1)) != 0
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        L.check(lib.pfn_contingency_pairs(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings), per_sample,
+                                          lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv, n_pq, float(tol), int(max_iter), _ROUTES[route],
+                                          severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(), status.data_ptr(),
+                                          L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, L.stream_ptr()),
                 "pfn_contingency_pairs")
-    return PairContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, pairs=pairs, base_flow=base_flow,
-                                 status=status, post_flow=table, route="lds" if in_lds else "global", flags=flags)
+    return PairContingencyResult(route="lds" if in_lds else "global", **out)
 
 
 def summarise_loadings(loading, monitored):

@@ -28,7 +28,17 @@ The N-2 pair screen (`contingency_screen_pairs`), same protocol: the 
 outages with the largest severity over the scenarios (the N-1 screen's, unrated), every pair of them is screened -- three launches:
 pair islands, one B' inverse per scenario, the rank-2 updates -- on the route "auto" picks and, where that is "lds", on the forced
 "global" route too; time per (scenario, pair), the base and the pair launch apart (the library's event brackets, a pass of their
-own), beside the brute force: `solve_power_flow(mode="dc")` over explicit [2, e - 2] lists, one per (scenario, non-islanding pair)."""
+own), beside the brute force: `solve_power_flow(mode="dc")` over explicit [2, e - 2] lists, one per (scenario, non-islanding pair).
+
+    python tools/contingency_bench.py --pairs --route sparse [--shape 118x186 --shape 6470x9005] [--samples 64] [--candidates 64]
+                                      [--waves-sweep 1 2 4 8 16] [--brute-pairs 64]
+
+The pair screen on the sparse route (`contingency_screen_pairs(route="sparse")`), same protocol.  Per shape a row per
+`waves` of the sweep and per column placement the shape allows with it: the wall time of the four launches, the islands, base,
+columns and pairs launch apart (the library's event brackets, a pass of their own) and the pair-islands launch's share.  Beside it,
+alternating in the same child: the dense pair screen where the shape is within its cap, else the brute force the parent commit has
+there -- `solve_power_flow(mode="dc", route="sparse", plan=<cover plan of the base list>)` over explicit [2, e - 2] lists of
+`--brute-pairs` non-islanding pairs spread evenly over the pair list, one per scenario, scaled per pair."""
 import argparse
 import json
 import os
@@ -164,6 +174,97 @@ def main_pairs(a):
     return 0
 
 
+def child_pairs_sparse(shape, samples, candidates, columns, waves, brute_pairs, repeats):
+    import torch
+    from poweflownet_amd import _lib as L
+    from poweflownet_amd.synth import make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen, contingency_screen_pairs
+    from poweflownet_amd.utils.powerflow import cover_plan, max_unknowns, solve_power_flow, sparse_plan
+    dev = torch.device("cuda:0")
+    n, e = (int(v) for v in shape.split("x"))
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    plan = sparse_plan(bt, ei, mode="dc")
+    single = contingency_screen(bt, spec, ei, rx, route="sparse", plan=plan)   # (not timed: its severities choose the candidates)
+    sev = torch.where(single.islands[None, :] == 0, single.severity, torch.full_like(single.severity, -1.0)).max(dim=0).values
+    lines = sorted(torch.topk(sev, min(candidates, int((single.islands == 0).sum()))).indices.tolist())
+    kw = {"route": "sparse", "plan": plan, "lines": lines, "columns": columns, "waves": waves}
+    res = contingency_screen_pairs(bt, spec, ei, rx, **kw)                  # (warm-up; its islands choose the brute force's pairs)
+    assert bool((res.status >= 0).all())
+    P = int(res.pairs.shape[0])
+    dense = n - 1 <= max_unknowns()
+    if dense:
+        def other():
+            return contingency_screen_pairs(bt, spec, ei, rx, lines=lines)
+        other_pairs = samples * P
+    else:
+        ok = res.pairs[res.islands == 0]
+        out = ok[torch.linspace(0, ok.shape[0] - 1, min(brute_pairs, ok.shape[0])).long()]    # [T, 2], a < b
+        T = int(out.shape[0])
+        idx = torch.arange(e - 2, device=dev)[None, :].expand(T, e - 2)
+        for k in range(2):
+            idx = idx + (idx >= out[:, k:k + 1])
+        lists = ei[:, idx].permute(1, 0, 2).contiguous()
+        sc = torch.arange(T, device=dev) % samples
+        rx_b, spec_b = rx[sc[:, None], idx].contiguous(), spec[sc].contiguous()
+        cover = cover_plan(bt, ei[None], mode="dc", base=ei)
+
+        def other():
+            return solve_power_flow(bt, spec_b, lists, rx_b, mode="dc", route="sparse", plan=cover)
+        other_pairs = T
+    assert bool((other().status >= 0).all())                               # (warm-up)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    t_screen, t_other = [], []
+    for _ in range(repeats):
+        t_screen.append(timed(lambda: contingency_screen_pairs(bt, spec, ei, rx, **kw)))
+        t_other.append(timed(other))
+    L.profile_report(reset=True)
+    L.profile_enable(True)                                                  # the four launches apart: event brackets, a pass of their own
+    for _ in range(repeats):
+        contingency_screen_pairs(bt, spec, ei, rx, **kw)
+    prof = L.profile_report()
+    L.profile_enable(False)
+    ms = {k: prof[name]["ms"] / repeats for k, name in (("islands_ms", "contingency_pair_islands"), ("base_ms", "contingency_sparse_base"),
+                                                         ("columns_ms", "contingency_pairs_sparse_columns"), ("pairs_ms", "contingency_pairs_sparse"))}
+    screen_s, other_s = statistics.median(t_screen), statistics.median(t_other)
+    print(json.dumps({"buses": n, "lines": e, "scenarios": samples, "candidates": len(lines), "pairs": P, "block": res.block, "columns": res.columns,
+                      "waves": waves or 4, "unknowns": plan.m, "nnz_l": plan.nnz_l, "screen_ms": 1e3 * screen_s, **ms,
+                      "islands_share": ms["islands_ms"] / sum(ms.values()), "screen_us_per_pair": 1e6 * screen_s / (samples * P),
+                      "other": "dense pair screen" if dense else "brute force", "other_pairs": other_pairs, "other_ms": 1e3 * other_s,
+                      "other_us_per_pair": 1e6 * other_s / other_pairs, "ratio": (other_s / other_pairs) / (screen_s / (samples * P))}))
+
+
+def main_pairs_sparse(a):
+    out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "rows": []}
+    for shape in a.shape or ["118x186", "6470x9005"]:
+        n = int(shape.split("x")[0])
+        for waves in a.waves_sweep:
+            for columns in (("lds", "global") if 4 * n * (1 + waves) + 15 <= 159 * 1024 else ("global",)):
+                rows = []
+                for _ in range(a.processes):
+                    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-pairs-sparse", shape, "--samples", str(a.samples),
+                                        "--candidates", str(a.candidates), "--columns", columns, "--waves", str(waves), "--brute-pairs",
+                                        str(a.brute_pairs), "--repeats", str(a.repeats)], capture_output=True, text=True, timeout=900)
+                    if r.returncode != 0:
+                        raise SystemExit(f"contingency_bench: the child for {shape} {columns} waves {waves} failed:\n{r.stdout}\n{r.stderr}")
+                    rows.append(json.loads(r.stdout.strip().splitlines()[-1]))
+                row = dict(rows[0])
+                for key in ("screen_ms", "islands_ms", "base_ms", "columns_ms", "pairs_ms", "islands_share", "screen_us_per_pair", "other_ms",
+                            "other_us_per_pair", "ratio"):
+                    vals = [x[key] for x in rows]
+                    row[key] = round(statistics.median(vals), 5)
+                    row[key + "_spread"] = [round(min(vals), 5), round(max(vals), 5)]
+                out["rows"].append(row)
+                print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
+
+
 def child_sparse(shape, samples, block, groups_x, brute_pairs, repeats):
     import torch
     from poweflownet_amd import _lib as L
@@ -266,7 +367,16 @@ def main(argv=None):
     ap.add_argument("--pairs", action="store_true", help="the N-2 pair screen, contingency_screen_pairs, DESIGN 7w")
     ap.add_argument("--candidates", type=int, default=16, help="pairs: the K worst non-islanding single outages are the candidates")
     ap.add_argument("--child-pairs", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--waves-sweep", type=int, nargs="*", default=[1, 2, 4, 8, 16], help="pairs, sparse: the pair launch's waves per workgroup")
+    ap.add_argument("--child-pairs-sparse", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--columns", default="auto", help=argparse.SUPPRESS)
+    ap.add_argument("--waves", type=int, default=0, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_pairs_sparse:
+        child_pairs_sparse(a.child_pairs_sparse, a.samples, a.candidates, a.columns, a.waves or None, a.brute_pairs, a.repeats)
+        return 0
+    if a.pairs and a.route == "sparse":
+        return main_pairs_sparse(a)
     if a.child_pairs:
         child_pairs(a.child_pairs, a.samples, a.candidates, a.brute_solves, a.repeats)
         return 0
