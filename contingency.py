@@ -17,6 +17,13 @@ DC plan --: the candidates are the union over the scenarios of each scenario's t
 10), every pair of them is screened with all lines monitored, the worst pairs of every scenario are AC-verified
 (`verify_pair_contingencies`, on the sparse solver where the screen took the sparse route), and
 results/<case>_contingency_pairs_{severity,worst_line,overloads,islands,pairs}.npy are written too.
+
+--model-run-id R [--cfg_json C] asks the trained NETWORK as well (`contingency_screen_model`): the checkpoint
+models/model_R.pt is loaded into the MaskEmbdMultiMPN that C describes (default configs/standard.json), the way error_per_feature.py
+loads it; the normalisation statistics are `<data-dir>/params/data_params_R.pt` where that file exists, else those of the training
+split of --data-dir (synthetic scenarios have none: identity).  Beside each scenario's top DC outages it prints the network's top
+outages with their AC-verified loadings (`verify_contingencies` on the network's result) and writes
+results/<case>_contingency_model_{severity,worst_line,overloads}.npy.  Without --model-run-id nothing changes.
 """
 import argparse
 import os
@@ -54,6 +61,8 @@ def main(argv=None):
     ap.add_argument("--candidates", type=int, default=10, help="--pairs: every scenario's top K non-islanding outages are candidates")
     ap.add_argument("--split", type=float, nargs=3, default=[.5, .2, .3], help="train / val / test fractions of the dataset")
     ap.add_argument("--out-dir", default="results")
+    ap.add_argument("--model-run-id", default=None, help="also screen with the network of models/model_<id>.pt (contingency_screen_model)")
+    ap.add_argument("--cfg_json", default="configs/standard.json", help="--model-run-id: the network's hidden_dim, n_gnn_layers, K")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
@@ -94,7 +103,61 @@ def main(argv=None):
         np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_{name}.npy"), getattr(res, name).cpu().numpy())
     if a.pairs:
         screen_pairs(a, res, islands, bt, spec, ei, rx, ratings, kw, solver_kw)
+    if a.model_run_id is not None:
+        screen_model(a, islands, bt, spec, ei, rx, ratings, solver_kw)
     return 0
+
+
+def model_statistics(a):
+    """{xymean, xystd, edgemean, edgestd} of the run: its saved parameters, else the training split's own; synthetic: none"""
+    import torch
+    if a.data_dir is None:
+        print("synthetic scenarios carry no statistics: the network sees them un-normalised")
+        return {}
+    names = ("xymean", "xystd", "edgemean", "edgestd")
+    params = os.path.join(a.data_dir, "params", f"data_params_{a.model_run_id}.pt")
+    if os.path.exists(params):
+        p = torch.load(params, map_location="cpu")
+        return {k: p[k] for k in names}
+    from poweflownet_amd.datasets import PowerFlowData
+    print(f"no {params}: the statistics of the training split are taken")
+    train = PowerFlowData(root=a.data_dir, case=a.case, split=list(a.split), task="train")
+    return dict(zip(names, train.get_data_means_stds()))
+
+
+def screen_model(a, islands, bt, spec, ei, rx, ratings, solver_kw):
+    """--model-run-id: the network's screen of the same scenarios, its worst outages AC-verified, and the three result files"""
+    import json
+
+    from poweflownet_amd.networks.MPN import MaskEmbdMultiMPN
+    from poweflownet_amd.utils.contingency import contingency_screen_model, verify_contingencies
+    from poweflownet_amd.utils.evaluation import load_model
+    cfg_path = a.cfg_json if os.path.exists(a.cfg_json) else os.path.join(os.path.dirname(os.path.abspath(__file__)), a.cfg_json)
+    with open(cfg_path) as f:
+        cfg = json.load(f)
+    model = MaskEmbdMultiMPN(nfeature_dim=4, efeature_dim=2, output_dim=4, hidden_dim=int(cfg["hidden_dim"]), n_gnn_layers=int(cfg["n_gnn_layers"]),
+                             K=int(cfg["K"]), dropout_rate=float(cfg["dropout_rate"])).to(spec.device)
+    model, _ = load_model(model, a.model_run_id, spec.device)
+    res = contingency_screen_model(model, bt, spec, ei, rx, ratings, **model_statistics(a))
+    S, e = int(spec.shape[0]), int(ei.shape[1])
+    print(f"network {a.model_run_id}: {S} scenarios x {e} outages in chunks of {res.chunk} items")
+    top = min(a.verify_top, int((islands == 0).sum()))
+    ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top, **solver_kw)
+    pairs, net, ac = ver.pairs.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy()    # (dc_severity: the network's figure)
+    net_worst, ac_worst = res.worst_line[ver.pairs[:, 0], ver.pairs[:, 1]].cpu().numpy(), ver.worst_line.cpu().numpy()
+    status = ver.status.cpu().numpy()
+    for s in range(S):
+        rows = [f"line {pairs[t, 1]}: network {net[t]:.3f} AC {'failed' if status[t] < 0 else format(ac[t], '.3f')} "
+                f"worst line {net_worst[t]}{'=' if net_worst[t] == ac_worst[t] else '!='}{ac_worst[t]}" for t in np.flatnonzero(pairs[:, 0] == s)]
+        print(f"scenario {s} network: " + "; ".join(rows))
+    solved = status >= 0
+    with np.errstate(invalid="ignore"):
+        gap = np.abs(net - ac)[solved & np.isfinite(net)]
+    print(f"{len(pairs)} pairs verified, {int((~solved).sum())} AC solves failed; worst line agrees in {int((solved & (net_worst == ac_worst)).sum())}; "
+          f"|network - AC| severity: mean {gap.mean() if gap.size else float('nan'):.3g}, max {gap.max() if gap.size else float('nan'):.3g}; "
+          f"{int((solved & (net < 1) & (ac > 1)).sum())} of {int((solved & (net < 1)).sum())} the network called secure are overloaded under AC")
+    for name in ("severity", "worst_line", "overloads"):
+        np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_model_{name}.npy"), getattr(res, name).cpu().numpy())
 
 
 def screen_pairs(a, res, islands, bt, spec, ei, rx, ratings, kw, solver_kw):

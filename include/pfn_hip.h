@@ -942,6 +942,46 @@ int pfn_contingency_pairs_sparse(const int64_t* edge_index, int64_t n_lines, con
                                  const void* plan_dev, int threads, int block_route, int groups, int column_route, int waves,
                                  void* stream);
 
+/* N-1 with the NETWORK's prediction (csrc/contingency_model.hip): the two launches around a model forward.  Work item
+ * t = s * n_lines + k is scenario s with line k out, islanding outages included, so every shape is static; a chunk is `chunk`
+ * consecutive items from item0[0] -- a DEVICE int64 word, so that one captured chunk serves every chunk of a screen.  Inputs as
+ * pfn_contingency_dc's (rx, spec DEVICE fp64, bus_type DEVICE int32, ONE line list); n_lines >= 2.  No host sync, no allocation
+ * (capturable), no atomics; an item's bits are a function of its own inputs, whatever the chunk.
+ *
+ * pfn_contingency_model_batch: one workgroup per chunk position b; its item is item0[0] + b clamped to the last item (the tail of
+ * the last chunk repeats it).  It writes what the dataset plus its collate produce for the graph "scenario s without line k":
+ *   x            fp32 [chunk n_bus, 4] = (float(spec) * (1 - mask) - mean4) / div4, mask the bus type's row of (0,0,1,1) slack,
+ *                (0,1,0,1) PV, (1,1,0,0) PQ; every operation rounded on its own, in this order: the dataset's bits.  div4 / mean4 /
+ *                edge_div2 / edge_mean2 are HOST floats, div = std + 1e-7 formed in fp32 by the caller; null: 1 / 0.
+ *   pred_mask    fp32 [chunk n_bus, 4]; bus_type_out int64 [chunk n_bus].
+ *   edge_index_out  int64 [2, chunk (n_lines - 1)]: the lines l != k in stored order, bus ids offset by b n_bus, all sources then
+ *                all targets (collate's layout).  A line that names a bus outside [0, n_bus) sets bit 1 of flags[0] and is written as
+ *                the local pair (0, 0); pfn_contingency_islands reports -4 there.
+ *   edge_attr    fp32 [chunk (n_lines - 1), 2] = (float(rx) - edge_mean2) / edge_div2.
+ * The five tensors, spec and rx must be 16-byte aligned (16-byte stores and loads).
+ *
+ * pfn_contingency_model_loadings: one workgroup per chunk position; positions past the last item return at once.  `out` fp32
+ * [chunk n_bus, 4] is the forward's output.  Per bus the row is merged: out * std4 + mean4 (HOST floats, std = the divisor above;
+ * null: 1 / 0) where the mask says "predict", float(spec) where the entry is given.  (Vm, Va) become rectangular voltages with
+ * pfn_branch_flows' arithmetic, loading of line l != k is I_l / (float)rating_l with r, x = float(rx) -- the bits of
+ * pfn_branch_flows on the merged table and the reduced list -- and the reduction is pfn_contingency_dc's: severity fp32, worst_line
+ * and overloads int32, each [n_samples n_lines]; ratings, monitoring and the non-finite rule as there.  Where islands[k] != 0:
+ * +inf, -1, -1 and a NaN row.
+ *   loading      optional fp32 [n_samples n_lines, n_lines] (row = item, column = line of the ORIGINAL list; NaN at line k).
+ *   predictions  optional fp32 [n_samples n_lines, n_bus, 4]: the merged table (written for islanding items too).
+ *   route        0 auto, 1 LDS, 2 direct.  LDS: one sincos per bus, 8 n_bus bytes, up to pfn_contingency_model_lds_max_bus() buses;
+ *                direct: the phasors are formed per line end.  Same bits.
+ * PFN_EINVAL: bad sizes (n_lines < 2, chunk < 1), route 1 where it does not fit, null or misaligned pointers.                      */
+int64_t pfn_contingency_model_lds_max_bus(void);
+int pfn_contingency_model_batch(const int32_t* bus_type, const double* spec, const int64_t* edge_index, const double* rx, int64_t n_samples,
+                                int64_t n_bus, int64_t n_lines, const int64_t* item0, int64_t chunk, const float* div4, const float* mean4,
+                                const float* edge_div2, const float* edge_mean2, float* x, float* pred_mask, int64_t* bus_type_out,
+                                int64_t* edge_index_out, float* edge_attr, int32_t* flags, void* stream);
+int pfn_contingency_model_loadings(const float* out, const int32_t* bus_type, const double* spec, const int64_t* edge_index, const double* rx,
+                                   const double* ratings, int ratings_per_sample, const int32_t* islands, int64_t n_samples, int64_t n_bus,
+                                   int64_t n_lines, const int64_t* item0, int64_t chunk, const float* std4, const float* mean4, int route,
+                                   float* severity, int32_t* worst_line, int32_t* overloads, float* loading, float* predictions, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

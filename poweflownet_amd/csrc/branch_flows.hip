@@ -7,6 +7,7 @@
 // finished error table.  Pure functions of their inputs: one owner per (line, quantity), a fixed combine order, no float atomics.
 #include <algorithm>
 
+#include "branch_line.hpp"
 #include "pfn_internal.hpp"
 #include "reduce.hpp"
 
@@ -19,7 +20,7 @@ namespace pfn {
 // writes 16-byte rows.  Where 16 n_bus bytes do not fit the LDS of a compute unit (BF_LDS_MAX_BUS) the direct kernel forms the
 // phasors per line end from global memory.  Nothing here depends on the work split: every output element is a function of its
 // own inputs.
-constexpr int BF_LDS_MAX_BUS = (kLdsCuBytes - kLdsReserve) / 16;        // 10176 buses
+// (BF_LDS_MAX_BUS: branch_line.hpp)
 constexpr int BF_SMALL_THREADS = 256, BF_BIG_THREADS = 1024;
 constexpr int BF_BIG_LDS = 32 * 1024;              // a sample's phasors beyond this: few workgroups per CU, so each gets 16 waves
 
@@ -37,30 +38,8 @@ struct BfArgs {
     float std[2], mean[2], estd[2], emean[2];      // (Vm, Va) and (r, x)
 };
 
-// (e, f) of one bus row; the angle as bus_of (physics.hip) forms it.  No contraction: the direct kernel inlines this into the
-// line expressions, where vm * c - ... would otherwise fuse and differ from the value the LDS kernel stores
-__device__ __forceinline__ float2 bf_phasor(const float* __restrict__ table, int64_t row, bool norm, const float* sd, const float* mu) {
-#pragma clang fp contract(off)
-    const float2 v = *reinterpret_cast<const float2*>(table + 4 * row);
-    const float vm = norm ? denorm(v.x, sd[0], mu[0]) : v.x;
-    const float va = (norm ? denorm(v.y, sd[1], mu[1]) : v.y) * (3.14159265358979323846f / 180.0f);
-    float s, c;
-    sincosf(va, &s, &c);
-    return make_float2(vm * c, vm * s);
-}
-
-// {I, P, Q, loss} of the line i -> j with series impedance r + jx; P and Q as power_imbalance_fwd_kernel writes them.  Every
-// operation rounded on its own: what hipcc fuses differs between the instantiations of the kernel below, and the flows of a table
-// must not depend on whether a second table came along or on which kernel served the gathers
-__device__ __forceinline__ float4 bf_line(float2 vi, float2 vj, float r, float x) {
-#pragma clang fp contract(off)
-    const float d = r * r + x * x;
-    const float g = r / d, b = -x / d;
-    const float de = vi.x - vj.x, df = vi.y - vj.y;
-    const float m2 = de * de + df * df;
-    const float t1 = vi.x * vj.x - vi.x * vi.x + vi.y * vj.y - vi.y * vi.y, t2 = vi.y * vj.x - vi.x * vj.y;
-    return make_float4(sqrtf(m2) / sqrtf(d), g * t1 + b * t2, g * t2 - b * t1, g * m2);
-}
+// (the rectangular voltage of a bus row and the four quantities of a line, bf_phasor and bf_line: branch_line.hpp, shared with the
+//  network's N-1 screen, contingency_model.hip)
 
 template <bool TWO, bool LDS>
 __global__ __launch_bounds__(BF_BIG_THREADS) void branch_flows_kernel(const BfArgs a) {

@@ -8,20 +8,27 @@ fp32 FACTOR of B' under a `sparse_plan(..., mode="dc")` and substitutes 64 outag
 `pfn_contingency_sparse`, two launches behind the islands).  `contingency_screen_pairs` is the N-2 screen: every pair of candidate
 lines out together, a rank-2 update of the same inverse (csrc/contingency_pairs.hip: `pfn_contingency_pair_islands`,
 `pfn_contingency_pairs`) or, with `route="sparse"`, of one substituted column per candidate under the same plan
-(csrc/contingency_pairs_sparse.hip: `pfn_contingency_pairs_sparse`); `verify_pair_contingencies` is its AC check.  No CPU path."""
+(csrc/contingency_pairs_sparse.hip: `pfn_contingency_pairs_sparse`); `verify_pair_contingencies` is its AC check.
+`contingency_screen_model` asks the NETWORK instead of the DC model: every (scenario, outage) becomes one graph of a batch
+(csrc/contingency_model.hip: `pfn_contingency_model_batch`), the model predicts, and `pfn_contingency_model_loadings` turns the
+predictions into line currents and the screen's three figures -- reactive flow and voltage magnitude included.  No CPU path."""
+import contextlib
 import ctypes as C
 import operator
 from dataclasses import dataclass
 
 import torch
+import torch.nn as nn
 
 from .. import _lib as L
+from .captured import capture_state, held_adjacencies, no_gc, topology_owners, warm_up
 from .powerflow import STATUS, SparsePlan, cover_plan, solve_power_flow  # noqa: F401  (STATUS: the texts of `ContingencyResult.status`)
 
 _ROUTES = {"auto": 0, "lds": 1, "global": 2}
 _BLOCKS = {"auto": 0, "lds": 1, "global": 2}
 _COLUMNS = {"auto": 0, "lds": 1, "global": 2}
 _COUNTS_ATTR = "_pfn_bus_counts"  # on a bus_type tensor: (version, (n_pv, n_pq, slack)) -- one host read per tensor
+_COUNTS_EAGER_FIRST = "contingency_screen: the bus_type counts are read on the host once per tensor; call it eagerly once before capturing"
 
 
 @dataclass
@@ -161,7 +168,7 @@ def _bus_counts(bus_type):
     got = kept[1] if kept is not None and kept[0] == bus_type._version else None
     if got is None:
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("contingency_screen: the bus_type counts are read on the host once per tensor; call it eagerly once before capturing")
+            raise RuntimeError(_COUNTS_EAGER_FIRST)
         bt = bus_type.long()
         info = torch.cat([torch.bincount(bt.clamp(0, 3), minlength=4), (bt < 0).sum().view(1), (bt == 0).long().argmax().view(1)]).tolist()
         if info[0] != 1 or info[3] != 0 or info[4] != 0:
@@ -550,3 +557,252 @@ def verify_pair_contingencies(result, bus_type, spec, edge_index, rx, ratings=No
     return PairContingencyVerification(triples=torch.cat([sc[:, None], removed], dim=1), pair_index=pi, table=solved.table, status=solved.status,
                                        loading=loading, severity=severity, worst_line=worst, overloads=overloads,
                                        dc_severity=result.severity[sc, pi])
+
+
+# ================================================================================ N-1 with the network's prediction
+MODEL_CHUNK = 744   # items per chunk where the caller names none: the fastest of tools/contingency_bench.py --model at case118, S = 16
+_STEPS_ATTR = "_pfn_contingency_model_steps"  # on the model: {shape key: _ModelScreenStep} of the graphed calls
+_MAX_STEPS = 8                                # (GraphedEvalStep.max_children: beyond it the oldest shape is dropped and captured again)
+
+
+@dataclass
+class ModelContingencyResult:
+    """`contingency_screen_model`'s answer.  Per (scenario s, outage k), by `ContingencyResult`'s rules but from the NETWORK's
+    prediction: `severity` [S, e] float32 (the largest loading I_l / rating_l over the monitored lines l != k, I_l the line current of
+    the merged prediction; +inf where the outage islands buses, NaN where a monitored loading is not finite), `worst_line` [S, e]
+    int32 (ties to the lowest; -1 where none), `overloads` [S, e] int32 (-1 where islanding).  `islands` [e] int32 as in
+    `ContingencyResult`.  `loading` [S, e, e] float32 with `keep_table` (row = outage, column = line in the ORIGINAL numbering; NaN at
+    the outaged line and in an islanding row), `predictions` [S, e, n, 4] float32 with `keep_predictions` (the merged, de-normalised
+    table: the network's value where the bus type leaves the entry to be predicted, float(spec) where it is given; written for
+    islanding outages too, where it means nothing); else None.  `flags` [1] int32 (bit 1: a line names a bus outside the grid).
+    `chunk`: the items per chunk that ran; `captures`: graph captures the serving step has made so far (0: eager).
+
+    `verify_contingencies(result, ...)` takes it as it takes a `ContingencyResult` (it reads `islands`, `ranking` and `severity`);
+    the `dc_severity` column of its answer then carries THIS screen's figure, the network's, not a DC one."""
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    islands: torch.Tensor
+    loading: object = None
+    predictions: object = None
+    flags: object = None
+    chunk: int = 0
+    captures: int = 0
+
+    def ranking(self, top):
+        """`ContingencyResult.ranking`'s order: NaN first, then +inf, then descending, ties to the lowest outage id."""
+        return _rank(self.severity, top, "ranking")
+
+
+def _stat_floats(v, count, what):
+    """a statistic of the dataset (a tensor or a sequence, any shape that holds `count` values first) as fp32 host floats, or None"""
+    if v is None:
+        return None
+    t = torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1)
+    if t.numel() < count or t.numel() % count:
+        raise ValueError(f"contingency_screen_model: {what} must hold {count} values; got {t.numel()}")
+    return t[:count]
+
+
+def _model_stats(xymean, xystd, edgemean, edgestd):
+    """(div4, mean4, ediv2, emean2) as tuples of host floats or None (identity): the divisor std + 1e-7 formed in fp32, as the
+    dataset forms it and as `denormalize` multiplies by it"""
+    def div(v, count, what):
+        t = _stat_floats(v, count, what)
+        return None if t is None else tuple(float(a) for a in (t + 1e-7).tolist())
+
+    def mean(v, count, what):
+        t = _stat_floats(v, count, what)
+        return None if t is None else tuple(float(a) for a in t.tolist())
+    return div(xystd, 4, "xystd"), mean(xymean, 4, "xymean"), div(edgestd, 2, "edgestd"), mean(edgemean, 2, "edgemean")
+
+
+def _c_floats(v):
+    return None if v is None else (C.c_float * len(v))(*v)
+
+
+@contextlib.contextmanager
+def _screen_state(model):
+    """The state the screen's forwards run in, for the call's duration only: every module in eval mode, no_grad, and -- on a model
+    that keeps an adjacency per edge_index (MaskEmbdMultiMPN) -- `dynamic_topology` and `segment_build` on: every chunk has its own
+    line lists, rebuilt on the device without a host sync, one workgroup per graph.  Whatever was there before comes back, also when
+    the call raises.  Yields the adjacency owners."""
+    modes = [(m, m.training) for m in model.modules()]
+    owners = topology_owners(model)
+    try:
+        model.eval()
+        with torch.no_grad(), capture_state(owners, model, True, hasattr(model, "segment_build")):
+            yield owners
+    finally:
+        for m, was in modes:
+            m.training = was
+
+
+class _ModelScreenStep:
+    """The chunk loop of one screen shape: the batch a chunk's launch fills, the three steps of a chunk, their capture and replay.
+    Eager, the kernels read the caller's tensors and each chunk names its first item by a pointer into `starts`; graphed, the step
+    owns copies of the inputs (the captured launches hold their addresses) and the host copies the chunk's first item into the ONE
+    device word `item0` the captured kernels read, then replays.  A captured chunk is a chain: no parallel branches."""
+
+    def __init__(self, model, S, n, e, B, dev, stats, per_sample, has_ratings, keep_table, keep_predictions, own_inputs):
+        from ..data import Batch
+        self.model, self.S, self.n, self.e, self.B, self.dev = model, S, n, e, B, dev
+        self.stats = stats
+        self.c_stats = tuple(_c_floats(v) for v in stats)
+        self.per_sample = per_sample
+        T = S * e
+        self.starts = torch.arange(0, T, B, dtype=torch.int64, device=dev)
+        self.item0 = torch.zeros(1, dtype=torch.int64, device=dev)
+        batch = Batch()
+        batch.x = torch.empty(B * n, 4, dtype=torch.float32, device=dev)
+        batch.pred_mask = torch.empty(B * n, 4, dtype=torch.float32, device=dev)
+        batch.bus_type = torch.empty(B * n, dtype=torch.int64, device=dev)
+        batch.edge_index = torch.empty(2, B * (e - 1), dtype=torch.int64, device=dev)
+        batch.edge_attr = torch.empty(B * (e - 1), 2, dtype=torch.float32, device=dev)
+        batch.batch = torch.arange(B, device=dev).repeat_interleave(n)      # constants of the chunk shape
+        batch.ptr = torch.arange(B + 1, device=dev) * n
+        self.batch = batch
+        self.islands = torch.empty(e, dtype=torch.int32, device=dev)
+        self.severity = torch.empty(S, e, dtype=torch.float32, device=dev)
+        self.worst = torch.empty(S, e, dtype=torch.int32, device=dev)
+        self.overloads = torch.empty(S, e, dtype=torch.int32, device=dev)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.loading = torch.empty(S, e, e, dtype=torch.float32, device=dev) if keep_table else None
+        self.predictions = torch.empty(S, e, n, 4, dtype=torch.float32, device=dev) if keep_predictions else None
+        self.bt = self.spec = self.ei = self.rx = self.ratings = None
+        self.own = own_inputs
+        if own_inputs:
+            self.bt = torch.empty(n, dtype=torch.int32, device=dev)
+            self.spec = torch.empty(S, n, 4, dtype=torch.float64, device=dev)
+            self.ei = torch.empty(2, e, dtype=torch.int64, device=dev)
+            self.rx = torch.empty(S, e, 2, dtype=torch.float64, device=dev)
+            self.ratings = torch.empty((S, e) if per_sample else (e,), dtype=torch.float64, device=dev) if has_ratings else None
+        self.graph, self.held, self.side, self.captures = None, None, None, 0
+
+    def bind(self, bt, spec, ei, rx, ratings, slack):
+        """the inputs of this call (eager: taken as they are; graphed: copied into the step's own) and their islands verdict"""
+        if self.own:
+            self.bt.copy_(bt)
+            self.spec.copy_(spec)
+            self.ei.copy_(ei)
+            self.rx.copy_(rx)
+            if ratings is not None:
+                self.ratings.copy_(ratings)
+        else:
+            self.bt, self.spec, self.ei, self.rx, self.ratings = bt, spec, ei, rx, ratings
+        self.flags.zero_()
+        L.check(L.load().pfn_contingency_islands(self.ei.data_ptr(), self.e, self.n, slack, self.islands.data_ptr(), L.stream_ptr()),
+                "pfn_contingency_islands")
+
+    def chunk(self, item0):
+        """the three steps of the chunk whose first item the device word `item0` holds"""
+        lib, b, (div4, mean4, ediv2, emean2) = L.load(), self.batch, self.c_stats
+        L.check(lib.pfn_contingency_model_batch(self.bt.data_ptr(), self.spec.data_ptr(), self.ei.data_ptr(), self.rx.data_ptr(), self.S, self.n,
+                                                self.e, item0.data_ptr(), self.B, div4, mean4, ediv2, emean2, b.x.data_ptr(),
+                                                b.pred_mask.data_ptr(), b.bus_type.data_ptr(), b.edge_index.data_ptr(), b.edge_attr.data_ptr(),
+                                                self.flags.data_ptr(), L.stream_ptr()), "pfn_contingency_model_batch")
+        out = self.model(b)
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (self.B * self.n, 4) or out.device != self.dev:
+            raise RuntimeError(f"contingency_screen_model: the model must return float32 ({self.B * self.n}, 4) on {self.dev}; got "
+                               f"{getattr(out, 'dtype', type(out))} {tuple(getattr(out, 'shape', ()))}")
+        out = out.detach()
+        out = out if out.is_contiguous() and out.data_ptr() % 16 == 0 else out.clone(memory_format=torch.contiguous_format)
+        L.check(lib.pfn_contingency_model_loadings(out.data_ptr(), self.bt.data_ptr(), self.spec.data_ptr(), self.ei.data_ptr(), self.rx.data_ptr(),
+                                                   L.ptr(self.ratings), int(self.per_sample), self.islands.data_ptr(), self.S, self.n, self.e,
+                                                   item0.data_ptr(), self.B, div4, mean4, 0, self.severity.data_ptr(), self.worst.data_ptr(),
+                                                   self.overloads.data_ptr(), L.ptr(self.loading), L.ptr(self.predictions), L.stream_ptr()),
+                "pfn_contingency_model_loadings")
+
+    def run_eager(self):
+        for c in range(int(self.starts.numel())):
+            self.chunk(self.starts[c:c + 1])
+
+    def run_graphed(self, owners):
+        if self.graph is None:
+            if self.side is None:
+                self.side = torch.cuda.Stream()
+            warm_up(self.side, lambda: self.chunk(self.item0))              # (item0 holds 0: chunk 0, which the loop below runs again)
+            g = torch.cuda.CUDAGraph()
+            with no_gc(), torch.cuda.graph(g):
+                self.chunk(self.item0)
+            self.graph, self.held = g, held_adjacencies(owners)
+            self.captures += 1
+        for c in range(int(self.starts.numel())):
+            self.item0.copy_(self.starts[c:c + 1])
+            self.graph.replay()
+
+
+def _screen_model_options(model, edge_index, chunk, keep_table, keep_predictions, graphed):
+    """what `contingency_screen_model` asks of its own arguments, on the host, before anything touches the library"""
+    who = "contingency_screen_model"
+    if not isinstance(model, nn.Module):
+        raise ValueError(f"{who}: model must be a torch.nn.Module whose forward(batch) returns [N, 4] float32; got {type(model).__name__}")
+    if chunk is not None and (isinstance(chunk, bool) or not isinstance(chunk, int) or not 1 <= chunk < 2 ** 24):
+        raise ValueError(f"{who}: chunk must be None or an int in [1, 2^24); got {chunk!r}")
+    for name, v in (("keep_table", keep_table), ("keep_predictions", keep_predictions), ("graphed", graphed)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {name} must be a bool; got {v!r}")
+    if torch.is_tensor(edge_index) and edge_index.dim() == 2 and edge_index.shape[1] == 1:
+        raise ValueError(f"{who}: a grid of one line leaves no line once it is out: nothing to screen")
+
+
+def contingency_screen_model(model, bus_type, spec, edge_index, rx, ratings=None, *, xymean=None, xystd=None, edgemean=None, edgestd=None,
+                             chunk=None, keep_table=False, keep_predictions=False, graphed=False) -> ModelContingencyResult:
+    """Screen every single line outage of every scenario with the NETWORK's prediction: `bus_type`, `spec`, `edge_index`, `rx` and
+    `ratings` exactly as `contingency_screen` takes them (e >= 2: ValueError otherwise).  `model`: an `nn.Module` on the inputs'
+    device whose `forward(batch)` returns [N, 4] float32 for a `data.Batch` carrying x, pred_mask, bus_type, edge_index, edge_attr,
+    batch, ptr; it runs in eval mode under no_grad, a `MaskEmbdMultiMPN` with `dynamic_topology` and `segment_build` on, and gets
+    all of it back afterwards.  `xymean` / `xystd` / `edgemean` / `edgestd`: the training set's statistics (None: identity); the
+    divisor is std + 1e-7 formed in fp32, the dataset's.
+
+    Item t = s * e + k is scenario s without line k; ALL S * e items run, the islanding ones too (static shapes, nothing read back),
+    `chunk` consecutive items at a time (None: `MODEL_CHUNK`; never more than S * e), the last chunk padded with repeats of the last
+    item whose results are not written.  Per chunk: `pfn_contingency_model_batch` writes the batch the dataset and its collate
+    would have built, the model predicts, `pfn_contingency_model_loadings` merges prediction and specification, forms the line
+    currents with `branch_flows`' arithmetic and reduces by the screen's rules; `pfn_contingency_islands` runs first and its verdict
+    overwrites the islanding items (+inf, -1, -1, a NaN row).  `graphed`: the three steps of a chunk are captured once per shape
+    (kept on the model, reused by later calls: `captures` on the result counts them) and replayed for every chunk, the chunk's first
+    item written into one device word before each replay; the first call with a new `bus_type` tensor must be eager.  One host read
+    (the bus_type counts, once per tensor)."""
+    who = "contingency_screen_model"
+    _screen_model_options(model, edge_index, chunk, keep_table, keep_predictions, graphed)
+    stats = _model_stats(xymean, xystd, edgemean, edgestd)
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    if e < 2:
+        raise ValueError(f"{who}: a grid of one line leaves no line once it is out: nothing to screen")
+    ratings = _ratings(ratings, S, e, who)
+    if graphed:
+        kept = getattr(bus_type, _COUNTS_ATTR, None)
+        if kept is None or kept[0] != bus_type._version:
+            raise RuntimeError(_COUNTS_EAGER_FIRST)
+    _, _, slack = _bus_counts(bus_type)
+    dev = spec.device
+    bt = bus_type.to(torch.int32).contiguous()
+    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    T = S * e
+    B = max(1, min(MODEL_CHUNK if chunk is None else chunk, T))
+    per_sample = ratings is not None and ratings.dim() == 2
+    shape = (S, n, e, B, dev, stats, per_sample, ratings is not None, keep_table, keep_predictions)
+    with torch.cuda.device(dev), _screen_state(model) as owners:
+        if not graphed or S == 0:
+            step = _ModelScreenStep(model, *shape, own_inputs=False)
+            step.bind(bt, spec, edge_index, rx, ratings, slack)
+            step.run_eager()
+        else:
+            key = shape + (tuple(p.data_ptr() for p in model.parameters()),)   # (a parameter whose storage moved: capture again)
+            steps = model.__dict__.setdefault(_STEPS_ATTR, {})
+            step = steps.get(key)
+            if step is None:
+                if len(steps) >= _MAX_STEPS:
+                    steps.pop(next(iter(steps)))
+                step = steps[key] = _ModelScreenStep(model, *shape, own_inputs=True)
+            step.bind(bt, spec, edge_index, rx, ratings, slack)
+            try:
+                step.run_graphed(owners)
+            except BaseException:
+                steps.pop(key, None)                                          # a failed capture leaves nothing half-made behind
+                raise
+    take = (lambda t: None if t is None else t.clone()) if graphed else (lambda t: t)   # (a graphed step's outputs are overwritten by its next call)
+    return ModelContingencyResult(severity=take(step.severity), worst_line=take(step.worst), overloads=take(step.overloads),
+                                  islands=take(step.islands), loading=take(step.loading), predictions=take(step.predictions),
+                                  flags=take(step.flags), chunk=B, captures=step.captures)

@@ -38,7 +38,17 @@ The pair screen on the sparse route (`contingency_screen_pairs(route="sparse")`,
 columns and pairs launch apart (the library's event brackets, a pass of their own) and the pair-islands launch's share.  Beside it,
 alternating in the same child: the dense pair screen where the shape is within its cap, else the brute force the parent commit has
 there -- `solve_power_flow(mode="dc", route="sparse", plan=<cover plan of the base list>)` over explicit [2, e - 2] lists of
-`--brute-pairs` non-islanding pairs spread evenly over the pair list, one per scenario, scaled per pair."""
+`--brute-pairs` non-islanding pairs spread evenly over the pair list, one per scenario, scaled per pair.
+
+    python tools/contingency_bench.py --model [--graphed] [--chunk 64 128 186 256 372 512 744] [--model-samples 16] [--ac-outages 16]
+                                      [--case 118 --case 14]
+
+The network's screen (`contingency_screen_model`), same protocol, with the random-weight MaskEmbdMultiMPN of
+configs/standard.json (bits do not matter for time).  Per case, alternating in the same child: (a) the entry for every `--chunk` of
+the sweep, eager and -- with --graphed -- replayed from its captured chunk; (b) the composition it replaces, per chunk of the same
+size: torch index-built reduced lists and normalisation, the forward with the adjacency rebuilt on the generic route, the merge,
+`branch_flows`, `summarise_loadings`; (c) `contingency_screen` (DC) for the same scenarios; (d) `solve_power_flow(mode="ac")` over
+explicit per-outage lists of `--ac-outages` non-islanding outages spread evenly over the list, for every scenario, scaled per pair."""
 import argparse
 import json
 import os
@@ -88,6 +98,147 @@ def child(case, samples, brute_solves, repeats):
                       "brute_scenarios": Sb, "brute_solves": Sb * K, "screen_ms": 1e3 * statistics.median(t_screen),
                       "brute_ms": 1e3 * statistics.median(t_brute), "screen_us_per_pair": screen_us, "brute_us_per_pair": brute_us,
                       "ratio": brute_us / screen_us}))
+
+
+def child_model(case, samples, chunks, graphed, ac_outages, repeats):
+    import torch
+    from poweflownet_amd.data import Batch
+    from poweflownet_amd.datasets import PowerFlowData
+    from poweflownet_amd.loss import branch_flows
+    from poweflownet_amd.networks.MPN import MaskEmbdMultiMPN
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen, contingency_screen_model, summarise_loadings
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    dev = torch.device("cuda:0")
+    n, e = CASES[case]
+    S, T = samples, samples * e
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, S, seed=0))
+    with open(os.path.join(HERE, "configs", "standard.json")) as f:
+        cfg = json.load(f)
+    torch.manual_seed(0)
+    model = MaskEmbdMultiMPN(4, 2, 4, int(cfg["hidden_dim"]), int(cfg["n_gnn_layers"]), int(cfg["K"]), float(cfg["dropout_rate"])).to(dev).eval()
+    stats = {"xymean": torch.tensor([[1.0, 0.0, 0.0, 0.0]]), "xystd": torch.tensor([[0.05, 5.0, 0.3, 0.1]]),
+             "edgemean": torch.tensor([[0.0175, 0.09]]), "edgestd": torch.tensor([[0.007, 0.035]])}
+    dc = contingency_screen(bt, spec, ei, rx)                              # (c), warm-up; also the bus_type tensor's eager first call
+    ratings = 1.5 * dc.base_flow.abs().max(dim=0).values
+    # (d) the AC solves' inputs, built once and not timed
+    ok = torch.nonzero(dc.islands == 0).flatten()
+    outages = ok[torch.linspace(0, ok.numel() - 1, min(ac_outages, ok.numel())).long()]
+    K = int(outages.numel())
+    ar = torch.arange(e - 1, device=dev)
+    idx_ac = ar[None, :] + (ar[None, :] >= outages[:, None])               # [K, e - 1]
+    lists = ei[:, idx_ac].permute(1, 0, 2).repeat(S, 1, 1).contiguous()
+    rx_ac = rx[:, idx_ac].reshape(S * K, e - 1, 2).contiguous()
+    spec_ac = spec.repeat_interleave(K, dim=0).contiguous()
+    assert bool((solve_power_flow(bt, spec_ac, lists, rx_ac, mode="ac").status >= 0).all())      # (warm-up)
+    # (b) the composition's constants
+    mask = torch.tensor(PowerFlowData.bus_type_mask)[bt.cpu()].float().to(dev)                  # [n, 4]
+    xm, xs, em, es = (stats[k].to(dev) for k in ("xymean", "xystd", "edgemean", "edgestd"))
+    rate = ratings.float()
+    sev_c, worst_c, over_c = (torch.empty(T, dtype=d, device=dev) for d in (torch.float32, torch.int32, torch.int32))
+
+    @torch.no_grad()
+    def composition(chunk):
+        was = model.dynamic_topology
+        model.dynamic_topology = True                                       # (a new line list per chunk: rebuilt on the device, the generic build)
+        try:
+            for item0 in range(0, T, chunk):
+                items = torch.arange(item0, item0 + chunk, device=dev).clamp(max=T - 1)
+                s, k = items // e, items % e
+                idx = ar[None, :] + (ar[None, :] >= k[:, None])             # [B, e - 1]
+                y = spec[s].float()
+                b = Batch()
+                b.x = ((y * (1.0 - mask) - xm) / (xs + 1e-7)).reshape(-1, 4)
+                b.pred_mask, b.bus_type = mask.repeat(chunk, 1), bt.repeat(chunk)
+                local = ei[:, idx]                                          # [2, B, e - 1]
+                b.edge_index = (local + (torch.arange(chunk, device=dev) * n)[None, :, None]).reshape(2, -1)
+                r = rx[s[:, None], idx].float()
+                b.edge_attr = ((r - em) / (es + 1e-7)).reshape(-1, 2)
+                b.batch = torch.arange(chunk, device=dev).repeat_interleave(n)
+                b.ptr = torch.arange(chunk + 1, device=dev) * n
+                out = model(b).view(chunk, n, 4)
+                pred = torch.where(mask.bool()[None], out * (xs + 1e-7) + xm, y)
+                flows = branch_flows(pred, local.permute(1, 0, 2).contiguous(), r.contiguous())[0]
+                loading = torch.full((chunk, e), float("nan"), device=dev)
+                loading.scatter_(1, idx, flows[:, :, 0] / rate[idx])
+                monitored = (rate > 0)[None, :] & (torch.arange(e, device=dev)[None, :] != k[:, None])
+                live = min(chunk, T - item0)
+                for dst, src in zip((sev_c, worst_c, over_c), summarise_loadings(loading, monitored)):
+                    dst[item0:item0 + live] = src[:live]
+        finally:
+            model.dynamic_topology = was
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    forms = ["eager"] + (["graphed"] if graphed else [])
+    runs = {(c, f): (lambda c=c, f=f: contingency_screen_model(model, bt, spec, ei, rx, ratings, chunk=c, graphed=f == "graphed", **stats))
+            for c in chunks for f in forms}
+    runs.update({(c, "composition"): (lambda c=c: composition(c)) for c in chunks})
+    runs[(0, "dc")] = lambda: contingency_screen(bt, spec, ei, rx, ratings)
+    runs[(0, "ac")] = lambda: solve_power_flow(bt, spec_ac, lists, rx_ac, mode="ac")
+    for fn in runs.values():                                               # warm-up of every shape the timed window uses (captures included)
+        fn()
+        fn()
+    # the entry and the composition agree on what they compute (same items, same rules) before either is timed
+    ref = contingency_screen_model(model, bt, spec, ei, rx, ratings, chunk=chunks[0], **stats)
+    composition(chunks[0])
+    live = (ref.islands == 0).repeat(S)
+    assert bool(torch.isfinite(ref.severity.view(-1)[live]).all())
+    agree = float((ref.severity.view(-1)[live] - sev_c[live]).abs().max() / ref.severity.view(-1)[live].abs().max())
+    times = {key: [] for key in runs}
+    for _ in range(repeats):
+        for key, fn in runs.items():
+            times[key].append(timed(fn))
+    med = {key: statistics.median(v) for key, v in times.items()}
+    rows = []
+    for c in chunks:
+        row = {"chunk": c, "composition_ms": 1e3 * med[(c, "composition")]}
+        for f in forms:
+            row[f + "_ms"] = 1e3 * med[(c, f)]
+            row[f + "_us_per_pair"] = 1e6 * med[(c, f)] / T
+            row["composition_over_" + f] = med[(c, "composition")] / med[(c, f)]
+        rows.append(row)
+    ac_us = 1e6 * med[(0, "ac")] / (S * K)
+    print(json.dumps({"case": case, "buses": n, "lines": e, "scenarios": S, "items": T, "hidden_dim": int(cfg["hidden_dim"]), "rows": rows,
+                      "dc_ms": 1e3 * med[(0, "dc")], "dc_us_per_pair": 1e6 * med[(0, "dc")] / T, "ac_solves": S * K, "ac_ms": 1e3 * med[(0, "ac")],
+                      "ac_us_per_pair": ac_us, "entry_vs_composition_max_rel_severity_gap": agree}))
+
+
+def main_model(a):
+    out = {"repeats": a.repeats, "processes": a.processes, "cases": {}}
+    for case in a.case or ["118", "14"]:
+        kids = []
+        for _ in range(a.processes):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-model", case, "--model-samples", str(a.model_samples), "--repeats",
+                                str(a.repeats), "--ac-outages", str(a.ac_outages), "--chunk"] + [str(c) for c in a.chunk]
+                               + (["--graphed"] if a.graphed else []), capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                raise SystemExit(f"contingency_bench: the model child for case {case} failed:\n{r.stdout}\n{r.stderr}")
+            kids.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        row = dict(kids[0])
+        for key in ("dc_ms", "dc_us_per_pair", "ac_ms", "ac_us_per_pair"):
+            vals = [x[key] for x in kids]
+            row[key], row[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+        row["rows"] = []
+        for i, first in enumerate(kids[0]["rows"]):
+            merged = {"chunk": first["chunk"]}
+            for key in [k for k in first if k != "chunk"]:
+                vals = [x["rows"][i][key] for x in kids]
+                merged[key], merged[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+            for f in ("eager", "graphed"):
+                if f + "_us_per_pair" in merged:
+                    merged["ac_over_" + f] = round(row["ac_us_per_pair"] / merged[f + "_us_per_pair"], 3)
+            row["rows"].append(merged)
+        fastest = {f: min(row["rows"], key=lambda m: m[f + "_ms"])["chunk"] for f in ("eager", "graphed") if f + "_ms" in row["rows"][0]}
+        row["fastest_chunk"] = fastest
+        out["cases"][case] = row
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
 
 
 def child_pairs(case, samples, candidates, brute_solves, repeats):
@@ -371,7 +522,18 @@ def main(argv=None):
     ap.add_argument("--child-pairs-sparse", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--columns", default="auto", help=argparse.SUPPRESS)
     ap.add_argument("--waves", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--model", action="store_true", help="the network's screen, contingency_screen_model, DESIGN 7y")
+    ap.add_argument("--graphed", action="store_true", help="model: also time the entry replayed from its captured chunk")
+    ap.add_argument("--chunk", type=int, nargs="*", default=[64, 128, 186, 256, 372, 512, 744], help="model: the chunk sizes of the sweep")
+    ap.add_argument("--model-samples", type=int, default=16, help="model: scenarios")
+    ap.add_argument("--ac-outages", type=int, default=16, help="model: the AC solves cover this many non-islanding outages of every scenario")
+    ap.add_argument("--child-model", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_model:
+        child_model(a.child_model, a.model_samples, a.chunk, a.graphed, a.ac_outages, a.repeats)
+        return 0
+    if a.model:
+        return main_model(a)
     if a.child_pairs_sparse:
         child_pairs_sparse(a.child_pairs_sparse, a.samples, a.candidates, a.columns, a.waves or None, a.brute_pairs, a.repeats)
         return 0
