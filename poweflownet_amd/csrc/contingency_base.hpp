@@ -3,7 +3,9 @@
 // ld = m | 1, m = n - 1) by the row owners in stored order exactly as the fast-decoupled modes build theirs, THEIR Gauss-Jordan in
 // place (powerflow_dense.hpp), theta refined, theta -= X F, under the fp64 residual F = B' theta + P of mode 1 to tol / max_iter
 // (status = the refinement solves used), the fp64 base flows f_l = (theta_a - theta_b) / x_l and the scenario's status.  A scenario's
-// base flows and status are the same bits from either kernel.
+// base flows and status are the same bits from either kernel.  Beside it, what else the two dense screens share: the entries' common
+// argument block (CtCommon, with the CtBaseIn of a scenario and the pointer-alignment check) and the sensitivity column
+// w = X[:, i] - X[:, j] (ct_column, row-major or transposed storage).
 #pragma once
 #include "powerflow_dense.hpp"
 
@@ -59,6 +61,63 @@ struct CtBaseIn {
     double tol;
     int n, e, max_iter, n_pv, n_pq;
 };
+
+// What the two dense entries take alike (pfn_contingency_dc: items = outages; pfn_contingency_pairs: items = pairs).  It IS the N-1
+// kernel's argument block; the pair kernels' block (contingency_pairs.hip CpArgs) repeats these names with its own fields among them
+// in the order it has always had -- the order of a kernel's arguments decides which of them the base solve keeps in scalar registers,
+// and the pair base launch measured 1.5 to 3 % slower with its fields moved behind a shared prefix --, so the two helpers below
+// take either block by its field names.
+struct CtCommon {
+    const int64_t* edge_index;                      // [2, e], one list for all scenarios
+    const double* rx;                               // [S, e, 2]
+    const int32_t* bus_type;                        // [n]
+    const double* spec;                             // [S, n, 4]
+    const double* ratings;                          // [e], [S, e] or null (1.0 everywhere)
+    const int32_t* islands;                         // [items], the islands launch's output
+    float* severity;                                // [S, items]
+    int32_t* worst_line;                            // [S, items]
+    int32_t* overloads;                             // [S, items]
+    double* base_flow;                              // [S, e]
+    int32_t* status;                                // [S]
+    float* post_flow;                               // [S, items, e] or null
+    int32_t* flags;
+    void* ws;                                       // the global route's fp32 slabs or null
+    double tol;
+    int n, e, max_iter, n_pv, n_pq, ratings_per_sample;
+};
+template <typename Args>
+__device__ __forceinline__ CtBaseIn ct_base_in(const Args& a, int s) {
+    return CtBaseIn{a.edge_index, a.rx + (int64_t)s * 2 * a.e, a.bus_type, a.spec + (int64_t)s * 4 * a.n,
+                    a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * a.e : 0) : nullptr, a.base_flow + (int64_t)s * a.e, a.status + s,
+                    a.flags, a.tol, a.n, a.e, a.max_iter, a.n_pv, a.n_pq};
+}
+// the alignment of their pointers (null is aligned: ratings, post_flow, the N-1 entry's lines)
+template <typename Args>
+static inline int ct_check_aligned(const char* who, const Args& a, const int32_t* lines) {
+    const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    PFN_CHECK_ARG((at(a.ws) & 15) == 0 && ((at(a.edge_index) | at(a.rx) | at(a.spec) | at(a.ratings) | at(a.base_flow)) & 7) == 0 &&
+                      ((at(a.bus_type) | at(a.islands) | at(a.severity) | at(a.worst_line) | at(a.overloads) | at(a.status) | at(a.post_flow) |
+                        at(a.flags) | at(lines)) & 3) == 0,
+                  "%s: the workspace must be 16-byte aligned, fp64 and int64 arrays 8-byte, fp32 and int32 arrays 4-byte", who);
+    return PFN_OK;
+}
+
+// w = X[:, i] - X[:, j], the sensitivity column of the outage of a line whose ends have the unknowns ci and cj (-1: the slack, whose
+// column of X is zero), by the threads first, first + step, ... into w [n], zero at the slack.  TRANSPOSED: the matrix is kept as
+// XT[c * ld + r] = X[r][c] (the pair screen's slab) -- a template flag, so that the compiler sees the one address expression.
+template <bool TRANSPOSED>
+__device__ __forceinline__ void ct_column(float* w, const float* X, int ld, const int* aidx, int n, int ci, int cj, int first, int step) {
+    for (int b = first; b < n; b += step) {
+        const int r = aidx[b];
+        float v = 0.f;
+        if (r >= 0) {
+            const float xi = ci >= 0 ? (TRANSPOSED ? X[ci * ld + r] : X[r * ld + ci]) : 0.f;
+            const float xj = cj >= 0 ? (TRANSPOSED ? X[cj * ld + r] : X[r * ld + cj]) : 0.f;
+            v = xi - xj;
+        }
+        w[b] = v;
+    }
+}
 
 // Every thread of the workgroup calls it with the same arguments.  Returns the scenario's code (0, or the negative status), uniform;
 // on 0 the vectors hold the staged lines, the unknown numbering, theta and the fp64 base flows, and X (mm x mm, ld = m | 1; LDS or

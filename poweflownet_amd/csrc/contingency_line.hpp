@@ -1,6 +1,8 @@
 // The per-line arithmetic of the contingency screens, spelled once: for the dense N-1 kernel (contingency.hip) and the sparse route
 // (contingency_sparse.hip) den_k and the post-outage flow of line l from the outage's sensitivity vector; for the N-2 pair screen
-// (contingency_pairs.hip, contingency_pairs_sparse.hip) the ct_pair_* functions below.  All fp32.
+// (contingency_pairs.hip, contingency_pairs_sparse.hip) the ct_pair_* functions below.  All fp32.  What becomes of a line's flow
+// afterwards -- its loading, the maximum with its ties, the overload count, the three stores -- is contingency_monitor.hpp, for every
+// screen; the dense sensitivity column itself is contingency_base.hpp's ct_column.
 #pragma once
 #include <hip/hip_runtime.h>
 

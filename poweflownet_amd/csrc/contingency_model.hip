@@ -13,18 +13,21 @@
 // the row is MERGED -- the de-normalised output where the bus type's mask says "predict", float(spec) where the entry is given -- and
 // becomes a rectangular voltage in LDS (bf_phasor_of: one sincosf per bus, 8 bytes per bus); the threads then stride over the e lines
 // of the ORIGINAL list, loading_l = bf_line(...).x / rating_l for l != k (branch_line.hpp: branch_flows.hip's text, hence its bits),
-// and the workgroup reduces by contingency.hip's rules: the maximum with ties to the lowest line, a non-finite monitored loading
-// counts as the largest and makes the severity NaN, no monitored line gives (0, -1, 0), overloads are an integer count.  Beyond
+// and the workgroup reduces by the one tail of all screens (contingency_monitor.hpp): the maximum with ties to the lowest line, a
+// non-finite monitored loading counts as the largest and makes the severity NaN, no monitored line gives (0, -1, 0), overloads are an
+// integer count; the same merge serves the wave's shuffles and thread 0's loop over the waves' partials.  Beyond
 // BF_LDS_MAX_BUS the phasors are formed per line end (the direct route, same bits).  Every cross-thread reduction is a max or an
 // integer sum and every output has one owner: an item's bits are a function of its own inputs, whatever the chunk.  No host sync,
 // no allocation (capturable), no float atomics.
 #include "branch_line.hpp"
+#include "contingency_monitor.hpp"
 #include "pfn_internal.hpp"
 
 namespace pfn {
 
 constexpr int CM_THREADS = 256;
 constexpr int CM_SCRATCH = 64;                     // dynamic LDS in front of the phasors: the four waves' partial reductions
+static_assert(CM_SCRATCH == (CM_THREADS / 64) * sizeof(CtWorst), "a CtWorst per wave");
 
 // PowerFlowData.bus_type_mask as bits (bit f = 1: feature f is predicted): slack (0,0,1,1), PV (0,1,0,1), PQ (1,1,0,0)
 __device__ __forceinline__ int cm_mask_bits(int type) { return type <= 0 ? 0xC : (type == 1 ? 0xA : 0x3); }
@@ -165,7 +168,7 @@ __global__ __launch_bounds__(CM_THREADS) void contingency_model_loadings_kernel(
     const double* rat = a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * e : 0) : nullptr;
     float* row = a.loading ? a.loading + item * e : nullptr;
     float* pred = a.predictions ? a.predictions + item * 4 * n : nullptr;
-    const float nanv = __builtin_nanf(""), infv = __builtin_inff();
+    const float nanv = __builtin_nanf("");
     float2* ph = reinterpret_cast<float2*>(cm_smem + CM_SCRATCH);         // LDS: [n] (e, f)
     // ---- merge, keep the table where asked for, phasors
     if (LDS || pred) {
@@ -177,20 +180,13 @@ __global__ __launch_bounds__(CM_THREADS) void contingency_model_loadings_kernel(
     }
     // an islanding outage (or a line list with a bad id: -4): +inf, so that it ranks first, -1, -1 and a NaN row
     if (a.islands[k] != 0) {
-        if (row)
-            for (int l = t; l < e; l += nt) row[l] = nanv;
-        if (t == 0) {
-            a.severity[item] = infv;
-            a.worst_line[item] = -1;
-            a.overloads[item] = -1;
-        }
+        ct_skip(false, row, e, t, nt, a.severity[item], a.worst_line[item], a.overloads[item]);
         return;
     }
     if (LDS) __syncthreads();
-    // ---- the lines of the original list: loading; per thread the largest with the lowest line, and the overload count
+    // ---- the lines of the original list: loading; the workgroup's worst (contingency_monitor.hpp)
     const uint64_t nb = (uint64_t)n;
-    float best = -1.f;                              // (a loading is >= 0; a non-finite one counts as +inf and poisons the severity)
-    int arg = 0x7fffffff, cnt = 0, wild = 0;
+    CtWorst worst = ct_worst_none();
     for (int l = t; l < e; l += nt) {
         if (l == k) {
             if (row) row[l] = nanv;
@@ -213,43 +209,15 @@ __global__ __launch_bounds__(CM_THREADS) void contingency_model_loadings_kernel(
             load = bf_line(vi, vj, (float)z.x, (float)z.y).x / r;
         }
         if (row) row[l] = load;
-        if (r > 0.f) {                              // (a rating that is not > 0 -- zero, negative, NaN -- is unmonitored)
-            const bool finite = load < infv;
-            const float key = finite ? load : infv;
-            wild |= !finite;
-            cnt += load > 1.f;
-            if (key > best) { best = key; arg = l; }
-        }
+        if (r > 0.f) ct_worst_add(worst, l, load);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_xor(best, off);
-        const int oa = __shfl_xor(arg, off);
-        if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-        cnt += __shfl_xor(cnt, off);
-        wild |= __shfl_xor(wild, off);
-    }
-    float* w_best = reinterpret_cast<float*>(cm_smem);                    // LDS scratch: [4] best | [4] arg | [4] cnt | [4] wild
-    int* w_int = reinterpret_cast<int*>(cm_smem) + 4;
-    if (lane == 0) {
-        w_best[wave] = best;
-        w_int[wave] = arg;
-        w_int[4 + wave] = cnt;
-        w_int[8 + wave] = wild;
-    }
+    worst = ct_worst_wave(worst);
+    CtWorst* part = reinterpret_cast<CtWorst*>(cm_smem);                  // LDS scratch: the waves' partials
+    if (lane == 0) part[wave] = worst;
     __syncthreads();
     if (t == 0) {
-        for (int w = 1; w < nw; ++w) {              // wave order; a max with the lowest line and integer sums: no order to keep
-            const float ob = w_best[w];
-            const int oa = w_int[w];
-            if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-            cnt += w_int[4 + w];
-            wild |= w_int[8 + w];
-        }
-        const bool none = arg == 0x7fffffff;
-        a.severity[item] = none ? 0.f : (wild ? nanv : best);
-        a.worst_line[item] = none ? -1 : arg;
-        a.overloads[item] = cnt;
+        for (int w = 1; w < nw; ++w) ct_worst_merge(worst, part[w]);      // (a max with the lowest line and integer sums: no order to keep)
+        ct_store(ct_figures(worst), a.severity[item], a.worst_line[item], a.overloads[item]);
     }
 }
 
@@ -360,15 +328,8 @@ int pfn_contingency_model_loadings(const float* out, const int32_t* bus_type, co
     ProfScope ps("contingency_model_loadings", rows * (16.0 + 32.0 + 4.0 + (predictions ? 16.0 : 0.0)) + lines * (16.0 + 16.0 + 8.0 + (loading ? 4.0 : 0.0)),
                  rows * 24.0 + lines * 24.0, s);
     const bool lds = route == 1 || (route == 0 && n_bus <= BF_LDS_MAX_BUS);
-    if (lds) {
-        static std::atomic<uint64_t> raised{0};
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_model_loadings_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-        contingency_model_loadings_kernel<true><<<(int)chunk, CM_THREADS, CM_SCRATCH + (size_t)n_bus * 8, s>>>(a);
-    } else {
-        contingency_model_loadings_kernel<false><<<(int)chunk, CM_THREADS, CM_SCRATCH, s>>>(a);
-    }
-    PFN_CHECK_LAUNCH();
-    return PFN_OK;
+    return launch_either<contingency_model_loadings_kernel<true>, contingency_model_loadings_kernel<false>>(lds, (int)chunk, CM_THREADS,
+                                                                                                            CM_SCRATCH + (size_t)n_bus * 8, CM_SCRATCH, s, a);
 }
 
 }  // extern "C"

@@ -2,10 +2,11 @@
 // pairs are those of `c` candidate lines (strictly increasing ids): pair p = (lines[i], lines[j]), i < j, row-major in (i, j),
 // P = c (c - 1) / 2; all e lines stay monitored.  Three launches.
 //
-// pfn_contingency_pair_islands: one workgroup per first candidate i loops over the second candidates j > i and asks
-// topology_reach.hpp's reach routine which buses the slack still reaches with BOTH lines skipped (two keep flags cleared in LDS: no
-// [P, 2, e - 2] lists exist anywhere).  islands[p] > 0 is an islanding pair -- also where neither line is a bridge; it is decided
-// combinatorially, from the line list alone, never from a small determinant.
+// pfn_contingency_pair_islands (contingency.hip, beside the N-1 islands kernel whose LDS layout, staging and entry checks it shares):
+// one workgroup per first candidate i loops over the second candidates j > i and asks topology_reach.hpp's reach routine which buses
+// the slack still reaches with BOTH lines skipped (two keep flags cleared in LDS: no [P, 2, e - 2] lists exist anywhere).
+// islands[p] > 0 is an islanding pair -- also where neither line is a bridge; it is decided combinatorially, from the line list
+// alone, never from a small determinant.
 //
 // pfn_contingency_pairs, two kernels.  With X = B'^-1 (zeros at the slack), w_k and phi_{l,k} as in contingency.hip:
 //     M = [[1 - phi_aa, -phi_ab], [-phi_ba, 1 - phi_bb]]      t = M^-1 (f_a, f_b)
@@ -20,58 +21,21 @@
 //   PAIRS, one workgroup per (scenario, first candidate i), so that a single scenario still fills the machine: the vectors come from
 //   the slab, XT too where it fits LDS beside them (full-width loads; "lds") -- else it is read from the slab ("global"), same code,
 //   same bits.  The workgroup forms w_a once; wave w takes the second candidates i + 1 + w, i + 1 + w + nw, ...: w_b into the wave's
-//   own vector, the four phi of M, t by Cramer's rule, then the lanes stride over the lines: post-pair flow, loading |f| / rating.
-//   The wave reduces by max (ties to the lowest line) and by an integer sum; lane 0 writes severity, worst line and overload count
-//   of (s, p); the table row, where asked for, is written coalesced by the lanes.
+//   own vector (both by contingency_base.hpp's ct_column), the four phi of M, t by Cramer's rule, then the lanes stride over the
+//   lines: post-pair flow, loading |f| / rating.  The wave reduces and lane 0 writes severity, worst line and overload count of
+//   (s, p) by the one tail of all screens (contingency_monitor.hpp); the table row, where asked for, is written coalesced by the lanes.
 // The per-line and 2 x 2 arithmetic is contingency_line.hpp's ct_pair_*, compiled without contraction; every cross-thread reduction
 // is a max or an integer sum, one owner per output: the bits of (scenario, a, b) are a pure function of the scenario's inputs and
 // the two lines, whatever the batch, the candidate list, the workgroup size or count, or the route.  No host sync, no allocation
 // (capturable), no float atomics.
 #include "contingency_base.hpp"
 #include "contingency_line.hpp"
-#include "topology_reach.hpp"
+#include "contingency_monitor.hpp"
 
 namespace pfn {
 
-// ------------------------------------------------------------------------------------------------------ islands
-// dynamic LDS: ID from[e] | ID to[e] | uint8 keep[e] | uint8 reached[n] (contingency.hip's)
-__host__ __device__ inline size_t cp_islands_lds_bytes(int n, int e) {
-    const size_t id = n <= 65536 ? 2 : 4;
-    return tp_align4(2 * id * (size_t)e) + tp_align4((size_t)e) + tp_align4((size_t)n);
-}
-
-template <typename ID>
-__global__ __launch_bounds__(1024) void contingency_pair_islands_kernel(const int64_t* __restrict__ ei, int n, int e, int root,
-                                                                        const int32_t* __restrict__ lines, int c, int32_t* __restrict__ islands) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char cp_smem[];
-    __shared__ int s_count;
-    const int t = threadIdx.x, nt = blockDim.x;
-    const int i = blockIdx.x;
-    ID* from = reinterpret_cast<ID*>(cp_smem);
-    ID* to = from + e;
-    uint8_t* keep = cp_smem + tp_align4(2 * sizeof(ID) * (size_t)e);
-    uint8_t* reached = keep + tp_align4((size_t)e);
-    const bool bad = tp_bad_lines(ei, e, n) != 0;   // (an id outside [0, n) is never followed: every pair reports it)
-    if (!bad)
-        for (int l = t; l < e; l += nt) {           // (a thread stages and flags the lines it will walk: tp_unreached's ownership)
-            from[l] = (ID)ei[l];
-            to[l] = (ID)ei[e + l];
-        }
-    const int a = lines[i];
-    int32_t* out = islands + cp_first_pair(i, c);
-    for (int j = i + 1; j < c; ++j) {
-        const int b = lines[j];
-        int count = PF_BAD_LINE;                    // (also a candidate that is no line: the pair is never computed)
-        if (!bad && (unsigned)a < (unsigned)e && (unsigned)b < (unsigned)e) {
-            for (int l = t; l < e; l += nt) keep[l] = l != a && l != b;
-            count = tp_unreached<ID>(from, to, keep, e, n, root, reached, &s_count);
-        }
-        if (t == 0) out[j - i - 1] = count;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ DC
-struct CpArgs {
+struct CpArgs {                                     // (contingency_base.hpp CtCommon's names, and the pair screen's own among them)
     const int64_t* edge_index;                      // [2, e], one list for all scenarios
     const double* rx;                               // [S, e, 2]
     const int32_t* bus_type;                        // [n]
@@ -113,10 +77,7 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void contingency_pairs_base_kernel(
     float* X;
     if constexpr (LDS) X = reinterpret_cast<float*>(cp_smem + ct_vec_bytes(n, e, 0));
     else X = XT;
-    const CtBaseIn in{a.edge_index, a.rx + (int64_t)s * 2 * e, a.bus_type, a.spec + (int64_t)s * 4 * n,
-                      a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * e : 0) : nullptr, a.base_flow + (int64_t)s * e, a.status + s,
-                      a.flags, a.tol, n, e, a.max_iter, a.n_pv, a.n_pq};
-    if (ct_base_solve(in, v, X) != 0) return;       // (a failed scenario's slab is never read)
+    if (ct_base_solve(ct_base_in(a, s), v, X) != 0) return;   // (a failed scenario's slab is never read)
     // ---- the staged vectors, for the pair launch
     float* f32 = XT + pf_mat_floats(m);
     float* x32 = f32 + e;
@@ -184,89 +145,39 @@ __global__ __launch_bounds__(PF_BIG_THREADS) void contingency_pairs_kernel(const
             XT = reinterpret_cast<const float*>(xl);
         }
         __syncthreads();
-        // ---- w_a = X[:, i] - X[:, j] of line a = (i -> j), zero at the slack; a column of X at the slack is zero
-        const int ci = aidx[la[la_id]], cj = aidx[lb[la_id]];
-        for (int b = t; b < n; b += nt) {
-            const int r = aidx[b];
-            float v = 0.f;
-            if (r >= 0) {
-                const float xi = ci >= 0 ? XT[ci * ld + r] : 0.f;
-                const float xj = cj >= 0 ? XT[cj * ld + r] : 0.f;
-                v = xi - xj;
-            }
-            wa[b] = v;
-        }
+        ct_column<true>(wa, XT, ld, aidx, n, aidx[la[la_id]], aidx[lb[la_id]], t, nt);   // w_a, once per workgroup
         __syncthreads();
     }
 
-    const float nanv = __builtin_nanf(""), infv = __builtin_inff();
     const int64_t p0 = cp_first_pair(i, c);
     for (int j = i + 1 + wave; j < c; j += nw) {
         const int64_t p = p0 + (j - i - 1);
         const int64_t o = (int64_t)s * a.P + p;
         float* row = a.post_flow ? a.post_flow + o * e : nullptr;
-        // a failed scenario: NaN and -1; an islanding pair: +inf, so that it ranks first, -1, -1 and a NaN row
         const int lb_id = a.lines[j];
-        if (failed || !a_ok || (unsigned)lb_id >= (unsigned)e || a.islands[p] != 0) {
-            if (row)
-                for (int l = lane; l < e; l += 64) row[l] = nanv;
-            if (lane == 0) {
-                a.severity[o] = failed ? nanv : infv;
-                a.worst_line[o] = -1;
-                a.overloads[o] = -1;
-            }
+        if (failed || !a_ok || (unsigned)lb_id >= (unsigned)e || a.islands[p] != 0) {   // a failed scenario, an islanding pair
+            ct_skip(failed, row, e, lane, 64, a.severity[o], a.worst_line[o], a.overloads[o]);
             continue;
         }
-        // ---- w_b, into the wave's own vector
-        const int di = aidx[la[lb_id]], dj = aidx[lb[lb_id]];
-        for (int b = lane; b < n; b += 64) {
-            const int r = aidx[b];
-            float v = 0.f;
-            if (r >= 0) {
-                const float xi = di >= 0 ? XT[di * ld + r] : 0.f;
-                const float xj = dj >= 0 ? XT[dj * ld + r] : 0.f;
-                v = xi - xj;
-            }
-            wb[b] = v;
-        }
+        ct_column<true>(wb, XT, ld, aidx, n, aidx[la[lb_id]], aidx[lb[lb_id]], lane, 64);   // w_b, into the wave's own vector
         __syncwarp();                               // (the wave's own LDS vector: written by its lanes, gathered by its lanes)
         const int aa = la[la_id], ab = lb[la_id], ba = la[lb_id], bb = lb[lb_id];
         const float xa = x32[la_id], xb = x32[lb_id];
         float ta, tb;
         ct_pair_solve(ct_pair_phi(wa[aa], wa[ab], xa), ct_pair_phi(wb[aa], wb[ab], xa), ct_pair_phi(wa[ba], wa[bb], xb),
                       ct_pair_phi(wb[ba], wb[bb], xb), f32[la_id], f32[lb_id], &ta, &tb);
-        // ---- the lines: post-pair flow, loading; per lane the largest loading with the lowest line, and the overload count
-        float best = -1.f;                          // (a loading is >= 0; a non-finite one counts as +inf and poisons the severity)
-        int arg = 0x7fffffff, cnt = 0, wild = 0;
+        // ---- the lines: post-pair flow, loading; the wave's worst (contingency_monitor.hpp)
+        CtWorst worst = ct_worst_none();
         for (int l = lane; l < e; l += 64) {
             const bool out = l == la_id || l == lb_id;
             const int fa = la[l], fb = lb[l];
             const float post = out ? 0.f : ct_pair_post(ct_pair_phi(wa[fa], wa[fb], x32[l]), ct_pair_phi(wb[fa], wb[fb], x32[l]), f32[l], ta, tb);
             if (row) row[l] = post;
             const float r = rat[l];
-            if (!out && r > 0.f) {                  // (a rating that is not > 0 -- zero, negative, NaN -- is unmonitored)
-                const float load = fabsf(post) / r;
-                const bool finite = load < infv;
-                const float key = finite ? load : infv;
-                wild |= !finite;
-                cnt += load > 1.f;
-                if (key > best) { best = key; arg = l; }
-            }
+            if (!out && r > 0.f) ct_worst_add(worst, l, ct_loading(post, r));
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oa = __shfl_xor(arg, off);
-            if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-            cnt += __shfl_xor(cnt, off);
-            wild |= __shfl_xor(wild, off);
-        }
-        if (lane == 0) {
-            const bool none = arg == 0x7fffffff;
-            a.severity[o] = none ? 0.f : (wild ? nanv : best);
-            a.worst_line[o] = none ? -1 : arg;
-            a.overloads[o] = cnt;
-        }
+        worst = ct_worst_wave(worst);
+        if (lane == 0) ct_store(ct_figures(worst), a.severity[o], a.worst_line[o], a.overloads[o]);
         __syncwarp();                               // (the next pair overwrites the vector)
     }
 }
@@ -281,37 +192,6 @@ static bool cp_sizes_ok(int64_t S, int64_t n, int64_t e, int64_t c) {
 using namespace pfn;
 
 extern "C" {
-
-int pfn_contingency_pair_islands(const int64_t* edge_index, int64_t n_lines, int64_t n_bus, int64_t root, const int32_t* lines,
-                                 int64_t n_candidates, int32_t* islands, void* stream) {
-    const char* who = "pfn_contingency_pair_islands";
-    PFN_CHECK_ARG(n_bus >= 1 && n_lines >= 0 && n_lines < (1ll << 24) && n_bus < (1ll << 24), "%s: bad sizes (%lld buses and %lld lines)", who,
-                  (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(n_candidates >= 0 && n_candidates <= n_lines, "%s: %lld candidates among %lld lines", who, (long long)n_candidates,
-                  (long long)n_lines);
-    PFN_CHECK_ARG(root >= 0 && root < n_bus, "%s: root %lld is outside [0, %lld)", who, (long long)root, (long long)n_bus);
-    const int n = (int)n_bus, e = (int)n_lines, c = (int)n_candidates;
-    const size_t bytes = cp_islands_lds_bytes(n, e);
-    PFN_CHECK_ARG(bytes <= (size_t)(kLdsCuBytes - kLdsReserve), "%s: %d buses and %d lines need %zu bytes of LDS, %d are there", who, n, e, bytes,
-                  kLdsCuBytes - kLdsReserve);
-    if (c < 2) return PFN_OK;
-    PFN_CHECK_ARG(edge_index && lines && islands, "%s: null pointer", who);
-    PFN_CHECK_ARG((reinterpret_cast<uintptr_t>(edge_index) & 7) == 0 && ((reinterpret_cast<uintptr_t>(islands) | reinterpret_cast<uintptr_t>(lines)) & 3) == 0,
-                  "%s: edge_index must be 8-byte aligned, lines and islands 4-byte", who);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const double pairs = 0.5 * (double)c * (double)(c - 1);
-    ProfScope ps("contingency_pair_islands", (double)(c - 1) * 16.0 * (double)e + pairs * 4.0, 0.0, s);
-    static std::atomic<uint64_t> raised16{0}, raised32{0};
-    if (n <= 65536) {
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pair_islands_kernel<uint16_t>), kLdsCuBytes - kLdsReserve, raised16));
-        contingency_pair_islands_kernel<uint16_t><<<c - 1, tp_threads(n, e), bytes, s>>>(edge_index, n, e, (int)root, lines, c, islands);
-    } else {
-        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pair_islands_kernel<uint32_t>), kLdsCuBytes - kLdsReserve, raised32));
-        contingency_pair_islands_kernel<uint32_t><<<c - 1, tp_threads(n, e), bytes, s>>>(edge_index, n, e, (int)root, lines, c, islands);
-    }
-    PFN_CHECK_LAUNCH();
-    return PFN_OK;
-}
 
 size_t pfn_contingency_pairs_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_candidates, int route) {
     if (n_samples <= 0 || !cp_sizes_ok(n_samples, n_bus, n_lines, n_candidates) || n_bus > PF_MAX_UNKNOWNS + 1 || route < 0 || route > 2) return 0;
@@ -348,52 +228,29 @@ int pfn_contingency_pairs(const int64_t* edge_index, int64_t n_lines, const doub
     if (n_samples == 0 || n_lines == 0) return PFN_OK;
     PFN_CHECK_ARG(edge_index && rx && bus_type && spec && base_flow && status && flags && ws, "%s: null pointer", who);
     PFN_CHECK_ARG(c < 2 || (lines && islands && severity && worst_line && overloads), "%s: null pointer", who);
-    PFN_CHECK_ARG(((reinterpret_cast<uintptr_t>(ws)) & 15) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(edge_index) | reinterpret_cast<uintptr_t>(rx) | reinterpret_cast<uintptr_t>(spec) |
-                        reinterpret_cast<uintptr_t>(ratings) | reinterpret_cast<uintptr_t>(base_flow)) & 7) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(bus_type) | reinterpret_cast<uintptr_t>(islands) | reinterpret_cast<uintptr_t>(severity) |
-                        reinterpret_cast<uintptr_t>(worst_line) | reinterpret_cast<uintptr_t>(overloads) | reinterpret_cast<uintptr_t>(status) |
-                        reinterpret_cast<uintptr_t>(post_flow) | reinterpret_cast<uintptr_t>(flags) | reinterpret_cast<uintptr_t>(lines)) & 3) == 0,
-                  "%s: the workspace must be 16-byte aligned, fp64 and int64 arrays 8-byte, fp32 and int32 arrays 4-byte", who);
     const size_t slab = cp_slab_bytes(n, e), need = (size_t)n_samples * slab;
+    const int64_t P = (int64_t)c * (c - 1) / 2;
+    const CpArgs a{edge_index, rx, bus_type, spec, ratings, lines, islands, severity, worst_line, overloads, base_flow, status, post_flow, flags,
+                   static_cast<unsigned char*>(ws), tol, slab, P, n, e, c, max_iter, (int)n_pv, (int)n_pq, ratings_per_sample != 0};
+    PFN_TRY(ct_check_aligned(who, a, lines));
     if (ws_bytes < need) {
         set_error("%s: needs a workspace of %zu bytes (got %zu)", who, need, ws_bytes);
         return PFN_ENOSPACE;
     }
-    const int64_t P = (int64_t)c * (c - 1) / 2;
-    CpArgs a{edge_index, rx, bus_type, spec, ratings, lines, islands, severity, worst_line, overloads, base_flow, status, post_flow, flags,
-             static_cast<unsigned char*>(ws), tol, slab, P, n, e, c, max_iter, (int)n_pv, (int)n_pq, ratings_per_sample != 0};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double ss = (double)n_samples, mm = (double)m, ee = (double)e, pp = (double)P;
     {
         ProfScope ps("contingency_pairs_base", ss * (ee * 44.0 + (double)n * 36.0 + mm * mm * 4.0), ss * (2.0 * mm * mm * mm + 6.0 * mm * mm), s);
-        if (ct_fits_lds(n, e)) {                    // (the N-1 screen's rule: the inverse is formed in LDS where it fits there)
-            static std::atomic<uint64_t> raised{0};
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_base_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-            contingency_pairs_base_kernel<true><<<(int)n_samples, threads, vec_base + mat, s>>>(a);
-        } else {
-            static std::atomic<uint64_t> raised_g{0};
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_base_kernel<false>), kLdsCuBytes - kLdsReserve, raised_g));
-            contingency_pairs_base_kernel<false><<<(int)n_samples, threads, vec_base, s>>>(a);
-        }
-        PFN_CHECK_LAUNCH();
+        // (the N-1 screen's rule: the inverse is formed in LDS where it fits there)
+        PFN_TRY((launch_either<contingency_pairs_base_kernel<true>, contingency_pairs_base_kernel<false>>(ct_fits_lds(n, e), (int)n_samples, threads,
+                                                                                                          vec_base + mat, vec_base, s, a)));
     }
     if (c < 2) return PFN_OK;
     {
         const bool lds = route == 1 || (route == 0 && fits);
         ProfScope ps("contingency_pairs", ss * ((double)(c - 1) * (lds ? (double)mat : 0.0) + pp * (8.0 * mm + 12.0 + (post_flow ? 4.0 * ee : 0.0))),
                      ss * pp * (2.0 * mm + 12.0 * ee), s);
-        const int grid = (int)(n_samples * (c - 1));
-        if (lds) {
-            static std::atomic<uint64_t> raised{0};
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-            contingency_pairs_kernel<true><<<grid, threads, vec + mat, s>>>(a);
-        } else {
-            static std::atomic<uint64_t> raised_g{0};
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_kernel<false>), kLdsCuBytes - kLdsReserve, raised_g));
-            contingency_pairs_kernel<false><<<grid, threads, vec, s>>>(a);
-        }
-        PFN_CHECK_LAUNCH();
+        PFN_TRY((launch_either<contingency_pairs_kernel<true>, contingency_pairs_kernel<false>>(lds, (int)(n_samples * (c - 1)), threads, vec + mat, vec, s, a)));
     }
     return PFN_OK;
 }

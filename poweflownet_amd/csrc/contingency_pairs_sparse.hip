@@ -16,14 +16,15 @@
 //
 // PAIRS, contingency_pairs_sparse_kernel, the hot path: one workgroup of `waves` waves per (scenario, first candidate i).  Wave w
 // takes the second candidates i + 1 + w, i + 1 + w + waves, ...: the four phi of M, t by ct_pair_solve, then the lanes stride over the
-// lines -- ct_pair_phi twice, ct_pair_post, the loading |f| / rating -- and contingency_pairs.hip's reduction: max with ties to the
-// lowest line, an integer sum, the non-finite flag; lane 0 writes the three outputs, the lanes write the table row coalesced.  The
-// per-line vectors (f32, x32, rat, pa, pb: 20 bytes a line) stay in the slab and are read coalesced; only the two columns are placed:
-// in LDS (w_a once per workgroup, one w_b per wave) or gathered from the column table -- one template, the same bits.
+// lines -- ct_pair_phi twice, ct_pair_post, the loading |f| / rating -- and the one tail of all screens (contingency_monitor.hpp):
+// max with ties to the lowest line, an integer sum, the non-finite flag; lane 0 writes the three outputs, the lanes write the table
+// row coalesced.  The per-line vectors (f32, x32, rat, pa, pb: 20 bytes a line) stay in the slab and are read coalesced; only the two
+// columns are placed: in LDS (w_a once per workgroup, one w_b per wave) or gathered from the column table -- one template, the same bits.
 // The arithmetic is contingency_line.hpp's ct_pair_*, compiled without contraction; one owner per output: the bits of (scenario, a,
 // b) are a pure function of the scenario's inputs, the plan and the two lines, whatever the batch, the candidate list, G, `threads`,
 // `waves` or either placement.  No host sync, no allocation (capturable), no float atomics.
 #include "contingency_line.hpp"
+#include "contingency_monitor.hpp"
 #include "contingency_sparse_core.hpp"
 
 namespace pfn {
@@ -130,22 +131,14 @@ __global__ __launch_bounds__(1024) void contingency_pairs_sparse_kernel(const Cp
         wa = wl;
     }
 
-    const float nanv = __builtin_nanf(""), infv = __builtin_inff();
     const int64_t p0 = cp_first_pair(i, c);
     for (int j = i + 1 + wave; j < c; j += nw) {
         const int64_t p = p0 + (j - i - 1);
         const int64_t o = (int64_t)s * a.P + p;
         float* row = a.post_flow ? a.post_flow + o * e : nullptr;
-        // a failed scenario: NaN and -1; an islanding pair: +inf, so that it ranks first, -1, -1 and a NaN row
         const int lb_id = a.lines[j];
-        if (failed || !a_ok || (unsigned)lb_id >= (unsigned)e || a.islands[p] != 0) {
-            if (row)
-                for (int l = lane; l < e; l += 64) row[l] = nanv;
-            if (lane == 0) {
-                a.severity[o] = failed ? nanv : infv;
-                a.worst_line[o] = -1;
-                a.overloads[o] = -1;
-            }
+        if (failed || !a_ok || (unsigned)lb_id >= (unsigned)e || a.islands[p] != 0) {   // a failed scenario, an islanding pair
+            ct_skip(failed, row, e, lane, 64, a.severity[o], a.worst_line[o], a.overloads[o]);
             continue;
         }
         // ---- w_b: the wave's own vector, or the table's column where it lies
@@ -161,9 +154,8 @@ __global__ __launch_bounds__(1024) void contingency_pairs_sparse_kernel(const Cp
         float ta, tb;
         ct_pair_solve(ct_pair_phi(wa[aa], wa[ab], xa), ct_pair_phi(wb[aa], wb[ab], xa), ct_pair_phi(wa[ba], wa[bb], xb),
                       ct_pair_phi(wb[ba], wb[bb], xb), f32[la_id], f32[lb_id], &ta, &tb);
-        // ---- the lines: post-pair flow, loading; per lane the largest loading with the lowest line, and the overload count
-        float best = -1.f;                          // (a loading is >= 0; a non-finite one counts as +inf and poisons the severity)
-        int arg = 0x7fffffff, cnt = 0, wild = 0;
+        // ---- the lines: post-pair flow, loading; the wave's worst (contingency_monitor.hpp)
+        CtWorst worst = ct_worst_none();
         for (int l = lane; l < e; l += 64) {
             const bool out = l == la_id || l == lb_id;
             const int fa = pa[l], fb = pb[l];
@@ -171,29 +163,10 @@ __global__ __launch_bounds__(1024) void contingency_pairs_sparse_kernel(const Cp
             const float post = out ? 0.f : ct_pair_post(ct_pair_phi(wa[fa], wa[fb], x), ct_pair_phi(wb[fa], wb[fb], x), f32[l], ta, tb);
             if (row) row[l] = post;
             const float r = rat[l];
-            if (!out && r > 0.f) {                  // (a rating that is not > 0 -- zero, negative, NaN -- is unmonitored)
-                const float load = fabsf(post) / r;
-                const bool finite = load < infv;
-                const float key = finite ? load : infv;
-                wild |= !finite;
-                cnt += load > 1.f;
-                if (key > best) { best = key; arg = l; }
-            }
+            if (!out && r > 0.f) ct_worst_add(worst, l, ct_loading(post, r));
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_xor(best, off);
-            const int oa = __shfl_xor(arg, off);
-            if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
-            cnt += __shfl_xor(cnt, off);
-            wild |= __shfl_xor(wild, off);
-        }
-        if (lane == 0) {
-            const bool none = arg == 0x7fffffff;
-            a.severity[o] = none ? 0.f : (wild ? nanv : best);
-            a.worst_line[o] = none ? -1 : arg;
-            a.overloads[o] = cnt;
-        }
+        worst = ct_worst_wave(worst);
+        if (lane == 0) ct_store(ct_figures(worst), a.severity[o], a.worst_line[o], a.overloads[o]);
         if constexpr (LDS) __syncwarp();            // (the next pair overwrites the vector)
     }
 }
@@ -268,31 +241,17 @@ int pfn_contingency_pairs_sparse(const int64_t* edge_index, int64_t n_lines, con
     {
         const double tl = (double)cs_tiles(c);
         ProfScope ps("contingency_pairs_sparse_columns", ss * (tl * nz * 6.0 + cc * (mm + 1.0) * 4.0), ss * tl * 64.0 * 2.0 * nz, s);
-        static std::atomic<uint64_t> raised{0};
         const unsigned char* plan_b = static_cast<const unsigned char*>(plan_dev);
-        if (blk_lds) {
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_sparse_columns_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-            contingency_pairs_sparse_columns_kernel<true><<<(int)G, 64, cs_block_bytes(m), s>>>(plan_b, ws_b, cols0, nullptr, status, lines, islands, stride,
-                                                                                                n, e, m, nnz, c, (int)n_samples);
-        } else {
-            contingency_pairs_sparse_columns_kernel<false><<<(int)G, 64, 0, s>>>(plan_b, ws_b, cols0, reinterpret_cast<float*>(ws_b + slabs), status,
-                                                                                 lines, islands, stride, n, e, m, nnz, c, (int)n_samples);
-        }
-        PFN_CHECK_LAUNCH();
+        float* blocks = blk_lds ? nullptr : reinterpret_cast<float*>(ws_b + slabs);
+        PFN_TRY((launch_either<contingency_pairs_sparse_columns_kernel<true>, contingency_pairs_sparse_columns_kernel<false>>(
+            blk_lds, (int)G, 64, cs_block_bytes(m), 0, s, plan_b, ws_b, cols0, blocks, status, lines, islands, stride, n, e, m, nnz, c, (int)n_samples)));
     }
     {
         const int64_t P = (int64_t)c * (c - 1) / 2;
         const CpsArgs b{ws_b, cols0, status, lines, islands, severity, worst_line, overloads, post_flow, stride, P, n, e, m, nnz, c};
         ProfScope ps("contingency_pairs_sparse", ss * pp * (8.0 * mm + 20.0 * ee + 12.0 + (post_flow ? 4.0 * ee : 0.0)), ss * pp * 12.0 * ee, s);
-        const int grid = (int)(n_samples * (c - 1));
-        if (col_lds) {
-            static std::atomic<uint64_t> raised_l{0};
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_pairs_sparse_kernel<true>), kLdsCuBytes - kLdsReserve, raised_l));
-            contingency_pairs_sparse_kernel<true><<<grid, 64 * nw, cps_lds_bytes(m, nw), s>>>(b);
-        } else {
-            contingency_pairs_sparse_kernel<false><<<grid, 64 * nw, 0, s>>>(b);
-        }
-        PFN_CHECK_LAUNCH();
+        PFN_TRY((launch_either<contingency_pairs_sparse_kernel<true>, contingency_pairs_sparse_kernel<false>>(col_lds, (int)(n_samples * (c - 1)), 64 * nw,
+                                                                                                              cps_lds_bytes(m, nw), 0, s, b)));
     }
     return PFN_OK;
 }

@@ -15,10 +15,12 @@
 // ascending (W[r] = fma(-L_rj, W[j], W[r])), backward descending (W[j] /= U_jj, W[r] = fma(-U_rj, W[j], W[r])): the column bounds,
 // row ids and factor values do not depend on the lane and are loaded once per wave.  Then den_k from two gathers and ONE loop over
 // the lines in ascending order with contingency.hip's per-line expression (contingency_line.hpp): the lane keeps the largest loading
-// under strict > (ties to the lowest line), the overload count and the non-finite flag in registers and writes its three outputs.
+// under strict > (ties to the lowest line), the overload count and the non-finite flag in registers and writes its three outputs --
+// the accumulator and the stores of every screen's tail (contingency_monitor.hpp); a lane per outage, so nothing is merged.
 // Workgroup g of G takes the items (scenario, tile) g, g + G, ...; an item's arithmetic does not know G.  W sits in LDS where
 // 256 (m + 1) bytes fit, else in the workgroup's block of the workspace: the same code, the same bits.
 #include "contingency_line.hpp"
+#include "contingency_monitor.hpp"
 #include "contingency_sparse_core.hpp"
 
 namespace pfn {
@@ -150,7 +152,6 @@ __global__ __launch_bounds__(64) void contingency_sparse_outages_kernel(const un
     float* __restrict__ W;                          // [m + 1][64]; this lane's column is W[r * 64], r = 0 .. m
     if constexpr (LDS) W = reinterpret_cast<float*>(cs_smem) + lane;
     else W = blocks + (size_t)blockIdx.x * 64 * ((size_t)m + 1) + lane;
-    const float nanv = __builtin_nanf(""), infv = __builtin_inff();
     const int tiles = (e + 63) >> 6;
     const int64_t items = (int64_t)n_samples * tiles;
     W[(size_t)m * 64] = 0.f;                        // (the slack's row: no column of the factor reaches it)
@@ -166,48 +167,35 @@ __global__ __launch_bounds__(64) void contingency_sparse_outages_kernel(const un
         if (status[s] < 0) {
             if (live) {
                 if (out_row)
-                    for (int l = 0; l < e; ++l) out_row[l] = nanv;
-                severity[o] = nanv;
-                worst_line[o] = -1;
-                overloads[o] = -1;
+                    for (int l = 0; l < e; ++l) out_row[l] = __builtin_nanf("");
+                ct_store(ct_figures_skipped(true), severity[o], worst_line[o], overloads[o]);
             }
             continue;
         }
-        // the scenario's slab as the base launch left it (cs_slab's layout)
-        const float* __restrict__ fac = reinterpret_cast<const float*>(slabs + (size_t)s * ws_stride + (size_t)8 * (2 * (size_t)n + m));
-        const float* __restrict__ f32 = fac + nnz;
-        const float* __restrict__ x32 = f32 + e;
-        const float* __restrict__ rat = x32 + e;
-        const int32_t* __restrict__ pa = reinterpret_cast<const int32_t*>(rat + e);
-        const int32_t* __restrict__ pb = pa + e;
+        // the scenario's slab as the base launch left it
+        const CsLines v = cs_lines(slabs, ws_stride, s, n, m, nnz, e);
+        const float* __restrict__ fac = v.fac;
+        const float* __restrict__ f32 = v.f32;
+        const float* __restrict__ x32 = v.x32;
+        const float* __restrict__ rat = v.rat;
+        const int32_t* __restrict__ pa = v.pa;
+        const int32_t* __restrict__ pb = v.pb;
         // an islanding outage keeps a zero right-hand side: +inf, -1, -1 and a NaN row in the end
         const bool run = live && islands[kc] == 0;
         const int pi = pa[kc], pj = pb[kc];
         cs_substitute(W, colptr, diag, row32, fac, m, run, pi, pj);
-        // ---- den_k from two gathers, then the lines in ascending order: post-outage flow, loading, the running maximum
+        // ---- den_k from two gathers, then the lines in ascending order: post-outage flow, loading, the lane's worst
+        //      (contingency_monitor.hpp: a lane per outage, so nothing is merged)
         const float den = ct_den(W[(size_t)pi * 64], W[(size_t)pj * 64], x32[kc]);
         const float fk = f32[kc];
-        float best = -1.f;                          // (a loading is >= 0; a non-finite one counts as +inf and poisons the severity)
-        int arg = 0x7fffffff, cnt = 0, wild = 0;
+        CtWorst worst = ct_worst_none();
         for (int l = 0; l < e; ++l) {
             const float post = l == k ? 0.f : ct_post(W[(size_t)pa[l] * 64], W[(size_t)pb[l] * 64], x32[l], den, f32[l], fk);
-            if (out_row && live) out_row[l] = run ? post : nanv;
+            if (out_row && live) out_row[l] = run ? post : __builtin_nanf("");
             const float r = rat[l];
-            if (l != k && r > 0.f) {                // (a rating that is not > 0 -- zero, negative, NaN -- is unmonitored)
-                const float load = fabsf(post) / r;
-                const bool finite = load < infv;
-                const float key = finite ? load : infv;
-                wild |= !finite;
-                cnt += load > 1.f;
-                if (key > best) { best = key; arg = l; }
-            }
+            if (l != k && r > 0.f) ct_worst_add(worst, l, ct_loading(post, r));
         }
-        if (live) {
-            const bool none = arg == 0x7fffffff;
-            severity[o] = run ? (none ? 0.f : (wild ? nanv : best)) : infv;
-            worst_line[o] = run && !none ? arg : -1;
-            overloads[o] = run ? cnt : -1;
-        }
+        if (live) ct_store(run ? ct_figures(worst) : ct_figures_skipped(false), severity[o], worst_line[o], overloads[o]);
     }
 }
 
@@ -304,18 +292,9 @@ int pfn_contingency_sparse(const int64_t* edge_index, int64_t n_lines, const dou
         const double tl = (double)cs_tiles(e);
         ProfScope ps("contingency_sparse_outages", ss * (tl * (nz * 6.0 + ee * 20.0) + ee * (12.0 + (post_flow ? 4.0 * ee : 0.0))),
                      ss * tl * 64.0 * (2.0 * nz + 8.0 * ee), s);
-        static std::atomic<uint64_t> raised{0};
-        const unsigned char* slab0 = static_cast<const unsigned char*>(ws);
-        const unsigned char* plan_b = static_cast<const unsigned char*>(plan_dev);
-        if (lds) {
-            PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(contingency_sparse_outages_kernel<true>), kLdsCuBytes - kLdsReserve, raised));
-            contingency_sparse_outages_kernel<true><<<(int)G, 64, cs_block_bytes(m), s>>>(plan_b, slab0, nullptr, status, islands, severity, worst_line,
-                                                                                          overloads, post_flow, stride, n, e, m, nnz, (int)n_samples);
-        } else {
-            contingency_sparse_outages_kernel<false><<<(int)G, 64, 0, s>>>(plan_b, slab0, a.blocks, status, islands, severity, worst_line, overloads,
-                                                                           post_flow, stride, n, e, m, nnz, (int)n_samples);
-        }
-        PFN_CHECK_LAUNCH();
+        PFN_TRY((launch_either<contingency_sparse_outages_kernel<true>, contingency_sparse_outages_kernel<false>>(
+            lds, (int)G, 64, cs_block_bytes(m), 0, s, static_cast<const unsigned char*>(plan_dev), static_cast<const unsigned char*>(ws), a.blocks, status,
+            islands, severity, worst_line, overloads, post_flow, stride, n, e, m, nnz, (int)n_samples)));
     }
     return PFN_OK;
 }

@@ -65,6 +65,22 @@ int next_sweep_direction();
 int ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& done);
 constexpr int kLdsCuBytes = 160 * 1024;            // LDS of one compute unit
 constexpr int kLdsReserve = 1024;                  // (kept free of a kernel's dynamic region: its static words)
+// "raise the dynamic-LDS limit once per device, then launch" for a kernel with two instantiations -- the LDS and the global placement
+// of a contingency screen, the 16-bit and the 32-bit ids of its islands launch --, each with its own dynamic LDS bytes.  The
+// instantiations are template arguments: every pair has its own two counters without anybody naming them.
+template <auto KFirst, auto KSecond, typename... Args>
+static int launch_either(bool first, int grid, int threads, size_t bytes_first, size_t bytes_second, hipStream_t s, const Args&... a) {
+    static std::atomic<uint64_t> raised_first{0}, raised_second{0};
+    if (first) {
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(KFirst), kLdsCuBytes - kLdsReserve, raised_first));
+        KFirst<<<grid, threads, bytes_first, s>>>(a...);
+    } else {
+        PFN_TRY(ensure_dynamic_lds(reinterpret_cast<const void*>(KSecond), kLdsCuBytes - kLdsReserve, raised_second));
+        KSecond<<<grid, threads, bytes_second, s>>>(a...);
+    }
+    PFN_CHECK_LAUNCH();
+    return PFN_OK;
+}
 
 static inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline int ld_of(int f) { return (int)round_up(f, 4); }

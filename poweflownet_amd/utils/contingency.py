@@ -204,6 +204,34 @@ def _check(bus_type, spec, edge_index, rx, who):
     return S, n, e
 
 
+def _prepare(who, bus_type, spec, edge_index, rx, ratings, plan=None, after_check=None):
+    """What the DC screens do with their inputs, in this order: `_check`, `after_check(n, e)` (a screen's own refusals), `_ratings`,
+    the plan's device (`route="sparse"`), `_bus_counts`, then int32 `bus_type` and contiguous inputs.  Returns (S, n, e,
+    (n_pv, n_pq, slack), bus_type, spec, edge_index, rx, ratings)."""
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    if after_check is not None:
+        after_check(n, e)
+    ratings = _ratings(ratings, S, e, who)
+    if plan is not None:
+        _plan_device(who, plan, spec.device)
+    counts = _bus_counts(bus_type)
+    return S, n, e, counts, bus_type.to(torch.int32).contiguous(), spec.contiguous(), edge_index.contiguous(), rx.contiguous(), ratings
+
+
+def _outputs(S, e, items, dev, keep_table):
+    """The tensors a DC screen of `items` outages or pairs per scenario fills, as the result's fields: `severity`, `worst_line`,
+    `overloads` [S, items], `base_flow` [S, e], `status` [S], `flags` [1] (zeroed) and `post_flow` [S, items, e] or None."""
+    return dict(severity=torch.empty(S, items, dtype=torch.float32, device=dev), worst_line=torch.empty(S, items, dtype=torch.int32, device=dev),
+                overloads=torch.empty(S, items, dtype=torch.int32, device=dev), base_flow=torch.empty(S, e, dtype=torch.float64, device=dev),
+                status=torch.empty(S, dtype=torch.int32, device=dev), flags=torch.zeros(1, dtype=torch.int32, device=dev),
+                post_flow=torch.empty(S, items, e, dtype=torch.float32, device=dev) if keep_table else None)
+
+
+def _plan_device(who, plan, dev):
+    if plan.blob.device != dev:
+        raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
+
+
 def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8, max_iter=10, route="auto", keep_table=False, plan=None,
                        block="auto", groups=None, threads=None) -> ContingencyResult:
     """Screen every single line outage of every scenario under the DC model: `bus_type` [n] (exactly one slack), `spec` [S, n, 4] and
@@ -228,33 +256,22 @@ def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8
         raise ValueError(f"{who}: route must be one of {sorted(_ROUTES) + ['sparse']}")
     if plan is not None or block != "auto" or groups is not None or threads is not None:
         raise ValueError(f"{who}: plan, block, groups and threads go with route='sparse' only")
-    S, n, e = _check(bus_type, spec, edge_index, rx, who)
-    ratings = _ratings(ratings, S, e, who)
-    n_pv, n_pq, slack = _bus_counts(bus_type)
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings)
     dev = spec.device
-    bt = bus_type.to(torch.int32).contiguous()
-    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
     lib = L.load()
     islands = torch.empty(e, dtype=torch.int32, device=dev)
-    severity = torch.empty(S, e, dtype=torch.float32, device=dev)
-    worst = torch.empty(S, e, dtype=torch.int32, device=dev)
-    overloads = torch.empty(S, e, dtype=torch.int32, device=dev)
-    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
-    status = torch.empty(S, dtype=torch.int32, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    table = torch.empty(S, e, e, dtype=torch.float32, device=dev) if keep_table else None
+    out = _outputs(S, e, e, dev, keep_table)
     need = int(lib.pfn_contingency_workspace_bytes(S, n, e, _ROUTES[route]))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
     with torch.cuda.device(dev):
         L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
         L.check(lib.pfn_contingency_dc(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
                                        int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
-                                       int(max_iter), _ROUTES[route], severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(),
-                                       base_flow.data_ptr(), status.data_ptr(), L.ptr(table), flags.data_ptr(), L.ptr(ws), need,
-                                       L.stream_ptr()),
+                                       int(max_iter), _ROUTES[route], out["severity"].data_ptr(), out["worst_line"].data_ptr(),
+                                       out["overloads"].data_ptr(), out["base_flow"].data_ptr(), out["status"].data_ptr(), L.ptr(out["post_flow"]),
+                                       out["flags"].data_ptr(), L.ptr(ws), need, L.stream_ptr()),
                 "pfn_contingency_dc")
-    return ContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, base_flow=base_flow, status=status,
-                             post_flow=table, route="global" if need else "lds", flags=flags)
+    return ContingencyResult(islands=islands, route="global" if need else "lds", **out)
 
 
 def _sparse_options(who, spec, edge_index, plan, block, groups, threads):
@@ -274,31 +291,15 @@ def _sparse_options(who, spec, edge_index, plan, block, groups, threads):
             raise ValueError(f"{who}: the plan is for (n, e) = {(plan.n, plan.e)}; the call has {(int(spec.shape[1]), int(edge_index.shape[1]))}")
 
 
-def _plan_device(who, plan, dev):
-    if plan.blob.device != dev:
-        raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
-
-
 def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_table, plan, block, groups, threads) -> ContingencyResult:
     """`contingency_screen(route="sparse")`: islands, base, outages -- three launches, the one host read of `_bus_counts`."""
     who = "contingency_screen"
     _sparse_options(who, spec, edge_index, plan, block, groups, threads)
-    S, n, e = _check(bus_type, spec, edge_index, rx, who)
-    ratings = _ratings(ratings, S, e, who)
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings, plan=plan)
     dev = spec.device
-    _plan_device(who, plan, dev)
-    n_pv, n_pq, slack = _bus_counts(bus_type)
-    bt = bus_type.to(torch.int32).contiguous()
-    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
     lib = L.load()
     islands = torch.empty(e, dtype=torch.int32, device=dev)
-    severity = torch.empty(S, e, dtype=torch.float32, device=dev)
-    worst = torch.empty(S, e, dtype=torch.int32, device=dev)
-    overloads = torch.empty(S, e, dtype=torch.int32, device=dev)
-    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
-    status = torch.empty(S, dtype=torch.int32, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    table = torch.empty(S, e, e, dtype=torch.float32, device=dev) if keep_table else None
+    out = _outputs(S, e, e, dev, keep_table)
     header, g = C.addressof(plan.header), 0 if groups is None else groups
     with torch.cuda.device(dev):
         need = int(lib.pfn_contingency_sparse_workspace_bytes(S, e, header, _BLOCKS[block], g)) if S else 0
@@ -307,12 +308,12 @@ def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_
         L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
         L.check(lib.pfn_contingency_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
                                            int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
-                                           int(max_iter), severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(),
-                                           status.data_ptr(), L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, header, plan.blob.data_ptr(),
-                                           0 if threads is None else threads, _BLOCKS[block], g, L.stream_ptr()),
+                                           int(max_iter), out["severity"].data_ptr(), out["worst_line"].data_ptr(), out["overloads"].data_ptr(),
+                                           out["base_flow"].data_ptr(), out["status"].data_ptr(), L.ptr(out["post_flow"]), out["flags"].data_ptr(),
+                                           ws.data_ptr(), need, header, plan.blob.data_ptr(), 0 if threads is None else threads, _BLOCKS[block], g,
+                                           L.stream_ptr()),
                 "pfn_contingency_sparse")
-    return ContingencyResult(severity=severity, worst_line=worst, overloads=overloads, islands=islands, base_flow=base_flow, status=status,
-                             post_flow=table, route="sparse", flags=flags, block="lds" if in_lds else "global")
+    return ContingencyResult(islands=islands, route="sparse", block="lds" if in_lds else "global", **out)
 
 
 _LINES_KEPT = {}  # (device, candidate tuple) -> (int32 [c] lines, int64 [P, 2] pairs) on the device: a capture after its eager call uploads nothing
@@ -371,21 +372,16 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
             raise ValueError(f"{who}: lines must be strictly increasing (sorted, no duplicates)")
         if lines[0] < 0 or (e_given is not None and lines[-1] >= e_given):
             raise ValueError(f"{who}: lines must lie within [0, {e_given}); got {lines[0]} .. {lines[-1]}")
-    S, n, e = _check(bus_type, spec, edge_index, rx, who)
-    if e < 2:
-        raise ValueError(f"{who}: a grid of {e} line has no pair to screen")
-    lib = L.load()
-    cap = int(lib.pfn_powerflow_max_unknowns())
-    if route != "sparse" and n - 1 > cap:
-        raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); beyond it: "
-                         f"route='sparse' with plan=sparse_plan(bus_type, edge_index, mode='dc')")
-    ratings = _ratings(ratings, S, e, who)
-    dev = spec.device
-    if route == "sparse":
-        _plan_device(who, plan, dev)
-    n_pv, n_pq, slack = _bus_counts(bus_type)
-    bt = bus_type.to(torch.int32).contiguous()
-    spec, rx, edge_index = spec.contiguous(), rx.contiguous(), edge_index.contiguous()
+    def pairs_fit(n, e):
+        if e < 2:
+            raise ValueError(f"{who}: a grid of {e} line has no pair to screen")
+        cap = int(L.load().pfn_powerflow_max_unknowns())
+        if route != "sparse" and n - 1 > cap:
+            raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); beyond it: "
+                             f"route='sparse' with plan=sparse_plan(bus_type, edge_index, mode='dc')")
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings,
+                                                                                plan=plan if route == "sparse" else None, after_check=pairs_fit)
+    dev, lib = spec.device, L.load()
     if lines is None:                                                         # all lines: built on the device, nothing uploaded
         c = e
         ij = torch.triu_indices(c, c, 1, device=dev)
@@ -395,15 +391,9 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
         lines_d, pairs = _device_lines(lines, dev)
     P = c * (c - 1) // 2
     islands = torch.empty(P, dtype=torch.int32, device=dev)
-    severity = torch.empty(S, P, dtype=torch.float32, device=dev)
-    worst = torch.empty(S, P, dtype=torch.int32, device=dev)
-    overloads = torch.empty(S, P, dtype=torch.int32, device=dev)
-    base_flow = torch.empty(S, e, dtype=torch.float64, device=dev)
-    status = torch.empty(S, dtype=torch.int32, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
-    table = torch.empty(S, P, e, dtype=torch.float32, device=dev) if keep_table else None
-    out = dict(severity=severity, worst_line=worst, overloads=overloads, islands=islands, pairs=pairs, base_flow=base_flow, status=status,
-               post_flow=table, flags=flags)
+    out = dict(islands=islands, pairs=pairs, **_outputs(S, e, P, dev, keep_table))
+    figures = [out[k].data_ptr() for k in ("severity", "worst_line", "overloads", "base_flow", "status")]
+    figures += [L.ptr(out["post_flow"]), out["flags"].data_ptr()]              # (in the C entries' order)
     per_sample = int(ratings is not None and ratings.dim() == 2)
     with torch.cuda.device(dev):
         L.check(lib.pfn_contingency_pair_islands(edge_index.data_ptr(), e, n, slack, lines_d.data_ptr(), c, islands.data_ptr(), L.stream_ptr()),
@@ -418,10 +408,8 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
             ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             L.check(lib.pfn_contingency_pairs_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings), per_sample,
                                                      lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv, n_pq, float(tol), int(max_iter),
-                                                     severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(),
-                                                     status.data_ptr(), L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, header,
-                                                     plan.blob.data_ptr(), 0 if threads is None else threads, _BLOCKS[block], g, _COLUMNS[columns], w,
-                                                     L.stream_ptr()),
+                                                     *figures, ws.data_ptr(), need, header, plan.blob.data_ptr(), 0 if threads is None else threads,
+                                                     _BLOCKS[block], g, _COLUMNS[columns], w, L.stream_ptr()),
                     "pfn_contingency_pairs_sparse")
             return PairContingencyResult(route="sparse", block="lds" if block_lds else "global", columns="lds" if columns_lds else "global", **out)
         need = int(lib.pfn_contingency_pairs_workspace_bytes(S, n, e, c, 2)) if S else 0
@@ -429,8 +417,7 @@ def contingency_screen_pairs(bus_type, spec, edge_index, rx, ratings=None, *, li
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
         L.check(lib.pfn_contingency_pairs(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings), per_sample,
                                           lines_d.data_ptr(), c, islands.data_ptr(), S, n, n_pv, n_pq, float(tol), int(max_iter), _ROUTES[route],
-                                          severity.data_ptr(), worst.data_ptr(), overloads.data_ptr(), base_flow.data_ptr(), status.data_ptr(),
-                                          L.ptr(table), flags.data_ptr(), ws.data_ptr(), need, L.stream_ptr()),
+                                          *figures, ws.data_ptr(), need, L.stream_ptr()),
                 "pfn_contingency_pairs")
     return PairContingencyResult(route="lds" if in_lds else "global", **out)
 
