@@ -24,6 +24,11 @@ loads it; the normalisation statistics are `<data-dir>/params/data_params_R.pt` 
 split of --data-dir (synthetic scenarios have none: identity).  Beside each scenario's top DC outages it prints the network's top
 outages with their AC-verified loadings (`verify_contingencies` on the network's result) and writes
 results/<case>_contingency_model_{severity,worst_line,overloads}.npy.  Without --model-run-id nothing changes.
+
+--ac [--halves H] adds the AC screen (`contingency_screen_ac`: compensated 1P1Q, H fast-decoupled half-iterations per outage from
+the AC base solution, 2 by default; dense route only) with the same ratings: per scenario its top outages with the DC severity, the
+1P1Q severity and the AC-verified severity side by side, how often each screen names the AC worst line, the voltage figures, and
+results/<case>_contingency_ac_{severity,worst_line,overloads,vm_min,vm_min_bus,v_violations,mismatch}.npy.
 """
 import argparse
 import os
@@ -63,6 +68,8 @@ def main(argv=None):
     ap.add_argument("--out-dir", default="results")
     ap.add_argument("--model-run-id", default=None, help="also screen with the network of models/model_<id>.pt (contingency_screen_model)")
     ap.add_argument("--cfg_json", default="configs/standard.json", help="--model-run-id: the network's hidden_dim, n_gnn_layers, K")
+    ap.add_argument("--ac", action="store_true", help="also screen under AC by compensated 1P1Q (contingency_screen_ac; dense route)")
+    ap.add_argument("--halves", type=int, default=2, help="--ac: fast-decoupled half-iterations per outage (2: 1P1Q, 4: 2P2Q)")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
@@ -105,7 +112,48 @@ def main(argv=None):
         screen_pairs(a, res, islands, bt, spec, ei, rx, ratings, kw, solver_kw)
     if a.model_run_id is not None:
         screen_model(a, islands, bt, spec, ei, rx, ratings, solver_kw)
+    if a.ac:
+        screen_ac(a, res, islands, bt, spec, ei, rx, ratings, solver_kw)
     return 0
+
+
+def screen_ac(a, dc_res, islands, bt, spec, ei, rx, ratings, solver_kw):
+    """--ac: the AC screen of the same scenarios with the same ratings, its worst outages AC-verified beside the DC screen's figures,
+    the voltage figures, and the seven result files"""
+    import torch
+
+    from poweflownet_amd.utils.contingency import contingency_screen_ac, verify_contingencies
+    res = contingency_screen_ac(bt, spec, ei, rx, ratings, halves=a.halves)
+    S, e = int(spec.shape[0]), int(ei.shape[1])
+    failed = int((res.status < 0).sum())
+    print(f"AC screen: {a.halves} half-iterations per outage, {S} scenarios x {e} outages, inverses on the {res.route} placement, "
+          f"{res.group} outages per workgroup; base solves {int(res.status.clamp(min=0).max())} half-iterations at most, {failed} failed")
+    top = min(a.verify_top, int((islands == 0).sum()))
+    ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top, **solver_kw)
+    sc, out = ver.pairs[:, 0], ver.pairs[:, 1]
+    pairs, fd, ac, status = ver.pairs.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy(), ver.status.cpu().numpy()
+    dc = dc_res.severity[sc, out].cpu().numpy()                            # (dc_severity above: this screen's figure, the 1P1Q one)
+    dc_worst, fd_worst, ac_worst = dc_res.worst_line[sc, out].cpu().numpy(), res.worst_line[sc, out].cpu().numpy(), ver.worst_line.cpu().numpy()
+    vmin, vbus, vviol = (getattr(res, k)[sc, out].cpu().numpy() for k in ("vm_min", "vm_min_bus", "v_violations"))
+    mis = res.mismatch[sc, out].cpu().numpy()
+    for s in range(S):
+        rows = [f"line {pairs[t, 1]}: DC {dc[t]:.3f} 1P1Q {fd[t]:.3f} AC {'failed' if status[t] < 0 else format(ac[t], '.3f')} "
+                f"worst line {dc_worst[t]}/{fd_worst[t]}/{ac_worst[t]} Vmin {vmin[t]:.3f} at bus {vbus[t]} ({vviol[t]} outside) mismatch {mis[t]:.1e}"
+                for t in np.flatnonzero(pairs[:, 0] == s)]
+        print(f"scenario {s} AC screen: " + "; ".join(rows))
+    solved = status >= 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        err_dc, err_fd = (np.abs(v - ac)[solved & np.isfinite(v)] / ac[solved & np.isfinite(v)] for v in (dc, fd))
+    med = lambda v: float(np.median(v)) if v.size else float("nan")           # noqa: E731
+    print(f"{len(pairs)} pairs verified, {int((~solved).sum())} AC solves failed; worst line equals AC's: DC {int((solved & (dc_worst == ac_worst)).sum())}, "
+          f"1P1Q {int((solved & (fd_worst == ac_worst)).sum())}; relative severity error, median: DC {med(err_dc):.2g}, 1P1Q {med(err_fd):.2g}; "
+          f"{int((solved & (fd < 1) & (ac > 1)).sum())} of {int((solved & (fd < 1)).sum())} the AC screen called secure are overloaded under AC")
+    ok = (res.islands == 0)[None, :] & (res.status >= 0)[:, None]
+    low = torch.where(ok, res.vm_min, torch.full_like(res.vm_min, float("inf")))
+    print(f"voltage: lowest Vm over all screened outages {float(low.min()):.4f}; {int((ok & (res.v_violations > 0)).sum())} of {int(ok.sum())} "
+          f"(scenario, outage) pairs leave a PQ bus outside the limits; largest mismatch {float(res.mismatch[ok].max()) if bool(ok.any()) else float('nan'):.2e}")
+    for name in ("severity", "worst_line", "overloads", "vm_min", "vm_min_bus", "v_violations", "mismatch"):
+        np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_ac_{name}.npy"), getattr(res, name).cpu().numpy())
 
 
 def model_statistics(a):

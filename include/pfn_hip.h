@@ -982,6 +982,50 @@ int pfn_contingency_model_loadings(const float* out, const int32_t* bus_type, co
                                    int64_t n_lines, const int64_t* item0, int64_t chunk, const float* std4, const float* mean4, int route,
                                    float* severity, int32_t* worst_line, int32_t* overloads, float* loading, float* predictions, void* stream);
 
+/* AC N-1 screening, compensated 1P1Q on the dense route (csrc/contingency_ac.hip): for every scenario and every single line outage,
+ * `halves` half-iterations of the fast-decoupled power flow from the scenario's AC base solution, the inverses of B' and B''
+ * corrected for the missing line by a rank-1 update.  Inputs as pfn_contingency_dc's (ONE line list, bus_type DEVICE int32, spec
+ * [S, n, 4] and rx [S, e, 2] DEVICE fp64, ratings [e] or [S, e] or null, islands from pfn_contingency_islands) plus `init`
+ * [S, n, 2] = (Vm, Va in degrees) or null, the base solve's start.  variant 0: XB, 1: BX (pfn_powerflow_solve_init's modes 2 and
+ * 3: their B' and B'' over the full list).  Two launches, no host sync, no allocation (capturable), no float atomics; n_bus - 1 <=
+ * pfn_powerflow_max_unknowns().
+ *
+ * BASE, one workgroup per scenario: the fast-decoupled solve to tol within max_iter half-iterations -- the SAME code as
+ * pfn_powerflow_solve_init's modes 2 / 3, so base_table fp64 [S, n, 4] (32-byte aligned), status int32 [S] and residual fp64 [S] carry
+ * that call's bits.  It keeps X' = B'^-1 and X'' = B''^-1 (fp32), the fp64 base state and a per-bus list of line ends in the
+ * scenario's slab of `ws` (pfn_contingency_ac_workspace_bytes, 16-byte aligned; PFN_ENOSPACE when short).
+ *
+ * OUTAGES, one wave per (scenario s, outage k = (i -> j)), `group` of them to a workgroup, for a non-islanding outage of a scenario
+ * with status >= 0.  From the base state, for h = 0 .. halves - 1: F = the fp64 mismatch of the grid WITHOUT line k (a bus's terms
+ * in stored line order); even h (every h where there is no PQ bus): theta -= X'_k (dP / Vm) over the angle buses; odd h:
+ * Vm -= X''_k (dQ / Vm) over the PQ buses; X_k g = X g + w (w . g) / (1 / c_k - a^T w), a = e_i - e_j restricted to the matrix's
+ * buses, w = X a, c_k the line's weight in the matrix (1 / x or x / (r^2 + x^2)); the fp32 entries in fp64 arithmetic, the corrected
+ * matrix never formed.  Then
+ *   mismatch      fp64 [S, e]: max |F| at the final state -- how far from converged the estimate is;
+ *   severity, worst_line, overloads   fp32 / int32 / int32 [S, e]: pfn_contingency_dc's rules over the loadings I_l / (float)rating_l
+ *                 of the lines l != k, I_l the fp32 current of pfn_branch_flows' arithmetic on the fp32-rounded final state;
+ *   vm_min, vm_min_bus, v_violations  fp32 / int32 / int32 [S, e] over the PQ buses from the fp32-rounded final Vm: the lowest (ties to
+ *                 the lowest bus; bus -1 and NaN without a PQ bus) and the count of Vm < v_lo or > v_hi, compared in fp32; a non-finite
+ *                 Vm counts, is the lowest, and makes vm_min NaN;
+ *   post_current  optional fp32 [S, e, e] (row = outage, column = line; NaN at l = k); post_state optional fp32 [S, e, n, 2] = (Vm, Va
+ *                 in degrees), 8-byte aligned.
+ * An islanding outage (islands[k] != 0): +inf, -1, -1; NaN voltage figures and mismatch with -1 integers; NaN rows.  A failed
+ * scenario (status < 0, -1 .. -5 as in pfn_powerflow_solve_init): NaN floats and -1 integers for all its outages; flags[0] bit 0 with -5.
+ * halves = 0: the figures of the base state with line k unmonitored.
+ *   route   0 auto, 1 both inverses copied into LDS beside the waves' vectors (PFN_EINVAL where they do not fit), 2 read from the slab;
+ *   group   0 auto, or the waves per workgroup, 1 .. 16.  No bit of any output depends on either.
+ * pfn_contingency_ac_waves: the waves per workgroup a call with these arguments runs, *in_lds its placement; 0 where it is refused.
+ * PFN_EINVAL: bad sizes or counts, halves < 0, variant outside {0, 1}, v_lo > v_hi or NaN, beyond the dense cap, route / group that do
+ * not fit, null or misaligned pointers.                                                                                            */
+size_t pfn_contingency_ac_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_pq);
+int pfn_contingency_ac_waves(int64_t n_bus, int64_t n_pq, int route, int group, int* in_lds);
+int pfn_contingency_ac(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                       const double* init, const double* ratings, int ratings_per_sample, const int32_t* islands, int64_t n_samples,
+                       int64_t n_bus, int64_t n_pv, int64_t n_pq, int variant, int halves, float v_lo, float v_hi, double tol, int max_iter,
+                       int route, int group, float* severity, int32_t* worst_line, int32_t* overloads, float* vm_min, int32_t* vm_min_bus,
+                       int32_t* v_violations, double* mismatch, double* base_table, int32_t* status, double* residual, float* post_current,
+                       float* post_state, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

@@ -44,6 +44,7 @@ SYMBOLS = (
     "pfn_contingency_pair_islands", "pfn_contingency_pairs_workspace_bytes", "pfn_contingency_pairs",
     "pfn_contingency_pairs_sparse_workspace_bytes", "pfn_contingency_pairs_sparse",
     "pfn_contingency_model_lds_max_bus", "pfn_contingency_model_batch", "pfn_contingency_model_loadings",
+    "pfn_contingency_ac_workspace_bytes", "pfn_contingency_ac_waves", "pfn_contingency_ac",
 )
 
 # enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
@@ -207,6 +208,10 @@ def load() -> C.CDLL:
                                                   C.POINTER(C.c_float), C.POINTER(C.c_float), p, p, p, p, p, p, p]),
         "pfn_contingency_model_loadings": (C.c_int, [p, p, p, p, p, p, C.c_int, p, i64, i64, i64, p, i64, C.POINTER(C.c_float),
                                                      C.POINTER(C.c_float), C.c_int, p, p, p, p, p, p]),
+        "pfn_contingency_ac_workspace_bytes": (sz, [i64, i64, i64, i64]),
+        "pfn_contingency_ac_waves": (C.c_int, [i64, i64, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+        "pfn_contingency_ac": (C.c_int, [p, i64, p, p, p, p, p, C.c_int, p, i64, i64, i64, i64, C.c_int, C.c_int, f32, f32, C.c_double,
+                                         C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

@@ -29,7 +29,9 @@
 //
 // What this kernel shares with the sparse routes -- the status codes, the start state, the line-end terms, the stopping rule, the
 // table write-back, the argument checks -- is powerflow_common.hpp's; the Newton pass itself (rows, LU, update), shared with the
-// Q-limit kernel, and the route decision are powerflow_dense.hpp's.
+// Q-limit kernel, and the route decision are powerflow_dense.hpp's -- and so is the sample's whole solve (pf_solve_sample, with the
+// fast-decoupled matrices' build in pf_fd_inverses): the AC contingency screen's base launch (contingency_ac.hip) runs the same text,
+// so its base table is this kernel's, bit for bit.  The kernel below places the matrix and calls it.
 #include <algorithm>
 
 #include "powerflow_dense.hpp"
@@ -37,142 +39,20 @@
 namespace pfn {
 
 // (the dense cap, the workgroup sizes, pf_ld, pf_mat_floats and the Gauss-Jordan inverse: powerflow_dense.hpp, with contingency.hip)
-// the sample's vectors: double vm, th, sp, sq [n], F [m]; int aidx, vidx [n]; rounded to 16 bytes
-__host__ __device__ inline size_t pf_vec_bytes(int n, int m) { return ((size_t)8 * (4 * (size_t)n + m) + (size_t)8 * n + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t pf_fd_extra_bytes(int m) { return ((size_t)8 * m + 15) & ~(size_t)15; }      // modes 2, 3: F / Vm [m]
-
-struct PfArgs {
-    PfProblem p;                                    // (p.ws: the global route's fp32 slabs)
-    int m, n_pv, n_pq, mode, lines_per_sample;
-};
+// (the sample's vectors, pf_vec_bytes / pf_fd_extra_bytes, the argument block PfArgs and the sample's whole solve, pf_solve_sample:
+// powerflow_dense.hpp, with contingency_ac.hip's base launch)
 
 template <bool LDS, bool FD>
 __global__ __launch_bounds__(PF_BIG_THREADS) void powerflow_kernel(const PfArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
-    __shared__ double s_red[16];
-    __shared__ int s_ok, s_slack;
-    const int t = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
     const int s = blockIdx.x;
     const PfProblem& p = a.p;
-    const int n = p.n, e = p.e, m = a.m, ld = pf_ld(m);
-    const bool dc = !FD && a.mode == 1;
-    const int mp = n - 1, mq = a.n_pq, ldp = pf_ld(mp), ldq = pf_ld(mq);      // FD: B' [mp x mp], B'' [mq x mq] behind it
-    double* vm = reinterpret_cast<double*>(pf_smem);
-    double* th = vm + n;
-    double* sp = th + n;
-    double* sq = sp + n;
-    double* F = sq + n;
-    int* aidx = reinterpret_cast<int*>(F + m);
-    int* vidx = aidx + n;
-    double* G = reinterpret_cast<double*>(pf_smem + pf_vec_bytes(n, m));      // FD only: F / Vm [m]
+    const int n = p.n, m = a.m;
+    const int mp = n - 1, mq = a.n_pq;
     float* A;
     if constexpr (LDS) A = reinterpret_cast<float*>(pf_smem + pf_vec_bytes(n, m) + (FD ? pf_fd_extra_bytes(m) : 0));
     else A = static_cast<float*>(p.ws) + (size_t)s * (FD ? pf_mat_floats(mp) + pf_mat_floats(mq) : pf_mat_floats(m));
-    float* Bq = A + pf_mat_floats(mp);
-    const PfSample sm = pf_sample(p, s);
-    const int64_t* ei = p.edge_index + (a.lines_per_sample ? (int64_t)s * 2 * e : 0);
-    const double* rx = sm.rx;
-    const PfDense d{ei, rx, sm.spec, sm.spec + 3, 4, n, e, aidx, vidx, vm, th, sp, sq, F};
-    int code = 0;                                   // (uniform over the workgroup wherever it is tested)
-    double res = __builtin_nan("");
-
-    // ---- the lines name buses of the grid?  (an id outside [0, n) is never followed)
-    int bad = 0;
-    for (int k = t; k < e; k += nt) bad |= (uint64_t)ei[k] >= (uint64_t)n || (uint64_t)ei[e + k] >= (uint64_t)n;
-    // ---- unknown numbering; the host's n_pv / n_pq (they decided m, the route and the LDS size) against the device bus types
-    if (t == 0) {
-        int na = 0, nv = 0, ns = 0, npv = 0, npq = 0, odd = 0, slack = 0;
-        for (int i = 0; i < n; ++i) {
-            const int ty = p.bus_type[i];
-            int ia = -1, iv = -1;
-            if (ty == 0) { ++ns; slack = i; }
-            else if (ty == 1) { ++npv; ia = na++; }
-            else if (ty == 2) { ++npq; ia = na++; if (!dc) iv = (n - 1) + nv++; }
-            else odd = 1;
-            aidx[i] = ia;
-            vidx[i] = iv;
-        }
-        s_slack = slack;
-        s_ok = !odd && ns == 1 && npv == a.n_pv && npq == a.n_pq;
-    }
-    bad = __syncthreads_or(bad);
-    if (!s_ok) {
-        code = PF_BAD_TYPES;
-        if (t == 0) p.flags[0] = p.flags[0] | 1;    // (every writer stores the same bit over the same word)
-    } else if (bad) {
-        code = PF_BAD_LINE;
-    }
-
-    int it = 0;
-    if (code == 0 && pf_start_state(p, sm, p.bus_type, s_slack, dc, nt, vm, th)) code = PF_NON_FINITE;
-    if (code == 0) {
-        int half = 0;                               // FD: 0 the P half comes next, 1 the Q half
-        for (;; ++it) {
-            // ---- line sums, mismatch and matrix rows (powerflow_dense.hpp)
-            pf_dense_rows<FD>(d, dc, A, m, ld, G);
-            // ---- max |F| in fp64; a non-finite entry counts as +inf
-            double mx = 0.0;
-            for (int k = t; k < m; k += nt) mx = fmax(mx, pf_abs_clamped(F[k]));
-            res = pf_block_max(mx, s_red, nw);
-            const int stop = pf_stop(res, p.tol, it, p.max_iter);
-            if (stop < 0) { code = stop; break; }
-            if (stop) break;
-            if constexpr (FD) {
-                if (it == 0) {
-                    // ---- B' and B'', once: Laplacians of the stored lines (parallel lines add, a self-loop cancels), bus i's rows
-                    //      by bus i in stored order, the diagonal summed in fp64 and added last; then inverted in place
-                    const bool xb = a.mode == 2;
-                    for (int k = t; k < (int)(pf_mat_floats(mp) + pf_mat_floats(mq)); k += nt) A[k] = 0.f;
-                    __syncthreads();
-                    for (int i = t; i < n; i += nt) {
-                        const int ra = aidx[i], rv = vidx[i];
-                        double dp = 0.0, dq = 0.0;
-                        for (int k = 0; k < e; ++k) {
-                            const int la = (int)ei[k], lb = (int)ei[e + k];
-                            if (la != i && lb != i) continue;
-                            const double r = rx[2 * k], x = rx[2 * k + 1];
-                            const double w1 = 1.0 / x, w2 = x / (r * r + x * x);
-                            const double wp = xb ? w1 : w2, wq = xb ? w2 : w1;
-#pragma unroll 1
-                            for (int side = 0; side < 2; ++side) {
-                                if ((side ? lb : la) != i) continue;
-                                const int j = side ? la : lb;
-                                const int ca = aidx[j], cv = vidx[j];
-                                dp += wp;
-                                dq += wq;
-                                if (ra >= 0 && ca >= 0) A[ra * ldp + ca] += (float)(-wp);
-                                if (rv >= 0 && cv >= 0) Bq[(rv - mp) * ldq + (cv - mp)] += (float)(-wq);
-                            }
-                        }
-                        if (ra >= 0) A[ra * ldp + ra] += (float)dp;
-                        if (rv >= 0) Bq[(rv - mp) * ldq + (rv - mp)] += (float)dq;
-                    }
-                    __syncthreads();
-                    if (!pf_invert_in_place(A, mp, ldp) || !pf_invert_in_place(Bq, mq, ldq)) { code = PF_SINGULAR; break; }
-                }
-                // ---- one half-iteration: a mat-vec with the resident inverse, row by its owner, fp64 sum in column order
-                for (int i = t; i < n; i += nt) {
-                    const int r = half ? vidx[i] - mp : aidx[i];
-                    if (r < 0) continue;
-                    const float* row = half ? Bq + r * ldq : A + r * ldp;
-                    const double* g = half ? G + mp : G;
-                    const int cols = half ? mq : mp;
-                    double acc = 0.0;
-                    for (int c = 0; c < cols; ++c) acc += (double)row[c] * g[c];
-                    if (half) vm[i] -= acc;
-                    else th[i] -= acc;
-                }
-                __syncthreads();
-                half = mq ? !half : 0;
-                continue;
-            }
-            // ---- A dx = F by LU with partial pivoting, then x += dx (powerflow_dense.hpp)
-            if (!pf_lu_solve(A, ld, m, F)) { code = PF_SINGULAR; break; }
-            pf_dense_update(d, A, ld);
-        }
-    }
-
-    pf_write_back(p, sm, s, dc, nt, code, it, res, vm, th, sp, sq);
+    pf_solve_sample<FD>(a, s, pf_smem, A);
 }
 
 static int pf_unknowns(int64_t n, int64_t n_pq, int mode) { return (int)((n - 1) + (mode == 1 ? 0 : n_pq)); }

@@ -11,7 +11,11 @@ lines out together, a rank-2 update of the same inverse (csrc/contingency_pairs.
 (csrc/contingency_pairs_sparse.hip: `pfn_contingency_pairs_sparse`); `verify_pair_contingencies` is its AC check.
 `contingency_screen_model` asks the NETWORK instead of the DC model: every (scenario, outage) becomes one graph of a batch
 (csrc/contingency_model.hip: `pfn_contingency_model_batch`), the model predicts, and `pfn_contingency_model_loadings` turns the
-predictions into line currents and the screen's three figures -- reactive flow and voltage magnitude included.  No CPU path."""
+predictions into line currents and the screen's three figures -- reactive flow and voltage magnitude included.
+`contingency_screen_ac` is the AC screen by compensated 1P1Q (csrc/contingency_ac.hip: `pfn_contingency_ac`, two launches behind the
+islands): the fast-decoupled base solve of `solve_power_flow(mode="fdxb" | "fdbx")` per scenario, then a wave per (scenario, outage)
+takes `halves` half-iterations with B'^-1 and B''^-1 corrected for the missing line by a rank-1 update, and reports the loadings
+from line currents together with the lowest voltage, the voltage violations and the remaining mismatch.  No CPU path."""
 import contextlib
 import ctypes as C
 import operator
@@ -793,3 +797,120 @@ def contingency_screen_model(model, bus_type, spec, edge_index, rx, ratings=None
     return ModelContingencyResult(severity=take(step.severity), worst_line=take(step.worst), overloads=take(step.overloads),
                                   islands=take(step.islands), loading=take(step.loading), predictions=take(step.predictions),
                                   flags=take(step.flags), chunk=B, captures=step.captures)
+
+
+# ================================================================================ N-1 under AC: compensated 1P1Q
+_VARIANTS = {"xb": 0, "bx": 1}
+
+
+@dataclass
+class ACContingencyResult:
+    """`contingency_screen_ac`'s answer.  Per (scenario s, outage k), by `ContingencyResult`'s rules but from `halves` fast-decoupled
+    half-iterations under AC: `severity` [S, e] float32 (the largest loading I_l / rating_l over the monitored lines l != k; +inf
+    where the outage islands buses, NaN where the scenario failed or a loading is not finite), `worst_line`, `overloads` [S, e]
+    int32; `vm_min` [S, e] float32, `vm_min_bus` [S, e] int32 (the lowest Vm over the PQ buses and its bus, ties to the lowest; NaN /
+    -1 without a PQ bus) and `v_violations` [S, e] int32 (PQ buses outside `v_limits`; a non-finite Vm counts and makes `vm_min`
+    NaN); `mismatch` [S, e] float64, max |F| of the reduced grid at the final state.  Islanding outages: +inf, -1, -1, NaN voltage
+    figures and mismatch, -1 integers; failed scenarios: NaN and -1 throughout.  `islands` [e] int32 as in `ContingencyResult`.  Per
+    scenario: `base_table` [S, n, 4] float64, `status` [S] int32 and `residual` [S] float64 -- the bits of
+    `solve_power_flow(mode="fd" + variant)`.  `post_current` [S, e, e] float32 (row = outage, column = line, NaN at l = k) with
+    `keep_table`, `post_state` [S, e, n, 2] float32 = (Vm, Va in degrees) with `keep_state`, else None.  `flags` [1] int32 (bit 0:
+    `bus_type` changed under the launch).  `route`: "lds" or "global", where the outage launch read the two inverses; `group`: its
+    waves per workgroup.  All on the device, nothing read back."""
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    vm_min: torch.Tensor
+    vm_min_bus: torch.Tensor
+    v_violations: torch.Tensor
+    mismatch: torch.Tensor
+    islands: torch.Tensor
+    base_table: torch.Tensor
+    status: torch.Tensor
+    residual: torch.Tensor
+    post_current: object
+    post_state: object
+    route: str
+    flags: object = None
+    group: int = 0
+
+    def ranking(self, top):
+        """`ContingencyResult.ranking`'s order: NaN first, then +inf, then descending, ties to the lowest outage id."""
+        return _rank(self.severity, top, "ranking")
+
+
+def _screen_ac_options(variant, halves, v_limits, route, group, keep_table, keep_state):
+    """what `contingency_screen_ac` asks of its own arguments, on the host, before anything touches the library"""
+    who = "contingency_screen_ac"
+    if variant not in _VARIANTS:
+        raise ValueError(f"{who}: variant must be one of {sorted(_VARIANTS)}; got {variant!r}")
+    if isinstance(halves, bool) or not isinstance(halves, int) or not 0 <= halves < 2 ** 31:
+        raise ValueError(f"{who}: halves must be an int >= 0; got {halves!r}")
+    try:
+        lo, hi = (float(v) for v in v_limits)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: v_limits must be a pair of floats (low, high); got {v_limits!r}") from None
+    if not lo <= hi:
+        raise ValueError(f"{who}: v_limits must be in order, low <= high; got {v_limits!r}")
+    if route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    if group is not None and (isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= 16):
+        raise ValueError(f"{who}: group must be None or the waves per workgroup, an int in [1, 16]; got {group!r}")
+    for name, v in (("keep_table", keep_table), ("keep_state", keep_state)):
+        if not isinstance(v, bool):
+            raise ValueError(f"{who}: {name} must be a bool; got {v!r}")
+    return lo, hi
+
+
+def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, variant="xb", halves=2, v_limits=(0.9, 1.1), tol=1e-8, max_iter=60,
+                          init=None, route="auto", group=None, keep_table=False, keep_state=False) -> ACContingencyResult:
+    """Screen every single line outage of every scenario under AC by compensated 1P1Q: inputs and their checks are
+    `contingency_screen`'s.  The base is the fast-decoupled solve of the full grid (`variant` "xb" or "bx", from the flat start or
+    `init` [S, n, 2] = (Vm, Va in degrees), to `tol` within `max_iter` half-iterations) -- `solve_power_flow(mode="fd" + variant)`'s
+    code and bits.  Every non-islanding outage then takes `halves` half-iterations (P first, alternating) from the base state with
+    B'^-1 and B''^-1 corrected for the missing line by a rank-1 update; 2 is the classical 1P1Q, 4 buys about two more digits,
+    0 gives the base state's figures with line k unmonitored.  `mismatch` says how far from converged each estimate is.
+    `v_limits`: the band of `v_violations`.  `route`: "auto", "lds" (raises where the two inverses do not fit LDS beside the waves'
+    vectors) or "global" (read from the workspace); `group`: the outages, one wave each, per workgroup, None: chosen with the
+    placement; the same bits whatever the two are.  These are the dense routes: beyond `max_unknowns()` it raises.
+    Three launches (islands, base, outages); one host read (the bus_type counts, once per tensor); nothing is read back.  The result
+    goes into `verify_contingencies` as a `ContingencyResult` does."""
+    who = "contingency_screen_ac"
+    lo, hi = _screen_ac_options(variant, halves, v_limits, route, group, keep_table, keep_state)
+
+    if torch.is_tensor(spec) and spec.dim() == 3:                             # on the host, before anything touches a device
+        cap = int(L.load().pfn_powerflow_max_unknowns())
+        if int(spec.shape[1]) - 1 > cap:
+            raise ValueError(f"{who}: {int(spec.shape[1]) - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); "
+                             f"the sparse route is not built")
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings)
+    dev = spec.device
+    if init is not None:
+        L.require_device(init, what=f"{who} init")
+        if init.dtype != torch.float64 or tuple(init.shape) != (S, n, 2) or init.device != dev:
+            raise RuntimeError(f"{who}: init must be float64 ({S}, {n}, 2) = (Vm, Va in degrees) on {dev}; got {init.dtype} {tuple(init.shape)}")
+        init = init.contiguous()
+    lib = L.load()
+    in_lds = C.c_int(0)
+    waves = int(lib.pfn_contingency_ac_waves(n, n_pq, _ROUTES[route], 0 if group is None else group, C.byref(in_lds)))
+    if waves == 0:
+        raise RuntimeError(f"{who}: route {route!r} with group {group!r}: the two inverses of {n} buses and the waves' vectors do not fit LDS")
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)        # noqa: E731
+    out = dict(severity=f32(S, e), worst_line=i32(S, e), overloads=i32(S, e), vm_min=f32(S, e), vm_min_bus=i32(S, e), v_violations=i32(S, e),
+               mismatch=torch.empty(S, e, dtype=torch.float64, device=dev), base_table=torch.empty(S, n, 4, dtype=torch.float64, device=dev),
+               status=i32(S), residual=torch.empty(S, dtype=torch.float64, device=dev), post_current=f32(S, e, e) if keep_table else None,
+               post_state=f32(S, e, n, 2) if keep_state else None, flags=torch.zeros(1, dtype=torch.int32, device=dev))
+    islands = torch.empty(e, dtype=torch.int32, device=dev)
+    need = int(lib.pfn_contingency_ac_workspace_bytes(S, n, e, n_pq))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    order = ("severity", "worst_line", "overloads", "vm_min", "vm_min_bus", "v_violations", "mismatch", "base_table", "status", "residual",
+             "post_current", "post_state", "flags")
+    with torch.cuda.device(dev):
+        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+        L.check(lib.pfn_contingency_ac(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),
+                                       int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, _VARIANTS[variant],
+                                       halves, lo, hi, float(tol), int(max_iter), _ROUTES[route], 0 if group is None else group,
+                                       *[L.ptr(out[k]) for k in order], ws.data_ptr(), need, L.stream_ptr()),
+                "pfn_contingency_ac")
+    return ACContingencyResult(islands=islands, route="lds" if in_lds.value else "global", group=waves, **out)

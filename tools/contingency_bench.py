@@ -48,7 +48,16 @@ configs/standard.json (bits do not matter for time).  Per case, alternating in t
 the sweep, eager and -- with --graphed -- replayed from its captured chunk; (b) the composition it replaces, per chunk of the same
 size: torch index-built reduced lists and normalisation, the forward with the adjacency rebuilt on the generic route, the merge,
 `branch_flows`, `summarise_loadings`; (c) `contingency_screen` (DC) for the same scenarios; (d) `solve_power_flow(mode="ac")` over
-explicit per-outage lists of `--ac-outages` non-islanding outages spread evenly over the list, for every scenario, scaled per pair."""
+explicit per-outage lists of `--ac-outages` non-islanding outages spread evenly over the list, for every scenario, scaled per pair.
+
+    python tools/contingency_bench.py --ac [--ac-samples 16] [--case 118 --case 14]
+
+The AC screen (`contingency_screen_ac`), same protocol, ALL outages of `--ac-samples` scenarios.  Per case, alternating in
+the same child: the screen with `halves` 2 and 4 (three launches each: islands, base, outages), the base and the outage launch apart
+(the library's event brackets, a pass of their own); the path it replaces, `solve_power_flow(mode="ac", init=<the base solution>)`
+over explicit reduced lists of every (scenario, non-islanding outage), built as `verify_contingencies` builds them (the build is not
+timed); and `contingency_screen` (DC) for the same scenarios.  tol 1e-8; the screen's base solve may take 60 half-iterations, the
+Newton solves 10 iterations.  The screen has no predecessor: no threshold."""
 import argparse
 import json
 import os
@@ -98,6 +107,83 @@ def child(case, samples, brute_solves, repeats):
                       "brute_scenarios": Sb, "brute_solves": Sb * K, "screen_ms": 1e3 * statistics.median(t_screen),
                       "brute_ms": 1e3 * statistics.median(t_brute), "screen_us_per_pair": screen_us, "brute_us_per_pair": brute_us,
                       "ratio": brute_us / screen_us}))
+
+
+def child_ac(case, samples, repeats):
+    import torch
+    from poweflownet_amd import _lib as L
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen, contingency_screen_ac
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    dev = torch.device("cuda:0")
+    n, e = CASES[case]
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    res = contingency_screen_ac(bt, spec, ei, rx)                          # (warm-up; its islands choose the replaced path's outages)
+    contingency_screen_ac(bt, spec, ei, rx, halves=4)
+    dc = contingency_screen(bt, spec, ei, rx)
+    outages = torch.nonzero(res.islands == 0).flatten()
+    K = int(outages.numel())
+    # the replaced path's inputs, built once and not timed: scenario s, outage k -> sample s * K + k of [S K, 2, e - 1] lists
+    ar = torch.arange(e - 1, device=dev)
+    idx = ar[None, :] + (ar[None, :] >= outages[:, None])                  # [K, e - 1]
+    lists = ei[:, idx].permute(1, 0, 2).repeat(samples, 1, 1).contiguous()
+    rx_b = rx[:, idx].reshape(samples * K, e - 1, 2).contiguous()
+    spec_b = spec.repeat_interleave(K, dim=0).contiguous()
+    init_b = res.base_table[:, :, :2].repeat_interleave(K, dim=0).contiguous()
+    newton = solve_power_flow(bt, spec_b, lists, rx_b, mode="ac", init=init_b)      # (warm-up)
+    assert bool((res.status >= 0).all()) and bool((dc.status >= 0).all())
+    solved = newton.status >= 0
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    runs = {"halves2": lambda: contingency_screen_ac(bt, spec, ei, rx), "halves4": lambda: contingency_screen_ac(bt, spec, ei, rx, halves=4),
+            "newton": lambda: solve_power_flow(bt, spec_b, lists, rx_b, mode="ac", init=init_b), "dc": lambda: contingency_screen(bt, spec, ei, rx)}
+    times = {k: [] for k in runs}
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            times[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    launches = {}
+    for halves in (2, 4):                                                  # the launches apart: a pass of its own
+        L.profile_enable(True)
+        contingency_screen_ac(bt, spec, ei, rx, halves=halves)
+        rep = L.profile_report()
+        L.profile_enable(False)
+        launches[halves] = {k: round(rep[k]["ms"], 4) for k in ("contingency_islands", "contingency_ac_base", "contingency_ac_outages") if k in rep}
+    T = samples * e
+    print(json.dumps({"case": case, "buses": n, "lines": e, "scenarios": samples, "outages": e, "non_islanding": K, "placement": res.route,
+                      "waves": res.group, "halves2_ms": 1e3 * med["halves2"], "halves4_ms": 1e3 * med["halves4"], "newton_ms": 1e3 * med["newton"],
+                      "dc_ms": 1e3 * med["dc"], "halves2_us_per_pair": 1e6 * med["halves2"] / T, "halves4_us_per_pair": 1e6 * med["halves4"] / T,
+                      "newton_us_per_pair": 1e6 * med["newton"] / (samples * K), "dc_us_per_pair": 1e6 * med["dc"] / T,
+                      "newton_solves": samples * K, "newton_failed": int((~solved).sum()), "newton_iterations_max": int(newton.status.max()),
+                      "base_halves_max": int(res.status.max()), "launches_halves2_ms": launches[2], "launches_halves4_ms": launches[4]}))
+
+
+def main_ac(a):
+    out = {"tol": 1e-8, "repeats": a.repeats, "processes": a.processes, "cases": {}}
+    for case in a.case or ["118", "14"]:
+        kids = []
+        for _ in range(a.processes):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-ac", case, "--ac-samples", str(a.ac_samples), "--repeats",
+                                str(a.repeats)], capture_output=True, text=True, timeout=900)
+            if r.returncode != 0:
+                raise SystemExit(f"contingency_bench: the AC child for case {case} failed:\n{r.stdout}\n{r.stderr}")
+            kids.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        row = dict(kids[0])
+        for key in [k for k in kids[0] if k.endswith("_ms") and not k.startswith("launches") or k.endswith("_us_per_pair")]:
+            vals = [x[key] for x in kids]
+            row[key], row[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+        for h in ("halves2", "halves4"):
+            row["newton_over_" + h] = round(row["newton_us_per_pair"] / row[h + "_us_per_pair"], 3)
+            row[h + "_over_dc"] = round(row[h + "_us_per_pair"] / row["dc_us_per_pair"], 3)
+        out["cases"][case] = row
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
 
 
 def child_model(case, samples, chunks, graphed, ac_outages, repeats):
@@ -528,7 +614,15 @@ def main(argv=None):
     ap.add_argument("--model-samples", type=int, default=16, help="model: scenarios")
     ap.add_argument("--ac-outages", type=int, default=16, help="model: the AC solves cover this many non-islanding outages of every scenario")
     ap.add_argument("--child-model", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--ac", action="store_true", help="the AC screen, contingency_screen_ac, DESIGN 7z")
+    ap.add_argument("--ac-samples", type=int, default=16, help="ac: scenarios")
+    ap.add_argument("--child-ac", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_ac:
+        child_ac(a.child_ac, a.ac_samples, a.repeats)
+        return 0
+    if a.ac:
+        return main_ac(a)
     if a.child_model:
         child_model(a.child_model, a.model_samples, a.chunk, a.graphed, a.ac_outages, a.repeats)
         return 0
