@@ -26,9 +26,11 @@ outages with their AC-verified loadings (`verify_contingencies` on the network's
 results/<case>_contingency_model_{severity,worst_line,overloads}.npy.  Without --model-run-id nothing changes.
 
 --ac [--halves H] adds the AC screen (`contingency_screen_ac`: compensated 1P1Q, H fast-decoupled half-iterations per outage from
-the AC base solution, 2 by default; dense route only) with the same ratings: per scenario its top outages with the DC severity, the
-1P1Q severity and the AC-verified severity side by side, how often each screen names the AC worst line, the voltage figures, and
-results/<case>_contingency_ac_{severity,worst_line,overloads,vm_min,vm_min_bus,v_violations,mismatch}.npy.
+the AC base solution, 2 by default) with the same ratings: per scenario its top outages with the DC severity, the 1P1Q severity and
+the AC-verified severity side by side, how often each screen names the AC worst line, the voltage figures, and
+results/<case>_contingency_ac_{severity,worst_line,overloads,vm_min,vm_min_bus,v_violations,mismatch}.npy.  Where the DC screen takes
+the sparse route -- beyond the dense cap by itself, anywhere with --route sparse -- so does the AC screen, under one
+`sparse_plan(mode="fd")` built beside the DC plan.
 """
 import argparse
 import os
@@ -68,7 +70,7 @@ def main(argv=None):
     ap.add_argument("--out-dir", default="results")
     ap.add_argument("--model-run-id", default=None, help="also screen with the network of models/model_<id>.pt (contingency_screen_model)")
     ap.add_argument("--cfg_json", default="configs/standard.json", help="--model-run-id: the network's hidden_dim, n_gnn_layers, K")
-    ap.add_argument("--ac", action="store_true", help="also screen under AC by compensated 1P1Q (contingency_screen_ac; dense route)")
+    ap.add_argument("--ac", action="store_true", help="also screen under AC by compensated 1P1Q (contingency_screen_ac) on the route of the DC screen")
     ap.add_argument("--halves", type=int, default=2, help="--ac: fast-decoupled half-iterations per outage (2: 1P1Q, 4: 2P2Q)")
     a = ap.parse_args(argv)
     import torch
@@ -113,21 +115,29 @@ def main(argv=None):
     if a.model_run_id is not None:
         screen_model(a, islands, bt, spec, ei, rx, ratings, solver_kw)
     if a.ac:
-        screen_ac(a, res, islands, bt, spec, ei, rx, ratings, solver_kw)
+        screen_ac(a, res, islands, bt, spec, ei, rx, ratings, solver_kw, sparse=kw["route"] == "sparse")
     return 0
 
 
-def screen_ac(a, dc_res, islands, bt, spec, ei, rx, ratings, solver_kw):
-    """--ac: the AC screen of the same scenarios with the same ratings, its worst outages AC-verified beside the DC screen's figures,
-    the voltage figures, and the seven result files"""
+def screen_ac(a, dc_res, islands, bt, spec, ei, rx, ratings, solver_kw, sparse=False):
+    """--ac: the AC screen of the same scenarios with the same ratings on the DC screen's route (`sparse`: under one fast-decoupled
+    plan built here), its worst outages AC-verified beside the DC screen's figures, the voltage figures, and the seven result files"""
     import torch
 
     from poweflownet_amd.utils.contingency import contingency_screen_ac, verify_contingencies
-    res = contingency_screen_ac(bt, spec, ei, rx, ratings, halves=a.halves)
+    from poweflownet_amd.utils.powerflow import sparse_plan
+    kw = {}
+    if sparse:
+        plan = sparse_plan(bt, ei, mode="fd")                              # once, beside the DC plan
+        print(f"sparse route of the AC screen: B' of {plan.m} and B'' of {plan.m_q} unknowns, nnz(L) {plan.nnz_l}, plan built in {plan.build_s:.2f} s")
+        kw = {"route": "sparse", "plan": plan}
+    res = contingency_screen_ac(bt, spec, ei, rx, ratings, halves=a.halves, **kw)
     S, e = int(spec.shape[0]), int(ei.shape[1])
     failed = int((res.status < 0).sum())
-    print(f"AC screen: {a.halves} half-iterations per outage, {S} scenarios x {e} outages, inverses on the {res.route} placement, "
-          f"{res.group} outages per workgroup; base solves {int(res.status.clamp(min=0).max())} half-iterations at most, {failed} failed")
+    where = (f"sparse factors, 64 outages per workgroup, blocks on the {res.block} placement" if sparse
+             else f"inverses on the {res.route} placement, {res.group} outages per workgroup")
+    print(f"AC screen: {a.halves} half-iterations per outage, {S} scenarios x {e} outages, {where}; "
+          f"base solves {int(res.status.clamp(min=0).max())} half-iterations at most, {failed} failed")
     top = min(a.verify_top, int((islands == 0).sum()))
     ver = verify_contingencies(res, bt, spec, ei, rx, ratings, top=top, **solver_kw)
     sc, out = ver.pairs[:, 0], ver.pairs[:, 1]

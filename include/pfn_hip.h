@@ -1026,6 +1026,41 @@ int pfn_contingency_ac(const int64_t* edge_index, int64_t n_lines, const double*
                        int32_t* v_violations, double* mismatch, double* base_table, int32_t* status, double* residual, float* post_current,
                        float* post_state, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* AC N-1 screening beyond the dense cap (csrc/contingency_ac_sparse.hip): pfn_contingency_ac's screen -- the same definitions, outputs
+ * and statuses -- from the sparse fp32 FACTORS of B' and B'' under the fast-decoupled plan of the sparse power-flow route
+ * (pfn_powerflow_sparse_fd_plan: plan_header its first 32 words on the host, plan_dev the blob on the device) where
+ * pfn_contingency_ac keeps their dense inverses: "X g" and "w = X a" are each one forward and one backward substitution in fp64 on
+ * the fp32 factor (pfn_powerflow_solve_sparse_fd's expression and column order), w . g ONE serial fp64 sum in ascending unknown
+ * order.  Status -6 is added where the device line list is not the plan's.  Arguments as pfn_contingency_ac's with `route, group`
+ * replaced by the plan and the sparse route's options.  Two launches behind pfn_contingency_islands, no host sync, no allocation
+ * (capturable), no atomics:
+ *   base     pfn_powerflow_solve_sparse_fd's launch itself (mode 2 + variant; `threads` 0 / 64 / 256 as there): base_table, status
+ *            and residual carry that call's bits; the fp64 base state and both factors stay in the scenario's slab of `ws`.
+ *   outages  a lane per outage, a one-wave workgroup per tile of 64 consecutive outages of a scenario.  A lane's fp64 vectors --
+ *            theta and Vm by bus, the half's right-hand side / solution and w by unknown -- are columns of one block
+ *            [2 n_bus + 2 max(m_p, m_q)][64]; everything the lanes share is read wave-uniformly; no barrier, no shuffle.  w is
+ *            formed anew in every half.  Workgroup g of G takes the items (scenario, tile) g, g + G, ...; groups = 0:
+ *            G = min(n_samples * tiles, 4 * compute units), else G = min(n_samples * tiles, groups).
+ *   block_route  0 auto, 1 LDS, 2 global: the block sits in LDS where pfn_contingency_ac_sparse_block_bytes(plan_header) =
+ *            512 (2 n_bus + 2 max(m_p, m_q)) bytes fit the 159 KiB a workgroup may take (n_bus <= 80), else in a per-workgroup
+ *            block of `ws`; same code, same bits.
+ * pfn_contingency_ac_sparse_workspace_bytes(n_samples, n_lines, plan_header, block_route, groups): the scenarios' slabs first
+ * (pfn_powerflow_sparse_fd_workspace_bytes), then G blocks on the global placement; 0 for arguments the call would refuse.  An
+ * outage's bits are a function of its scenario's inputs and the plan, whatever the batch, `threads`, G or the placement.
+ * n_pq that is not the plan's count of PQ buses: every scenario -5 and bit 0 of flags[0], as pfn_contingency_ac reports counts that
+ * contradict bus_type.  PFN_EINVAL: no fast-decoupled plan or one for another n_bus / n_lines, bad sizes or counts, halves < 0,
+ * variant outside {0, 1}, v_lo > v_hi or NaN, bad tol / max_iter / threads / block_route / groups, block_route 1 where the block does
+ * not fit, 32-bit row ids, null or misaligned pointers; PFN_ENOSPACE: too little ws.                                               */
+size_t pfn_contingency_ac_sparse_block_bytes(const void* plan_header);
+size_t pfn_contingency_ac_sparse_workspace_bytes(int64_t n_samples, int64_t n_lines, const void* plan_header, int block_route, int groups);
+int pfn_contingency_ac_sparse(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                              const double* init, const double* ratings, int ratings_per_sample, const int32_t* islands, int64_t n_samples,
+                              int64_t n_bus, int64_t n_pv, int64_t n_pq, int variant, int halves, float v_lo, float v_hi, double tol, int max_iter,
+                              const void* plan_header, const void* plan_dev, int threads, int block_route, int groups, float* severity,
+                              int32_t* worst_line, int32_t* overloads, float* vm_min, int32_t* vm_min_bus, int32_t* v_violations, double* mismatch,
+                              double* base_table, int32_t* status, double* residual, float* post_current, float* post_state, int32_t* flags, void* ws,
+                              size_t ws_bytes, void* stream);
+
 /* ----------------------------------------------------------------------- Diagnostic environment switches
  * The library reads these environment variables (each ONCE per process, through one function, pfn::diag_env).  They select
  * between kernels that compute the SAME result -- the parity tests use them to hold a fused kernel against the generic one it

@@ -414,7 +414,7 @@ int pfn_contingency_ac(const int64_t* edge_index, int64_t n_lines, const double*
     PFN_CHECK_ARG(route >= 0 && route <= 2, "%s: route must be 0 (auto), 1 (LDS) or 2 (global)", who);
     PFN_CHECK_ARG(group >= 0 && group <= CA_MAX_WAVES, "%s: group must be 0 (auto) or the waves per workgroup, 1 .. %d", who, CA_MAX_WAVES);
     PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "%s: max_iter must be >= 0 and tol > 0", who);
-    PFN_CHECK_ARG(n_bus - 1 <= PF_MAX_UNKNOWNS, "%s: %lld unknowns per scenario exceed the dense screen's %d; the sparse route is not built", who,
+    PFN_CHECK_ARG(n_bus - 1 <= PF_MAX_UNKNOWNS, "%s: %lld unknowns per scenario exceed the dense screen's %d; beyond it: pfn_contingency_ac_sparse", who,
                   (long long)(n_bus - 1), PF_MAX_UNKNOWNS);
     const int n = (int)n_bus, e = (int)n_lines, mq = (int)n_pq, m = (n - 1) + mq;
     bool lds = false;

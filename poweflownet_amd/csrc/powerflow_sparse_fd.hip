@@ -12,9 +12,12 @@
 // float atomics, only the max crosses threads: a sample's bits depend neither on its batch nor on the workgroup size.
 //
 // The mismatch walk's line-end term, the start state, the stopping rule, the view of a sub-plan and its check against the device
-// arrays, the table write-back and the sizes of a sample are powerflow_common.hpp's, shared with every route.
+// arrays, the table write-back and the sizes of a sample are powerflow_common.hpp's, shared with every route.  The host side of the
+// call -- its checks and the launch -- is pfd_solve, exported through powerflow_sparse_fd.hpp: the AC N-1 screen of the sparse route
+// (contingency_ac_sparse.hip) makes it for its base launch.
 #include "powerflow_common.hpp"
 #include "powerflow_sparse_core.hpp"
+#include "powerflow_sparse_fd.hpp"
 
 namespace pfn {
 
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(THREADS) void powerflow_sparse_fd_kernel(const PfdA
     pf_write_back(p, sm, s, false, nt, code, it, res, vm, th, sp, sq);
 }
 
-static int pfd_check_header(const int32_t* h, const char* who) {
+int pfd_check_header(const int32_t* h, const char* who) {
     PFN_CHECK_ARG(h, "%s: null plan header", who);
     PFN_CHECK_ARG(h[PFP_H_MAGIC] == PFD_MAGIC && h[PFP_H_VERSION] == PFP_VERSION && h[PFP_H_MODE] == PFD_MODE,
                   "%s: not a fast-decoupled sparse power-flow plan (magic %08x, version %d)", who, (unsigned)h[PFP_H_MAGIC], (int)h[PFP_H_VERSION]);
@@ -170,24 +173,11 @@ static int pfd_check_header(const int32_t* h, const char* who) {
     return PFN_OK;
 }
 
-}  // namespace pfn
-
-using namespace pfn;
-
-extern "C" {
-
-size_t pfn_powerflow_sparse_fd_workspace_bytes(int64_t n_samples, const void* plan_header) {
-    const int32_t* h = static_cast<const int32_t*>(plan_header);
-    if (n_samples <= 0 || pfd_check_header(h, "pfn_powerflow_sparse_fd_workspace_bytes") != PFN_OK) return 0;
-    return (size_t)n_samples * pf_sample_bytes(h[PFP_H_N], std::max(h[PFP_H_M], h[PFD_H_M_Q]), h[PFP_H_NNZ]);
-}
-
-int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
-                                         const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
-                                         int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
-                                         const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
-                                         int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = line_mask || unplaced ? "pfn_powerflow_solve_sparse_fd_masked" : "pfn_powerflow_solve_sparse_fd";
+// the whole call under the caller's name: the checks, then the one launch (powerflow_sparse_fd.hpp)
+int pfd_solve(const char* who, const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask, const int32_t* unplaced,
+              const int32_t* bus_type, const double* spec, const double* init, int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter,
+              const void* plan_header, const void* plan_dev, int threads, double* table, int32_t* status, double* residual, int32_t* flags, void* ws,
+              size_t ws_bytes, void* stream) {
     const int32_t* h = static_cast<const int32_t*>(plan_header);
     PFN_TRY(pfd_check_header(h, who));
     PFN_CHECK_ARG(mode == 2 || mode == 3, "%s: mode must be 2 (fdxb) or 3 (fdbx); modes 0 and 1 are pfn_powerflow_solve_sparse's", who);
@@ -211,6 +201,28 @@ int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_li
                  (double)n_samples * ((double)n_lines * 16.0 + (double)n * 64.0 + (init ? (double)n * 16.0 : 0.0)) + (double)h[PFP_H_BYTES],
                  (double)n_samples * 2.0 * (madds + 20.0 * (double)h[PFP_H_NNZ]), s);
     return pf_launch_sparse(powerflow_sparse_fd_kernel<64>, powerflow_sparse_fd_kernel<256>, threads, h[PFP_H_MAX_COL], n_samples, lds, s, a);
+}
+
+}  // namespace pfn
+
+using namespace pfn;
+
+extern "C" {
+
+size_t pfn_powerflow_sparse_fd_workspace_bytes(int64_t n_samples, const void* plan_header) {
+    const int32_t* h = static_cast<const int32_t*>(plan_header);
+    if (n_samples <= 0 || pfd_check_header(h, "pfn_powerflow_sparse_fd_workspace_bytes") != PFN_OK) return 0;
+    return (size_t)n_samples * pf_sample_bytes(h[PFP_H_N], std::max(h[PFP_H_M], h[PFD_H_M_Q]), h[PFP_H_NNZ]);
+}
+
+int pfn_powerflow_solve_sparse_fd_masked(const int64_t* edge_index, int64_t n_lines, const double* rx, const uint8_t* line_mask,
+                                         const int32_t* unplaced, const int32_t* bus_type, const double* spec, const double* init,
+                                         int64_t n_samples, int64_t n_bus, int mode, double tol, int max_iter, const void* plan_header,
+                                         const void* plan_dev, int threads, double* table, int32_t* status, double* residual,
+                                         int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+    return pfd_solve(line_mask || unplaced ? "pfn_powerflow_solve_sparse_fd_masked" : "pfn_powerflow_solve_sparse_fd", edge_index, n_lines, rx, line_mask,
+                     unplaced, bus_type, spec, init, n_samples, n_bus, mode, tol, max_iter, plan_header, plan_dev, threads, table, status, residual, flags,
+                     ws, ws_bytes, stream);
 }
 
 int pfn_powerflow_solve_sparse_fd(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,

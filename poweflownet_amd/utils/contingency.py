@@ -15,7 +15,9 @@ predictions into line currents and the screen's three figures -- reactive flow a
 `contingency_screen_ac` is the AC screen by compensated 1P1Q (csrc/contingency_ac.hip: `pfn_contingency_ac`, two launches behind the
 islands): the fast-decoupled base solve of `solve_power_flow(mode="fdxb" | "fdbx")` per scenario, then a wave per (scenario, outage)
 takes `halves` half-iterations with B'^-1 and B''^-1 corrected for the missing line by a rank-1 update, and reports the loadings
-from line currents together with the lowest voltage, the voltage violations and the remaining mismatch.  No CPU path."""
+from line currents together with the lowest voltage, the voltage violations and the remaining mismatch; beyond the dense cap
+`route="sparse"` with a `sparse_plan(..., mode="fd")` runs the same screen on the sparse fp32 factors of B' and B''
+(csrc/contingency_ac_sparse.hip: `pfn_contingency_ac_sparse`), a lane per outage, 64 outages to a one-wave workgroup.  No CPU path."""
 import contextlib
 import ctypes as C
 import operator
@@ -278,8 +280,9 @@ def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8
     return ContingencyResult(islands=islands, route="global" if need else "lds", **out)
 
 
-def _sparse_options(who, spec, edge_index, plan, block, groups, threads):
-    """what `route="sparse"` asks of its own options, on the host, before anything touches the library: both screens"""
+def _sparse_options(who, spec, edge_index, plan, block, groups, threads, mode="dc"):
+    """what `route="sparse"` asks of its own options, on the host, before anything touches the library: every screen (`mode`: the
+    plan it takes -- "dc" for the DC screens, "fd" for the AC one)"""
     if block not in _BLOCKS:
         raise ValueError(f"{who}: block must be one of {sorted(_BLOCKS)}")
     if groups is not None and (isinstance(groups, bool) or not isinstance(groups, int) or not 1 <= groups < 2 ** 31):
@@ -287,9 +290,9 @@ def _sparse_options(who, spec, edge_index, plan, block, groups, threads):
     if threads not in (None, 64, 256):
         raise ValueError(f"{who}: threads must be None, 64 or 256; got {threads!r}")
     if not isinstance(plan, SparsePlan):
-        raise ValueError(f"{who}: route 'sparse' needs plan=sparse_plan(bus_type, edge_index, mode='dc'); got {plan!r}")
-    if plan.mode != "dc":
-        raise ValueError(f"{who}: route 'sparse' takes a plan of mode 'dc'; this one has mode {plan.mode!r}")
+        raise ValueError(f"{who}: route 'sparse' needs plan=sparse_plan(bus_type, edge_index, mode={mode!r}); got {plan!r}")
+    if plan.mode != mode:
+        raise ValueError(f"{who}: route 'sparse' takes a plan of mode {mode!r}; this one has mode {plan.mode!r}")
     if torch.is_tensor(spec) and spec.dim() == 3 and torch.is_tensor(edge_index) and edge_index.dim() == 2:
         if (plan.n, plan.e) != (int(spec.shape[1]), int(edge_index.shape[1])):
             raise ValueError(f"{who}: the plan is for (n, e) = {(plan.n, plan.e)}; the call has {(int(spec.shape[1]), int(edge_index.shape[1]))}")
@@ -816,7 +819,8 @@ class ACContingencyResult:
     `solve_power_flow(mode="fd" + variant)`.  `post_current` [S, e, e] float32 (row = outage, column = line, NaN at l = k) with
     `keep_table`, `post_state` [S, e, n, 2] float32 = (Vm, Va in degrees) with `keep_state`, else None.  `flags` [1] int32 (bit 0:
     `bus_type` changed under the launch).  `route`: "lds" or "global", where the outage launch read the two inverses; `group`: its
-    waves per workgroup.  All on the device, nothing read back."""
+    waves per workgroup.  `route` "sparse": the screen ran on the sparse factors; `block` then says where the outage blocks sat
+    ("lds" or "global") and `group` is 0.  All on the device, nothing read back."""
     severity: torch.Tensor
     worst_line: torch.Tensor
     overloads: torch.Tensor
@@ -833,6 +837,7 @@ class ACContingencyResult:
     route: str
     flags: object = None
     group: int = 0
+    block: object = None
 
     def ranking(self, top):
         """`ContingencyResult.ranking`'s order: NaN first, then +inf, then descending, ties to the lowest outage id."""
@@ -852,8 +857,8 @@ def _screen_ac_options(variant, halves, v_limits, route, group, keep_table, keep
         raise ValueError(f"{who}: v_limits must be a pair of floats (low, high); got {v_limits!r}") from None
     if not lo <= hi:
         raise ValueError(f"{who}: v_limits must be in order, low <= high; got {v_limits!r}")
-    if route not in _ROUTES:
-        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    if route != "sparse" and route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES) + ['sparse']}")
     if group is not None and (isinstance(group, bool) or not isinstance(group, int) or not 1 <= group <= 16):
         raise ValueError(f"{who}: group must be None or the waves per workgroup, an int in [1, 16]; got {group!r}")
     for name, v in (("keep_table", keep_table), ("keep_state", keep_state)):
@@ -863,7 +868,8 @@ def _screen_ac_options(variant, halves, v_limits, route, group, keep_table, keep
 
 
 def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, variant="xb", halves=2, v_limits=(0.9, 1.1), tol=1e-8, max_iter=60,
-                          init=None, route="auto", group=None, keep_table=False, keep_state=False) -> ACContingencyResult:
+                          init=None, route="auto", group=None, keep_table=False, keep_state=False, plan=None, block="auto", groups=None,
+                          threads=None) -> ACContingencyResult:
     """Screen every single line outage of every scenario under AC by compensated 1P1Q: inputs and their checks are
     `contingency_screen`'s.  The base is the fast-decoupled solve of the full grid (`variant` "xb" or "bx", from the flat start or
     `init` [S, n, 2] = (Vm, Va in degrees), to `tol` within `max_iter` half-iterations) -- `solve_power_flow(mode="fd" + variant)`'s
@@ -872,18 +878,36 @@ def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, varia
     0 gives the base state's figures with line k unmonitored.  `mismatch` says how far from converged each estimate is.
     `v_limits`: the band of `v_violations`.  `route`: "auto", "lds" (raises where the two inverses do not fit LDS beside the waves'
     vectors) or "global" (read from the workspace); `group`: the outages, one wave each, per workgroup, None: chosen with the
-    placement; the same bits whatever the two are.  These are the dense routes: beyond `max_unknowns()` it raises.
+    placement; the same bits whatever the two are.  These are the dense routes: beyond `max_unknowns()` they raise.
     Three launches (islands, base, outages); one host read (the bus_type counts, once per tensor); nothing is read back.  The result
-    goes into `verify_contingencies` as a `ContingencyResult` does."""
+    goes into `verify_contingencies` as a `ContingencyResult` does.
+
+    `route="sparse"` with `plan=sparse_plan(bus_type, edge_index, mode="fd")`: the same screen beyond `max_unknowns()` from the sparse
+    fp32 FACTORS of B' and B'' (csrc/contingency_ac_sparse.hip: `pfn_contingency_ac_sparse`) -- the same fields,
+    definitions and statuses, plus status -6 where the device line list is not the plan's; every other argument means what it means
+    on the dense routes.  The base is `solve_power_flow(mode="fd" + variant, route="sparse", plan=plan)`'s launch and bits; the
+    outage launch takes a lane per outage, 64 consecutive outages of a scenario to a one-wave workgroup.  "auto" never takes it;
+    without a plan, with a plan of another mode or of another n / e it raises ValueError.  There `block`: where a tile's fp64 vectors
+    sit -- "auto" (LDS where the block of about 2048 n bytes fits, up to 80 buses), "lds" (raises where it does not) or "global" (a
+    block of the workspace per workgroup); `groups`: the number of one-wave workgroups the (scenario, tile) items are dealt to,
+    None: min(S * tiles, 4 * compute units), each with a block of its own on the global placement; `threads`: the base solve's workgroup, None, 64 or 256.  No bit depends on any of the
+    three.  `group` does not go with it; the result's `group` is 0 and its `block` "lds" or "global"."""
     who = "contingency_screen_ac"
     lo, hi = _screen_ac_options(variant, halves, v_limits, route, group, keep_table, keep_state)
-
-    if torch.is_tensor(spec) and spec.dim() == 3:                             # on the host, before anything touches a device
+    sparse = route == "sparse"
+    if sparse:
+        if group is not None:
+            raise ValueError(f"{who}: group goes with the dense routes only; route 'sparse' takes block, groups and threads")
+        _sparse_options(who, spec, edge_index, plan, block, groups, threads, mode="fd")
+    elif plan is not None or block != "auto" or groups is not None or threads is not None:
+        raise ValueError(f"{who}: plan, block, groups and threads go with route='sparse' only")
+    if not sparse and torch.is_tensor(spec) and spec.dim() == 3:              # on the host, before anything touches a device
         cap = int(L.load().pfn_powerflow_max_unknowns())
         if int(spec.shape[1]) - 1 > cap:
             raise ValueError(f"{who}: {int(spec.shape[1]) - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); "
-                             f"the sparse route is not built")
-    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings)
+                             f"beyond it: route='sparse' with plan=sparse_plan(bus_type, edge_index, mode='fd')")
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings,
+                                                                                plan=plan if sparse else None)
     dev = spec.device
     if init is not None:
         L.require_device(init, what=f"{who} init")
@@ -891,10 +915,18 @@ def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, varia
             raise RuntimeError(f"{who}: init must be float64 ({S}, {n}, 2) = (Vm, Va in degrees) on {dev}; got {init.dtype} {tuple(init.shape)}")
         init = init.contiguous()
     lib = L.load()
-    in_lds = C.c_int(0)
-    waves = int(lib.pfn_contingency_ac_waves(n, n_pq, _ROUTES[route], 0 if group is None else group, C.byref(in_lds)))
-    if waves == 0:
-        raise RuntimeError(f"{who}: route {route!r} with group {group!r}: the two inverses of {n} buses and the waves' vectors do not fit LDS")
+    in_lds, waves = C.c_int(0), 0
+    if sparse:
+        header, g = C.addressof(plan.header), 0 if groups is None else groups
+        fits = int(lib.pfn_contingency_ac_sparse_workspace_bytes(1, e, header, 1, g)) != 0    # (0: the forced LDS placement is refused)
+        if block == "lds" and not fits:
+            raise RuntimeError(f"{who}: block 'lds': an outage block of {n} buses needs {int(lib.pfn_contingency_ac_sparse_block_bytes(header))} "
+                               f"bytes and does not fit LDS")
+        in_lds.value = int(block != "global" and fits)
+    else:
+        waves = int(lib.pfn_contingency_ac_waves(n, n_pq, _ROUTES[route], 0 if group is None else group, C.byref(in_lds)))
+        if waves == 0:
+            raise RuntimeError(f"{who}: route {route!r} with group {group!r}: the two inverses of {n} buses and the waves' vectors do not fit LDS")
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
     i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)        # noqa: E731
     out = dict(severity=f32(S, e), worst_line=i32(S, e), overloads=i32(S, e), vm_min=f32(S, e), vm_min_bus=i32(S, e), v_violations=i32(S, e),
@@ -902,10 +934,22 @@ def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, varia
                status=i32(S), residual=torch.empty(S, dtype=torch.float64, device=dev), post_current=f32(S, e, e) if keep_table else None,
                post_state=f32(S, e, n, 2) if keep_state else None, flags=torch.zeros(1, dtype=torch.int32, device=dev))
     islands = torch.empty(e, dtype=torch.int32, device=dev)
-    need = int(lib.pfn_contingency_ac_workspace_bytes(S, n, e, n_pq))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     order = ("severity", "worst_line", "overloads", "vm_min", "vm_min_bus", "v_violations", "mismatch", "base_table", "status", "residual",
              "post_current", "post_state", "flags")
+    if sparse:
+        with torch.cuda.device(dev):                                          # (the default `groups` asks the current device for its compute units)
+            need = int(lib.pfn_contingency_ac_sparse_workspace_bytes(S, e, header, _BLOCKS[block], g)) if S else 0
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+            L.check(lib.pfn_contingency_ac_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),
+                                                  int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq,
+                                                  _VARIANTS[variant], halves, lo, hi, float(tol), int(max_iter), header, plan.blob.data_ptr(),
+                                                  0 if threads is None else threads, _BLOCKS[block], g, *[L.ptr(out[k]) for k in order],
+                                                  ws.data_ptr(), need, L.stream_ptr()),
+                    "pfn_contingency_ac_sparse")
+        return ACContingencyResult(islands=islands, route="sparse", group=0, block="lds" if in_lds.value else "global", **out)
+    need = int(lib.pfn_contingency_ac_workspace_bytes(S, n, e, n_pq))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
         L.check(lib.pfn_contingency_ac(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),

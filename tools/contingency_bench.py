@@ -57,7 +57,18 @@ the same child: the screen with `halves` 2 and 4 (three launches each: islands, 
 (the library's event brackets, a pass of their own); the path it replaces, `solve_power_flow(mode="ac", init=<the base solution>)`
 over explicit reduced lists of every (scenario, non-islanding outage), built as `verify_contingencies` builds them (the build is not
 timed); and `contingency_screen` (DC) for the same scenarios.  tol 1e-8; the screen's base solve may take 60 half-iterations, the
-Newton solves 10 iterations.  The screen has no predecessor: no threshold."""
+Newton solves 10 iterations.  The screen has no predecessor: no threshold.
+
+    python tools/contingency_bench.py --ac --route sparse [--shape 118x186 --shape 6470x9005] [--ac-samples 16] [--groups-sweep 1 2 4]
+                                      [--brute-pairs 64]
+
+The AC screen on the sparse route (`contingency_screen_ac(route="sparse")`), same protocol.  Per shape a row per
+multiple of the compute units in the sweep (4 is the default `groups`): the screen with `halves` 2 and 4, the base and the outage
+launch apart (the library's event brackets, a pass of their own; `dominant_launch` names the larger), beside -- alternating in the
+same child -- the path it replaces, `solve_power_flow(mode="ac", route="sparse", init=<the base solution>)` through ONE cover plan
+over explicit reduced lists: every (scenario, non-islanding outage) where the shape is within the dense cap, else `--brute-pairs`
+outages spread evenly over the list, one scenario each, scaled per pair (`newton_scaled_to_all_ms`); and, within the dense cap, the
+dense AC screen."""
 import argparse
 import json
 import os
@@ -182,6 +193,108 @@ def main_ac(a):
             row[h + "_over_dc"] = round(row[h + "_us_per_pair"] / row["dc_us_per_pair"], 3)
         out["cases"][case] = row
         print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out))
+    return 0
+
+
+def child_ac_sparse(shape, samples, groups_x, brute_pairs, repeats):
+    import torch
+    from poweflownet_amd import _lib as L
+    from poweflownet_amd.synth import make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen_ac
+    from poweflownet_amd.utils.powerflow import cover_plan, max_unknowns, solve_power_flow, sparse_plan
+    dev = torch.device("cuda:0")
+    n, e = (int(v) for v in shape.split("x"))
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    plan = sparse_plan(bt, ei, mode="fd")
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    kw = {"route": "sparse", "plan": plan, "groups": groups_x * cus if groups_x else None}
+    res = contingency_screen_ac(bt, spec, ei, rx, **kw)                    # (warm-up; its islands choose the replaced path's outages)
+    contingency_screen_ac(bt, spec, ei, rx, halves=4, **kw)
+    assert bool((res.status >= 0).all())
+    # the replaced path: Newton from the base solution over explicit reduced lists under ONE cover plan; every non-islanding outage
+    # of every scenario where the dense solver would take them too, else `brute_pairs` outages spread evenly, one scenario each
+    dense = n - 1 <= max_unknowns()
+    ok = torch.nonzero(res.islands == 0).flatten()
+    outages = ok if dense else ok[torch.linspace(0, ok.numel() - 1, min(brute_pairs, ok.numel())).long()]
+    K = int(outages.numel())
+    ar = torch.arange(e - 1, device=dev)
+    idx = ar[None, :] + (ar[None, :] >= outages[:, None])                  # [K, e - 1]
+    if dense:
+        lists = ei[:, idx].permute(1, 0, 2).repeat(samples, 1, 1).contiguous()
+        rx_b = rx[:, idx].reshape(samples * K, e - 1, 2).contiguous()
+        spec_b = spec.repeat_interleave(K, dim=0).contiguous()
+        init_b = res.base_table[:, :, :2].repeat_interleave(K, dim=0).contiguous()
+    else:
+        sc = torch.arange(K, device=dev) % samples
+        lists = ei[:, idx].permute(1, 0, 2).contiguous()
+        rx_b, spec_b, init_b = rx[sc[:, None], idx].contiguous(), spec[sc].contiguous(), res.base_table[sc][:, :, :2].contiguous()
+    T = int(lists.shape[0])
+    cover = cover_plan(bt, ei[None], mode="ac", base=ei)
+    runs = {"halves2": lambda: contingency_screen_ac(bt, spec, ei, rx, **kw), "halves4": lambda: contingency_screen_ac(bt, spec, ei, rx, halves=4, **kw),
+            "newton": lambda: solve_power_flow(bt, spec_b, lists, rx_b, mode="ac", route="sparse", plan=cover, init=init_b)}
+    if dense:
+        runs["dense2"] = lambda: contingency_screen_ac(bt, spec, ei, rx)
+        runs["dense4"] = lambda: contingency_screen_ac(bt, spec, ei, rx, halves=4)
+    newton = runs["newton"]()                                              # (warm-up)
+    for fn in runs.values():
+        fn()
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    times = {k: [] for k in runs}
+    for _ in range(repeats):
+        for k, fn in runs.items():
+            times[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    launches = {}
+    for halves in (2, 4):                                                  # the launches apart: event brackets, a pass of their own
+        L.profile_enable(True)
+        contingency_screen_ac(bt, spec, ei, rx, halves=halves, **kw)
+        rep = L.profile_report()
+        L.profile_enable(False)
+        launches[halves] = {k: round(v["ms"], 4) for k, v in rep.items() if k.startswith(("contingency_", "powerflow_sparse_fd"))}
+    P = samples * e
+    row = {"buses": n, "lines": e, "scenarios": samples, "outages": e, "non_islanding": int(ok.numel()), "block": res.block, "groups_x_cus": groups_x,
+           "cus": cus, "nnz_l": plan.nnz_l, "plan_build_s": plan.build_s, "halves2_ms": 1e3 * med["halves2"], "halves4_ms": 1e3 * med["halves4"],
+           "newton_ms": 1e3 * med["newton"], "halves2_us_per_pair": 1e6 * med["halves2"] / P, "halves4_us_per_pair": 1e6 * med["halves4"] / P,
+           "newton_us_per_pair": 1e6 * med["newton"] / T, "newton_solves": T, "newton_scaled_to_all_ms": 1e3 * med["newton"] / T * samples * int(ok.numel()),
+           "newton_failed": int((newton.status < 0).sum()), "newton_iterations_max": int(newton.status.max()), "base_halves_max": int(res.status.max()),
+           "launches_halves2_ms": launches[2], "launches_halves4_ms": launches[4]}
+    if dense:
+        row.update({"dense2_ms": 1e3 * med["dense2"], "dense4_ms": 1e3 * med["dense4"], "dense2_us_per_pair": 1e6 * med["dense2"] / P,
+                    "dense4_us_per_pair": 1e6 * med["dense4"] / P})
+    print(json.dumps(row))
+
+
+def main_ac_sparse(a):
+    out = {"tol": 1e-8, "repeats": a.repeats, "processes": a.processes, "rows": []}
+    for shape in a.shape or ["118x186", "6470x9005"]:
+        for gx in ([1, 2, 4] if a.groups_sweep is None else a.groups_sweep):
+            kids = []
+            for _ in range(a.processes):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-ac-sparse", shape, "--ac-samples", str(a.ac_samples), "--groups-x",
+                                    str(gx), "--brute-pairs", str(a.brute_pairs), "--repeats", str(a.repeats)], capture_output=True, text=True, timeout=1100)
+                if r.returncode != 0:
+                    raise SystemExit(f"contingency_bench: the AC child for {shape} x{gx} failed:\n{r.stdout}\n{r.stderr}")
+                kids.append(json.loads(r.stdout.strip().splitlines()[-1]))
+            row = dict(kids[0])
+            for key in [k for k in kids[0] if k.endswith("_ms") and not k.startswith("launches") or k.endswith("_us_per_pair")]:
+                vals = [x[key] for x in kids]
+                row[key], row[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+            for h in ("halves2", "halves4"):
+                row["newton_over_" + h] = round(row["newton_us_per_pair"] / row[h + "_us_per_pair"], 3)
+            if "dense2_us_per_pair" in row:
+                row["sparse_over_dense2"] = round(row["halves2_us_per_pair"] / row["dense2_us_per_pair"], 3)
+                row["sparse_over_dense4"] = round(row["halves4_us_per_pair"] / row["dense4_us_per_pair"], 3)
+            dom = row["launches_halves2_ms"]
+            row["dominant_launch"] = max((k for k in dom if k != "contingency_islands"), key=lambda k: dom[k]) if dom else None
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
     print(json.dumps(out))
     return 0
 
@@ -565,7 +678,7 @@ def main_sparse(a):
     out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "rows": []}
     for shape in a.shape or ["118x186", "600x835", "6470x9005"]:
         n = int(shape.split("x")[0])
-        configs = [(b, 0) for b in (("lds", "global") if 256 * n <= 159 * 1024 else ("global",))] + [("auto", g) for g in a.groups_sweep]
+        configs = [(b, 0) for b in (("lds", "global") if 256 * n <= 159 * 1024 else ("global",))] + [("auto", g) for g in ([1, 4, 16] if a.groups_sweep is None else a.groups_sweep)]
         for block, gx in configs:
             rows = []
             for _ in range(a.processes):
@@ -596,7 +709,8 @@ def main(argv=None):
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--route", default="dense", choices=("dense", "sparse"), help="sparse: contingency_screen(route='sparse'), DESIGN 7v")
     ap.add_argument("--shape", action="append", default=None, help="sparse: BUSESxLINES (repeatable)")
-    ap.add_argument("--groups-sweep", type=int, nargs="*", default=[1, 4, 16], help="sparse: groups as multiples of the compute units")
+    ap.add_argument("--groups-sweep", type=int, nargs="*", default=None,
+                    help="sparse: groups as multiples of the compute units (default 1 4 16; with --ac 1 2 4, 4 being the default groups)")
     ap.add_argument("--brute-pairs", type=int, default=64, help="sparse, beyond the dense cap: the brute force solves this many outages")
     ap.add_argument("--child-sparse", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--block", default="auto", help=argparse.SUPPRESS)
@@ -617,7 +731,13 @@ def main(argv=None):
     ap.add_argument("--ac", action="store_true", help="the AC screen, contingency_screen_ac, DESIGN 7z")
     ap.add_argument("--ac-samples", type=int, default=16, help="ac: scenarios")
     ap.add_argument("--child-ac", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--child-ac-sparse", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_ac_sparse:
+        child_ac_sparse(a.child_ac_sparse, a.ac_samples, a.groups_x, a.brute_pairs, a.repeats)
+        return 0
+    if a.ac and a.route == "sparse":
+        return main_ac_sparse(a)
     if a.child_ac:
         child_ac(a.child_ac, a.ac_samples, a.repeats)
         return 0
