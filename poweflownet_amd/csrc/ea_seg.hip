@@ -1350,7 +1350,8 @@ static bool seg_plan(int seg, int n, int ld, SegPlan& p, bool bwd_limits = true)
     int remv, nq;
     col_plan(ld, remv, nq);
     p.ny = nq;   // one block column per 32-column quarter
-    return p.ny >= 1 && ld <= 8 * SG_NCH &&   // (one k piece: every layer width of the model is <= ld)
+    return p.ny >= 1 && ld <= 8 * SG_NCH &&   // (one k piece: every HIDDEN width of the model is <= ld; the last layer's output
+                                              //  width, the k extent of its dS product, is bounded apart: ea_seg_bwd_out_ok)
            (!bwd_limits || p.nblocks <= 1024) &&   // (the dWe partial buffer holds 1024 row blocks)
            seg_lds_bytes(p.trows, p.rows_pb, p.cap, true) <= (size_t)SG_LDS_BYTES &&
            seg_lds_bytes(p.trows, p.rows_pb, p.cap, false) <= (size_t)SG_LDS_BYTES;
@@ -1366,6 +1367,10 @@ bool ea_seg_fit(int seg, int n, int fe, int ld, bool bwd) {
     const long per_cu = 4L;
     return !off && fe == 2 && seg_plan(seg, n, ld, p, bwd) && (long)p.nblocks * p.ny <= per_cu * device_cus();
 }
+// The backward kernel multiplies dS = gout W2 over k < fo as ONE piece: K8 = roundup8(fo) k's of the W2 quarter in the SG_NCH * 256
+// floats of the dS room, SG_NCH chunks per fragment.  A hidden layer's fo is the hidden width (<= ld, seg_plan); the network's last
+// layer has fo = output_dim, any width -- past 136 the copy would leave the room and the multiply drop the k's beyond it.
+bool ea_seg_bwd_out_ok(int fo) { return ((fo + 7) & ~7) <= 8 * SG_NCH; }
 int ea_seg_blocks(int seg, int n, int ld) {
     SegPlan p;
     return seg_plan(seg, n, ld, p) ? p.nblocks : 0;
@@ -1441,6 +1446,10 @@ int launch_ea_seg_bwd(const GraphView& g, const EaSegBwdArgs& a, int seg, hipStr
     }
     const size_t lds = seg_lds_bytes(p.trows, p.rows_pb, p.cap, true);
     const bool dsg = a.Bd == nullptr;
+    if (!dsg && !ea_seg_bwd_out_ok(a.fo)) {   // (make_route never sends such a layer here)
+        set_error("ea_seg_bwd: the dS product takes output widths <= %d, not %d (internal)", 8 * SG_NCH, a.fo);
+        return PFN_EINVAL;
+    }
     static std::atomic<uint64_t> raised0{0}, raised1{0}, raised2{0};
     if (a.mse.y && !(dsg && a.ld / 4 <= SG_W2A_CH && a.mse.S && a.mse.b2 && a.mse.deg && a.mse.out && a.mse.gout && a.mse.partial &&
                      a.mse.counter && a.mse.loss && (!a.mse.maskf || (a.mse.counts && a.mse.count_blocks == p.nblocks)))) {

@@ -612,6 +612,9 @@ static int make_route(const pfn_mpn_config& c, const Layout& lo, int seg, int64_
     r.fused_front = front_fused_ok(lo.f0, lo.h);
     r.ea_seg_fwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false);
     r.ea_seg_bwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true);
+    // ... and the LAST layer's dS product, whose k extent is output_dim, must be one piece (roundup8(fo) <= 8 * SG_NCH = 136): a wider
+    // output takes the generic backward behind the graph-resident forward, the pairing of a batch beyond the backward's 1,024 blocks
+    if (!ea_seg_bwd_out_ok(lo.fo)) r.ea_seg_bwd = false;
     // ReLU masks are saved BY THE GENERIC WALK when a backward pass was announced, Fe = 2, the layer's forward walk is the generic one
     // and so are the backward walks (the graph-resident walks save and read theirs under seg_gates, below -- or recompute from P | Q)
     for (int i = 0; i < 2; ++i) {

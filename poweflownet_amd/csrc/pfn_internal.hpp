@@ -429,6 +429,7 @@ struct EaSegBwdArgs {
     const unsigned* gates = nullptr;
 };
 bool ea_seg_fit(int seg, int n, int fe, int ld, bool bwd);
+bool ea_seg_bwd_out_ok(int fo);   // the backward kernel's dS product takes a last layer of this output width (one k piece)
 // mask_embd + residual AND the first EdgeAggregation's edge stage in one graph-resident launch (ea_seg.hip front_seg_fwd_kernel),
 // carrying the forward pass's weight re-layout jobs like launch_front_fwd_pack; writes maskf, me_h (when f.me_h), x0, P, Q, S
 bool front_seg_fit(int seg, int n, int h, int fe);

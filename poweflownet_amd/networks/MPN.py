@@ -153,13 +153,19 @@ class _GraphCache:
     no host sync, hipGraph-capturable; a node id out of range or an edge between two graphs of the batch turns the output into
     NaN, pfn_graph_poison_if_bad, instead of raising).  Only the FIRST build of a shape is validated with a read-back (and raises).
     The last VALIDATED build is kept next to the current one: a caller that comes back to that very tensor (evaluation between
-    training batches, two loaders taking turns) gets the validated adjacency -- and with it the loss tail -- back."""
+    training batches, two loaders taking turns) gets the validated adjacency -- and with it the loss tail -- back.
+    A segment hint that the validated build of a (shape, hint) REJECTED is remembered: a batch with `ptr` but no host-side size
+    list may mix sizes whose total divides by the graph count (14, 6, 14, 6 -> "10-node graphs"), and the unverified rebuilds of
+    that shape would take the hint on trust and poison every output.  They are handed seg_hint = 0 instead; a later batch of the
+    shape that would have honoured the hint then merely runs on the generic kernels.  (`rebuild`, a topology that changes per
+    batch, has no validated build to learn from: there the hint stays the caller's promise, checked by the poison alone.)"""
 
     def __init__(self):
         self._ref, self._key, self._graph = None, None, None
         self._validated = None        # (weakref of its edge_index, key, graph) of the last build whose checks were read back
         self.device_rebuilds = 0      # new tensors of the cached shape that took the sync-free path
         self._adopted = None          # (weakref of an edge_index, its adjacency) offered by `adopt` for the next `get`
+        self._rejected = set()        # key[2:] of every validated build whose segment hint the device check refused
 
     def adopt(self, edge_index: torch.Tensor, graph: GraphCSR) -> None:
         """The NEXT `get` for this very `edge_index` tensor returns `graph` instead of building: for a caller that built the
@@ -188,10 +194,14 @@ class _GraphCache:
         same_shape = self._key is not None and key[2:] == self._key[2:] and self._graph is not None and edge_index.device == self._graph.device
         if same_shape and not rebuild:
             self.device_rebuilds += 1
+            if key[2:] in self._rejected:     # (the validated build of this shape refused the hint: not taken on trust)
+                seg_hint, segment_build = 0, None
         g = GraphCSR(edge_index, num_nodes, mode, seg_hint=seg_hint, async_checks=rebuild or same_shape, segment_build=segment_build)
         self._ref, self._key, self._graph = weakref.ref(edge_index), key, g
         if not g.unverified:
             self._validated = (self._ref, key, g)
+            if seg_hint > 0 and g.seg_nodes != seg_hint:
+                self._rejected.add(key[2:])
         return g
 
 

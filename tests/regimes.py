@@ -84,6 +84,16 @@ def ea_seg_fit(seg, n, fe, ld, bwd, cus):
     return fe == 2 and p is not None and p["nblocks"] * p["ny"] <= PER_CU * cus
 
 
+def ea_seg_bwd_out_ok(fo):
+    """ea_seg.hip ea_seg_bwd_out_ok: the backward kernel's dS product takes the last layer's output width as ONE k piece."""
+    return ((fo + 7) & ~7) <= 8 * SG_NCH
+
+
+def ea_seg_bwd_fit(seg, n, fe, ld, cus, fo=4):
+    """Route::ea_seg_bwd (model.hip make_route): ea_seg_fit's backward form AND the output-width clause."""
+    return ea_seg_fit(seg, n, fe, ld, True, cus) and ea_seg_bwd_out_ok(fo)
+
+
 def seg_lin_hops_shape_ok(ld, h):
     """seg_lin_hops_fit's operand-shape clause (K = ncols = H = 129-shaped layers only)."""
     remv, nq = col_plan(ld)
@@ -123,32 +133,37 @@ def front_seg_fit(seg, n, h, fe, cus):
     return ld // 4 <= 64 and front_latency_regime(h, n) and ea_seg_fit(seg, n, fe, ld, False, cus)
 
 
-def ea_saves_mask(train, n, fe, ld, seg, fused_front, i, cus):
+def edge_fwd_out_ok(fe, h, fo, ldo):
+    """edge.hip: the last layer's output Linear rides in its generic edge walk (edge_fwd_out_kernel)."""
+    return fe == 2 and 1 <= fo <= 4 and ldo == 4 and ld_of(h) // 4 <= 256
+
+
+def ea_saves_mask(train, n, fe, ld, seg, fused_front, i, cus, fo=4):
     generic_fwd = not ea_seg_fit(seg, n, fe, ld, False, cus) or (fused_front and i == 0)
-    return train and fe == 2 and generic_fwd and not ea_seg_fit(seg, n, fe, ld, True, cus)
+    return train and fe == 2 and generic_fwd and not ea_seg_bwd_fit(seg, n, fe, ld, cus, fo)
 
 
-def first_layer_fly(train, n, h, L, fe, seg, cus, f0=4):
+def first_layer_fly(train, n, h, L, fe, seg, cus, f0=4, fo=4):
     fused_front = front_fused_ok(f0, h)
     return (fused_front and L > 1 and fe == 2 and f0 == 4 and not front_latency_regime(h, n)
-            and (not train or ea_saves_mask(train, n, fe, ld_of(h), seg, fused_front, 0, cus)))
+            and (not train or ea_saves_mask(train, n, fe, ld_of(h), seg, fused_front, 0, cus, fo)))
 
 
-def uses_seg_front(train, n, h, L, fe, seg, cus, f0=4):
+def uses_seg_front(train, n, h, L, fe, seg, cus, f0=4, fo=4):
     ld = ld_of(h)
-    return (front_fused_ok(f0, h) and ea_seg_fit(seg, n, fe, ld, False, cus) and not first_layer_fly(train, n, h, L, fe, seg, cus, f0)
-            and L > 1 and front_seg_fit(seg, n, h, fe, cus) and not (train and fe == 2 and not ea_seg_fit(seg, n, fe, ld, True, cus)))
+    return (front_fused_ok(f0, h) and ea_seg_fit(seg, n, fe, ld, False, cus) and not first_layer_fly(train, n, h, L, fe, seg, cus, f0, fo)
+            and L > 1 and front_seg_fit(seg, n, h, fe, cus) and not (train and fe == 2 and not ea_seg_bwd_fit(seg, n, fe, ld, cus, fo)))
 
 
 def mse_tail_ok(train, n, h, L, fe, seg, cus, fo=4):
     ld = ld_of(h)
-    return (train and n > 0 and L > 1 and fe == 2 and fo == 4 and lin_out4_ok(h, fo, 4, n) and ea_seg_fit(seg, n, fe, ld, False, cus)
-            and ea_seg_fit(seg, n, fe, ld, True, cus) and ld // 4 <= 34)
+    return (train and n > 0 and L > 1 and fe == 2 and fo == 4 and ld_of(fo) == 4 and lin_out4_ok(h, fo, ld_of(fo), n)
+            and ea_seg_fit(seg, n, fe, ld, False, cus) and ea_seg_bwd_fit(seg, n, fe, ld, cus, fo) and ld // 4 <= 34)
 
 
-def mse_tail_available(train, n, h, L, fe, seg, cus):
+def mse_tail_available(train, n, h, L, fe, seg, cus, fo=4):
     """pfn_mpn_mse_tail_ok: what the attached MSELoss / Masked_L2_loss need."""
-    return mse_tail_ok(train, n, h, L, fe, seg, cus) and uses_seg_front(train, n, h, L, fe, seg, cus)
+    return mse_tail_ok(train, n, h, L, fe, seg, cus, fo) and uses_seg_front(train, n, h, L, fe, seg, cus, fo=fo)
 
 
 # ------------------------------------------------------------------------------------------ TAGConv hops (edge.hip)
@@ -292,14 +307,17 @@ def gemm_nt_plan(M, cin, cout, nterm, cus):
 
 
 # ------------------------------------------------------------------------------------------ a whole MaskEmbdMultiMPN step
-def route(n, seg, H, L, K, fe, train, cus):
-    """model.hip make_route for MaskEmbdMultiMPN(4, fe, 4, H, L, K) without the diagnostic switches: the Route's fields by name."""
+def route(n, seg, H, L, K, fe, train, cus, fo=4):
+    """model.hip make_route for MaskEmbdMultiMPN(4, fe, fo, H, L, K) without the diagnostic switches: the Route's fields by name."""
     ld = ld_of(H)
     fused_front = front_fused_ok(4, H)
-    r = dict(fused_front=fused_front, ea_seg_fwd=ea_seg_fit(seg, n, fe, ld, False, cus), ea_seg_bwd=ea_seg_fit(seg, n, fe, ld, True, cus),
-             mask0=ea_saves_mask(train, n, fe, ld, seg, fused_front, 0, cus), mask1=ea_saves_mask(train, n, fe, ld, seg, fused_front, 1, cus),
-             l0_fly=first_layer_fly(train, n, H, L, fe, seg, cus), seg_front=uses_seg_front(train, n, H, L, fe, seg, cus),
-             lin_out4=lin_out4_ok(H, 4, 4, n), mse_tail=mse_tail_ok(train, n, H, L, fe, seg, cus), hops=hop_kernel(seg, n, K))
+    r = dict(fused_front=fused_front, ea_seg_fwd=ea_seg_fit(seg, n, fe, ld, False, cus), ea_seg_bwd=ea_seg_bwd_fit(seg, n, fe, ld, cus, fo),
+             mask0=ea_saves_mask(train, n, fe, ld, seg, fused_front, 0, cus, fo),
+             mask1=ea_saves_mask(train, n, fe, ld, seg, fused_front, 1, cus, fo),
+             l0_fly=first_layer_fly(train, n, H, L, fe, seg, cus, fo=fo), seg_front=uses_seg_front(train, n, H, L, fe, seg, cus, fo=fo),
+             lin_out4=lin_out4_ok(H, fo, ld_of(fo), n), mse_tail=mse_tail_ok(train, n, H, L, fe, seg, cus, fo), hops=hop_kernel(seg, n, K))
+    # saved gates (without its diagnostic switch): every EdgeAggregation graph-resident, forward and backward
+    r["seg_gates"] = train and fe == 2 and r["ea_seg_fwd"] and r["ea_seg_bwd"] and (r["seg_front"] or not fused_front)
     # (front_recomputes_meh: me_h holds front_bwd_wg_kernel's partial sums -- a bound on the batch that is not restated; the check
     #  only needs that it is never set without l0_fly)
     r["meh_recompute"] = train and r["l0_fly"]
@@ -320,23 +338,29 @@ def route_contradictions(r):
         "mse_tail -> ea_seg_fwd, ea_seg_bwd, lin_out4": not r["mse_tail"] or (r["ea_seg_fwd"] and r["ea_seg_bwd"] and r["lin_out4"]),
         "slh -> fused hops, row-major": not (r["slh_fwd"] or r["slh_bwd"]) or (r["hops"] == "fused" and not r["big_cm"]),
         "big_cm -> big hops": not r["big_cm"] or r["hops"] == "big",
+        "seg_gates -> no generic walk": not r.get("seg_gates", False) or (
+            r["ea_seg_fwd"] and r["ea_seg_bwd"] and not r["mask0"] and not r["mask1"] and not r["l0_fly"]
+            and (r["seg_front"] or not r["fused_front"])),
     }
     return [name for name, ok in checks.items() if not ok]
 
 
-def model_regime(n, seg, H, L, K, fe, train, cus):
-    """The regime of every stage of MaskEmbdMultiMPN(4, fe, 4, H, L, K) on n rows of graphs of `seg` nodes, and the profile classes
+def model_regime(n, seg, H, L, K, fe, train, cus, fo=4, gea=False):
+    """The regime of every stage of MaskEmbdMultiMPN(4, fe, fo, H, L, K) on n rows of graphs of `seg` nodes, and the profile classes
     that must and must not appear in its forward (+ backward, when `train`).  `train` is the model's need_backward: a forward under
-    autograd whose backward pass runs, with or without dropout.
+    autograd whose backward pass runs, with or without dropout.  `gea`: the backward pass is also asked for the edge-attribute
+    gradient, which only the generic (recomputing) backward walks form (model_backward: `seg_bwd = r.ea_seg_bwd && !gea`).
 
     L is n_gnn_layers.  Only what the restated predicates decide is listed; the rest of a launch sequence is not pinned here."""
     ld = ld_of(H)
     fwd_seg = ea_seg_fit(seg, n, fe, ld, False, cus)
-    bwd_seg = ea_seg_fit(seg, n, fe, ld, True, cus)
-    seg_front = uses_seg_front(train, n, H, L, fe, seg, cus)
+    bwd_seg = ea_seg_bwd_fit(seg, n, fe, ld, cus, fo) and not gea
+    seg_front = uses_seg_front(train, n, H, L, fe, seg, cus, fo=fo)
+    # the last layer's output Linear inside its generic edge walk (ea_forward's out_in_walk)
+    out_in_walk = not fwd_seg and edge_fwd_out_ok(fe, H, fo, ld_of(fo))
     r = dict(ld=ld, ny=col_plan(ld)[1], ea_seg_fwd=fwd_seg, ea_seg_bwd=bwd_seg and train, seg_front=seg_front,
-             front_latency=front_latency_regime(H, n), lin_out4=lin_out4_ok(H, 4, 4, n),
-             l0_fly=first_layer_fly(train, n, H, L, fe, seg, cus), mse_tail=mse_tail_available(train, n, H, L, fe, seg, cus),
+             front_latency=front_latency_regime(H, n), lin_out4=lin_out4_ok(H, fo, ld_of(fo), n), out_in_walk=out_in_walk,
+             l0_fly=first_layer_fly(train, n, H, L, fe, seg, cus, fo=fo), mse_tail=mse_tail_available(train, n, H, L, fe, seg, cus, fo),
              hops=hop_kernel(seg, n, K), slh=seg_lin_hops_fit(seg, n, ld, H, K, cus) and L > 1,
              edge_rows=not train and fe == 2 and not fwd_seg and edge_rows_ok(seg, n, ld, cus),
              row_hops=K > 0 and hop_kernel(seg, n, K) == "fused" and row_hops_ok(seg, n, ld, cus))
@@ -361,12 +385,17 @@ def model_regime(n, seg, H, L, K, fe, train, cus):
         must.add("edge_bwd")
     if fwd_seg:
         must.add("ea_seg_fwd")           # (the last EdgeAggregation is never layer 0: never behind front_seg_fwd)
-    # the output Linear: in the last layer's generic edge walk (edge_fwd_out_kernel) unless that layer ran graph-resident; then
-    # lin_out4 where lin_out4_ok holds (on the plain loss path: an attached loss tail forms the rows in the backward's first launch)
-    if fwd_seg and r["lin_out4"]:
+    # the output Linear: in the last layer's generic edge walk (edge_fwd_out_kernel: Fe = 2, Fo <= 4) unless that layer ran
+    # graph-resident; else lin_out4 where lin_out4_ok holds (on the plain loss path: an attached loss tail forms the rows in the
+    # backward's first launch); else gemm_nt with N = Fo
+    if not out_in_walk and r["lin_out4"]:
         must.add("lin_out4")
     else:
         must_not.add("lin_out4")
+        if not out_in_walk:
+            must.add("gemm_nt")
+    if K == 0:                           # no hop of any kind (HOPS_NONE): a TAGConv is its k = 0 product alone
+        must_not.update({"hop_norm", "fused_hops_fwd", "fused_hops_bwd", "seg_lin_hops_fwd", "seg_lin_hops_bwd"})
     if not r["slh"]:
         must_not.update({"seg_lin_hops_fwd", "seg_lin_hops_bwd"})
     if K > 0 and r["hops"] in ("fused", "big") and not r["slh"]:

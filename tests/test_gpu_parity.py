@@ -162,6 +162,33 @@ def test_tagconv_odd_shapes_vs_oracle(cin, cout, K, nodes):
         assert_close(a, b, RTOL, f"tensor {i}")
 
 
+@pytest.mark.parametrize("cin,cout,nodes", [(8, 5, 77), (129, 129, 300)])
+def test_tagconv_without_hops_vs_oracle(cin, cout, nodes):
+    """K = 0: out = x W_0^T + b, no hop of any kind (HOPS_NONE); the backward is tag_backward's K == 0 branch, one GEMM that
+    writes grad_x itself.  Forward, grad_x, the weight and the bias gradient against the oracle layer."""
+    torch.manual_seed(cin * 100 + cout)
+    ref = ref_cpu.TAGConv(cin, cout, 0)
+    with torch.no_grad():
+        ref.bias.normal_(std=0.2)
+    ours = TAGConv(cin, cout, K=0)
+    ours.load_state_dict(ref.state_dict())
+    ours = ours.to(DEV)
+    ei = torch.randint(0, nodes, (2, 4 * nodes))
+    x, g = torch.randn(nodes, cin), torch.randn(nodes, cout)
+
+    def run(mod, x, ei, g):
+        x = x.clone().requires_grad_(True)
+        y = mod(x, ei)
+        y.backward(g)
+        return [y.detach(), x.grad] + [p.grad for p in mod.parameters()]
+
+    want = run(ref, x, ei, g)
+    got = run(ours, x.to(DEV), ei.to(DEV), g.to(DEV))
+    assert len(got) == 4 and tuple(got[0].shape) == (nodes, cout)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert_close(a, b, RTOL, f"TAGConv({cin}, {cout}, K=0) tensor {i}")
+
+
 # --------------------------------------------------------------------------------------------- whole model
 def _model_from(fx, shared, dropout=0.0):
     params = params_from(load("g4_params_standard")) if shared else params_from(fx)

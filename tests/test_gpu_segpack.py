@@ -223,6 +223,42 @@ def test_equal_counts_of_two_sizes_stay_finite_batch_after_batch():
     assert m._graphs.device_rebuilds >= 2
 
 
+def test_batches_with_ptr_but_no_size_list_stay_finite_batch_after_batch():
+    """What a real PyG loader hands over: `ptr`, no host-side size list.  14 + 6 + 14 + 6 = 40 rows in 4 graphs divides into
+    "10-node graphs"; the first, validated build rejects that hint, and the cache remembers it (_GraphCache._rejected): every later
+    tensor of the shape -- built unverified, the checks left on the device -- gets no hint instead of the rejected one on trust
+    (which poisoned every output).  Three fresh batches (new tensors, new samples), then a UNIFORM batch of the very same shape
+    (4 x 10 nodes, the same 58 stored edges), which would have honoured the hint and now merely runs on the generic kernels.
+    (`dynamic_topology=True` has no validated build to learn from and is left as it is: there the hint is the caller's promise.)"""
+    from poweflownet_amd.data import Batch
+    from poweflownet_amd.synth import make_graph, make_topology
+    m, ref = _models(h=33, layers=3, K=2, seed=7)
+    sizes = [14, 6, 14, 6]
+    shape = None
+    for rep in range(3):
+        data = make_ragged_batch(sizes, seed=20 + rep)
+        del data.__dict__["_graph_sizes"]
+        assert data.ptr.tolist() == [0, 14, 20, 34, 40]
+        shape = tuple(data.edge_index.shape)
+        with torch.no_grad():
+            out = m(data.to(DEV))
+            want = ref(data)
+        assert m._graphs._graph.seg_nodes == 0, rep
+        assert torch.isfinite(out).all(), rep
+        assert_close(out, want, RTOL, f"ptr without a size list, batch {rep}")
+    assert m._graphs.device_rebuilds >= 2
+    edges = [15, 14, 15, 14]
+    uniform = Batch.from_data_list([make_graph(10, e, seed=90 + g, edge_index=make_topology(10, e, g)) for g, e in enumerate(edges)])
+    del uniform.__dict__["_graph_sizes"]
+    assert tuple(uniform.edge_index.shape) == shape and uniform.x.shape[0] == 40
+    with torch.no_grad():
+        out = m(uniform.to(DEV))
+        want = ref(uniform)
+    assert m._graphs.device_rebuilds >= 3 and m._graphs._graph.seg_nodes == 0
+    assert torch.isfinite(out).all()
+    assert_close(out, want, RTOL, "a uniform batch of the shape whose hint was rejected")
+
+
 def test_a_size_list_that_lies_raises_on_the_validated_build():
     m, _ = _models(h=12, layers=2, K=2)
     d = make_ragged_batch([14, 5, 14, 5]).to(DEV)

@@ -222,11 +222,16 @@ REGIME_PINS = {
                    "size_t i = (size_t)(bwd ? 2 : 1) * (rows_pb + 1 + cap);", "return (f + i) * 4 + 16;",
                    "const long per_cu = 4L;",
                    "return !off && fe == 2 && seg_plan(seg, n, ld, p, bwd) && (long)p.nblocks * p.ny <= per_cu * device_cus();",
-                   "return !off && ld / 4 <= 64 && front_latency_regime(h, n) && ea_seg_fit(seg, n, fe, ld, false);"),
+                   "return !off && ld / 4 <= 64 && front_latency_regime(h, n) && ea_seg_fit(seg, n, fe, ld, false);",
+                   "bool ea_seg_bwd_out_ok(int fo) { return ((fo + 7) & ~7) <= 8 * SG_NCH; }"),
     "seg_lin_hops.hip": ("const long per_cu = 4L;   // (ea_seg_fit's bound)", "fused_hops_fit(seg, ld, n) &&",
                          "slh_plan(seg, n, ld, nterm, p) && (long)p.nblocks * p.ny <= per_cu * device_cus();"),
     # (make_route: every whole-model decision, once per entry point; hop_kind: the TAGConv hop kernel)
     "model.hip": ("r.ea_seg_fwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, false);", "r.ea_seg_bwd = ea_seg_fit(seg, lo.n, lo.fe, lo.ld, true);",
+                  "if (!ea_seg_bwd_out_ok(lo.fo)) r.ea_seg_bwd = false;",
+                  "const bool seg_walk = o.ea_in && o.ea_out && (fo > 4 || ldgo == 4);",
+                  "const bool out_in_walk = !seg_walk && !o.walk_done && w2 && act.act == ACT_NONE && edge_fwd_out_ok(fe, h, fo, ldo) && o.back_fused;",
+                  "r.seg_gates = !no_gates && train && lo.fe == 2 && r.ea_seg_fwd && r.ea_seg_bwd && (r.seg_front || !r.fused_front);",
                   "r.fused_front = front_fused_ok(lo.f0, lo.h);",
                   "const bool generic_fwd = !r.ea_seg_fwd || (r.fused_front && i == 0);",
                   "r.mask[i] = train && lo.fe == 2 && generic_fwd && !r.ea_seg_bwd;",
@@ -268,7 +273,8 @@ REGIME_PINS = {
                  "if (seg <= 0 || seg > 1023 || (long)seg * nchunk > (long)ER_IPT * ER_THREADS || 8 * nchunk > ER_THREADS) return 0;",
                  "int gpb = std::min((ER_IPT * ER_THREADS) / (seg * nchunk), 1023 / seg);",
                  "while (gpb > 0 && (size_t)gpb * seg * nchunk * 16 + 4096 > (size_t)66 * 1024) --gpb;",
-                 "if (!off && gpb > 0 && (long)(ngraphs + gpb - 1) / gpb >= 4L * device_cus()) {"),
+                 "if (!off && gpb > 0 && (long)(ngraphs + gpb - 1) / gpb >= 4L * device_cus()) {",
+                 "bool edge_fwd_out_ok(int fe, int h, int fo, int ldo) { return fe == 2 && fo >= 1 && fo <= 4 && ldo == 4 && ld_of(h) / 4 <= 256; }"),
     # the TAGConv products
     "gemm_nt.hip": ("constexpr int NT_THREADS = 512;", "constexpr int NCH = 17;", "constexpr int KP = 8 * NCH;", "constexpr int NT_MAX_PIECES = 16;",
                     "constexpr int NT_LDS_BYTES = 160 * 1024;", "constexpr int TINY_MAX_PIECES = 8;",
@@ -334,11 +340,47 @@ def test_route_invariants_hold_over_a_sweep_of_models_and_batches():
                             assert R.route_contradictions(r) == [], (cus, H, seg, B, train, L, K, r)
                             count += 1
     assert count == 4 * 9 * 17 * 12 * 2 * 4
+    # ... and over the output width: the last layer's dS product is one k piece up to fo = 136 (ea_seg_bwd_out_ok); a wider output
+    # pairs the graph-resident forward with the generic backward, which must leave every other decision consistent
+    assert [R.ea_seg_bwd_out_ok(fo) for fo in (1, 3, 4, 5, 136, 137, 200)] == [True] * 5 + [False] * 2
+    count = 0
+    for fo in (1, 3, 4, 5, 136, 137, 200):
+        for cus in (32, 256):
+            for H in (3, 7, 16, 33, 64, 65, 129, 136, 137, 256):
+                for seg in (1, 14, 118, 128, 129, 1996, 1997, 8193):
+                    for B in (1, 2, 6, 37, 278, 2341, 33000):
+                        for train in (False, True):
+                            for fe in (1, 2, 6):
+                                for L, K in ((2, 0), (3, 2), (2, 3)):
+                                    n = seg * B
+                                    r = R.route(n, seg, H, L, K, fe, train, cus, fo=fo)
+                                    assert R.route_contradictions(r) == [], (fo, cus, H, seg, B, train, fe, L, K, r)
+                                    # the clause itself, and what follows from the existing lines: no gates, no graph-resident
+                                    # front, no loss tail without the graph-resident backward
+                                    assert r["ea_seg_bwd"] == (R.ea_seg_fit(seg, n, fe, R.ld_of(H), True, cus) and fo <= 136)
+                                    if train and fe == 2 and not r["ea_seg_bwd"]:
+                                        assert not r["seg_gates"] and not r["seg_front"] and not r["mse_tail"]
+                                        assert r["mask0"] == (not r["ea_seg_fwd"] or r["fused_front"]) and r["mask1"] == (not r["ea_seg_fwd"])
+                                    assert r["mse_tail"] <= (fo == 4) and r["lin_out4"] <= (fo <= 4)
+                                    reg = R.model_regime(n, seg, H, L, K, fe, train, cus, fo=fo)
+                                    assert not (reg["must"] & reg["must_not"]), (fo, cus, H, seg, B, train, fe, L, K, reg)
+                                    if fo == 4:       # the keyword's default is the old restatement
+                                        assert r == R.route(n, seg, H, L, K, fe, train, cus)
+                                        assert reg == R.model_regime(n, seg, H, L, K, fe, train, cus)
+                                    count += 1
+    assert count == 7 * 2 * 10 * 8 * 7 * 2 * 3 * 3
     # the check itself: a route with one decision flipped is refused
     r = R.route(118 * 128, 118, 129, 4, 3, 2, True, 256)
     assert r["mse_tail"] and r["seg_front"] and r["slh_fwd"] and R.route_contradictions(r) == []
     for key, value in (("ea_seg_fwd", False), ("mask0", True), ("l0_fly", True), ("hops", "generic"), ("big_cm", 118 * 128)):
         assert R.route_contradictions(dict(r, **{key: value})) != [], key
+    # the wide output at the flagship batch: forward graph-resident, backward generic, layer 0's masks saved by its generic walk
+    for fo, bwd in ((136, True), (137, False), (200, False)):
+        r = R.route(118 * 128, 118, 129, 4, 3, 2, True, 256, fo=fo)
+        assert r["ea_seg_fwd"] and r["ea_seg_bwd"] == bwd and r["seg_gates"] == bwd and r["seg_front"] == bwd and r["mask0"] == (not bwd)
+        reg = R.model_regime(118 * 128, 118, 129, 4, 3, 2, True, 256, fo=fo)
+        assert ("ea_seg_bwd" in reg["must"]) == bwd and ("edge_bwd" in reg["must"]) == (not bwd)
+        assert ("ea_seg_bwd" in reg["must_not"]) == (not bwd)
 
 
 def test_regime_pins_fail_on_a_moved_threshold(tmp_path):
