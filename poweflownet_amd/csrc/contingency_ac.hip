@@ -21,14 +21,16 @@
 //     mismatch = max |F| once more; the fp32 (Vm, Va in degrees) of the final state; phasors by branch_line.hpp bf_phasor_of, the
 //     current of every line l != k by bf_line(...).x (lanes own lines), loading I_l / rating_l; severity, worst line and overloads by
 //     contingency_monitor.hpp's tail; vm_min, vm_min_bus, v_violations over the PQ buses.
+// A bus's mismatch, the line weights and 1 / c_k - a^T w, the per-bus and per-line tails, the stores and the fill values of a skipped
+// outage are contingency_ac_core.hpp's, one text with the sparse route (contingency_ac_sparse.hip); this file keeps the half step by
+// rows of the inverses, the butterfly and the wave's merges.
 // Only wave-level fences stand between the steps; the one workgroup barrier is behind the copy of both inverses into LDS on the LDS
 // placement (the global placement reads the slab: same code, same bits).  Every cross-lane reduction is a max, a min, an integer sum
 // or that fixed-order dot product: a result's bits are a pure function of the scenario's inputs, whatever the batch, the waves per
 // workgroup or the placement.  No float atomics, no host read, no allocation: capturable.
 #include <algorithm>
 
-#include "branch_line.hpp"
-#include "contingency_monitor.hpp"
+#include "contingency_ac_core.hpp"
 #include "powerflow_dense.hpp"
 
 namespace pfn {
@@ -62,15 +64,7 @@ struct CaArgs {
     PfArgs pf;                                      // the base solve as powerflow.hip's kernel takes it (pf.p.ws is not used)
     const double* ratings;                          // [e], [S, e] or null (1.0 everywhere)
     const int32_t* islands;                         // [e]
-    float* severity;                                // [S, e]
-    int32_t* worst_line;
-    int32_t* overloads;
-    float* vm_min;
-    int32_t* vm_min_bus;
-    int32_t* v_violations;
-    double* mismatch;
-    float* post_current;                            // [S, e, e] or null
-    float* post_state;                              // [S, e, n, 2] or null
+    CaOut out;                                      // (where its nine pointers always stood: the argument layout does not move)
     unsigned char* slabs;
     float v_lo, v_hi;
     int halves, ratings_per_sample;
@@ -162,34 +156,9 @@ __device__ __forceinline__ double ca_mismatch(const CaWave& v, const int mode) {
     for (int i = v.lane; i < v.n; i += 64) {
         const int ra = v.aidx[i], rq = v.qidx[i];
         if (ra < 0) continue;                       // the slack: no equation
-        const double vi = v.vm[i], ti = v.th[i];
-        double sP = 0.0, sQ = 0.0;
-        for (int q = v.adjptr[i]; q < v.adjptr[i + 1]; ++q) {
-            const int2 lj = v.adj[q];
-            if (lj.x == v.k) continue;
-            pf_ac_end(v.rx[2 * lj.x], v.rx[2 * lj.x + 1], vi, ti, v.vm[lj.y], v.th[lj.y], sP, sQ);
-        }
-        const double fp = v.spec[4 * i + 2] - sP;
-        mx = fmax(mx, pf_abs_clamped(fp));
-        if (mode == 0) v.g[ra] = fp / vi;
-        if (rq >= 0) {
-            const double fq = v.spec[4 * i + 3] - sQ;
-            mx = fmax(mx, pf_abs_clamped(fq));
-            if (mode == 1) v.g[rq] = fq / vi;
-        }
+        mx = ca_bus_mismatch<1, 0>(mx, v.th, v.vm, v.g, v.adj, v.adjptr[i], v.adjptr[i + 1], v.rx, v.spec, i, ra, rq, v.k, mode);
     }
     return mx;
-}
-
-// the lowest voltage over the PQ buses: (key, bus) with ties to the lowest bus; a non-finite Vm counts as the lowest and is a violation
-struct CaLow {
-    float best;                                     // +inf: none
-    int arg, cnt, wild;
-};
-__device__ __forceinline__ void ca_low_merge(CaLow& w, const CaLow& o) {
-    if (o.best < w.best || (o.best == w.best && o.arg < w.arg)) { w.best = o.best; w.arg = o.arg; }
-    w.cnt += o.cnt;
-    w.wild |= o.wild;
 }
 
 template <bool LDS>
@@ -220,19 +189,10 @@ __global__ __launch_bounds__(CA_MAX_WAVES * 64) void contingency_ac_outage_kerne
     if (k >= e) return;
 
     const int64_t o = (int64_t)s * e + k;
-    float* crow = a.post_current ? a.post_current + o * e : nullptr;
-    float* srow = a.post_state ? a.post_state + o * 2 * n : nullptr;
-    const float nanf32 = __builtin_nanf("");
+    float* crow = a.out.post_current ? a.out.post_current + o * e : nullptr;
+    float* srow = a.out.post_state ? a.out.post_state + o * 2 * n : nullptr;
     if (code != 0 || a.islands[k] != 0) {           // a failed scenario, an islanding outage
-        ct_skip(code != 0, crow, e, lane, 64, a.severity[o], a.worst_line[o], a.overloads[o]);
-        if (srow)
-            for (int q = lane; q < 2 * n; q += 64) srow[q] = nanf32;
-        if (lane == 0) {
-            a.vm_min[o] = nanf32;
-            a.vm_min_bus[o] = -1;
-            a.v_violations[o] = -1;
-            a.mismatch[o] = __builtin_nan("");
-        }
+        ca_skip(code != 0, a.out, o, crow, srow, e, n, lane, 64);
         return;
     }
 
@@ -266,11 +226,10 @@ __global__ __launch_bounds__(CA_MAX_WAVES * 64) void contingency_ac_outage_kerne
     }
     __syncwarp();
     // ---- 1 / c_k - a^T w of both matrices (c: the line's weight in the matrix)
-    const double rk = sm.rx[2 * k], xk = sm.rx[2 * k + 1];
-    const double c1 = 1.0 / xk, c2 = xk / (rk * rk + xk * xk);
-    const bool xb = a.pf.mode == 2;
-    const double denp = 1.0 / (xb ? c1 : c2) - (wp[bi] - wp[bj]);
-    const double denq = 1.0 / (xb ? c2 : c1) - (wq[bi] - wq[bj]);
+    const double2 ck = ca_weights(sm.rx[2 * k], sm.rx[2 * k + 1]);
+    const bool bx = a.pf.mode != 2;
+    const double denp = ca_den(ck, bx, false, wp[bi] - wp[bj]);
+    const double denq = ca_den(ck, bx, true, wq[bi] - wq[bj]);
 
     for (int h = 0; h < a.halves; ++h) {
         const bool qhalf = mq != 0 && (h & 1);
@@ -308,20 +267,8 @@ __global__ __launch_bounds__(CA_MAX_WAVES * 64) void contingency_ac_outage_kerne
     for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
 
     // ---- the fp32 state, the phasors and the voltage figures over the PQ buses
-    CaLow low{__builtin_inff(), CT_NO_LINE, 0, 0};
-    for (int b = lane; b < n; b += 64) {
-        const float vm32 = (float)vm[b];
-        const float va32 = (float)(aidx[b] < 0 ? sm.spec[4 * b + 1] : th[b] * (1.0 / PF_RAD));
-        ph[b] = bf_phasor_of(vm32, va32);
-        if (srow) *reinterpret_cast<float2*>(srow + 2 * b) = make_float2(vm32, va32);
-        if (qidx[b] >= 0) {
-            const bool finite = fabsf(vm32) < __builtin_inff();
-            const float key = finite ? vm32 : -__builtin_inff();
-            low.wild |= !finite;
-            low.cnt += !finite || vm32 < a.v_lo || vm32 > a.v_hi;
-            if (key < low.best) { low.best = key; low.arg = b; }
-        }
-    }
+    CaLow low = ca_low_none();
+    for (int b = lane; b < n; b += 64) ca_bus_tail<1>(low, th, vm, ph, srow, sm.spec, b, aidx[b] < 0, qidx[b] >= 0, a.v_lo, a.v_hi);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1)
         ca_low_merge(low, CaLow{__shfl_xor(low.best, off), __shfl_xor(low.arg, off), __shfl_xor(low.cnt, off), __shfl_xor(low.wild, off)});
@@ -330,22 +277,9 @@ __global__ __launch_bounds__(CA_MAX_WAVES * 64) void contingency_ac_outage_kerne
     // ---- the currents of the lines l != k, their loadings, the wave's worst (contingency_monitor.hpp)
     const double* rat = a.ratings ? a.ratings + (a.ratings_per_sample ? (int64_t)s * e : 0) : nullptr;
     CtWorst worst = ct_worst_none();
-    for (int l = lane; l < e; l += 64) {
-        float cur = nanf32;
-        if (l != k) cur = bf_line(ph[(int)ei[l]], ph[(int)ei[e + l]], (float)sm.rx[2 * l], (float)sm.rx[2 * l + 1]).x;
-        if (crow) crow[l] = cur;
-        const float r = rat ? (float)rat[l] : 1.f;
-        if (l != k && r > 0.f) ct_worst_add(worst, l, cur / r);
-    }
+    for (int l = lane; l < e; l += 64) ca_line_tail<1>(worst, ph, ei, sm.rx, rat, crow, e, l, k);
     worst = ct_worst_wave(worst);
-    if (lane == 0) {
-        ct_store(ct_figures(worst), a.severity[o], a.worst_line[o], a.overloads[o]);
-        const bool none = low.arg == CT_NO_LINE;
-        a.vm_min[o] = none || low.wild ? nanf32 : low.best;
-        a.vm_min_bus[o] = none ? -1 : low.arg;
-        a.v_violations[o] = low.cnt;
-        a.mismatch[o] = mx;
-    }
+    if (lane == 0) ca_store(a.out, o, worst, low, mx);
 }
 
 // the waves per workgroup and the placement of a call: 0 where it is refused.  route 0: both inverses in LDS beside 16, 8 or 4
@@ -406,14 +340,9 @@ int pfn_contingency_ac(const int64_t* edge_index, int64_t n_lines, const double*
     const char* who = "pfn_contingency_ac";
     PFN_CHECK_ARG(n_samples >= 0 && n_bus >= 2 && n_lines >= 0 && n_samples < (1ll << 29) && n_lines < (1ll << 24) && n_bus < (1ll << 24),
                   "%s: bad sizes (%lld scenarios of %lld buses and %lld lines)", who, (long long)n_samples, (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(n_pv >= 0 && n_pq >= 0 && n_pv + n_pq == n_bus - 1, "%s: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses",
-                  who, (long long)n_pv, (long long)n_pq, (long long)n_bus);
-    PFN_CHECK_ARG(variant == 0 || variant == 1, "%s: variant must be 0 (XB) or 1 (BX)", who);
-    PFN_CHECK_ARG(halves >= 0, "%s: halves must be >= 0; got %d", who, halves);
-    PFN_CHECK_ARG(v_lo <= v_hi, "%s: v_limits must be in order (low <= high, no NaN); got (%g, %g)", who, (double)v_lo, (double)v_hi);
+    PFN_TRY(ca_check_options(who, n_bus, n_pv, n_pq, variant, halves, v_lo, v_hi, tol, max_iter));
     PFN_CHECK_ARG(route >= 0 && route <= 2, "%s: route must be 0 (auto), 1 (LDS) or 2 (global)", who);
     PFN_CHECK_ARG(group >= 0 && group <= CA_MAX_WAVES, "%s: group must be 0 (auto) or the waves per workgroup, 1 .. %d", who, CA_MAX_WAVES);
-    PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "%s: max_iter must be >= 0 and tol > 0", who);
     PFN_CHECK_ARG(n_bus - 1 <= PF_MAX_UNKNOWNS, "%s: %lld unknowns per scenario exceed the dense screen's %d; beyond it: pfn_contingency_ac_sparse", who,
                   (long long)(n_bus - 1), PF_MAX_UNKNOWNS);
     const int n = (int)n_bus, e = (int)n_lines, mq = (int)n_pq, m = (n - 1) + mq;
@@ -422,22 +351,13 @@ int pfn_contingency_ac(const int64_t* edge_index, int64_t n_lines, const double*
     PFN_CHECK_ARG(waves > 0, "%s: route %d with %d waves per workgroup: both inverses of %d buses (%zu bytes) and %zu bytes per wave need more than the %d bytes of LDS",
                   who, route, group, n, ca_mat_bytes(n, mq), ca_wave_bytes(n), kLdsCuBytes - kLdsReserve);
     if (n_samples == 0 || n_lines == 0) return PFN_OK;
-    PFN_CHECK_ARG(edge_index && rx && bus_type && spec && islands && severity && worst_line && overloads && vm_min && vm_min_bus && v_violations &&
-                      mismatch && base_table && status && residual && flags,
-                  "%s: null pointer", who);
-    const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    PFN_CHECK_ARG((at(base_table) & 31) == 0 && (at(ws) & 15) == 0 &&
-                      ((at(edge_index) | at(rx) | at(spec) | at(init) | at(ratings) | at(residual) | at(mismatch) | at(post_state)) & 7) == 0 &&
-                      ((at(bus_type) | at(islands) | at(severity) | at(worst_line) | at(overloads) | at(vm_min) | at(vm_min_bus) | at(v_violations) |
-                        at(status) | at(post_current) | at(flags)) & 3) == 0,
-                  "%s: base_table must be 32-byte aligned, the workspace 16-byte, fp64 and int64 arrays and post_state 8-byte, fp32 and int32 arrays 4-byte",
-                  who);
+    const CaOut out{severity, worst_line, overloads, vm_min, vm_min_bus, v_violations, mismatch, post_current, post_state};
+    PFN_TRY(ca_check_pointers(who, edge_index, rx, bus_type, spec, init, ratings, islands, out, base_table, status, residual, flags, ws, false, nullptr));
     const CaSlab lay = ca_slab(n, e, mq);
     PFN_TRY(pf_check_workspace(who, ws, ws_bytes, (size_t)n_samples * lay.bytes));
     const size_t base_lds = pf_vec_bytes(n, m) + pf_fd_extra_bytes(m);
     CaArgs a{{{edge_index, rx, bus_type, spec, init, base_table, status, residual, flags, nullptr, tol, n, e, max_iter}, m, (int)n_pv, mq, 2 + variant, 0},
-             ratings, islands, severity, worst_line, overloads, vm_min, vm_min_bus, v_violations, mismatch, post_current, post_state,
-             static_cast<unsigned char*>(ws), v_lo, v_hi, halves, ratings_per_sample != 0};
+             ratings, islands, out, static_cast<unsigned char*>(ws), v_lo, v_hi, halves, ratings_per_sample != 0};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const double mm = (double)(n - 1), qq = (double)mq, ee = (double)e, hh = (double)halves;
     {

@@ -1,7 +1,9 @@
 // The AC N-1 screen beyond the dense cap (gfx950): compensated 1P1Q on the sparse route.  pfn_contingency_ac_sparse, two launches
 // behind pfn_contingency_islands, for grids whose B' and B'' are kept as sparse fp32 FACTORS under the fast-decoupled plan of the
 // sparse power-flow route (powerflow_plan.hpp, mode "fd") where contingency_ac.hip keeps their dense inverses.  Same definitions,
-// same outputs, same statuses as pfn_contingency_ac, plus -6 where the device line list is not the plan's.
+// same outputs, same statuses as pfn_contingency_ac, plus -6 where the device line list is not the plan's -- because a bus's
+// mismatch, 1 / c_k - a^T w, the per-bus and per-line tails, the stores and the fill values are contingency_ac_core.hpp's, one text
+// for both routes; this file keeps the substitutions, the serial w . g and the lane's loops.
 //
 // BASE launch: powerflow_sparse_fd.hip's kernel through its exported call (powerflow_sparse_fd.hpp pfd_solve) -- base table, status
 // and residual are pfn_powerflow_solve_sparse_fd's bits because they are its launch.  The sample's slab of the workspace then holds
@@ -30,8 +32,7 @@
 // tile slot is past e runs nothing and writes its fill values.  No host read, no allocation: capturable.
 #include <algorithm>
 
-#include "branch_line.hpp"
-#include "contingency_monitor.hpp"
+#include "contingency_ac_core.hpp"
 #include "contingency_sparse_core.hpp"
 #include "powerflow_sparse_fd.hpp"
 
@@ -47,18 +48,6 @@ static inline int64_t cas_groups(int64_t n_samples, int64_t e, int groups) {
     const int64_t want = groups > 0 ? (int64_t)groups : (int64_t)CAS_GROUPS_PER_CU * device_cus();
     return items < want ? items : want;
 }
-
-struct CasOut {
-    float* severity;                                // [S, e]
-    int32_t* worst_line;
-    int32_t* overloads;
-    float* vm_min;
-    int32_t* vm_min_bus;
-    int32_t* v_violations;
-    double* mismatch;
-    float* post_current;                            // [S, e, e] or null
-    float* post_state;                              // [S, e, n, 2] or null
-};
 
 // ---- the lane's column of a vector V [rows][64] (V points at the lane's word of row 0) through one factor, fp64 on fp32 entries:
 // V[r] -= (double)fac * y for the B entries at i of one column; the rows of a column are distinct, so the B loads go out together
@@ -121,26 +110,8 @@ __device__ __forceinline__ double cas_mismatch(const double* TH, const double* V
     for (int i = 0; i < n; ++i) {
         const int q1 = adjptr[i + 1];
         const int ra = uap[i], rq = uaq[i];
-        if (ra < 0) {                               // the slack: no equation
-            q = q1;
-            continue;
-        }
-        const double vi = VM[(size_t)i * 64], ti = TH[(size_t)i * 64];
-        double sP = 0.0, sQ = 0.0;
-        for (; q < q1; ++q) {
-            const int2 lj = adj[q];
-            const int line = lj.x >> 1;
-            if (line == k) continue;
-            pf_ac_end(rx[2 * line], rx[2 * line + 1], vi, ti, VM[(size_t)lj.y * 64], TH[(size_t)lj.y * 64], sP, sQ);
-        }
-        const double fp = spec[4 * i + 2] - sP;
-        mx = fmax(mx, pf_abs_clamped(fp));
-        if (mode == 0) G[(size_t)ra * 64] = fp / vi;
-        if (rq >= 0) {
-            const double fq = spec[4 * i + 3] - sQ;
-            mx = fmax(mx, pf_abs_clamped(fq));
-            if (mode == 1) G[(size_t)rq * 64] = fq / vi;
-        }
+        if (ra >= 0) mx = ca_bus_mismatch<64, 1>(mx, TH, VM, G, adj, q, q1, rx, spec, i, ra, rq, k, mode);       // (the slack: no equation)
+        q = q1;
     }
     return mx;
 }
@@ -150,7 +121,7 @@ template <bool LDS>
 __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
     const unsigned char* __restrict__ plan, const unsigned char* __restrict__ slabs, double* __restrict__ blocks, const int64_t* __restrict__ ei,
     const double* __restrict__ rx_all, const double* __restrict__ spec_all, const double* __restrict__ ratings, const int32_t* __restrict__ status,
-    const int32_t* __restrict__ islands, const CasOut out, size_t ws_stride, int n, int e, int mmax, int n_samples, int halves, int bx,
+    const int32_t* __restrict__ islands, const CaOut out, size_t ws_stride, int n, int e, int mmax, int n_samples, int halves, int bx,
     int ratings_per_sample, float v_lo, float v_hi) {
     extern __shared__ __attribute__((aligned(16))) unsigned char cas_smem[];
     const int lane = threadIdx.x;
@@ -178,7 +149,6 @@ __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
 
     const int tiles = (e + 63) >> 6;
     const int64_t items = (int64_t)n_samples * tiles;
-    const float nanf32 = __builtin_nanf("");
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const int s = (int)(item / tiles);
         const int k = (int)(item - (int64_t)s * tiles) * 64 + lane;
@@ -188,15 +158,7 @@ __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
         float* srow = out.post_state ? out.post_state + o * 2 * n : nullptr;
         const bool failed = status[s] < 0;
         if (failed || islands[k] != 0) {            // a failed scenario, an islanding outage: the fill values
-            if (crow)
-                for (int l = 0; l < e; ++l) crow[l] = nanf32;
-            if (srow)
-                for (int b = 0; b < 2 * n; ++b) srow[b] = nanf32;
-            ct_store(ct_figures_skipped(failed), out.severity[o], out.worst_line[o], out.overloads[o]);
-            out.vm_min[o] = nanf32;
-            out.vm_min_bus[o] = -1;
-            out.v_violations[o] = -1;
-            out.mismatch[o] = __builtin_nan("");
+            ca_skip(failed, out, o, crow, srow, e, n, 0, 1);
             continue;
         }
         // ---- the scenario's inputs and its slab as the base launch left it
@@ -210,8 +172,7 @@ __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
             VM[(size_t)b * 64] = svm[b];
         }
         const int bi = (int)ei[k], bj = (int)ei[e + k];
-        const double rk = rx[2 * k], xk = rx[2 * k + 1];
-        const double c1 = 1.0 / xk, c2 = xk / (rk * rk + xk * xk);
+        const double2 ck = ca_weights(rx[2 * k], rx[2 * k + 1]);
 
         double mx;
         for (int h = 0;; ++h) {
@@ -236,8 +197,7 @@ __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
             if (pj >= 0) W[(size_t)pj * 64] -= 1.0;
             cas_substitute(W, colptr, diag, row32, fac, m);
             // ---- 1 / c_k - a^T w (c: the line's weight in the half's matrix)
-            const double ck = (qhalf == (bx != 0)) ? c1 : c2;                 // XB: B' from 1 / x, B'' from x / (r^2 + x^2); BX the other way round
-            const double den = 1.0 / ck - ((pi >= 0 ? W[(size_t)pi * 64] : 0.0) - (pj >= 0 ? W[(size_t)pj * 64] : 0.0));
+            const double den = ca_den(ck, bx != 0, qhalf, (pi >= 0 ? W[(size_t)pi * 64] : 0.0) - (pj >= 0 ? W[(size_t)pj * 64] : 0.0));
             // ---- w . g, one sum in ascending unknown order; then G = X g
             double dot = 0.0;
             for (int r = 0; r < m; ++r) dot += W[(size_t)r * 64] * G[(size_t)r * 64];
@@ -252,36 +212,13 @@ __global__ __launch_bounds__(64) void contingency_ac_sparse_outages_kernel(
         }
 
         // ---- the fp32 state, the phasors and the voltage figures over the PQ buses, ascending: strict < keeps the lowest bus
-        float low = __builtin_inff();
-        int low_bus = -1, viol = 0, wild = 0;
-        for (int b = 0; b < n; ++b) {
-            const float vm32 = (float)VM[(size_t)b * 64];
-            const float va32 = (float)(uap[b] < 0 ? spec[4 * b + 1] : TH[(size_t)b * 64] * (1.0 / PF_RAD));
-            PH[(size_t)b * 64] = bf_phasor_of(vm32, va32);
-            if (srow) *reinterpret_cast<float2*>(srow + 2 * b) = make_float2(vm32, va32);
-            if (uaq[b] >= 0) {
-                const bool finite = fabsf(vm32) < __builtin_inff();
-                const float key = finite ? vm32 : -__builtin_inff();
-                wild |= !finite;
-                viol += !finite || vm32 < v_lo || vm32 > v_hi;
-                if (low_bus < 0 || key < low) { low = key; low_bus = b; }
-            }
-        }
+        CaLow low = ca_low_none();
+        for (int b = 0; b < n; ++b) ca_bus_tail<64>(low, TH, VM, PH, srow, spec, b, uap[b] < 0, uaq[b] >= 0, v_lo, v_hi);
         // ---- the currents of the lines l != k in ascending order, their loadings, the lane's worst (contingency_monitor.hpp)
         const double* __restrict__ rat = ratings ? ratings + (ratings_per_sample ? (int64_t)s * e : 0) : nullptr;
         CtWorst worst = ct_worst_none();
-        for (int l = 0; l < e; ++l) {
-            float cur = bf_line(PH[(size_t)ei[l] * 64], PH[(size_t)ei[e + l] * 64], (float)rx[2 * l], (float)rx[2 * l + 1]).x;
-            if (l == k) cur = nanf32;
-            if (crow) crow[l] = cur;
-            const float r = rat ? (float)rat[l] : 1.f;
-            if (l != k && r > 0.f) ct_worst_add(worst, l, cur / r);
-        }
-        ct_store(ct_figures(worst), out.severity[o], out.worst_line[o], out.overloads[o]);
-        out.vm_min[o] = low_bus < 0 || wild ? nanf32 : low;
-        out.vm_min_bus[o] = low_bus;
-        out.v_violations[o] = viol;
-        out.mismatch[o] = mx;
+        for (int l = 0; l < e; ++l) ca_line_tail<64>(worst, PH, ei, rx, rat, crow, e, l, k);
+        ca_store(out, o, worst, low, mx);
     }
 }
 
@@ -345,29 +282,15 @@ int pfn_contingency_ac_sparse(const int64_t* edge_index, int64_t n_lines, const 
     PFN_TRY(cas_check_shape(who, h, n_samples, n_lines, block_route, groups));
     PFN_CHECK_ARG(h[PFP_H_N] == n_bus, "%s: the plan is for %d buses and %d lines; the call has %lld and %lld", who, (int)h[PFP_H_N], (int)h[PFP_H_E],
                   (long long)n_bus, (long long)n_lines);
-    PFN_CHECK_ARG(n_pv >= 0 && n_pq >= 0 && n_pv + n_pq == n_bus - 1, "%s: %lld PV and %lld PQ buses do not leave exactly one slack among %lld buses",
-                  who, (long long)n_pv, (long long)n_pq, (long long)n_bus);
-    PFN_CHECK_ARG(variant == 0 || variant == 1, "%s: variant must be 0 (XB) or 1 (BX)", who);
-    PFN_CHECK_ARG(halves >= 0, "%s: halves must be >= 0; got %d", who, halves);
-    PFN_CHECK_ARG(v_lo <= v_hi, "%s: v_limits must be in order (low <= high, no NaN); got (%g, %g)", who, (double)v_lo, (double)v_hi);
-    PFN_CHECK_ARG(max_iter >= 0 && tol > 0.0, "%s: max_iter must be >= 0 and tol > 0", who);
+    PFN_TRY(ca_check_options(who, n_bus, n_pv, n_pq, variant, halves, v_lo, v_hi, tol, max_iter));
     const int n = h[PFP_H_N], e = (int)n_lines, m_q = h[PFD_H_M_Q], mmax = std::max(h[PFP_H_M], m_q);
     PFN_TRY(pf_check_sparse_launch(who, threads, nullptr, n_samples, h, mmax));
     const bool fits = cas_block_fits_lds(n, mmax);
     PFN_CHECK_ARG(block_route != 1 || fits, "%s: block_route 1 (LDS): an outage block of %d buses needs %zu bytes of LDS, %d are there", who, n,
                   cas_block_bytes(n, mmax), kLdsCuBytes - kLdsReserve);
     if (n_samples == 0 || n_lines == 0) return PFN_OK;
-    PFN_CHECK_ARG(edge_index && rx && bus_type && spec && islands && severity && worst_line && overloads && vm_min && vm_min_bus && v_violations &&
-                      mismatch && base_table && status && residual && flags && plan_dev,
-                  "%s: null pointer", who);
-    const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-    PFN_CHECK_ARG((at(base_table) & 31) == 0 && ((at(ws) | at(plan_dev)) & 15) == 0 &&
-                      ((at(edge_index) | at(rx) | at(spec) | at(init) | at(ratings) | at(residual) | at(mismatch) | at(post_state)) & 7) == 0 &&
-                      ((at(bus_type) | at(islands) | at(severity) | at(worst_line) | at(overloads) | at(vm_min) | at(vm_min_bus) | at(v_violations) |
-                        at(status) | at(post_current) | at(flags)) & 3) == 0,
-                  "%s: base_table must be 32-byte aligned, the workspace and the plan 16-byte, fp64 and int64 arrays and post_state 8-byte, fp32 and int32 "
-                  "arrays 4-byte",
-                  who);
+    const CaOut out{severity, worst_line, overloads, vm_min, vm_min_bus, v_violations, mismatch, post_current, post_state};
+    PFN_TRY(ca_check_pointers(who, edge_index, rx, bus_type, spec, init, ratings, islands, out, base_table, status, residual, flags, ws, true, plan_dev));
     const bool lds = block_route == 1 || (block_route == 0 && fits);
     const size_t stride = pf_sample_bytes(n, mmax, h[PFP_H_NNZ]), slabs = (size_t)n_samples * stride, block = cas_block_bytes(n, mmax);
     const int64_t G = cas_groups(n_samples, e, groups);
@@ -384,7 +307,6 @@ int pfn_contingency_ac_sparse(const int64_t* edge_index, int64_t n_lines, const 
     ProfScope ps("contingency_ac_sparse_outages",
                  ss * (tl * ((hh + 1.0) * (ee * 48.0 + nn * 40.0) + hh * nz * 6.0) + ee * (28.0 + (post_current ? 4.0 * ee : 0.0) + (post_state ? 8.0 * nn : 0.0))),
                  ss * tl * 64.0 * (hh * (2.0 * nz + 4.0 * nn) + (hh + 1.0) * 120.0 * ee + 30.0 * ee), s);
-    const CasOut out{severity, worst_line, overloads, vm_min, vm_min_bus, v_violations, mismatch, post_current, post_state};
     return launch_either<contingency_ac_sparse_outages_kernel<true>, contingency_ac_sparse_outages_kernel<false>>(
         lds, (int)G, 64, block, 0, s, static_cast<const unsigned char*>(plan_dev), static_cast<const unsigned char*>(ws),
         lds ? static_cast<double*>(nullptr) : reinterpret_cast<double*>(static_cast<unsigned char*>(ws) + slabs), edge_index, rx, spec, ratings,

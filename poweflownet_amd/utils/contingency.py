@@ -233,6 +233,22 @@ def _outputs(S, e, items, dev, keep_table):
                 post_flow=torch.empty(S, items, e, dtype=torch.float32, device=dev) if keep_table else None)
 
 
+def _outputs_ac(S, n, e, dev, keep_table, keep_state):
+    """The tensors an AC screen fills, as the result's fields and IN THE C ENTRIES' ORDER: the seven figures [S, e], `base_table`
+    [S, n, 4], `status`, `residual` [S], `post_current` [S, e, e] and `post_state` [S, e, n, 2] or None, `flags` [1] (zeroed)."""
+    new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)       # noqa: E731
+    f32, i32, f64 = torch.float32, torch.int32, torch.float64
+    return dict(severity=new(f32, S, e), worst_line=new(i32, S, e), overloads=new(i32, S, e), vm_min=new(f32, S, e), vm_min_bus=new(i32, S, e),
+                v_violations=new(i32, S, e), mismatch=new(f64, S, e), base_table=new(f64, S, n, 4), status=new(i32, S), residual=new(f64, S),
+                post_current=new(f32, S, e, e) if keep_table else None, post_state=new(f32, S, e, n, 2) if keep_state else None,
+                flags=torch.zeros(1, dtype=i32, device=dev))
+
+
+def _islands(edge_index, e, n, slack, out):
+    """the launch every screen starts with: `out` [e] int32, what the outage of each line islands (on the current device and stream)"""
+    L.check(L.load().pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, out.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+
+
 def _plan_device(who, plan, dev):
     if plan.blob.device != dev:
         raise RuntimeError(f"{who}: the plan lives on {plan.blob.device}, the inputs on {dev}")
@@ -270,7 +286,7 @@ def contingency_screen(bus_type, spec, edge_index, rx, ratings=None, *, tol=1e-8
     need = int(lib.pfn_contingency_workspace_bytes(S, n, e, _ROUTES[route]))
     ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
     with torch.cuda.device(dev):
-        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+        _islands(edge_index, e, n, slack, islands)
         L.check(lib.pfn_contingency_dc(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
                                        int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
                                        int(max_iter), _ROUTES[route], out["severity"].data_ptr(), out["worst_line"].data_ptr(),
@@ -312,7 +328,7 @@ def _screen_sparse(bus_type, spec, edge_index, rx, ratings, tol, max_iter, keep_
         need = int(lib.pfn_contingency_sparse_workspace_bytes(S, e, header, _BLOCKS[block], g)) if S else 0
         in_lds = block != "global" and (not S or need == int(lib.pfn_contingency_sparse_workspace_bytes(S, e, header, 1, g)))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
+        _islands(edge_index, e, n, slack, islands)
         L.check(lib.pfn_contingency_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
                                            int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, float(tol),
                                            int(max_iter), out["severity"].data_ptr(), out["worst_line"].data_ptr(), out["overloads"].data_ptr(),
@@ -685,8 +701,7 @@ class _ModelScreenStep:
         else:
             self.bt, self.spec, self.ei, self.rx, self.ratings = bt, spec, ei, rx, ratings
         self.flags.zero_()
-        L.check(L.load().pfn_contingency_islands(self.ei.data_ptr(), self.e, self.n, slack, self.islands.data_ptr(), L.stream_ptr()),
-                "pfn_contingency_islands")
+        _islands(self.ei, self.e, self.n, slack, self.islands)
 
     def chunk(self, item0):
         """the three steps of the chunk whose first item the device word `item0` holds"""
@@ -927,34 +942,22 @@ def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, varia
         waves = int(lib.pfn_contingency_ac_waves(n, n_pq, _ROUTES[route], 0 if group is None else group, C.byref(in_lds)))
         if waves == 0:
             raise RuntimeError(f"{who}: route {route!r} with group {group!r}: the two inverses of {n} buses and the waves' vectors do not fit LDS")
-    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)      # noqa: E731
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)        # noqa: E731
-    out = dict(severity=f32(S, e), worst_line=i32(S, e), overloads=i32(S, e), vm_min=f32(S, e), vm_min_bus=i32(S, e), v_violations=i32(S, e),
-               mismatch=torch.empty(S, e, dtype=torch.float64, device=dev), base_table=torch.empty(S, n, 4, dtype=torch.float64, device=dev),
-               status=i32(S), residual=torch.empty(S, dtype=torch.float64, device=dev), post_current=f32(S, e, e) if keep_table else None,
-               post_state=f32(S, e, n, 2) if keep_state else None, flags=torch.zeros(1, dtype=torch.int32, device=dev))
+    out = _outputs_ac(S, n, e, dev, keep_table, keep_state)
     islands = torch.empty(e, dtype=torch.int32, device=dev)
-    order = ("severity", "worst_line", "overloads", "vm_min", "vm_min_bus", "v_violations", "mismatch", "base_table", "status", "residual",
-             "post_current", "post_state", "flags")
-    if sparse:
-        with torch.cuda.device(dev):                                          # (the default `groups` asks the current device for its compute units)
+    with torch.cuda.device(dev):                                              # (sparse: the default `groups` asks the current device for its compute units)
+        if sparse:
+            entry, name = lib.pfn_contingency_ac_sparse, "pfn_contingency_ac_sparse"
             need = int(lib.pfn_contingency_ac_sparse_workspace_bytes(S, e, header, _BLOCKS[block], g)) if S else 0
-            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-            L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
-            L.check(lib.pfn_contingency_ac_sparse(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),
-                                                  int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq,
-                                                  _VARIANTS[variant], halves, lo, hi, float(tol), int(max_iter), header, plan.blob.data_ptr(),
-                                                  0 if threads is None else threads, _BLOCKS[block], g, *[L.ptr(out[k]) for k in order],
-                                                  ws.data_ptr(), need, L.stream_ptr()),
-                    "pfn_contingency_ac_sparse")
-        return ACContingencyResult(islands=islands, route="sparse", group=0, block="lds" if in_lds.value else "global", **out)
-    need = int(lib.pfn_contingency_ac_workspace_bytes(S, n, e, n_pq))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(lib.pfn_contingency_islands(edge_index.data_ptr(), e, n, slack, islands.data_ptr(), L.stream_ptr()), "pfn_contingency_islands")
-        L.check(lib.pfn_contingency_ac(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),
-                                       int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, _VARIANTS[variant],
-                                       halves, lo, hi, float(tol), int(max_iter), _ROUTES[route], 0 if group is None else group,
-                                       *[L.ptr(out[k]) for k in order], ws.data_ptr(), need, L.stream_ptr()),
-                "pfn_contingency_ac")
-    return ACContingencyResult(islands=islands, route="lds" if in_lds.value else "global", group=waves, **out)
+            middle = (header, plan.blob.data_ptr(), 0 if threads is None else threads, _BLOCKS[block], g)
+            placed = dict(route="sparse", group=0, block="lds" if in_lds.value else "global")
+        else:
+            entry, name = lib.pfn_contingency_ac, "pfn_contingency_ac"
+            need = int(lib.pfn_contingency_ac_workspace_bytes(S, n, e, n_pq))
+            middle = (_ROUTES[route], 0 if group is None else group)
+            placed = dict(route="lds" if in_lds.value else "global", group=waves)
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        _islands(edge_index, e, n, slack, islands)
+        L.check(entry(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(init), L.ptr(ratings),
+                      int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, _VARIANTS[variant], halves, lo, hi,
+                      float(tol), int(max_iter), *middle, *[L.ptr(t) for t in out.values()], ws.data_ptr(), need, L.stream_ptr()), name)
+    return ACContingencyResult(islands=islands, **placed, **out)
