@@ -31,6 +31,15 @@ the AC-verified severity side by side, how often each screen names the AC worst 
 results/<case>_contingency_ac_{severity,worst_line,overloads,vm_min,vm_min_bus,v_violations,mismatch}.npy.  Where the DC screen takes
 the sparse route -- beyond the dense cap by itself, anywhere with --route sparse -- so does the AC screen, under one
 `sparse_plan(mode="fd")` built beside the DC plan.
+
+--units [--unit-lines K] [--participation {slack,output}] adds the generator outages (`contingency_screen_units`, the dense routes
+only): the units are the PV buses, each losing max(-P, 0) of its scenario; `slack` lets the slack pick the lost output up, `output`
+shares it among the other units in proportion to their own output (a = unit_p).  --unit-lines K also screens every unit followed by
+a line outage, the lines being the union over the scenarios of each scenario's top-K non-islanding single outages.  It prints every
+scenario's top unit outages -- and unit x line items where asked -- DC beside AC-verified (`verify_unit_contingencies`: the bus
+types stay, so a PV bus keeps its voltage support) and writes
+results/<case>_contingency_units_{units,unit_p,severity,worst_line,overloads}.npy and, with --unit-lines,
+results/<case>_contingency_units_{lines,islands,line_severity,line_worst_line,line_overloads}.npy.
 """
 import argparse
 import os
@@ -72,6 +81,10 @@ def main(argv=None):
     ap.add_argument("--cfg_json", default="configs/standard.json", help="--model-run-id: the network's hidden_dim, n_gnn_layers, K")
     ap.add_argument("--ac", action="store_true", help="also screen under AC by compensated 1P1Q (contingency_screen_ac) on the route of the DC screen")
     ap.add_argument("--halves", type=int, default=2, help="--ac: fast-decoupled half-iterations per outage (2: 1P1Q, 4: 2P2Q)")
+    ap.add_argument("--units", action="store_true", help="also screen the outage of every unit (the PV buses) under DC (contingency_screen_units)")
+    ap.add_argument("--unit-lines", type=int, default=0, help="--units: every unit followed by each of every scenario's top K non-islanding line outages")
+    ap.add_argument("--participation", default="slack", choices=("slack", "output"),
+                    help="--units: who picks the lost output up -- the slack, or the other units in proportion to their output")
     a = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
@@ -116,7 +129,49 @@ def main(argv=None):
         screen_model(a, islands, bt, spec, ei, rx, ratings, solver_kw)
     if a.ac:
         screen_ac(a, res, islands, bt, spec, ei, rx, ratings, solver_kw, sparse=kw["route"] == "sparse")
+    if a.units:
+        screen_units(a, res, islands, bt, spec, ei, rx, ratings, kw)
     return 0
+
+
+def screen_units(a, res, islands, bt, spec, ei, rx, ratings, kw):
+    """--units: the generator outages of the same scenarios with the same ratings on the N-1 screen's dense route, with --unit-lines
+    followed by the worst single line outages; DC beside AC-verified, and the result files"""
+    from poweflownet_amd.utils.contingency import contingency_screen_units, verify_unit_contingencies
+    if kw["route"] == "sparse":
+        raise SystemExit("contingency.py --units: the sparse route of the unit screen is not built; this case is beyond the dense cap")
+    if a.unit_lines < 0:
+        raise SystemExit("contingency.py --units: --unit-lines must be >= 0")
+    S, e = int(spec.shape[0]), int(ei.shape[1])
+    lines = None
+    if a.unit_lines:
+        order = res.ranking(e)[0].cpu().numpy()
+        lines = sorted({int(k) for s in range(S) for k in [k for k in order[s] if islands[k] == 0][:a.unit_lines]}) or None
+    first = contingency_screen_units(bt, spec, ei, rx, ratings, route=kw["route"])      # (units=None: the PV buses; unit_p=None: max(-P, 0))
+    part = first.unit_p.contiguous() if a.participation == "output" else None
+    got = first if part is None and lines is None else contingency_screen_units(bt, spec, ei, rx, ratings, participation=part, lines=lines,
+                                                                                   route=kw["route"])
+    units = got.units.cpu().numpy()
+    G = len(units)
+    print(f"units: {G} PV buses x {S} scenarios on the {got.route} route, lost output picked up by "
+          f"{'the slack' if part is None else 'the other units in proportion to their output'}"
+          + (f"; {len(lines)} lines (top {a.unit_lines} of every scenario) behind every unit" if lines else ""))
+    ver = verify_unit_contingencies(got, bt, spec, ei, rx, ratings, top=min(a.verify_top, G))
+    items, dc, ac, status = ver.items.cpu().numpy(), ver.dc_severity.cpu().numpy(), ver.severity.cpu().numpy(), ver.status.cpu().numpy()
+    ac_worst = ver.worst_line.cpu().numpy()
+    for s in range(S):
+        for lined, label in ((False, "units"), (True, "unit x line")):
+            rows = [f"bus {units[items[t, 1]]}" + (f"+line {items[t, 2]}" if lined else "") + f": DC {dc[t]:.3f} "
+                    f"AC {'failed' if status[t] < 0 else format(ac[t], '.3f')} worst line {ac_worst[t]}"
+                    for t in np.flatnonzero((items[:, 0] == s) & ((items[:, 2] >= 0) == lined))]
+            if rows:
+                print(f"scenario {s} {label}: " + "; ".join(rows))
+    solved = status >= 0
+    print(f"{len(items)} unit items verified, {int((~solved).sum())} AC solves failed; "
+          f"{int((solved & (dc < 1) & (ac > 1)).sum())} of {int((solved & (dc < 1)).sum())} the DC unit screen called secure are overloaded under AC")
+    names = ["units", "unit_p", "severity", "worst_line", "overloads"] + (["lines", "islands", "line_severity", "line_worst_line", "line_overloads"] if lines else [])
+    for name in names:
+        np.save(os.path.join(a.out_dir, f"case{a.case}_contingency_units_{name}.npy"), getattr(got, name).cpu().numpy())
 
 
 def screen_ac(a, dc_res, islands, bt, spec, ei, rx, ratings, solver_kw, sparse=False):

@@ -876,6 +876,54 @@ int pfn_contingency_pairs(const int64_t* edge_index, int64_t n_lines, const doub
                           int route, float* severity, int32_t* worst_line, int32_t* overloads, double* base_flow, int32_t* status,
                           float* post_flow, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* Generator outages, alone and followed by a line outage (csrc/contingency_units.hip): the dense DC route only
+ * (n_bus - 1 <= pfn_powerflow_max_unknowns(); the sparse route is not built).  ONE launch, one workgroup per scenario (256 threads up
+ * to 90 unknowns, 1024 beyond), behind pfn_contingency_islands where candidate lines are given; no host sync, no allocation
+ * (capturable), no float atomics.  Inputs, model, X, base flows, ratings and statuses are pfn_contingency_dc's; added to them:
+ *   units          DEVICE int32 [n_units], the bus of every unit: any bus type, the slack's included; a bus may appear more than once
+ *                  (several units at one bus).  An id outside [0, n_bus) is never followed: EVERY scenario gets status -4.
+ *   unit_p         DEVICE fp64 [n_units] (unit_p_per_sample == 0) or [n_samples, n_units]: the output lost with the unit,
+ *                  generation-positive per-unit.
+ *   participation  DEVICE fp64 [n_units] / [n_samples, n_units], a_h >= 0, or null: all zero (the slack picks up everything).
+ *   lines          DEVICE int32 [n_candidates], strictly increasing ids in [0, n_lines), or null with n_candidates == 0: the unit x line
+ *                  part.  islands: pfn_contingency_islands' output [n_lines] (read at the candidates only; null without candidates).
+ * With c_g = X[:, b_g], A = sum_h a_h (fp64, stored order, one owner), rest_g = A - a_g (one fp64 subtraction) and the pickup vector
+ * u = sum_h a_h c_h (fp32, once per scenario), the outage of unit g changes the generation-positive injection by -p_g at b_g and, if
+ * rest_g > 0, by +p_g a_h / rest_g at b_h for every h != g (otherwise by nothing more: the slack absorbs p_g).  The angle change:
+ *     d_g = p_g ((u - a_g c_g) / rest_g - c_g)   (rest_g > 0)        d_g = -p_g c_g   (otherwise)
+ * evaluated as d_g = alpha_g u - beta_g c_g with alpha_g = p_g / rest_g and beta_g = p_g (a_g / rest_g + 1) formed in fp64 and rounded
+ * once to fp32 (alpha_g = 0, beta_g = p_g otherwise), then per stored line l = (a -> b)
+ *     f_l^(g) = f_l + (d_g[a] - d_g[b]) / x_l                                       -- fp32, every operation rounded on its own;
+ * all n_lines lines are monitored, none is out.  p_g = 0 is an ordinary item whose flows are the base flows.
+ * Unit x line (g, k), k = lines[j]: line k leaves the post-unit state,
+ *     f_l^(g,k) = f_l^(g) + phi_{l,k} / den_k * f_k^(g)  (l != k),   0 at k          -- pfn_contingency_dc's phi, den and expression;
+ * monitored are the lines l != k with a rating > 0; islands[k] != 0 gives (+inf, -1, -1) and a NaN row, never decided from den.
+ *   severity, worst_line, overloads   [n_samples, n_units], pfn_contingency_dc's figures and rules; post_flow fp32
+ *                  [n_samples, n_units, n_lines] or null.
+ *   line_severity, line_worst_line, line_overloads   [n_samples, n_units, n_candidates]; line_post_flow fp32
+ *                  [n_samples, n_units, n_candidates, n_lines] or null.  All four may be null with n_candidates == 0.
+ *   base_flow, status   pfn_contingency_dc's BITS for the same inputs (the same base solve) where the unit inputs are good.  In
+ *                  addition status -3 where a unit_p is not finite or a participation entry is not both finite and >= 0, and -4 as
+ *                  above; a status the base solve set stands.  A failed scenario's float outputs are NaN and its integer outputs -1;
+ *                  it touches nothing of another scenario.
+ *   route          0 auto, 1 LDS, 2 global, as pfn_contingency_dc: the unit screen's own vectors (24 n_units + 8 n_bus + 4 n_lines
+ *                  bytes, rounded up to 16) sit between that screen's vectors and X.  pfn_contingency_units_workspace_bytes(n_samples,
+ *                  n_bus, n_lines, n_units, route) is what the call needs: 0 exactly for the LDS route, else a slab of 4 m (m | 1) bytes
+ *                  (rounded up to 16, m = n_bus - 1) per scenario.
+ * A scenario's bits are a function of its own inputs, whatever the batch, the workgroup size, the route, the tables or the candidate
+ * lines: the unit figures are the same bits with and without lines.  PFN_EINVAL: bad sizes or counts (n_units < 1, more candidates
+ * than lines), more unknowns than the dense cap, vectors beyond LDS, route 1 where it does not fit, null or misaligned pointers;
+ * PFN_ENOSPACE: too little ws.  n_samples == 0 or n_lines == 0: PFN_OK, nothing is launched and NO output is written, as in
+ * pfn_contingency_dc (a grid without lines has no flow to report; contingency_screen_units refuses it on the host).                 */
+size_t pfn_contingency_units_workspace_bytes(int64_t n_samples, int64_t n_bus, int64_t n_lines, int64_t n_units, int route);
+int pfn_contingency_units(const int64_t* edge_index, int64_t n_lines, const double* rx, const int32_t* bus_type, const double* spec,
+                          const double* ratings, int ratings_per_sample, const int32_t* units, int64_t n_units, const double* unit_p,
+                          int unit_p_per_sample, const double* participation, int participation_per_sample, const int32_t* lines,
+                          int64_t n_candidates, const int32_t* islands, int64_t n_samples, int64_t n_bus, int64_t n_pv, int64_t n_pq,
+                          double tol, int max_iter, int route, float* severity, int32_t* worst_line, int32_t* overloads, double* base_flow,
+                          int32_t* status, float* post_flow, float* line_severity, int32_t* line_worst_line, int32_t* line_overloads,
+                          float* line_post_flow, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* The same screen beyond the dense cap (csrc/contingency_sparse.hip): B' is kept as a sparse fp32 FACTOR under the mode-1 plan of the
  * sparse power-flow route (pfn_powerflow_sparse_plan(..., mode 1, ...): plan_header its first 32 words on the host, plan_dev the blob
  * on the device) where pfn_contingency_dc keeps its inverse.  Model, definitions, outputs and statuses are pfn_contingency_dc's, and

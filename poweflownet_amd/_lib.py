@@ -46,6 +46,7 @@ SYMBOLS = (
     "pfn_contingency_model_lds_max_bus", "pfn_contingency_model_batch", "pfn_contingency_model_loadings",
     "pfn_contingency_ac_workspace_bytes", "pfn_contingency_ac_waves", "pfn_contingency_ac",
     "pfn_contingency_ac_sparse_block_bytes", "pfn_contingency_ac_sparse_workspace_bytes", "pfn_contingency_ac_sparse",
+    "pfn_contingency_units_workspace_bytes", "pfn_contingency_units",
 )
 
 # enum pfn_eval_term (include/pfn_hip.h), in order: the fp32 batch terms of pfn_eval_metrics
@@ -217,6 +218,9 @@ def load() -> C.CDLL:
         "pfn_contingency_ac_sparse_workspace_bytes": (sz, [i64, i64, p, C.c_int, C.c_int]),
         "pfn_contingency_ac_sparse": (C.c_int, [p, i64, p, p, p, p, p, C.c_int, p, i64, i64, i64, i64, C.c_int, C.c_int, f32, f32, C.c_double,
                                                 C.c_int, p, p, C.c_int, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p, p, p, p, p, sz, p]),
+        "pfn_contingency_units_workspace_bytes": (sz, [i64, i64, i64, i64, C.c_int]),
+        "pfn_contingency_units": (C.c_int, [p, i64, p, p, p, p, C.c_int, p, i64, p, C.c_int, p, C.c_int, p, i64, p, i64, i64, i64, i64,
+                                            C.c_double, C.c_int, C.c_int, p, p, p, p, p, p, p, p, p, p, p, p, sz, p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch

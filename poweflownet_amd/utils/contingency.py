@@ -17,7 +17,12 @@ islands): the fast-decoupled base solve of `solve_power_flow(mode="fdxb" | "fdbx
 takes `halves` half-iterations with B'^-1 and B''^-1 corrected for the missing line by a rank-1 update, and reports the loadings
 from line currents together with the lowest voltage, the voltage violations and the remaining mismatch; beyond the dense cap
 `route="sparse"` with a `sparse_plan(..., mode="fd")` runs the same screen on the sparse fp32 factors of B' and B''
-(csrc/contingency_ac_sparse.hip: `pfn_contingency_ac_sparse`), a lane per outage, 64 outages to a one-wave workgroup.  No CPU path."""
+(csrc/contingency_ac_sparse.hip: `pfn_contingency_ac_sparse`), a lane per outage, 64 outages to a one-wave workgroup.
+`contingency_screen_units` screens GENERATOR outages under the DC model on the dense routes (csrc/contingency_units.hip:
+`pfn_contingency_units`, one launch, one workgroup per scenario): a unit outage changes the right-hand side only, so the resident
+inverse answers it with one column, the lost output picked up by the slack or shared among the other units by participation
+factors; with `lines` every unit outage is followed by each candidate line outage (distribution factors on the post-unit flows,
+the islands launch first).  `verify_unit_contingencies` is its AC check on the shifted specification.  No CPU path."""
 import contextlib
 import ctypes as C
 import operator
@@ -961,3 +966,284 @@ def contingency_screen_ac(bus_type, spec, edge_index, rx, ratings=None, *, varia
                       int(ratings is not None and ratings.dim() == 2), islands.data_ptr(), S, n, n_pv, n_pq, _VARIANTS[variant], halves, lo, hi,
                       float(tol), int(max_iter), *middle, *[L.ptr(t) for t in out.values()], ws.data_ptr(), need, L.stream_ptr()), name)
     return ACContingencyResult(islands=islands, **placed, **out)
+
+
+# ================================================================================ generator outages, alone and with a line outage
+_UNITS_KEPT = {}  # (device, unit tuple) -> int32 [G] on the device: a capture after its eager call uploads nothing
+
+
+@dataclass
+class UnitContingencyResult:
+    """`contingency_screen_units`' answer.  `units` [G] int64: the bus of every unit; `unit_p` [S, G] float64: the output each outage
+    removes; `participation` [G] / [S, G] float64 or None as the call took it.  Per (scenario s, unit g): `severity` [S, G] float32,
+    `worst_line` [S, G] int32 and `overloads` [S, G] int32 by `ContingencyResult`'s rules with ALL lines monitored (NaN, -1, -1 where
+    the scenario failed).  `base_flow` [S, e] float64 and `status` [S] int32 carry `contingency_screen`'s bits for the same inputs
+    where the unit inputs are good; status -3 also where a `unit_p` is not finite or a participation factor is not finite and >= 0.
+    `post_flow` [S, G, e] float32 with `keep_table`, else None.  With `lines`: `lines` [c] int64, `islands` [c] int32 (buses the outage
+    of candidate line j cuts off the slack), and per (s, g, candidate j) `line_severity` [S, G, c] float32, `line_worst_line`,
+    `line_overloads` [S, G, c] int32 (+inf, -1, -1 where the line islands buses) and `line_post_flow` [S, G, c, e] float32 with
+    `keep_table`; without: all None.  `flags` [1] int32 (bit 0: `bus_type` changed under the launch).  All on the device, nothing
+    read back; `route`: "lds" or "global"."""
+    units: torch.Tensor
+    unit_p: torch.Tensor
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    base_flow: torch.Tensor
+    status: torch.Tensor
+    post_flow: object
+    route: str
+    lines: object = None
+    islands: object = None
+    line_severity: object = None
+    line_worst_line: object = None
+    line_overloads: object = None
+    line_post_flow: object = None
+    participation: object = None
+    flags: object = None
+
+    def ranking(self, top):
+        """(int64 [S, top] unit positions g, [S, top] their severities): `ContingencyResult.ranking`'s order -- NaN first, then
+        +inf, then descending, ties to the lowest position."""
+        return _rank(self.severity, top, "ranking")
+
+    def line_ranking(self, top):
+        """(int64 [S, top, 2] (unit position g, line id k), [S, top] their severities) over the unit x line items, in the same
+        order; ties to the lowest (g, candidate) in row-major order."""
+        if self.line_severity is None:
+            raise ValueError("line_ranking: the screen ran without lines")
+        S, G, c = self.line_severity.shape
+        order, sev = _rank(self.line_severity.reshape(S, G * c), top, "line_ranking")
+        return torch.stack([order // max(c, 1), self.lines[order % max(c, 1)]], dim=2), sev
+
+
+@dataclass
+class UnitContingencyVerification:
+    """`items` [T, 3] int64 (scenario, unit position g, line id k or -1 for the unit alone), the AC `table` [T, n, 4] float64 and
+    `status` [T] int32 of `solve_power_flow` on the shifted specification (without line k where k >= 0), `loading` [T, e] float32 =
+    I_l / rating_l in the ORIGINAL line numbering (NaN at the outaged line), `severity` / `worst_line` / `overloads` by the screen's
+    rules, and `dc_severity` [T] float32, the screen's figure for the item."""
+    items: torch.Tensor
+    table: torch.Tensor
+    status: torch.Tensor
+    loading: torch.Tensor
+    severity: torch.Tensor
+    worst_line: torch.Tensor
+    overloads: torch.Tensor
+    dc_severity: torch.Tensor
+
+
+def _host_units(units, n, who):
+    """the unit buses as a list of ints, checked on the host: a host sequence or a CPU int64 vector of at least one id, each within
+    [0, n) where n is known"""
+    if isinstance(units, (int, str, bytes)):                                  # (a bare count means nothing here; bool is an int)
+        raise ValueError(f"{who}: units must be a sequence of bus ids; got {units!r}")
+    if torch.is_tensor(units):
+        if units.device.type != "cpu" or units.dtype != torch.int64 or units.dim() != 1:
+            raise ValueError(f"{who}: units as a tensor must be a CPU int64 vector; got {units.dtype} {tuple(units.shape)} on {units.device}")
+        got = units.tolist()
+    else:
+        got = list(units)
+        try:
+            if any(isinstance(b, bool) for b in got):
+                raise TypeError
+            got = [operator.index(b) for b in got]                            # (numpy integers too)
+        except TypeError:
+            raise ValueError(f"{who}: units must be ints, the bus of every unit; got {got!r}") from None
+    if len(got) < 1:
+        raise ValueError(f"{who}: at least one unit is needed; got none")
+    if min(got) < 0 or (n is not None and max(got) >= n):
+        raise ValueError(f"{who}: units must lie within [0, {n}); got {min(got)} .. {max(got)}")
+    return got
+
+
+def _device_units(units, dev):
+    key = (str(dev), tuple(units))
+    got = _UNITS_KEPT.get(key)
+    if got is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("contingency_screen_units: the units are uploaded once per list; call it eagerly once before capturing")
+        if len(_UNITS_KEPT) >= 16:
+            _UNITS_KEPT.pop(next(iter(_UNITS_KEPT)))
+        got = _UNITS_KEPT[key] = torch.tensor(units, dtype=torch.int32).to(dev)
+    return got
+
+
+def _per_unit(t, S, G, name, who, dev):
+    """a per-unit float64 input, [G] or [S, G] on the inputs' device: (contiguous tensor, per-scenario flag)"""
+    L.require_device(t, what=f"{who} {name}")
+    if t.dtype != torch.float64 or tuple(t.shape) not in ((G,), (S, G)) or t.device != dev:
+        raise RuntimeError(f"{who}: {name} must be float64 ({G},) or ({S}, {G}) on {dev}; got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous(), int(t.dim() == 2)
+
+
+def contingency_screen_units(bus_type, spec, edge_index, rx, ratings=None, *, units=None, unit_p=None, participation=None, lines=None,
+                             tol=1e-8, max_iter=10, route="auto", keep_table=False) -> UnitContingencyResult:
+    """Screen every generator outage of every scenario under the DC model, alone and -- with `lines` -- followed by a line outage:
+    inputs and their checks are `contingency_screen`'s.  `units`: the bus of every unit, a host sequence or a CPU int64 tensor of
+    G >= 1 ids within [0, n) (checked on the host; ValueError otherwise); any bus type, the slack included, and a bus may appear more
+    than once (several units at one bus); None: the PV buses, ascending (formed on the device).  `unit_p`: float64 [G] or [S, G] on
+    the device, the output lost with the unit, generation-positive per-unit; None: max(-spec[s, units, 2], 0), formed on the device.
+    `participation`: float64 [G] or [S, G], a_h >= 0: the other units pick the lost output up in proportion a_h / (A - a_g); None (or
+    where A - a_g is not > 0): the slack absorbs it.  `lines`: None (units only), "all", or strictly increasing line ids within
+    [0, e) (a host sequence or a CPU int64 tensor; `contingency_screen_pairs`' rule): the items (unit g, then line k out of the
+    post-unit state).  All e lines are monitored for a unit outage, all but k for (g, k).  `route`: "auto", "lds" (raises where
+    B'^-1 does not fit LDS beside the vectors) or "global"; the same bits.  This is the dense route: `route="sparse"` and grids
+    beyond `max_unknowns()` raise -- the sparse route is not built.  One launch (two with `lines`: the islands launch first); one
+    host read (the bus_type counts, once per tensor); nothing is read back."""
+    who = "contingency_screen_units"
+    if route == "sparse":
+        raise ValueError(f"{who}: route 'sparse' is not built; the unit screen runs on the dense routes {sorted(_ROUTES)} only")
+    if route not in _ROUTES:
+        raise ValueError(f"{who}: route must be one of {sorted(_ROUTES)}")
+    if not isinstance(keep_table, bool):
+        raise ValueError(f"{who}: keep_table must be a bool; got {keep_table!r}")
+    n_given = int(spec.shape[1]) if torch.is_tensor(spec) and spec.dim() == 3 else None
+    e_given = int(edge_index.shape[1]) if torch.is_tensor(edge_index) and edge_index.dim() == 2 else None
+    if units is not None:                                                     # on the host, before anything touches the library
+        units = _host_units(units, n_given, who)
+    every_line = isinstance(lines, str)
+    if every_line:
+        if lines != "all":
+            raise ValueError(f"{who}: lines must be None, 'all' or line ids; got {lines!r}")
+    elif lines is not None:
+        lines = _candidates(lines, who)
+        if len(lines) < 1:
+            raise ValueError(f"{who}: lines needs at least one candidate line; got none (None: no unit x line part)")
+        if any(b <= a for a, b in zip(lines, lines[1:])):
+            raise ValueError(f"{who}: lines must be strictly increasing (sorted, no duplicates)")
+        if lines[0] < 0 or (e_given is not None and lines[-1] >= e_given):
+            raise ValueError(f"{who}: lines must lie within [0, {e_given}); got {lines[0]} .. {lines[-1]}")
+
+    def dense_only(n, e):
+        cap = int(L.load().pfn_powerflow_max_unknowns())
+        if n - 1 > cap:
+            raise ValueError(f"{who}: {n - 1} unknowns per scenario exceed the dense screen's {cap} (max_unknowns()); the sparse route is not built")
+    S, n, e, (n_pv, n_pq, slack), bt, spec, edge_index, rx, ratings = _prepare(who, bus_type, spec, edge_index, rx, ratings, after_check=dense_only)
+    dev, lib = spec.device, L.load()
+    if units is None:
+        if n_pv < 1:
+            raise ValueError(f"{who}: units=None means the PV buses, and this grid has none")
+        units_d = torch.sort((bt != 1).to(torch.int8), stable=True).indices[:n_pv].to(torch.int32)    # the PV buses, ascending: no read-back
+    else:
+        units_d = _device_units(units, dev)
+    G = int(units_d.shape[0])
+    if unit_p is None:
+        unit_p, p_each = torch.clamp(-spec[:, units_d.long(), 2], min=0.0).contiguous(), 1
+    else:
+        unit_p, p_each = _per_unit(unit_p, S, G, "unit_p", who, dev)
+    part, a_each = (None, 0) if participation is None else _per_unit(participation, S, G, "participation", who, dev)
+    if every_line:
+        c, lines_d = e, torch.arange(e, dtype=torch.int32, device=dev)
+    elif lines is not None:
+        c, lines_d = len(lines), _device_lines(lines, dev)[0]
+    else:
+        c, lines_d = 0, None
+    out = _outputs(S, e, G, dev, keep_table)
+    new = lambda dtype, *shape: torch.empty(*shape, dtype=dtype, device=dev)  # noqa: E731
+    line_out = dict(line_severity=None, line_worst_line=None, line_overloads=None, line_post_flow=None)
+    islands = None
+    if c:
+        islands = new(torch.int32, e)
+        line_out = dict(line_severity=new(torch.float32, S, G, c), line_worst_line=new(torch.int32, S, G, c),
+                        line_overloads=new(torch.int32, S, G, c), line_post_flow=new(torch.float32, S, G, c, e) if keep_table else None)
+    need = int(lib.pfn_contingency_units_workspace_bytes(S, n, e, G, _ROUTES[route]))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    with torch.cuda.device(dev):
+        if c:
+            _islands(edge_index, e, n, slack, islands)
+        L.check(lib.pfn_contingency_units(edge_index.data_ptr(), e, rx.data_ptr(), bt.data_ptr(), spec.data_ptr(), L.ptr(ratings),
+                                          int(ratings is not None and ratings.dim() == 2), units_d.data_ptr(), G, unit_p.data_ptr(), p_each,
+                                          L.ptr(part), a_each, L.ptr(lines_d), c, L.ptr(islands), S, n, n_pv, n_pq, float(tol), int(max_iter),
+                                          _ROUTES[route], out["severity"].data_ptr(), out["worst_line"].data_ptr(), out["overloads"].data_ptr(),
+                                          out["base_flow"].data_ptr(), out["status"].data_ptr(), L.ptr(out["post_flow"]),
+                                          *[L.ptr(line_out[k]) for k in ("line_severity", "line_worst_line", "line_overloads", "line_post_flow")],
+                                          out["flags"].data_ptr(), L.ptr(ws), need, L.stream_ptr()),
+                "pfn_contingency_units")
+    if c:
+        line_out.update(lines=lines_d.long(), islands=islands[lines_d.long()])
+    return UnitContingencyResult(units=units_d.long(), unit_p=unit_p if p_each else unit_p.expand(S, G), route="global" if need else "lds",
+                                 participation=part, **out, **line_out)
+
+
+def unit_outage_spec(spec, units, unit_p, participation, g):
+    """`spec` [T, n, 4] with the outage of the unit at position g[t] written into the demand-positive P column of row t, by the
+    definition of include/pfn_hip.h: P rises by p_g at the unit's bus and, where rest_g = A - a_g > 0, falls by p_g a_h / rest_g at
+    the bus of every other unit h (several units of one bus add up, in stored order).  `units` [G] int64, `unit_p` [T, G], `participation` [T, G] or
+    None, `g` [T] int64, all on `spec`'s device.  Returns a new tensor."""
+    T, G = int(unit_p.shape[0]), int(units.shape[0])
+    rows = torch.arange(T, device=spec.device)
+    p = unit_p[rows, g]                                                        # [T]
+    shift = torch.zeros(T, G, dtype=torch.float64, device=spec.device)
+    if participation is not None:
+        a = participation.expand(T, G)
+        A = torch.zeros(T, dtype=torch.float64, device=spec.device)
+        for h in range(G):                                                     # (A in stored order, as the kernel sums it)
+            A = A + a[:, h]
+        rest = A - a[rows, g]
+        share = torch.where((rest > 0)[:, None], -p[:, None] * a / torch.where(rest > 0, rest, torch.ones_like(rest))[:, None], shift)
+        share[rows, g] = 0.0
+        shift = share
+    shift[rows, g] = p
+    out = spec.clone()
+    for h, b in enumerate(units.tolist()):                                    # stored order, one addition each: the same bits every time
+        out[:, b, 2] += shift[:, h]
+    return out
+
+
+def verify_unit_contingencies(result, bus_type, spec, edge_index, rx, ratings=None, *, top=5, items=None,
+                              **solver_kw) -> UnitContingencyVerification:
+    """AC check of chosen items of a `contingency_screen_units` result (same inputs): `items` -- rows (scenario, unit position g) or
+    (scenario, g, line id k), k among the screen's lines (ValueError otherwise) -- or per scenario the `top` unit outages of
+    `result.ranking` and, where the screen had lines, the `top` items of `result.line_ranking`; items whose line islands buses are
+    skipped.  For every item `spec` is shifted by the outage (`unit_outage_spec`: the screen's `unit_p` and `participation`), line k
+    is removed where there is one, the unchanged `solve_power_flow(mode="ac", **solver_kw)` solves, `loss.branch_flows` gives the
+    line currents, and the loadings go back to the original line numbering.  THE BUS TYPES STAY AS THEY ARE: a PV bus that loses
+    its unit keeps its voltage set point, i.e. its reactive support -- converting a bus that lost its only unit to PQ is not built.
+    The rows are chosen on the host (T is small)."""
+    who = "verify_unit_contingencies"
+    S, n, e = _check(bus_type, spec, edge_index, rx, who)
+    ratings = _ratings(ratings, S, e, who)
+    dev = spec.device
+    G = int(result.units.shape[0])
+    held = [] if result.lines is None else result.lines.cpu().tolist()
+    isl = [] if result.islands is None else result.islands.cpu().tolist()
+    where = {k: j for j, k in enumerate(held)}
+    if items is None:
+        if isinstance(top, bool) or not isinstance(top, int) or top < 0:
+            raise ValueError(f"{who}: top must be an int >= 0; got {top!r}")
+        order = result.ranking(min(top, G))[0].cpu().tolist()
+        chosen = [(s, g, -1) for s in range(S) for g in order[s]]
+        if held:
+            pairs = result.line_ranking(G * len(held))[0].cpu().tolist()
+            chosen += [(s, g, k) for s in range(S) for g, k in [gk for gk in pairs[s] if isl[where[gk[1]]] == 0][:top]]
+    else:
+        chosen = []
+        for row in (items.tolist() if torch.is_tensor(items) else items):
+            row = tuple(int(v) for v in row)
+            s, g, k = row if len(row) == 3 else row + (-1,)
+            if not (0 <= s < S and 0 <= g < G) or (k != -1 and k not in where):
+                raise ValueError(f"{who}: {row} is no (scenario, unit[, line]) of this screen ({S} scenarios, {G} units, lines {held})")
+            if k == -1 or isl[where[k]] == 0:
+                chosen.append((s, g, k))
+    alone = [it for it in chosen if it[2] < 0]
+    lined = [it for it in chosen if it[2] >= 0]
+    parts = []
+    for group, K in [(grp, K) for grp, K in ((alone, 0), (lined, 1)) if grp] or [(alone, 0)]:
+        rows = torch.tensor(group, dtype=torch.int64, device=dev).reshape(-1, 3)
+        T = int(rows.shape[0])
+        sc, g = rows[:, 0], rows[:, 1]
+        part = None if result.participation is None else result.participation.expand(S, G)[sc]
+        shifted = unit_outage_spec(spec[sc], result.units, result.unit_p[sc], part, g)
+        rate = None if ratings is None else (ratings if ratings.dim() == 1 else ratings[sc].contiguous())
+        solved, loading, severity, worst, overloads = _verify_removed(bus_type, shifted, edge_index, rx[sc].contiguous(), rate, T, e,
+                                                                      torch.arange(T, device=dev), rows[:, 2:2 + K], dict(solver_kw))
+        if K:
+            pos = torch.tensor([where[k] for _, _, k in group], dtype=torch.int64, device=dev)
+            dc = result.line_severity[sc, g, pos]
+        else:
+            dc = result.severity[sc, g]
+        parts.append((rows, solved.table, solved.status, loading, severity, worst, overloads, dc))
+    cat = [torch.cat(col, dim=0) for col in zip(*parts)]
+    return UnitContingencyVerification(items=cat[0], table=cat[1], status=cat[2], loading=cat[3], severity=cat[4], worst_line=cat[5],
+                                       overloads=cat[6], dc_severity=cat[7])

@@ -68,7 +68,17 @@ launch apart (the library's event brackets, a pass of their own; `dominant_launc
 same child -- the path it replaces, `solve_power_flow(mode="ac", route="sparse", init=<the base solution>)` through ONE cover plan
 over explicit reduced lists: every (scenario, non-islanding outage) where the shape is within the dense cap, else `--brute-pairs`
 outages spread evenly over the list, one scenario each, scaled per pair (`newton_scaled_to_all_ms`); and, within the dense cap, the
-dense AC screen."""
+dense AC screen.
+
+    python tools/contingency_bench.py --units [--unit-lines 10] [--samples 4096] [--brute-solves 4096] [--case 118 --case 14]
+
+The generator-outage screen (`contingency_screen_units`), same protocol: the units are the PV buses, each losing
+max(-P, 0), the lost output shared among the others in equal parts.  Timed alternately in the same child: the screen with the units
+alone; with `--unit-lines` > 0 the screen with that many candidate lines behind every unit (the non-islanding single outages with
+the largest severity over the scenarios, as --pairs chooses them); the parent commit's `contingency_screen` at the same batch,
+which prices the shared base solve and inverse; and the BRUTE FORCE -- `solve_power_flow(mode="dc")` over explicitly modified
+`spec` tables, one per (scenario, unit), and over those tables with explicit reduced line lists, one per (scenario, unit, line) --
+on scenario counts small enough for about `--brute-solves` solves each, scaled per item."""
 import argparse
 import json
 import os
@@ -499,6 +509,90 @@ def child_pairs(case, samples, candidates, brute_solves, repeats):
     print(json.dumps(row))
 
 
+def child_units(case, samples, unit_lines, brute_solves, repeats):
+    import torch
+    from poweflownet_amd.synth import CASES, make_physical_inputs
+    from poweflownet_amd.utils.contingency import contingency_screen, contingency_screen_units, unit_outage_spec
+    from poweflownet_amd.utils.powerflow import solve_power_flow
+    dev = torch.device("cuda:0")
+    n, e = CASES[case]
+    ei, bt, rx, spec = (t.to(dev) for t in make_physical_inputs(n, e, samples, seed=0))
+    single = contingency_screen(bt, spec, ei, rx)                           # (warm-up; its severities choose the candidate lines)
+    sev = torch.where(single.islands[None, :] == 0, single.severity, torch.full_like(single.severity, -1.0)).max(dim=0).values
+    lines = sorted(torch.topk(sev, min(unit_lines, int((single.islands == 0).sum()))).indices.tolist()) if unit_lines else None
+    alone = contingency_screen_units(bt, spec, ei, rx)                      # (warm-up; units=None: the PV buses, unit_p=None: max(-P, 0))
+    G = int(alone.units.shape[0])
+    part = torch.ones(G, dtype=torch.float64, device=dev)
+    kw = {"participation": part}
+    alone = contingency_screen_units(bt, spec, ei, rx, **kw)
+    lined = contingency_screen_units(bt, spec, ei, rx, lines=lines, **kw) if lines else None
+    # the brute force's inputs, built once and not timed: scenario s, unit g -> sample s * G + g of [Sb G, n, 4] tables
+    Sb = max(1, min(samples, brute_solves // G))
+    sc, g = torch.arange(Sb, device=dev).repeat_interleave(G), torch.arange(G, device=dev).repeat(Sb)
+    spec_u = unit_outage_spec(spec[sc], alone.units, alone.unit_p[sc], part.expand(Sb * G, G), g).contiguous()
+    rx_u = rx[sc].contiguous()
+    brute = solve_power_flow(bt, spec_u, ei, rx_u, mode="dc")               # (warm-up)
+    assert bool((alone.status >= 0).all()) and bool((brute.status >= 0).all())
+    paths = {"units": lambda: contingency_screen_units(bt, spec, ei, rx, **kw), "n1_screen": lambda: contingency_screen(bt, spec, ei, rx),
+             "brute_units": lambda: solve_power_flow(bt, spec_u, ei, rx_u, mode="dc")}
+    K = Sl = 0
+    if lines:
+        out = lined.lines[lined.islands == 0]                                # the non-islanding candidates
+        K = int(out.numel())
+        Sl = max(1, min(samples, brute_solves // (G * K)))
+        ar = torch.arange(e - 1, device=dev)
+        idx = ar[None, :] + (ar[None, :] >= out[:, None])                   # [K, e - 1]
+        lists = ei[:, idx].permute(1, 0, 2).repeat(Sl * G, 1, 1).contiguous()           # sample (s * G + g) * K + k
+        rx_l = rx[:Sl][:, idx].repeat_interleave(G, dim=0).reshape(Sl * G * K, e - 1, 2).contiguous()
+        spec_l = spec_u[:Sl * G].repeat_interleave(K, dim=0).contiguous()
+        assert bool((solve_power_flow(bt, spec_l, lists, rx_l, mode="dc").status >= 0).all())                # (warm-up)
+        paths["unit_lines"] = lambda: contingency_screen_units(bt, spec, ei, rx, lines=lines, **kw)
+        paths["brute_unit_lines"] = lambda: solve_power_flow(bt, spec_l, lists, rx_l, mode="dc")
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+    t = {k: [] for k in paths}
+    for _ in range(repeats):
+        for k, fn in paths.items():
+            t[k].append(timed(fn))
+    med = {k: statistics.median(v) for k, v in t.items()}
+    row = {"case": case, "buses": n, "lines": e, "route": alone.route, "scenarios": samples, "units": G, "units_ms": 1e3 * med["units"],
+           "n1_screen_ms": 1e3 * med["n1_screen"], "units_us_per_item": 1e6 * med["units"] / (samples * G), "brute_units_scenarios": Sb,
+           "brute_units_ms": 1e3 * med["brute_units"], "brute_units_us_per_item": 1e6 * med["brute_units"] / (Sb * G)}
+    row["units_ratio"] = row["brute_units_us_per_item"] / row["units_us_per_item"]
+    if lines:
+        c = len(lines)
+        row.update({"candidates": c, "non_islanding": K, "unit_lines_ms": 1e3 * med["unit_lines"],
+                    "unit_lines_us_per_item": 1e6 * med["unit_lines"] / (samples * G * (1 + c)), "brute_unit_lines_scenarios": Sl,
+                    "brute_unit_lines_ms": 1e3 * med["brute_unit_lines"], "brute_unit_lines_us_per_item": 1e6 * med["brute_unit_lines"] / (Sl * G * K)})
+        row["unit_lines_ratio"] = row["brute_unit_lines_us_per_item"] / row["unit_lines_us_per_item"]
+    print(json.dumps(row))
+
+
+def main_units(a):
+    out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "cases": {}}
+    for case in a.case or ["118", "14"]:
+        rows = []
+        for _ in range(a.processes):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-units", case, "--samples", str(a.samples), "--brute-solves",
+                                str(a.brute_solves), "--repeats", str(a.repeats), "--unit-lines", str(a.unit_lines)], capture_output=True, text=True,
+                               timeout=600)
+            if r.returncode != 0:
+                raise SystemExit(f"contingency_bench: the units child for case {case} failed:\n{r.stdout}\n{r.stderr}")
+            rows.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        row = dict(rows[0])
+        for key in [k for k, v in rows[0].items() if isinstance(v, float)]:
+            vals = [x[key] for x in rows]
+            row[key], row[key + "_spread"] = round(statistics.median(vals), 4), [round(min(vals), 4), round(max(vals), 4)]
+        out["cases"][case] = row
+    print(json.dumps(out))
+    return 0
+
+
 def main_pairs(a):
     out = {"tol": 1e-8, "max_iter": 10, "repeats": a.repeats, "processes": a.processes, "cases": {}}
     for case in a.case or ["118", "14"]:
@@ -732,7 +826,15 @@ def main(argv=None):
     ap.add_argument("--ac-samples", type=int, default=16, help="ac: scenarios")
     ap.add_argument("--child-ac", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--child-ac-sparse", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--units", action="store_true", help="the generator-outage screen, contingency_screen_units, DESIGN 7zc")
+    ap.add_argument("--unit-lines", type=int, default=0, help="units: also screen every unit followed by each of the K worst single line outages")
+    ap.add_argument("--child-units", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if a.child_units:
+        child_units(a.child_units, a.samples, a.unit_lines, a.brute_solves, a.repeats)
+        return 0
+    if a.units:
+        return main_units(a)
     if a.child_ac_sparse:
         child_ac_sparse(a.child_ac_sparse, a.ac_samples, a.groups_x, a.brute_pairs, a.repeats)
         return 0
